@@ -4,8 +4,8 @@
   python bench.py --gpus N --steps K --warmup W
 
 N > 1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run
---nproc-per-node N ... bench.py --gpus N ...`: WORLD_SIZE is in the environment and must equal N) or bench.py re-executes
-itself under torch.distributed.run with N ranks.  Fewer than N visible GPUs is an error, never a silent 1-GPU run.
+--nproc-per-node N ... bench.py --gpus N ...`: WORLD_SIZE is in the environment and must equal N) or bench.py runs
+itself under torch.distributed.run with N ranks in a child process.  Fewer than N visible GPUs is an error, never a silent 1-GPU run.
 
 Workload (BASELINE.json configs[1]): 4-layer d_model=512 heads=8 dim-inner=2048 vgg_cnn Transformer,
 synthetic spectrogram batch (B=32 per GPU, 1, 161, T_src=800) fp32, targets (B, 99) int64 padded to T_tgt=100,
@@ -265,7 +265,7 @@ def cpu_baseline(state_dict, flags, batch, seconds_budget=150.0):
 
 # ------------------------------------------------------------------------------------------------ launch
 def respawn(a):
-    """--gpus N > 1 without a launcher: re-exec under torch.distributed.run, one rank per GPU."""
+    """--gpus N > 1 without a launcher: this command under torch.distributed.run in a child process, one rank per GPU."""
     import torch
     have = torch.cuda.device_count()
     if have < a.gpus:
@@ -274,7 +274,9 @@ def respawn(a):
     port = 29500 + os.getpid() % 400
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a fresh child process, never an exec: this one has already opened the GPU (device_count above)
+    rc = subprocess.run(cmd).returncode
+    sys.exit(128 - rc if rc < 0 else rc)      # killed by signal N: 128 + N, as a shell reports it
 
 
 def rccl_version_line(path):
@@ -288,6 +290,50 @@ def rccl_version_line(path):
     except OSError:
         pass
     return None
+
+
+DUMP_BYTES = 48 * 2 ** 20                # --dump-outputs: under 64 MB on disk however counted (npy headers, blocks, 10^6 bytes)
+
+
+def dump_outputs(out_dir, results, state):
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy (float32; float64 for float64 and integer tensors).
+    `results` (what the step returns to its caller: loss, sums, gold / arg-max tokens) is written whole; `state` (the model's state
+    after the step, state_dict names) whole while everything fits in DUMP_BYTES, else every tensor above a common element cap as a
+    fixed sample of that many flat elements (sorted indices drawn by numpy's generator seeded with the CRC32 of the name), so that
+    two runs with the same arguments write the same elements."""
+    import zlib
+
+    import numpy as np
+    import torch
+
+    def wide(t):
+        return t.dtype == torch.float64 or not (t.is_floating_point() or t.is_complex())
+
+    def host(t):
+        return t.detach().to(torch.float64 if wide(t) else torch.float32).cpu().numpy()
+
+    arrays = {k: host(v).reshape(-1) if v.dim() == 0 else host(v) for k, v in results.items()}
+    budget = DUMP_BYTES - sum(x.nbytes for x in arrays.values()) - 256 * (len(arrays) + len(state))    # (npy headers)
+    size = {k: (8 if wide(v) else 4) for k, v in state.items()}
+    need = lambda cap: sum(min(v.numel(), cap) * size[k] for k, v in state.items())
+    lo, hi = 0, max(v.numel() for v in state.values())                   # the largest cap that fits
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if need(mid) <= budget else (lo, mid - 1)
+    for k, v in state.items():
+        n = v.numel()
+        if n <= lo:
+            arrays[k] = host(v)
+        else:
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(n, lo, replace=False))
+            arrays[k] = host(v.detach().reshape(-1)[torch.from_numpy(idx).to(v.device)])
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+    return total
 
 
 def main():
@@ -316,6 +362,11 @@ def main():
     ap.add_argument("--soak-seconds", type=float, default=5.0, help="UNTIMED replay of the same step for about this long after the timed "
                     "region (reported under config.soak, excluded from `value`): gives an external GPU-busy sampler something to see -- "
                     "the timed region of the default run is a quarter of a second.  0 = off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="rank 0, right after the timed region: what the last timed step "
+                    "computed -- loss, sums [loss sum, non-PAD count, correct] (graph replay), gold and arg-max tokens, the model state after "
+                    "the update (a fixed seeded sample of the larger tensors) -- as DIR/<name>.npy, under 64 MB.  Same arguments, same inputs; "
+                    "the headline workload's step also gives the same bits, the other workloads still add some sums with float atomics "
+                    "(they agree to rounding, and a near-tied arg-max may flip)")
     a = ap.parse_args()
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and a.gpus > 1:
@@ -391,12 +442,15 @@ def main():
         core = model.module if hasattr(model, "module") else model
         sd_cpu = {k: v.detach().cpu().clone() for k, v in core.state_dict().items()}
 
+    last = {}                                # the eager step's gold / arg-max tokens (--dump-outputs)
+
     def eager_step():
         opt.zero_grad()
         pred, gold, hyp, _ = model(src, src_len, tgt)
         loss = calculate_loss(pred, gold, smoothing=0.1, loss_type="ce")
         ops.backward_from(loss)
         opt.step()
+        last["gold"], last["hyp"] = gold, hyp
         return loss
 
     # The step is replayed from captured hipGraphs (same kernels, no per-launch host cost): one graph on one GPU; under data
@@ -428,6 +482,11 @@ def main():
         return float(tmax.item()), dt, loss
 
     dt, dt_local, loss = timed(a.steps)
+    # before anything below runs another step
+    if a.dump_outputs and rank == 0:
+        res = ({"loss": gs.loss, "sums": gs.sums, "gold": gs.gold_seq, "hyp": gs.hyp_seq} if gs is not None else
+               {"loss": loss, "gold": last["gold"], "hyp": last["hyp"]})
+        dump_outputs(a.dump_outputs, res, (model.module if hasattr(model, "module") else model).state_dict())
     final_loss = gs.global_loss() if gs is not None else float(loss.item())
     # every rank's own clock over the same region (the reported time is their maximum): a straggler shows up as a spread here
     per_rank = [dt_local]

@@ -1096,18 +1096,44 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_nhwc_kernel(WgradNArgs p
       float v = bsum[i];
       v += __shfl_xor(v, 16, 64);
       v += __shfl_xor(v, 32, 64);
-      if (g == 0) atomicAdd(p.db + co0 + i * 16 + lr, v);
+      // with a workspace: the slot after the partial dW blocks, folded in workgroup order (no atomics, the same bits every run)
+      if (g == 0) {
+        if (p.ws) p.ws[(int64_t)gridDim.x * gridDim.y * (9 * 64 * 64) + ((int64_t)(co0 / 64) * gridDim.x + blockIdx.x) * 64 + i * 16 + lr] = v;
+        else atomicAdd(p.db + co0 + i * 16 + lr, v);
+      }
     }
   }
 }
 
-// dW[co0+co][ci0+ci][t] += sum over this slice of the workgroup partials ws[by][wg][t][co][ci]
+// db[64 cob + t] += the bias partials of co block cob, in workgroup order (slots [Cout / 64][wgx][64] after the partial dW blocks)
+// (256 threads: each wave adds a quarter of the workgroups with eight loads in flight, the quarters meet in LDS in wave order)
+__device__ inline void wgrad_bias_fold(const float* slots, float* db, int wgx, int cob) {
+  __shared__ float red[4][64];
+  const int t = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  const int per = (wgx + 3) / 4, w0 = grp * per, w1 = min(wgx, w0 + per);
+  const float* s = slots + (int64_t)cob * wgx * 64 + t;
+  float acc = 0.f;
+#pragma unroll 8
+  for (int w = w0; w < w1; ++w) acc += s[(int64_t)w * 64];
+  red[grp][t] = acc;
+  __syncthreads();
+  if (grp == 0) db[cob * 64 + t] += (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+}
+__global__ __launch_bounds__(256) void wgrad_bias_reduce_kernel(const float* __restrict__ ws, float* db, int wgx, int blocks_y) {
+  wgrad_bias_fold(ws + (int64_t)wgx * blocks_y * (9 * 64 * 64), db, wgx, blockIdx.x);
+}
+
+// dW[co0+co][ci0+ci][t] += sum over this slice of the workgroup partials ws[by][wg][t][co][ci]; db (optional) += the bias partials
 // No atomics (1.2 M same-line fp32 atomics were most of this kernel's time: 8 slices x 147 K elements x 4 blocks at the ~40 / ns the
 // chip sustains) and a fixed summation order: a workgroup owns 256 consecutive elements, its four waves each add a quarter of the
 // partial blocks with 16-byte loads (eight in flight), the quarters meet in LDS and wave 0 does the plain dw += .
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* dw, int wgx, int nci, int Cin) {
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* dw, float* db, int wgx, int nci, int Cin) {
   __shared__ float4 red[4][64];
   const int col = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  if (blockIdx.x == 9 * 64 * 64 / 256) {         // with db: one extra column of workgroups folds the bias partials
+    if (blockIdx.y % nci == 0) wgrad_bias_fold(ws + (int64_t)wgx * gridDim.y * (9 * 64 * 64), db, wgx, blockIdx.y / nci);
+    return;
+  }
   const int e = (blockIdx.x * 64 + col) * 4;             // 4 elements of the 9 x 64 x 64 block: (t, co, ci .. ci+3), ci fastest
   const int by = blockIdx.y;
   const int per = (wgx + 3) / 4;
@@ -1560,13 +1586,14 @@ extern "C" int64_t asr_conv3x3_wgrad_workspace(int B, int H, int W, int Cin, int
   if (B <= 0 || H <= 0 || W <= 0 || Cin % 64 != 0 || Cout % 64 != 0) return 0;
   int wgx, by, ppw;
   asr_conv3x3_wgrad_grid(B, H, W, Cin, Cout, &wgx, &by, &ppw);
-  return (int64_t)wgx * by * 9 * 64 * 64;
+  return (int64_t)wgx * by * 9 * 64 * 64 + (int64_t)wgx * Cout;      // partial dW blocks + bias partials
 }
 
 namespace {
 int conv3x3_wgrad_impl(const void* x, const void* dy, float* dw, float* db, float* workspace, int64_t workspace_floats, int B, int H,
                        int W, int Cin, int Cout, int dtype, bool reduce, hipStream_t s);
 }
+int asr_conv3x3_wgrad_fold(const float* workspace, float* dw, float* db, int B, int H, int W, int Cin, int Cout, hipStream_t s);
 extern "C" int asr_conv3x3_wgrad_nhwc(const void* x, const void* dy, float* dw, float* db, float* workspace,
                                       int64_t workspace_floats, int B, int H, int W, int Cin, int Cout, int dtype, hipStream_t s) {
   return conv3x3_wgrad_impl(x, dy, dw, db, workspace, workspace_floats, B, H, W, Cin, Cout, dtype, true, s);
@@ -1581,13 +1608,17 @@ extern "C" int asr_conv3x3_wgrad_partials(const void* x, const void* dy, float* 
 }
 // second stage: dw += the partial blocks of asr_conv3x3_wgrad_partials (same geometry arguments)
 extern "C" int asr_conv3x3_wgrad_reduce(const float* workspace, float* dw, int B, int H, int W, int Cin, int Cout, hipStream_t s) {
+  return asr_conv3x3_wgrad_fold(workspace, dw, nullptr, B, H, W, Cin, Cout, s);
+}
+// dw += the partial blocks and, with db, db += the bias partials (conv_level0.hip's weight gradient: one launch for both)
+int asr_conv3x3_wgrad_fold(const float* workspace, float* dw, float* db, int B, int H, int W, int Cin, int Cout, hipStream_t s) {
   ASR_CHECK_ARG(workspace && dw && B >= 0 && H > 0 && W > 0);
   if (Cin % 64 != 0 || Cout % 64 != 0) return ASR_EUNSUPPORTED;
   if (B == 0) return ASR_OK;
   int wgx, blocks_y, ppw;
   asr_conv3x3_wgrad_grid(B, H, W, Cin, Cout, &wgx, &blocks_y, &ppw);
   AsrProfScope prof(ASR_OP_CONV_WGRAD, s);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(9 * 64 * 64 / 256, (unsigned)blocks_y), dim3(256), 0, s, workspace, dw, wgx,
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(9 * 64 * 64 / 256 + (db ? 1 : 0), (unsigned)blocks_y), dim3(256), 0, s, workspace, dw, db, wgx,
                      Cin / 64, Cin);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
@@ -1609,7 +1640,7 @@ int conv3x3_wgrad_impl(const void* x, const void* dy, float* dw, float* db, floa
   p.ablate = ablate;
   int wgx, blocks_y;
   asr_conv3x3_wgrad_grid(B, H, W, Cin, Cout, &wgx, &blocks_y, &p.patches_per_wg);
-  p.ws = (workspace && workspace_floats >= (int64_t)wgx * blocks_y * 9 * 64 * 64) ? workspace : nullptr;
+  p.ws = (workspace && workspace_floats >= (int64_t)wgx * blocks_y * 9 * 64 * 64 + (int64_t)wgx * Cout) ? workspace : nullptr;
   const int esz = dtype == ASR_F32 ? 4 : 2;
   const size_t lds = (size_t)(180 + 128) * (64 * esz + 16);
   AsrProfScope prof(ASR_OP_CONV_WGRAD, s);
@@ -1628,8 +1659,11 @@ int conv3x3_wgrad_impl(const void* x, const void* dy, float* dw, float* db, floa
   else { allow_big_lds(conv3x3_wgrad_nhwc_kernel<bf16_t>, lds); hipLaunchKernelGGL((conv3x3_wgrad_nhwc_kernel<bf16_t>), dim3((unsigned)wgx, (unsigned)blocks_y), dim3(256), lds, s, p); }
   ASR_LAUNCH_CHECK();
   if (p.ws && reduce) {
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(9 * 64 * 64 / 256, (unsigned)blocks_y), dim3(256), 0, s, p.ws, dw, wgx,
+      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(9 * 64 * 64 / 256 + (db ? 1 : 0), (unsigned)blocks_y), dim3(256), 0, s, p.ws, dw, db, wgx,
                        p.nci, Cin);
+    ASR_LAUNCH_CHECK();
+  } else if (p.ws && db) {              // partials only: the bias partials are folded now, dW waits for asr_conv3x3_wgrad_reduce
+    hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)(Cout / 64)), dim3(256), 0, s, p.ws, db, wgx, blocks_y);
     ASR_LAUNCH_CHECK();
   }
   return ASR_OK;

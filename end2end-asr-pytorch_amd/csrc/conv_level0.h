@@ -15,7 +15,7 @@ struct L0Args {
   uint8_t* code;        // forward out / backward in: one selection byte per pooled element (0 = maximum is 0, 1 + k = first maximum at window position k)
   const bf16_t* dpool;  // backward in: gradient of `pool`
   float* ws;            // backward: per-workgroup partial sums (layout per kernel)
-  float* db;            // weight-gradient kernel: (64) bias gradient of conv.2, accumulated with atomics (as conv3x3_wgrad_dma does)
+  float* db;            // weight-gradient kernel: (64) bias gradient of conv.2; partials in ws slots, folded in a fixed order (as conv3x3_wgrad_dma)
   int B, H, W;
   int tiles_h, tiles_w, ntiles, patches_per_wg;   // filled by the launchers
   int wsplit;           // 1: conv.0's weights as whi + wlo (default); 0: bf16-rounded weights alone (tuning L0_WSPLIT)

@@ -32,7 +32,7 @@
 #include <type_traits>
 #include <utility>
 
-extern "C" int asr_conv3x3_wgrad_reduce(const float* workspace, float* dw, int B, int H, int W, int Cin, int Cout, hipStream_t s);
+int asr_conv3x3_wgrad_fold(const float* workspace, float* dw, float* db, int B, int H, int W, int Cin, int Cout, hipStream_t s);   // conv.hip
 
 namespace {
 
@@ -922,7 +922,8 @@ __global__ __launch_bounds__(256, 2) void vgg_level0_wgrad_kernel(L0Args p) {
     float v = bsum;
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
-    if (g == 0) atomicAdd(p.db + wave * 16 + lr, v);
+    // its slot after the partial dW blocks, folded in workgroup order with the reduce (conv.hip): no atomics, the same bits every run
+    if (g == 0) p.ws[(int64_t)gridDim.x * (9 * 64 * 64) + (int64_t)vid * 64 + wave * 16 + lr] = v;
   }
 }
 
@@ -1006,7 +1007,7 @@ extern "C" int64_t asr_vgg_level0_bwd_workspace(int B, int H, int W) {
   if (!l0_shape_ok(B, H, W)) return 0;
   int wgx, ppw;
   l0_wgrad_grid(B, H, W, &wgx, &ppw);
-  const int64_t a = (int64_t)wgx * 9 * 64 * 64, b = (int64_t)l0_cus() * 2 * 640;
+  const int64_t a = (int64_t)wgx * (9 * 64 * 64 + 64), b = (int64_t)l0_cus() * 2 * 640;      // (+ the bias partials)
   return a > b ? a : b;
 }
 
@@ -1046,7 +1047,7 @@ extern "C" int asr_vgg_level0_wgrad(const float* src, const float* w0, const flo
   a.tiles_h = (H + 7) / 8; a.tiles_w = (W + 15) / 16; a.ntiles = B * a.tiles_h * a.tiles_w;
   int wgx;
   l0_wgrad_grid(B, H, W, &wgx, &a.patches_per_wg);
-  if (workspace_floats < (int64_t)wgx * 9 * 64 * 64) return ASR_EINVAL;
+  if (workspace_floats < (int64_t)wgx * (9 * 64 * 64 + 64)) return ASR_EINVAL;
   const size_t lds = 2 * L0_STAGE + 2 * 1024 + 256;
   a.wsplit = asr_tuning("L0_WSPLIT", 1) != 0 ? 1 : 0;
   const int rc = l0_grant<vgg_level0_wgrad_kernel>(lds);
@@ -1056,5 +1057,5 @@ extern "C" int asr_vgg_level0_wgrad(const float* src, const float* w0, const flo
     hipLaunchKernelGGL(vgg_level0_wgrad_kernel, dim3((unsigned)wgx), dim3(256), lds, s, a);
     ASR_LAUNCH_CHECK();
   }
-  return asr_conv3x3_wgrad_reduce(workspace, dw2, B, H, W, 64, 64, s);
+  return asr_conv3x3_wgrad_fold(workspace, dw2, db2, B, H, W, 64, 64, s);
 }

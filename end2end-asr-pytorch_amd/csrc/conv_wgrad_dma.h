@@ -5,8 +5,8 @@
 struct WgdArgs {
   const bf16_t* x;      // (B, H, W, Cin) NHWC
   const bf16_t* dy;     // (B, H, W, Cout) NHWC
-  float* db;            // (Cout) accumulated with atomics, or null
-  float* ws;            // per-workgroup partial dW blocks [blocks_y][wgx][9][64 co][64 ci]
+  float* db;            // (Cout) or null: each workgroup's partial goes to its slot in ws, folded in a fixed order by conv.hip
+  float* ws;            // per-workgroup partial dW blocks [blocks_y][wgx][9][64 co][64 ci], then the bias partials [Cout / 64][wgx][64]
   int B, H, W, Cin, Cout, tiles_h, tiles_w, npatch, patches_per_wg, nci;
   int wgx, blocks_y, xcd_order;   // filled by the launcher: the grid is ONE dimension of wgx * blocks_y workgroups
 };

@@ -227,7 +227,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgdArgs p) {
     float v = bsum;
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
-    if (g == 0) atomicAdd(p.db + co0 + wave * 16 + lr, v);
+    // its slot after the partial dW blocks, folded in workgroup order by wgrad_reduce_kernel (conv.hip): no atomics, the same bits every run
+    if (g == 0) p.ws[(int64_t)p.wgx * p.blocks_y * (9 * 64 * 64) + ((int64_t)(by / p.nci) * p.wgx + bx) * 64 + wave * 16 + lr] = v;
   }
 }
 

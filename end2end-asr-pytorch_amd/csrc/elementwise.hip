@@ -79,15 +79,60 @@ template <typename T>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* __restrict__ tok, const T* __restrict__ dout,
                                                         float* dtable, int D, float scale, uint32_t thr, float inv_keep,
                                                         uint64_t seed0, const uint64_t* __restrict__ seed_dev, int pad_id) {
+  // No atomics: the FIRST position holding a token owns its table row and adds the gradients of every position holding it in
+  // position order (one writer per row, a fixed summation order: the same bits on every run); the other positions return.
+  __shared__ int list[256];
+  __shared__ int wcnt[4];
   const uint64_t seed = asr_mix_seed(seed0, seed_dev);
-  const int row = blockIdx.x;
+  const int row = blockIdx.x, n = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t id = tok[row];
   if (id == pad_id) return;                   // nn.Embedding(padding_idx=PAD): no gradient for the PAD row
+  for (int base = 0; base < row; base += 1024) {
+    bool hit = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = base + j * 256 + tid;
+      hit |= i < row && tok[i] == id;
+    }
+    if (__syncthreads_or(hit)) return;        // (block-uniform)
+  }
   float* d = dtable + id * (int64_t)D;
-  for (int c = threadIdx.x; c < D; c += blockDim.x) {
-    float g = DT<T>::ld(dout + (int64_t)row * D + c) * scale;
-    if (thr) g = asr_keep(seed, (uint64_t)row * D + c, thr) ? g * inv_keep : 0.f;
-    atomicAdd(d + c, g);
+  for (int chunk = row; chunk < n; chunk += 1024) {
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = chunk + j * 256 + tid;
+      any |= i < n && tok[i] == id;
+    }
+    if (!__syncthreads_or(any)) continue;     // (block-uniform; most tokens occur once)
+    for (int base = chunk; base < n && base < chunk + 1024; base += 256) {
+      const int i = base + tid;
+      const bool hit = i < n && tok[i] == id;
+      const unsigned long long m = __ballot(hit);
+      if (lane == 0) wcnt[wave] = __popcll(m);
+      __syncthreads();
+      int pos = __popcll(m & ((1ull << lane) - 1ull)), cnt = 0;
+      for (int w = 0; w < 4; ++w) {
+        if (w < wave) pos += wcnt[w];
+        cnt += wcnt[w];
+      }
+      if (hit) list[pos] = i;
+      __syncthreads();
+      // one read-modify-write of the table row per chunk; the positions' loads are independent (a frequent token -- V = 32 -- has
+      // dozens per chunk), the additions stay in position order
+      for (int c = tid; c < D; c += 256) {
+        float acc = d[c];
+#pragma unroll 4
+        for (int k = 0; k < cnt; ++k) {
+          const int r = list[k];
+          float g = DT<T>::ld(dout + (int64_t)r * D + c) * scale;
+          if (thr) g = asr_keep(seed, (uint64_t)r * D + c, thr) ? g * inv_keep : 0.f;
+          acc += g;
+        }
+        d[c] = acc;
+      }
+      __syncthreads();                          // (list / wcnt are rewritten by the next chunk)
+    }
   }
 }
 

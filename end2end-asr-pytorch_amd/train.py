@@ -8,6 +8,7 @@
 import json
 import logging
 import os
+import subprocess
 import sys
 
 import torch
@@ -120,14 +121,16 @@ def main():
 
 
 def _spawn_ranks():
-    """--parallel without an external launcher: re-exec this command line under torch.distributed.run, one rank per
+    """--parallel without an external launcher: run this command line under torch.distributed.run in a child process, one rank per
     device id (the reference's --device-ids flag keeps its meaning)."""
     n = len(constant.args.device_ids) if constant.args.device_ids else torch.cuda.device_count()
     if n <= 1:
         return False
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(29400 + os.getpid() % 500)] + sys.argv
-    os.execv(sys.executable, cmd)
+    # a fresh child process, never an exec: this one has already opened the GPU (device_count above)
+    rc = subprocess.run(cmd).returncode
+    sys.exit(128 - rc if rc < 0 else rc)      # killed by signal N: 128 + N, as a shell reports it
 
 
 if __name__ == '__main__':

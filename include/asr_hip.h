@@ -440,13 +440,14 @@ int asr_conv3x3_relu_pool_tcf_codecl(const void* x, const void* wk, const float*
 /* dW (Cout,Cin,3,3) += and db (Cout, optional) += straight from NHWC x (B,H,W,Cin) and dy (B,H,W,Cout): the transposed
  * MFMA operands are built in LDS with ds_read_b64_tr_b16, no planar copies (conv.hip; bf16 with a workspace: the LDS-DMA
  * pipelined kernel of conv_wgrad_dma.hip).                                                                      */
-/* workspace (fp32, >= asr_conv3x3_wgrad_workspace(...) elements, optional): per-workgroup partial dW blocks for a two-stage
- * reduction; without it every workgroup adds its 36,864 partial sums with fp32 atomics (more than half of the kernel time) */
+/* workspace (fp32, >= asr_conv3x3_wgrad_workspace(...) elements, optional): per-workgroup partial dW blocks and bias partials for
+ * a two-stage reduction in a fixed order (the same bits on every run); without it every workgroup adds its 36,864 partial sums
+ * and its bias partials with fp32 atomics (more than half of the kernel time, and the order varies)                             */
 int64_t asr_conv3x3_wgrad_workspace(int B, int H, int W, int Cin, int Cout);
 int asr_conv3x3_wgrad_nhwc(const void* x, const void* dy, float* dw_acc, float* db_acc, float* workspace,
                            int64_t workspace_floats, int B, int H, int W, int Cin, int Cout, int dtype, asr_stream_t stream);
 /* The two stages separately: asr_conv3x3_wgrad_partials leaves the per-workgroup partial dW blocks in `workspace` (required; db is
- * accumulated as usual), asr_conv3x3_wgrad_reduce adds them into dw -- an HBM-bound pass that a caller with a second stream runs
+ * complete when it returns: its partials are folded in a fixed order), asr_conv3x3_wgrad_reduce adds them into dw -- an HBM-bound pass that a caller with a second stream runs
  * next to the MFMA-bound data-gradient convolution that follows (asr_hip/functions.py: VGGFn.backward).                    */
 int asr_conv3x3_wgrad_partials(const void* x, const void* dy, float* db, float* workspace, int64_t workspace_floats, int B, int H,
                                int W, int Cin, int Cout, int dtype, asr_stream_t stream);

@@ -1005,6 +1005,36 @@ def test_conv3x3_wgrad_dma_pipeline(ops, cfg):
     close("wgrad dma db", db, bias.grad, torch.float32, scale=64)
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cfg", [(3, 97, 130, 64, 128), (2, 50, 200, 128, 64)])
+def test_conv3x3_wgrad_two_stages_equal_one_launch(ops, cfg, dtype):
+    """asr_conv3x3_wgrad_partials (db complete on return: its bias partials folded by wgrad_bias_reduce_kernel) + asr_conv3x3_wgrad_reduce
+    give the one-call weight gradient bit for bit -- both fold the same per-workgroup partials in the same fixed order, and so does a
+    repeat of either (no atomics).  dw / db start non-zero: both forms accumulate."""
+    from asr_hip import lib as L
+    B, H, W, Cin, Cout = cfg
+    g = torch.Generator().manual_seed(7 * H + W)
+    D = dev()
+    x = nhwc(q(torch.randn(B, Cin, H, W, generator=g), dtype)).to(D, dtype)
+    dy = nhwc(q(torch.randn(B, Cout, H, W, generator=g) / 8, dtype)).to(D, dtype)
+    dw0, db0 = torch.randn(Cout, Cin, 3, 3, generator=g).to(D), torch.randn(Cout, generator=g).to(D)
+    outs = []
+    for _ in range(2):
+        dw, db = dw0.clone(), db0.clone()
+        ops.conv3x3_wgrad_nhwc(x, dy, dw, db)
+        outs.append((dw, db))
+    n_ws = L.load().asr_conv3x3_wgrad_workspace(B, H, W, Cin, Cout)
+    ws = torch.empty(n_ws, device=D, dtype=torch.float32)
+    dw2, db2 = dw0.clone(), db0.clone()
+    L.call("asr_conv3x3_wgrad_partials", L.ptr(x), L.ptr(dy), L.ptr(db2), L.ptr(ws), n_ws, B, H, W, Cin, Cout, L.dt(x), L.stream())
+    L.call("asr_conv3x3_wgrad_reduce", L.ptr(ws), L.ptr(dw2), B, H, W, Cin, Cout, L.stream())
+    torch.cuda.synchronize()
+    for dw, db in outs[1:] + [(dw2, db2)]:
+        assert torch.equal(dw, outs[0][0]), float((dw - outs[0][0]).abs().max())
+        assert torch.equal(db, outs[0][1]), float((db - outs[0][1]).abs().max())
+    assert not torch.equal(db2, db0)
+
+
 @pytest.mark.parametrize("tw", ["0", "1", "2"])
 @pytest.mark.parametrize("cfg", [(3, 161, 232, True), (5, 97, 401, False), (1, 5, 7, True)])
 def test_conv3x3_c64_persistent(ops, tw, cfg, monkeypatch):
