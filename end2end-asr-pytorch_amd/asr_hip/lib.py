@@ -133,6 +133,11 @@ _SIGS = {
     "asr_bn_act_fwd": (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _I, _P]),
     "asr_bn_act_bwd_reduce": (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P, _I, _P]),
     "asr_bn_act_bwd": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "asr_lm_proj": (_I, [_P, _L, _P, _P, _L, _P, _P, _L, _I, _I, _I, _P]),
+    "asr_lstm_step": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _P]),
+    "asr_lm_nll_chunks": (_I, [_I]),
+    "asr_lm_nll_partials": (_I, [_P, _L, _P, _L, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "asr_lm_nll_finish": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
 }
 
 

@@ -1304,6 +1304,40 @@ def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True):
     return spect, n_frames.to(torch.int32)
 
 
+# ------------------------------------------------------------------------------------------------ LSTM language model (fp32)
+def lm_proj(x, w, bias, K, ids=None):
+    """(M, N) fp32 = X w^T + bias, X row m = x[ids[m]] (int32 ids) or x[m]; x / w zero-padded to 16 * ceil(K / 16) columns."""
+    M = ids.numel() if ids is not None else x.shape[0]
+    N = w.shape[0]
+    out = torch.empty((M, N), device=w.device, dtype=torch.float32)
+    L.call("asr_lm_proj", L.ptr(x), x.stride(0), L.ptr(ids), L.ptr(w), w.stride(0), L.ptr(bias), L.ptr(out), out.stride(0), M, N,
+           int(K), L.stream())
+    return out
+
+
+def lstm_step(xproj, h_prev, whh, c, h, n, H):
+    """One LSTM step for the first n rows (unit-major gates, csrc/lm.hip); h_prev None on the first step.  Updates c, h in place."""
+    L.call("asr_lstm_step", L.ptr(xproj), xproj.stride(0), L.ptr(h_prev), 0 if h_prev is None else h_prev.stride(0), L.ptr(whh),
+           whh.stride(0), L.ptr(c), c.stride(0), L.ptr(h), h.stride(0), int(n), int(H), L.stream())
+
+
+def lm_nll(h, w, bias, tgt, K, step_off, lens, per_token=False):
+    """Per-sequence sums (S,) fp32 of -log softmax(h w^T + bias)[tgt] over the time-major packed tokens (step_off, lens: int32,
+    sequences sorted longest first); with per_token also the (M,) per-token values.  The (M, V) logits are never stored."""
+    M, V = tgt.numel(), w.shape[0]
+    nchunk = L.load().asr_lm_nll_chunks(V)
+    part = torch.empty((M, nchunk, 2), device=h.device, dtype=torch.float32)
+    tgt_logit = torch.empty((M,), device=h.device, dtype=torch.float32)
+    L.call("asr_lm_nll_partials", L.ptr(h), h.stride(0), L.ptr(w), w.stride(0), L.ptr(bias), L.ptr(tgt), M, V, int(K), L.ptr(part),
+           L.ptr(tgt_logit), L.stream())
+    S = lens.numel()
+    nll_sum = torch.empty((S,), device=h.device, dtype=torch.float32)
+    nll_tok = torch.empty((M,), device=h.device, dtype=torch.float32) if per_token else None
+    L.call("asr_lm_nll_finish", L.ptr(part), nchunk, L.ptr(tgt_logit), L.ptr(step_off), L.ptr(lens), S, L.ptr(nll_tok),
+           L.ptr(nll_sum), L.stream())
+    return (nll_sum, nll_tok) if per_token else nll_sum
+
+
 # ------------------------------------------------------------------------------------------------ profiling
 def prof_enable(op, on=True):
     L.call("asr_prof_enable", int(op), int(on))

@@ -7,6 +7,8 @@ decoder rows whose input token is EOS are zeroed; targets are always padded to -
 it never applies.
 """
 
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -255,7 +257,9 @@ class Decoder(nn.Module):
         every step like the reference -- "graph" / "eager" / False give the same tokens (tests/test_gpu_decode.py), the fused
         step the same within the bf16 tolerance (tests/test_gpu_decode_fused.py)."""
         if lm_rescoring:
-            raise NotImplementedError("LM rescoring is outside the accelerated path (SURVEY.md section 2, row 12)")
+            raise NotImplementedError("LM rescoring applies to beam search only: it re-ranks the finished beam hypotheses, and greedy "
+                                      "decoding keeps one (the reference's greedy LM branch, transformer.py:357-372, cannot run: it "
+                                      "passes a str where calculate_lm_score expects label ids)")
         if not self._kv_cache_supported():
             use_cache = False
         if use_cache == "eager":                      # cached, launches issued from Python per token
@@ -288,19 +292,21 @@ class Decoder(nn.Module):
     @torch.no_grad()
     def beam_search(self, encoder_padded_outputs, beam_width=2, nbest=5, lm_rescoring=False, lm=None, lm_weight=0.1,
                     c_weight=1, prob_weight=1.0, use_cache=True):
-        """Per-utterance beam search with the reference's scoring (transformer.py:396-517, LM branch excluded).  With
+        """Per-utterance beam search with the reference's scoring (transformer.py:396-517).  With
         use_cache the live hypotheses of an utterance are one batch of the KV-cached decoder (one step = one token per
         hypothesis); the candidate bookkeeping on the host is the reference's, including its in-loop re-sort (:460).
         With more than one utterance the cached search runs for all of them at once (_beam_search_batched);
-        use_cache="per_utterance" keeps the utterance loop."""
-        if lm_rescoring:
-            raise NotImplementedError("LM rescoring is outside the accelerated path (SURVEY.md section 2, row 12)")
+        use_cache="per_utterance" keeps the utterance loop.  lm_rescoring=True with lm (utils/lstm_utils.LM) re-ranks the finished
+        hypotheses with the LM score (_rank_ended); the search itself prunes on the acoustic score alone, as in the reference."""
+        if lm_rescoring and lm is None:
+            raise ValueError("lm_rescoring=True needs lm (utils.lstm_utils.LM)")
+        lm = lm if lm_rescoring else None
         from asr_hip.decode import DecoderKVCache
         if not self._kv_cache_supported():
             use_cache = False
         if use_cache and use_cache != "per_utterance" and encoder_padded_outputs.size(0) > 1:
-            return self._beam_search_batched(encoder_padded_outputs, beam_width, nbest, c_weight)
-        ids_out, strs_out = [], []
+            return self._beam_search_batched(encoder_padded_outputs, beam_width, nbest, c_weight, lm, lm_weight)
+        all_ended = []
         max_len = encoder_padded_outputs.size(1)
         dev = encoder_padded_outputs.device
         for b in range(encoder_padded_outputs.size(0)):
@@ -333,7 +339,7 @@ class Decoder(nn.Module):
                 alive = []
                 for hyp in hyps:
                     if hyp['yseq'][-1] == constant.EOS_TOKEN:
-                        ended.append(self._finish_hyp(hyp, c_weight))
+                        ended.append(hyp)
                     else:
                         alive.append(hyp)
                 hyps = alive
@@ -341,14 +347,32 @@ class Decoder(nn.Module):
                     break
                 if use_cache:
                     cache.select([h['parent'] for h in hyps])
-            for hyp in sorted(ended, key=lambda h: h['final_score'], reverse=True)[:min(len(ended), nbest)]:
+            all_ended.append(ended)
+        return self._rank_ended(all_ended, nbest, c_weight, lm, lm_weight)
+
+    def _rank_ended(self, ended, nbest, c_weight, lm=None, lm_weight=0.1):
+        """The nbest finished hypotheses of every utterance (ended: one list per utterance) by final_score, best first
+        (reference: transformer.py:475-497, 499-514).  Without an LM final_score = score + sqrt(words) * c_weight.  With one,
+        final_score = score + lm_weight * (lm_score - 2 * oov) + sqrt(num_words) * c_weight, num_words = LM words + 1: the LM
+        score only re-ranks finished hypotheses, so those of ALL utterances are scored by ONE batched LM call here."""
+        if lm is not None:
+            from utils.lstm_utils import calculate_lm_scores
+            flat = [h for hs in ended for h in hs]
+            for hyp, (lm_score, num_words, oov) in zip(flat, calculate_lm_scores([h['yseq'] for h in flat], lm, self.id2label)):
+                hyp['lm_score'], hyp['num_words'] = lm_score - oov * 2, num_words
+                hyp['final_score'] = hyp['score'] + lm_weight * hyp['lm_score'] + math.sqrt(num_words) * c_weight
+        else:
+            for hs in ended:
+                for hyp in hs:
+                    self._finish_hyp(hyp, c_weight)
+        ids_out, strs_out = [], []
+        for hs in ended:
+            for hyp in sorted(hs, key=lambda h: h['final_score'], reverse=True)[:min(len(hs), nbest)]:
                 ids_out.append(hyp['yseq'])
                 strs_out.append(self.post_process_hyp(hyp))
         return ids_out, strs_out
 
-
     def _finish_hyp(self, hyp, c_weight):
-        import math
         s = "".join(self.id2label[t] for t in hyp['yseq'])
         for ch in (constant.PAD_CHAR, constant.SOS_CHAR, constant.EOS_CHAR):
             s = s.replace(ch, "")
@@ -356,7 +380,7 @@ class Decoder(nn.Module):
         hyp['final_score'] = hyp['score'] + math.sqrt(len(s.split())) * c_weight
         return hyp
 
-    def _beam_search_batched(self, encoder_padded_outputs, beam_width, nbest, c_weight):
+    def _beam_search_batched(self, encoder_padded_outputs, beam_width, nbest, c_weight, lm=None, lm_weight=0.1):
         """The same search for ALL utterances of the batch at once: utterance b owns decoder rows b * W .. b * W + W - 1 of ONE
         KV-cached decoder batch (its live hypotheses in the first rows, the others idle), so a step is one decoder step, one
         log-softmax / top-W launch and one device -> host copy for the whole batch instead of one of each per utterance.  The
@@ -394,7 +418,7 @@ class Decoder(nn.Module):
                 alive = []
                 for hyp in cand:
                     if hyp['yseq'][-1] == constant.EOS_TOKEN:
-                        ended[b].append(self._finish_hyp(hyp, c_weight))
+                        ended[b].append(hyp)
                     else:
                         alive.append(hyp)
                 hyps[b] = alive
@@ -405,12 +429,7 @@ class Decoder(nn.Module):
                 break
             if moved:
                 cache.select(rows, cross=False)           # parents stay inside their utterance: the cross keys / values do not move
-        ids_out, strs_out = [], []
-        for b in range(B):
-            for hyp in sorted(ended[b], key=lambda h: h['final_score'], reverse=True)[:min(len(ended[b]), nbest)]:
-                ids_out.append(hyp['yseq'])
-                strs_out.append(self.post_process_hyp(hyp))
-        return ids_out, strs_out
+        return self._rank_ended(ended, nbest, c_weight, lm, lm_weight)
 
 
 class DecoderLayer(nn.Module):

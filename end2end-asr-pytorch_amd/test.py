@@ -45,9 +45,8 @@ def evaluate(model, test_loader, lm=None):
 if __name__ == '__main__':
     from utils.data_loader import AudioDataLoader, BucketingSampler, SpectrogramDataset
     from utils.functions import load_model
+    from utils.lstm_utils import LM
     args = constant.args
-    if args.lm_rescoring:
-        raise SystemExit("LM rescoring is outside the accelerated path (SURVEY.md section 2, rows 12-14)")
     model, opt, epoch, metrics, loaded_args, label2id, id2label = load_model(args.continue_from)
     if getattr(loaded_args, "parallel", False):
         print("unwrap data parallel")
@@ -60,5 +59,6 @@ if __name__ == '__main__':
                                    normalize=True, augment=False)
     test_sampler = BucketingSampler(test_data, batch_size=args.batch_size)
     test_loader = AudioDataLoader(test_data, num_workers=args.num_workers, batch_sampler=test_sampler)
+    lm = LM(args.lm_path) if args.lm_rescoring else None      # reference: test.py:91-93
     print(model)
-    evaluate(model, test_loader)
+    evaluate(model, test_loader, lm=lm)

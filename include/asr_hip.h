@@ -528,6 +528,35 @@ int asr_stft_frames(const float* wav, int64_t wav_stride, const int32_t* lengths
 int asr_spect_finish(const float* reim, int64_t ld, const int32_t* lengths, float* spect, float* sums, float* sqdev, int B,
                      int F, int Tmax, int hop, int normalize, asr_stream_t stream);
 
+/* ---- LSTM language model for beam-search rescoring (reference: utils/lstm_utils.py LM.evaluate, RNNModel.forward; nn.LSTM gate
+ * order i, f, g, o).  fp32 storage and f32-input MFMA (v_mfma_f32_16x16x4_f32) whatever the ASR model's precision.
+ * Contraction operands: rows 16-byte aligned, leading dimensions multiples of 4 floats, and the K columns zero-padded to a multiple
+ * of 16 (the kernels contract 16 * ceil(K / 16) columns).  Each output element is computed by one lane in an order that does not
+ * depend on M / n / the batch, so a sentence's result is bitwise the same alone or in any batch.
+ *
+ * out (M, ldo) = X W^T + bias: X row m is x[ids[m]] (ids != NULL: the embedding gather of layer 0) or x[m]; W (N, ldw), N % 4 == 0.
+ * The input projection of one LSTM layer over all tokens, bias = b_ih + b_hh (lstm_utils.py:119-125, nn.LSTM's x W_ih^T part). */
+int asr_lm_proj(const float* x, int64_t ldx, const int32_t* ids, const float* w, int64_t ldw, const float* bias, float* out,
+                int64_t ldo, int M, int N, int K, asr_stream_t stream);
+/* One time step of one LSTM layer for the first n sequences (sorted longest first, so the running ones are a prefix):
+ * gates = xproj (n, 4H) + h_prev (n, H) W_hh^T, with xproj / whh in the UNIT-MAJOR gate order (row / column 4 j + q = gate q of
+ * unit j); c (n, ldc) <- sigma(f) c + sigma(i) tanh(g), h (n, ldh) <- sigma(o) tanh(c).  h_prev == NULL: the first step
+ * (h = c = 0, c is not read).  One launch per (layer, step), no inter-workgroup synchronisation
+ * (replaces nn.LSTM in RNNModel.forward, lstm_utils.py:185-193).                                                          */
+int asr_lstm_step(const float* xproj, int64_t ldx, const float* h_prev, int64_t ldhp, const float* whh, int64_t ldw, float* c,
+                  int64_t ldc, float* h, int64_t ldh, int n, int H, asr_stream_t stream);
+/* number of vocabulary chunks (256 words each) of asr_lm_nll_partials                                                     */
+int asr_lm_nll_chunks(int V);
+/* The output layer without logits in memory (lstm_utils.py:119-125: decoder Linear + CrossEntropyLoss): for every token m and
+ * vocabulary chunk k, part[m, k] = (max, sum exp(. - max)) of logits[m, chunk k] where logits = h W^T + bias (W (V, ldw)), and
+ * tgt_logit[m] = logits[m, tgt[m]] (0 <= tgt[m] < V).  part: (M, asr_lm_nll_chunks(V)) float pairs.                       */
+int asr_lm_nll_partials(const float* h, int64_t ldh, const float* w, int64_t ldw, const float* bias, const int32_t* tgt, int M, int V,
+                        int K, float* part, float* tgt_logit, asr_stream_t stream);
+/* nll_tok[m] = logsumexp(logits[m]) - tgt_logit[m] (chunks combined in index order), nll_sum[s] = sum over t < lens[s] of
+ * nll_tok[step_off[t] + s] (time-major packing of sequences sorted longest first).  nll_tok may be NULL.                  */
+int asr_lm_nll_finish(const float* part, int nchunk, const float* tgt_logit, const int32_t* step_off, const int32_t* lens, int S,
+                      float* nll_tok, float* nll_sum, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
