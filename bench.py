@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Throughput of the Transformer-ASR TRAINING STEP on MI355X (BASELINE.json metric: input spectrogram frames/s).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the line.  --full adds, after the
+timed region, what the headline figure does not need: the CPU baseline, the roofline pass (HIP events over extra eager steps)
+with the committed per-kernel figures it is read against, the argmax contract, the untimed soak and (N > 1) the all-reduce exposure.
 
 N > 1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N ...`: WORLD_SIZE is in the environment and must equal N) or bench.py runs
@@ -347,9 +351,12 @@ def main():
                          "lowrank = configs[4] (12-layer d512 Low-Rank Transformer, r = 64; use --precision fp8 for its fp8 path)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp8"])
     ap.add_argument("--dropout", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-exposure", action="store_true", help="N > 1: skip the extra no-collective steps that measure how much "
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure and report what the headline figure "
+                    "does not need: cpu_baseline, roofline, config.argmax_contract, the soak (--soak-seconds) and, N > 1, "
+                    "config.gradient_allreduce.  The --no-* switches below take parts of it away again")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline pass")
+    ap.add_argument("--no-exposure", action="store_true", help="--full, N > 1: skip the extra no-collective steps that measure how much "
                     "of the gradient all-reduce is exposed")
     ap.add_argument("--grad-wire", default="fp32", choices=["fp32", "bf16"], help="N > 1: dtype in which the gradient slices are "
                     "all-reduced (bf16 = half the bytes per xGMI link, summed in bf16 by the collective; asr_hip/ddp.py)")
@@ -359,15 +366,17 @@ def main():
                          "collectives captured inside ONE hipGraph; auto = one, verified against the four-body step on the capture batch, "
                          "falling back loudly (train.py's default).  Recorded in config.ddp_graph")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python instead of replaying hipGraphs")
-    ap.add_argument("--soak-seconds", type=float, default=5.0, help="UNTIMED replay of the same step for about this long after the timed "
+    ap.add_argument("--soak-seconds", type=float, default=None, help="UNTIMED replay of the same step for about this long after the timed "
                     "region (reported under config.soak, excluded from `value`): gives an external GPU-busy sampler something to see -- "
-                    "the timed region of the default run is a quarter of a second.  0 = off")
+                    "the timed region of the default run is a quarter of a second.  0 = off; default 5 with --full, else 0")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="rank 0, right after the timed region: what the last timed step "
                     "computed -- loss, sums [loss sum, non-PAD count, correct] (graph replay), gold and arg-max tokens, the model state after "
                     "the update (a fixed seeded sample of the larger tensors) -- as DIR/<name>.npy, under 64 MB.  Same arguments, same inputs; "
                     "the headline workload's step also gives the same bits, the other workloads still add some sums with float atomics "
                     "(they agree to rounding, and a near-tied arg-max may flip)")
     a = ap.parse_args()
+    if a.soak_seconds is None:
+        a.soak_seconds = 5.0 if a.full else 0.0
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and a.gpus > 1:
         respawn(a)
@@ -438,7 +447,7 @@ def main():
     src, src_len, tgt = synthetic_batch(a.batch, torch, t_src, t_tgt, vocab)
     src, tgt = src.cuda(), tgt.cuda()
     sd_cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not libri and not lowrank:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not libri and not lowrank:
         core = model.module if hasattr(model, "module") else model
         sd_cpu = {k: v.detach().cpu().clone() for k, v in core.state_dict().items()}
 
@@ -508,7 +517,7 @@ def main():
     # Exposed part of the gradient exchange: the same steps with the collectives switched off (ranks then drift apart -- this
     # runs after the timed region and nothing is measured afterwards that depends on the weights).
     exposure = None
-    if red is not None and red.active and not a.no_exposure:
+    if a.full and red is not None and red.active and not a.no_exposure:
         red.active = False
         dt_nc, _, _ = timed(a.steps)
         red.active = True
@@ -519,11 +528,12 @@ def main():
     # `prof_steps` EAGER steps of the same workload right after the timed region (events cannot be recorded inside a graph
     # replay).  Every rank takes part: the steps contain the gradient all-reduce.
     prof = None
+    roofline = a.full and not a.no_roofline
     fam_ops = {"conv3x3_igemm (3 fwd + 3 dgrad)": L.OP_CONV_IGEMM, "conv3x3_wgrad": L.OP_CONV_WGRAD,
                "linear GEMMs (fwd + dgrad + wgrad)": L.OP_GEMM, "attention fwd": L.OP_ATTN_FWD, "attention bwd": L.OP_ATTN_BWD}
-    if not a.no_roofline and (libri or lowrank):
+    if roofline and (libri or lowrank):
         fam_ops = {"GEMM family (asr_gemm_*)": L.OP_GEMM}
-    if not a.no_roofline:
+    if roofline:
         prof_steps = min(a.steps, 3)
         for op in fam_ops.values():
             ops.prof_enable(op, True)
@@ -663,7 +673,7 @@ def main():
                         bigr = max(mf, key=lambda k: mf[k]["ms_per_step"])
                         out["roofline"]["largest_family_by_time_replayed"] = bigr
                         out["roofline"]["frac_by_time_largest_family_replayed"] = mf[bigr]["frac"]
-        ac = argmax_contract(a)
+        ac = argmax_contract(a) if a.full else None
         if ac is not None:
             out["config"]["argmax_contract"] = ac
         if sd_cpu is not None:

@@ -23,12 +23,12 @@ python tools/prof_sequence.py "$db" ${O}_step_sequence.txt > /dev/null 2>&1
 head -1 ${O}_step_sequence.txt
 bash tools/gpu_pmc_traffic.sh $r > /dev/null 2>&1
 mkdir -p profiles; cp ${O}_replayed_families.json ${O}_roofline_traffic.json profiles/ 2>/dev/null      # bench.py reads them from profiles/
-python bench.py > ${O}_bench_line.json 2> ${O}_bench.err
+python bench.py --full > ${O}_bench_line.json 2> ${O}_bench.err
 if [ -z "$quick" ]; then
-  python bench.py --workload librispeech --steps 20 --warmup 5 --soak-seconds 0 > ${O}_bench_line_librispeech.json 2>> ${O}_bench.err
-  python bench.py --workload lowrank --steps 20 --warmup 5 --soak-seconds 0 > ${O}_bench_line_lowrank.json 2>> ${O}_bench.err
-  python bench.py --workload lowrank --precision fp8 --steps 20 --warmup 5 --soak-seconds 0 > ${O}_bench_line_lowrank_fp8.json 2>> ${O}_bench.err
-  B="python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-roofline --soak-seconds 0"
+  python bench.py --full --workload librispeech --steps 20 --warmup 5 --soak-seconds 0 > ${O}_bench_line_librispeech.json 2>> ${O}_bench.err
+  python bench.py --full --workload lowrank --steps 20 --warmup 5 --soak-seconds 0 > ${O}_bench_line_lowrank.json 2>> ${O}_bench.err
+  python bench.py --full --workload lowrank --precision fp8 --steps 20 --warmup 5 --soak-seconds 0 > ${O}_bench_line_lowrank_fp8.json 2>> ${O}_bench.err
+  B="python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-roofline --soak-seconds 0"
   for m in four one auto; do ASR_FORCE_DDP=1 $B --ddp-graph $m > ${O}_bench_line_ddp1_forced_$m.json 2>> ${O}_bench.err; done
   ASR_FORCE_DDP=1 $B --grad-wire bf16 > ${O}_bench_line_ddp1_forced_bf16wire.json 2>> ${O}_bench.err
   bash tools/gpu_pmc_mfma.sh ${r}_step > /dev/null 2>&1

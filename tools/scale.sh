@@ -21,10 +21,10 @@ for n in 1 2 4 8; do
     [ "$n" -eq 1 ] && [ "$batch" -ne 32 ] && continue
     port=$((29600 + n * 10 + batch % 7))
     if [ "$n" -eq 1 ]; then
-      line=$(cd "$root" && timeout 1200 python bench.py --gpus 1 --steps "$steps" --warmup "$warmup" --batch "$batch" --no-cpu-baseline --no-roofline 2>/dev/null | tail -1)
+      line=$(cd "$root" && timeout 1200 python bench.py --full --gpus 1 --steps "$steps" --warmup "$warmup" --batch "$batch" --no-cpu-baseline --no-roofline 2>/dev/null | tail -1)
     else
       line=$(cd "$root" && HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 \
-             --master-port "$port" bench.py --gpus "$n" --steps "$steps" --warmup "$warmup" --batch "$batch" --ddp-graph "$ddpg" --no-cpu-baseline --no-roofline 2>/dev/null | grep '^{' | tail -1)
+             --master-port "$port" bench.py --full --gpus "$n" --steps "$steps" --warmup "$warmup" --batch "$batch" --ddp-graph "$ddpg" --no-cpu-baseline --no-roofline 2>/dev/null | grep '^{' | tail -1)
     fi
     [ -n "$line" ] && echo "$line" >> "$tmp" || echo "{\"n_gpus\": $n, \"batch_per_gpu\": $batch, \"failed\": true}" >> "$tmp"
   done
