@@ -1265,13 +1265,16 @@ def bn_act_bwd(dout, y, M, C, mean, rstd, gamma, beta, lo, hi, dy, tH=0, tW=0, y
 _stft_const = {}
 
 
-def _stft_constants(n_fft, device):
-    """Symmetric Hamming window (n_fft) and the [cos | -sin] DFT basis (2*(n_fft/2+1), n_fft), fp32, computed in float64."""
-    key = (n_fft, str(device))
+def _stft_constants(n_fft, device, window="hamming"):
+    """Symmetric analysis window (n_fft; utils.audio.window_function) and the [cos | -sin] DFT basis (2*(n_fft/2+1), n_fft), fp32,
+    computed in float64."""
+    from utils.audio import resolve_window, window_function
+    window = resolve_window(window)
+    key = (n_fft, str(device), window)
     c = _stft_const.get(key)
     if c is None:
         k = torch.arange(n_fft, dtype=torch.float64)
-        win = (0.54 - 0.46 * torch.cos(2.0 * math.pi * k / (n_fft - 1))).float()
+        win = torch.from_numpy(window_function(window, n_fft))
         f = torch.arange(n_fft // 2 + 1, dtype=torch.float64)[:, None]
         ang = 2.0 * math.pi * f * k[None, :] / n_fft
         basis = torch.cat([torch.cos(ang), -torch.sin(ang)], dim=0).float()
@@ -1280,16 +1283,16 @@ def _stft_constants(n_fft, device):
     return c
 
 
-def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True):
+def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="hamming"):
     """Padded waveforms wav (B, L) fp32 + lengths (B) int32 (samples), both on the device -> (spect (B, 1, n_fft/2+1, Tmax)
     fp32 zero padded along T, n_frames (B) int32): log1p(|STFT|) normalised per utterance, the reference loader's features
     (utils/data_loader.py:72-89) computed on the GPU: framing kernel -> fp32 MFMA GEMM against the DFT basis -> magnitude /
-    log1p / mean / unbiased std kernels."""
+    log1p / mean / unbiased std kernels.  window: --window (hamming, hann, blackman, bartlett; symmetric)."""
     assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1 and lengths.dtype == torch.int32
     B, Lmax = wav.shape
     F = n_fft // 2 + 1
     Tmax = 1 + max(Lmax, 2) // hop
-    win, basis = _stft_constants(n_fft, wav.device)
+    win, basis = _stft_constants(n_fft, wav.device, window)
     frames = torch.empty((B * Tmax, n_fft), device=wav.device, dtype=torch.float32)
     L.call("asr_stft_frames", L.ptr(wav), wav.stride(0), L.ptr(lengths), L.ptr(win), L.ptr(frames), B, Tmax, n_fft, hop,
            L.stream())
@@ -1302,6 +1305,56 @@ def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True):
            hop, int(normalize), L.stream())
     n_frames = 1 + torch.clamp(lengths, min=2) // hop
     return spect, n_frames.to(torch.int32)
+
+
+def augment_wave(wav, lens, params, bank, sample_rate=16000, offsets=False):
+    """Tempo / gain perturbation and noise injection (asr_augment_wave) of padded waveforms wav (B, L) fp32 on
+    the device.  lens (B): input samples; params (B, 5) float64 on the host: {tempo (0: no tempo / gain), gain dB, noise clip index
+    (-1: none), noise start in seconds, noise level} as drawn by the loader; bank: utils.audio.NoiseBank or None.  Returns
+    (wav_out (B, max n_out) fp32 zero padded, lens_out (B) int32 on the device) and with offsets=True also the (B, segments) int32
+    WSOLA offsets the kernel chose."""
+    import numpy as np
+    from utils.audio import gain_multiplier, tempo_length, wsola_constants
+    assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1
+    B, Lmax = wav.shape
+    P = torch.as_tensor(params, dtype=torch.float64).cpu().numpy().reshape(B, -1)
+    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
+    if (n_in < 0).any() or (n_in > Lmax).any():
+        raise ValueError("augment_wave: lengths outside [0, %d]" % Lmax)
+    S, search, O = wsola_constants(sample_rate)
+    kp = np.zeros((B, 8), dtype=np.float64)
+    nclips = 0 if bank is None else int(bank.lengths.size)
+    for b in range(B):
+        tempo, gain, clip, start_s, level = P[b, :5]
+        n = int(n_in[b])
+        if tempo > 0:
+            n_out, m = tempo_length(n, tempo), float(gain_multiplier(gain))
+        else:
+            tempo, n_out, m = 0.0, n, 1.0
+        clip = int(clip)
+        start = 0
+        if clip >= 0:
+            if clip >= nclips:
+                raise ValueError("augment_wave: noise clip %d of a bank of %d" % (clip, nclips))
+            clen = int(bank.lengths[clip])
+            start = int(min(max(np.rint(start_s * sample_rate), 0), max(clen - n_out, 0)))
+        kp[b] = (tempo, m, clip, start, float(np.float32(level)), n_out, 0, 0)
+    n_outs = kp[:, 5].astype(np.int64)
+    Lout = max(int(n_outs.max()) if B else 0, 1)
+    dev = wav.device
+    out = torch.zeros((B, Lout), device=dev, dtype=torch.float32)
+    nseg = (Lout + (S - O) - 1) // (S - O)
+    offs = torch.zeros((B, nseg), device=dev, dtype=torch.int32) if offsets else None
+    lens_in = torch.from_numpy(n_in.astype(np.int32)).to(dev)
+    kp_dev = torch.from_numpy(kp).to(dev)
+    if bank is not None:
+        bdata, boff, blen = bank.data, bank.offsets, bank.lens
+    else:
+        bdata = boff = blen = None
+    L.call("asr_augment_wave", L.ptr(wav), wav.stride(0), L.ptr(lens_in), L.ptr(kp_dev), L.ptr(bdata), L.ptr(boff), L.ptr(blen),
+           nclips, L.ptr(out), out.stride(0), L.ptr(offs), nseg, B, S, search, O, L.stream())
+    lens_out = torch.from_numpy(n_outs.astype(np.int32)).to(dev)
+    return (out, lens_out, offs) if offsets else (out, lens_out)
 
 
 # ------------------------------------------------------------------------------------------------ LSTM language model (fp32)

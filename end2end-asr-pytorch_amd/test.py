@@ -7,8 +7,8 @@ from utils import constant
 from utils.metrics import calculate_cer, calculate_cer_en_zh, calculate_wer
 
 
-def evaluate(model, test_loader, lm=None):
-    """reference: test.py:19-62"""
+def evaluate(model, test_loader, lm=None, noise_dir=None):
+    """reference: test.py:19-62.  noise_dir: the checkpoint's --noise-dir (the reference injects noise into the test set too)."""
     args = constant.args
     model.eval()
     total_word = total_char = total_cer = total_wer = 0
@@ -16,13 +16,15 @@ def evaluate(model, test_loader, lm=None):
     with torch.no_grad():
         pbar = tqdm(iter(test_loader), leave=True, total=len(test_loader))
         for data in pbar:
-            src, tgt, _, src_lengths, _ = data
+            src, tgt, _, src_lengths, _ = data[:5]
+            aug = data[5] if len(data) > 5 else None      # noise draws when the checkpoint's run injected noise
             if constant.USE_CUDA:
                 src, tgt = src.cuda(), tgt.cuda()
             if getattr(args, "gpu_frontend", False):
                 from utils.audio import gpu_front_end
                 src, src_lengths = gpu_front_end(src, src_lengths, args.sample_rate, args.window_size, args.window_stride,
-                                                 args.src_max_len)
+                                                 args.src_max_len, window=getattr(args, "window", "hamming"), aug=aug,
+                                                 noise_dir=noise_dir)
             _, strs_hyps, strs_gold = model.evaluate(src, src_lengths, tgt, beam_search=args.beam_search,
                                                      beam_width=args.beam_width, beam_nbest=args.beam_nbest, lm=lm,
                                                      lm_rescoring=args.lm_rescoring, lm_weight=args.lm_weight,
@@ -52,6 +54,10 @@ if __name__ == '__main__':
         print("unwrap data parallel")
         model = model.module
     constant.args.tgt_max_len = max(constant.args.tgt_max_len, 301)      # greedy/beam search always run 300 steps
+    if getattr(loaded_args, "noise_dir", None) is not None and args.cuda and not args.gpu_frontend:
+        args.gpu_frontend = True                # noise injection runs on the GPU front end (utils/audio.py)
+        print("--noise-dir of the checkpoint: noise injection on the GPU front end (--gpu-frontend turned on)")
+    args.window = getattr(loaded_args, "window", "hamming")      # the features the model was trained on
     audio_conf = dict(sample_rate=loaded_args.sample_rate, window_size=loaded_args.window_size,
                       window_stride=loaded_args.window_stride, window=loaded_args.window, noise_dir=loaded_args.noise_dir,
                       noise_prob=loaded_args.noise_prob, noise_levels=(loaded_args.noise_min, loaded_args.noise_max))
@@ -61,4 +67,4 @@ if __name__ == '__main__':
     test_loader = AudioDataLoader(test_data, num_workers=args.num_workers, batch_sampler=test_sampler)
     lm = LM(args.lm_path) if args.lm_rescoring else None      # reference: test.py:91-93
     print(model)
-    evaluate(model, test_loader, lm=lm)
+    evaluate(model, test_loader, lm=lm, noise_dir=getattr(loaded_args, "noise_dir", None))

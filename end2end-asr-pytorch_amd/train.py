@@ -88,6 +88,12 @@ def main():
                       window=args.window, noise_dir=args.noise_dir, noise_prob=args.noise_prob,
                       noise_levels=(args.noise_min, args.noise_max))
     logging.info(audio_conf)
+    if (args.augment or args.noise_dir is not None) and args.cuda and not args.gpu_frontend:
+        # tempo / gain augmentation and noise injection run between the host-to-device copy and the STFT (csrc/augment.hip)
+        args.gpu_frontend = True
+        logging.info("--augment / --noise-dir: --gpu-frontend turned on")
+        if rank0:
+            print("--augment / --noise-dir: tempo, gain and noise run on the GPU front end (--gpu-frontend turned on)")
     label2id, id2label = build_labels(args.labels_path)
 
     train_data = SpectrogramDataset(audio_conf, manifest_filepath_list=args.train_manifest_list, label2id=label2id,

@@ -2,7 +2,10 @@
   * manifest: one "wav_path,transcript_path" per line (data_loader.py:112-119);
   * transcripts: SOS + lower-cased text + EOS mapped through label2id, unknown characters AND id 0 dropped (:133-141);
   * batch = (inputs f32 (B,1,F,Tmax) zero padded and sorted by length descending, targets i64 (B,Lmax) zero padded,
-             input_percentages f32 (B), input_sizes i32 (B), target_sizes i32 (B))   (:182-214).
+             input_percentages f32 (B), input_sizes i32 (B), target_sizes i32 (B))   (:182-214);
+  * with tempo / gain augmentation or noise injection (GPU front end only) a 6th element: the (B, 6) float64 draws
+    {input samples, tempo (0: none), gain dB, noise clip (-1: none), noise start s, noise level}, and the batch is sorted by, and
+    input_sizes / input_percentages count, the samples AFTER the tempo change (utils.audio.gpu_front_end applies the draws).
 BucketingSampler keeps the reference's consecutive bins and additionally shards them over data-parallel ranks.
 """
 import random
@@ -14,7 +17,9 @@ from torch.utils.data.sampler import Sampler
 
 from asr_hip.ddp import rank_shard
 from utils import constant
-from utils.audio import load_audio, log_spectrogram
+from utils.audio import load_audio, log_spectrogram, noise_files, resolve_window, tempo_length
+
+TEMPO_RANGE, GAIN_RANGE = (0.85, 1.15), (-6, 8)          # reference: utils/audio.py:54
 
 
 class SpectrogramParser(object):
@@ -22,11 +27,41 @@ class SpectrogramParser(object):
         self.window_stride = audio_conf['window_stride']
         self.window_size = audio_conf['window_size']
         self.sample_rate = audio_conf['sample_rate']
-        if audio_conf.get('window', 'hamming') != 'hamming':
-            raise NotImplementedError("only the hamming window (the reference default) is implemented")
-        if augment or audio_conf.get('noise_dir') is not None:
-            raise NotImplementedError("sox tempo/gain augmentation and noise injection are outside the accelerated path")
+        self.window = resolve_window(audio_conf.get('window', 'hamming'))
         self.normalize = normalize
+        self.augment = augment
+        self.noise_dir = audio_conf.get('noise_dir')
+        if (augment or self.noise_dir is not None) and not getattr(constant.args, "gpu_frontend", False):
+            raise NotImplementedError("tempo/gain augmentation (--augment) and noise injection (--noise-dir) run on the GPU front end "
+                                      "only: use --cuda (it turns on --gpu-frontend)")
+        self.noise_paths = None
+        if self.noise_dir is not None:
+            self.noise_paths, self.noise_lens = noise_files(self.noise_dir, self.sample_rate)
+            self.noise_index = {p: i for i, p in enumerate(self.noise_paths)}
+            self.noise_prob = float(audio_conf.get('noise_prob'))          # an untyped flag in the reference's CLI
+            self.noise_levels = tuple(audio_conf.get('noise_levels', (0.0, 0.5)))
+
+    def draw(self, n):
+        """The random draws for an utterance of n samples, on the global np.random in the reference's call order
+        (utils/audio.py:49-61, data_loader.py:62-70,160-170): (n, tempo, gain dB, noise clip, noise start s, level, n_out) with
+        tempo 0 = no tempo / gain, clip -1 = no noise; tempo and gain rounded through "%.3f" as sox's command line."""
+        tempo = gain = 0.0
+        n_out = n
+        if self.augment:
+            tempo = float("%.3f" % np.random.uniform(low=TEMPO_RANGE[0], high=TEMPO_RANGE[1]))
+            gain = float("%.3f" % np.random.uniform(low=GAIN_RANGE[0], high=GAIN_RANGE[1]))
+            n_out = tempo_length(n, tempo)
+        clip, start_s, level = -1, 0.0, 0.0
+        if self.noise_paths is not None and np.random.binomial(1, self.noise_prob):
+            clip = self.noise_index[np.random.choice(self.noise_paths)]
+            level = float(np.random.uniform(*self.noise_levels))
+            data_len = n_out / self.sample_rate
+            start_s = float(np.random.rand() * (self.noise_lens[clip] / self.sample_rate - data_len))
+        return (n, tempo, gain, clip, start_s, level, n_out)
+
+    @property
+    def augmenting(self):
+        return self.augment or self.noise_paths is not None
 
     def parse_audio(self, audio_path):
         y = load_audio(audio_path)
@@ -34,7 +69,8 @@ class SpectrogramParser(object):
             # ship the waveform as a 1-bin "spectrogram" (1, L): collate pads it like any other; utils.audio.gpu_front_end
             # turns the batch into log-spectrograms on the device
             return torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))[None, :]
-        return torch.from_numpy(log_spectrogram(y, self.sample_rate, self.window_size, self.window_stride, self.normalize))
+        return torch.from_numpy(log_spectrogram(y, self.sample_rate, self.window_size, self.window_stride, self.normalize,
+                                                window=self.window))
 
 
 class SpectrogramDataset(Dataset, SpectrogramParser):
@@ -56,6 +92,8 @@ class SpectrogramDataset(Dataset, SpectrogramParser):
         spect = self.parse_audio(audio_path)
         if not getattr(constant.args, "gpu_frontend", False):
             spect = spect[:, :constant.args.src_max_len]
+        if self.augmenting:
+            return spect, self.parse_transcript(transcript_path), self.draw(spect.size(1))
         return spect, self.parse_transcript(transcript_path)
 
     def parse_transcript(self, transcript_path):
@@ -68,9 +106,12 @@ class SpectrogramDataset(Dataset, SpectrogramParser):
 
 
 def _collate_fn(batch):
-    batch = sorted(batch, key=lambda s: s[0].size(1), reverse=True)
+    aug = len(batch[0]) > 2
+    size = (lambda s: s[2][6]) if aug else (lambda s: s[0].size(1))      # augmented: samples after the tempo change
+    batch = sorted(batch, key=size, reverse=True)
     B = len(batch)
-    t_max = batch[0][0].size(1)
+    t_max = max(s[0].size(1) for s in batch)
+    n_max = size(batch[0])
     f_bins = batch[0][0].size(0)
     l_max = max(len(s[1]) for s in batch)
     inputs = torch.zeros(B, 1, f_bins, t_max)
@@ -78,13 +119,17 @@ def _collate_fn(batch):
     input_sizes = torch.zeros(B, dtype=torch.int32)
     target_sizes = torch.zeros(B, dtype=torch.int32)
     input_percentages = torch.zeros(B, dtype=torch.float32)
-    for i, (spec, tgt) in enumerate(batch):
+    for i, s in enumerate(batch):
+        spec, tgt = s[0], s[1]
         t = spec.size(1)
         inputs[i, 0, :, :t] = spec
-        input_sizes[i] = t
-        input_percentages[i] = t / float(t_max)
+        input_sizes[i] = size(s)
+        input_percentages[i] = size(s) / float(n_max)
         target_sizes[i] = len(tgt)
         targets[i, :len(tgt)] = torch.tensor(tgt, dtype=torch.int64)
+    if aug:
+        draws = torch.tensor([s[2][:6] for s in batch], dtype=torch.float64)
+        return inputs, targets, input_percentages, input_sizes, target_sizes, draws
     return inputs, targets, input_percentages, input_sizes, target_sizes
 
 

@@ -528,6 +528,19 @@ int asr_stft_frames(const float* wav, int64_t wav_stride, const int32_t* lengths
 int asr_spect_finish(const float* reim, int64_t ld, const int32_t* lengths, float* spect, float* sums, float* sqdev, int B,
                      int F, int Tmax, int hop, int normalize, asr_stream_t stream);
 
+/* ---- tempo / gain perturbation and noise injection of the training waveforms (replaces the reference's sox subprocesses:
+ * load_randomly_augmented_audio / augment_audio_with_sox, utils/audio.py:35-61, and NoiseInjection.inject_noise, utils/data_loader.py
+ * :60-70,145-179; definition in DESIGN.md section 7).  One workgroup per utterance b: wav (B, wav_stride) fp32, lens (B) samples;
+ * params (B, 8) fp64 = {tempo (<= 0: pass the waveform through, no tempo / gain), m = float32(10^(gain/20)), noise clip index (< 0:
+ * none), crop start sample, noise level, n_out, 0, 0}.  Tempo: WSOLA with segment S, search window `search`, overlap O (sox's tempo
+ * defaults: 1312 / 235 / 192 at 16 kHz), then y = clamp(rint(w m 32768), -32768, 32767) / 32768.  Noise: y += level n E_y / E_n over
+ * n_out samples of clip `index` of the int16 bank (clip c = bank[bank_off[c] .. + bank_len[c]), read cyclically from the start
+ * sample), E = RMS in fp64, skipped when E_n == 0.  out (B, out_stride) fp32: samples [0, n_out) written (out_stride >= n_out).
+ * offsets: NULL or (B, off_stride) int32, the chosen offset of every WSOLA segment (segment 0: search / 2).                  */
+int asr_augment_wave(const float* wav, int64_t wav_stride, const int32_t* lens, const double* params, const int16_t* bank,
+                     const int64_t* bank_off, const int64_t* bank_len, int nclips, float* out, int64_t out_stride, int32_t* offsets,
+                     int64_t off_stride, int B, int S, int search, int O, asr_stream_t stream);
+
 /* ---- LSTM language model for beam-search rescoring (reference: utils/lstm_utils.py LM.evaluate, RNNModel.forward; nn.LSTM gate
  * order i, f, g, o).  fp32 storage and f32-input MFMA (v_mfma_f32_16x16x4_f32) whatever the ASR model's precision.
  * Contraction operands: rows 16-byte aligned, leading dimensions multiples of 4 floats, and the K columns zero-padded to a multiple
