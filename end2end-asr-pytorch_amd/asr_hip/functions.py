@@ -103,8 +103,8 @@ def _linear_bwd(dy2d, x2d, wparam, bparam, dx_out=None, accumulate=False, need_d
 
 
 # The output projection's data gradient IS the attention backward's dO: its epilogue also writes delta = rowsum(dO * O) per head
-# (asr_gemm_nn_rowdot), one dependent launch less per attention block (tuning NN_ROWDOT = 0 in the library = asr_attn_bwd computes delta
-# itself: the arm tests/test_gpu_ops.py holds the epilogue against).
+# (asr_gemm_nn_rowdot), one dependent launch less per attention block (where the library refuses the shape, asr_attn_bwd computes delta
+# itself: the form tests/test_gpu_ops.py holds the epilogue against).
 
 
 def _out_proj_bwd(dy2d, o2d, o32, wparam, bparam, Tq, dk):

@@ -166,24 +166,22 @@ def load():
     return lib
 
 
-# A/B switches of the library.  The library itself reads no environment variables: the ASR_<NAME>
-# variables present when the library is loaded are forwarded ONCE through asr_set_tuning(); set_tuning() changes them later.
-TUNING_NAMES = ("ATTN_GENERIC", "IGEMM_TH", "IGEMM_TPS", "IGEMM_WBUF", "CONV1_WGRAD_MFMA", "IGEMM_ABLATE", "C64", "CONV_POOL",
-                "WGRAD_ABLATE", "WGRAD_DMA", "CONV1_WGRAD_WGS", "C64_PER_CU", "C64_ABLATE", "C64_SHAPE", "GEMM_NS", "GEMM_TILE",
-                "GEMM_GENERIC", "TN_WGS", "TN_128", "TN_128_MIN", "TN_128_RM", "TN_NBUF", "NN_BIG", "NN_RING", "TN_GROUP_SLICE_MIN", "GEMM_BIG_MIN", "NT_RING", "TN_PIPE", "TN_PIPE_MIN", "GEMM_ABLATE", "ATTN_SHORT", "ATTN_SHORT_BWD", "ATTN_BOTH", "NNTN_STAGES",
-                "ATTN_PP", "ATTN_PP_MIN", "ATTN_PP_TAIL", "ATTN_PP_PRIO", "ATTN_PP_STAGGER", "ATTN_PP_STAGGER_SEL", "TN_GROUP_TILE", "TN_GROUP_MROWS",
-                "TN_GROUP_WGS", "WGRAD_XCD", "IGEMM_XCD", "C64_SPLIT", "GEMM_BIG", "GEMM_BIG_NS", "GEMM_BIG_NN", "L0_WSPLIT", "WS128", "WS64", "WS64_PER_CU", "WS_PAIR", "WS_BITS", "NN_ROWDOT", "ATTN_BWD_FUSED")
+# Switches of the library (the list of kTuningNames in csrc/prof.hip): test hooks, each forcing a path the dispatch
+# takes at other shapes.  The library reads no environment: ASR_<NAME> is forwarded ONCE at load, set_tuning() changes it later.
+TUNING_NAMES = ("GEMM_TILE", "GEMM_BIG", "GEMM_BIG_NS", "GEMM_BIG_NN", "NT_RING", "NN_RING", "TN_GROUP_TILE", "ATTN_BWD_FUSED",
+                "WS64", "WS128", "WS_PAIR", "L0_WSPLIT", "C64_SHAPE")
+ABLATE_NAMES = ("GEMM_ABLATE", "IGEMM_ABLATE", "C64_ABLATE", "WGRAD_ABLATE")     # -DASR_TUNE_ABLATE builds only: others refuse them, loudly
 
 
 def _forward_env_tuning(lib):
-    for name in TUNING_NAMES:
+    for name in TUNING_NAMES + ABLATE_NAMES:
         v = os.environ.get("ASR_" + name)
         if v is None:
             continue
         try:
             iv = int(v)
         except ValueError:
-            iv = 1                      # presence switches (ASR_ATTN_GENERIC=yes)
+            iv = 1                      # presence switches (ASR_WS64=yes)
         rc = lib.asr_set_tuning(name.encode(), iv)
         if rc != 0:
             raise RuntimeError("asr_set_tuning(%s) refused" % name)

@@ -1092,15 +1092,16 @@ __global__ __launch_bounds__(256) void attn_delta_bf16_d64_kernel(AttnArgs p) {
 bool fast_ok(const AttnArgs& p, int d, int dtype) {
   if (p.q_st >= (1 << 22) || p.k_st >= (1 << 22) || p.v_st >= (1 << 22) || p.o_st >= (1 << 22)) return false;   // 32-bit in-tile byte offsets
   if (p.key_pad && (int64_t)(p.B - 1) * p.m_sb + (int64_t)(p.Tq - 1) * p.m_sq + p.Tk >= ((int64_t)1 << 31)) return false;   // 32-bit mask offsets
-  return dtype == ASR_BF16 && d == HD && p.vec && p.Tq > 0 && p.Tk > 0 && asr_tuning("ATTN_GENERIC", 0) == 0;
+  return dtype == ASR_BF16 && d == HD && p.vec && p.Tq > 0 && p.Tk > 0;
 }
 
 }  // namespace
 
 int attn_fast_fwd(const AttnArgs& p, int d, int dtype, hipStream_t s) {
   if (!fast_ok(p, d, dtype) || (((uintptr_t)p.Out) & 7) != 0 || p.o_st % 4 != 0 || p.o_sb % 4 != 0) return ASR_EUNSUPPORTED;
-  if (!p.causal && p.Tk >= asr_tuning("ATTN_PP_MIN", 384) && asr_tuning("ATTN_PP", 1) != 0 && attn_pp_fwd(p, s) == ASR_OK) return ASR_OK;
-  if (p.Tq <= asr_tuning("ATTN_SHORT", 256)) {
+  constexpr int kPpMinKeys = 384, kShortQueries = 256;      // long-sequence kernel (attention_pp.hip) from this many keys; 64-query blocks up to this many queries
+  if (!p.causal && p.Tk >= kPpMinKeys && attn_pp_fwd(p, s) == ASR_OK) return ASR_OK;
+  if (p.Tq <= kShortQueries) {
     const dim3 grid((unsigned)(((p.Tq + 63) / 64) * p.B * p.H));
     if (p.thr) attn_fwd_bf16_d64_kernel<1, true><<<grid, dim3(256), 0, s>>>(p);
     else attn_fwd_bf16_d64_kernel<1, false><<<grid, dim3(256), 0, s>>>(p);
@@ -1136,29 +1137,19 @@ int attn_fast_bwd(const AttnArgs& p, int d, int dtype, hipStream_t s) {
     ASR_LAUNCH_CHECK();
     return ASR_OK;
   }
-  if ((p.parts & ASR_ATTN_DQ) && (p.parts & ASR_ATTN_DKV) && asr_tuning("ATTN_BOTH", 1) != 0) {
-    const bool short_q = p.Tq <= asr_tuning("ATTN_SHORT_BWD", 1 << 30), short_k = p.Tk <= asr_tuning("ATTN_SHORT_BWD", 1 << 30);
-    if (short_q == short_k) {
-      const int rows = short_q ? 64 : FQ;
-      const int n_dq = ((p.Tq + rows - 1) / rows) * p.B * p.H, n_dkv = ((p.Tk + rows - 1) / rows) * p.B * p.H;
-      if (short_q) attn_bwd_both_bf16_d64_kernel<1><<<dim3((unsigned)(n_dq + n_dkv)), dim3(256), 0, s>>>(p, n_dq);
-      else attn_bwd_both_bf16_d64_kernel<2><<<dim3((unsigned)(n_dq + n_dkv)), dim3(256), 0, s>>>(p, n_dq);
-      ASR_LAUNCH_CHECK();
-      return ASR_OK;
-    }
+  // 64-row blocks at every length (the 128-row instantiations of these three kernels sat behind a length threshold whose setting was "never")
+  if ((p.parts & ASR_ATTN_DQ) && (p.parts & ASR_ATTN_DKV)) {
+    const int n_dq = ((p.Tq + 63) / 64) * p.B * p.H, n_dkv = ((p.Tk + 63) / 64) * p.B * p.H;
+    attn_bwd_both_bf16_d64_kernel<1><<<dim3((unsigned)(n_dq + n_dkv)), dim3(256), 0, s>>>(p, n_dq);
+    ASR_LAUNCH_CHECK();
+    return ASR_OK;
   }
   if (p.parts & ASR_ATTN_DQ) {
-    if (p.Tq <= asr_tuning("ATTN_SHORT_BWD", 1 << 30))
-      attn_bwd_dq_bf16_d64_kernel<1><<<dim3((unsigned)(((p.Tq + 63) / 64) * p.B * p.H)), dim3(256), 0, s>>>(p);
-    else
-      attn_bwd_dq_bf16_d64_kernel<2><<<dim3((unsigned)(((p.Tq + FQ - 1) / FQ) * p.B * p.H)), dim3(256), 0, s>>>(p);
+    attn_bwd_dq_bf16_d64_kernel<1><<<dim3((unsigned)(((p.Tq + 63) / 64) * p.B * p.H)), dim3(256), 0, s>>>(p);
     ASR_LAUNCH_CHECK();
   }
   if (p.parts & ASR_ATTN_DKV) {
-    if (p.Tk <= asr_tuning("ATTN_SHORT_BWD", 1 << 30))
-      attn_bwd_dkv_bf16_d64_kernel<1><<<dim3((unsigned)(((p.Tk + 63) / 64) * p.B * p.H)), dim3(256), 0, s>>>(p);
-    else
-      attn_bwd_dkv_bf16_d64_kernel<2><<<dim3((unsigned)(((p.Tk + FQ - 1) / FQ) * p.B * p.H)), dim3(256), 0, s>>>(p);
+    attn_bwd_dkv_bf16_d64_kernel<1><<<dim3((unsigned)(((p.Tk + 63) / 64) * p.B * p.H)), dim3(256), 0, s>>>(p);
     ASR_LAUNCH_CHECK();
   }
   return ASR_OK;

@@ -496,14 +496,12 @@ int attn_pp_fwd(const AttnArgs& p, hipStream_t s) {
   constexpr int nw = 4;
   const int n_full = p.Tq / (32 * nw);
   const int rest = p.Tq - n_full * 32 * nw;
-  int n_tail = (rest + 31) / 32;
-  int nf = n_full;
-  if (asr_tuning("ATTN_PP_TAIL", 1) == 0 && rest > 0) { nf = n_full + 1; n_tail = 0; }      // A/B: leftover queries as one more (partly idle) chunk
+  const int n_tail = (rest + 31) / 32, nf = n_full;      // leftover queries: one-wave blocks of 32 (one more, partly idle, chunk lost the A/B)
   const dim3 grid((unsigned)((nf + n_tail) * BH));
   // measured (profiles/r03_attention_pp_stagger_pipe_ab.txt): any delay of 4 .. 12 x 64 cycles on block-id bit 3 takes the north-star
   // shape from 71.8 to 65.8 us at p = 0 and changes nothing elsewhere
-  const int prio = (int)asr_tuning("ATTN_PP_PRIO", 0) | ((int)asr_tuning("ATTN_PP_STAGGER", 8) << 8) |
-                   ((int)asr_tuning("ATTN_PP_STAGGER_SEL", 1) << 16);
+  constexpr int kPrio = 0, kStagger = 8, kStaggerSel = 1;
+  constexpr int prio = kPrio | (kStagger << 8) | (kStaggerSel << 16);
   if (p.thr) attn_fwd_pp_bf16_d64_kernel<true, nw><<<grid, dim3(64 * nw), 0, s>>>(p, nf, n_tail, prio);
   else attn_fwd_pp_bf16_d64_kernel<false, nw><<<grid, dim3(64 * nw), 0, s>>>(p, nf, n_tail, prio);
   ASR_LAUNCH_CHECK();

@@ -261,7 +261,7 @@ __device__ const uint4 conv_zero_page = {0u, 0u, 0u, 0u};      // source of halo
 struct ConvArgs {
   const void* x; const void* wk; const float* bias; const void* mask_src; void* y;
   void* pool; uint8_t* code;    // PT kernels: (B, W/2, Cout, H/2) pooled output + its selection bytes instead of y
-  int xcd_order;                // consecutive tiles on one XCD (tuning IGEMM_XCD, default 1)
+  int xcd_order;                // consecutive tiles on one XCD (always 1: the other order lost its A/B)
   int B, H, W, Cin, Cout, relu, tiles_h, tiles_w;
   int ablate;   // tuning only (ASR_IGEMM_ABLATE in -DASR_TUNE_ABLATE builds): 1 = no patch loads, 2 = no weight loads, 4 = no stores, 8 = no MFMAs
 };
@@ -1173,7 +1173,7 @@ int launch_igemm_t(const ConvArgs& a, hipStream_t s) {
   ConvArgs p = a;
   p.tiles_h = (p.H + TH - 1) / TH;
   p.tiles_w = (p.W + 15) / 16;
-  p.xcd_order = asr_tuning("IGEMM_XCD", 1) != 0;
+  p.xcd_order = 1;
   size_t lds = (size_t)((TH + 2) * 18 + WBUF * TPS * NCO) * (64 * sizeof(T));      // (>= the 24 KB the pooled epilogue stages)
   allow_big_lds(conv3x3_igemm_kernel<T, NCO, TH, TPS, WBUF, PT>, lds);
   hipLaunchKernelGGL((conv3x3_igemm_kernel<T, NCO, TH, TPS, WBUF, PT>), dim3((unsigned)(p.B * p.tiles_h * p.tiles_w)), dim3(256), lds, s, p);
@@ -1183,27 +1183,13 @@ int launch_igemm_t(const ConvArgs& a, hipStream_t s) {
 // Tile height: 16 rows in bf16 (wave tile 4 x 4 / 4 x 8 fragments: 2 / 2.7 MFMAs per LDS operand read), 8 rows in fp32 (LDS).
 // History of this choice: with register-staged patches and double-buffered weights the 16-row tile LOST to the 8-row one (a
 // workgroup per CU less); once the patch came in by LDS-DMA, the weights were single buffered and the mask loads of the epilogue
-// hoisted, it wins on every layer (profiles/r01_microbench_v7.txt; ASR_IGEMM_TH=8 restores the small tile).
-// ASR_IGEMM_TPS=2 stages TWO taps per step at Cout 64 with the 8-row tile -- measured slower.
+// hoisted, it wins on every layer (profiles/r01_microbench_v7.txt).  Two taps per step at Cout 64 with the 8-row tile measured slower.
 // Weights are SINGLE buffered in LDS (prefetched in registers): one more barrier per step, but one more workgroup per CU --
-// +9 % (Cout 64) to +23 % (Cout 128) measured; ASR_IGEMM_WBUF=2 restores the double buffer.
+// +9 % (Cout 64) to +23 % (Cout 128) measured.  At the 16-row tile two weight buffers or two taps per step still leave two workgroups
+// per CU (74 KB each) -- and change nothing: 307 - 313 us on the 128 -> 128 layer whichever way (profiles/r03_igemm_variants_ab.txt).
 template <typename T, int NCO>
 int launch_igemm(const ConvArgs& a, hipStream_t s) {
-  const int th = (int)asr_tuning("IGEMM_TH", 16);
-  const int tps = (int)asr_tuning("IGEMM_TPS", 1);
-  const int wbuf = (int)asr_tuning("IGEMM_WBUF", 1);
-  if constexpr (sizeof(T) == 2) {
-    if (th == 16) {
-      // (A/B, round 3: profiles/r03_igemm_variants_ab.txt) at the 16-row tile two weight buffers or two taps per step still leave two
-      // workgroups per CU (74 KB each) -- and change nothing: 307 - 313 us on the 128 -> 128 layer whichever way
-      if (wbuf == 2 && tps == 1) return launch_igemm_t<T, NCO, 16, 1, 2>(a, s);
-      if (tps == 2) return launch_igemm_t<T, NCO, 16, 2, 1>(a, s);
-      return launch_igemm_t<T, NCO, 16, 1, 1>(a, s);
-    }
-  }
-  if (sizeof(T) == 2 && NCO == 64 && tps == 2) return launch_igemm_t<T, NCO, 8, 2, 2>(a, s);
-  if (wbuf == 1) return launch_igemm_t<T, NCO, 8, 1, 1>(a, s);
-  return launch_igemm_t<T, NCO, 8, 1, 2>(a, s);
+  return launch_igemm_t<T, NCO, sizeof(T) == 2 ? 16 : 8, 1, 1>(a, s);
 }
 
 inline unsigned stream_grid(int64_t total_threads) {
@@ -1251,8 +1237,7 @@ extern "C" int asr_conv1_wgrad(const float* x, const void* dy, float* dw, float*
   const size_t lds = (size_t)C0 * 10 * sizeof(float);
   AsrProfScope prof(ASR_OP_CONV1, s);
   // bf16 storage, 64 channels: matrix-core kernel with the pixel as contraction index (conv1_wgrad_mfma.hip)
-  const bool mfma = asr_tuning("CONV1_WGRAD_MFMA", 1) != 0;
-  if (mfma && dtype == ASR_BF16 && C0 == 64) return asr_conv1_wgrad_mfma_launch(x, (const bf16_t*)dy, dw, db, B, H, W, s);
+  if (dtype == ASR_BF16 && C0 == 64) return asr_conv1_wgrad_mfma_launch(x, (const bf16_t*)dy, dw, db, B, H, W, s);
   if (dtype == ASR_F32) hipLaunchKernelGGL((conv1_wgrad_kernel<float>), dim3((unsigned)blocks), dim3(256), lds, s, x, (const float*)dy, dw, db, B, H, W, C0);
   else hipLaunchKernelGGL((conv1_wgrad_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), lds, s, x, (const bf16_t*)dy, dw, db, B, H, W, C0);
   ASR_LAUNCH_CHECK();
@@ -1300,11 +1285,15 @@ extern "C" int asr_conv3x3_igemm(const void* x, const void* wk, const float* bia
   ConvArgs p{};
   p.x = x; p.wk = wk; p.bias = bias; p.mask_src = mask_src; p.y = y;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
-  p.ablate = (int)asr_tuning("IGEMM_ABLATE", 0);
+#ifdef ASR_TUNE_ABLATE
+  p.ablate = (int)asr_tuning("IGEMM_ABLATE", 0);      // timing builds: the generic kernel with parts of its work left out
+  const bool ablate = p.ablate != 0;
+#else
+  constexpr bool ablate = false;
+#endif
   AsrProfScope prof(ASR_OP_CONV_IGEMM, s);
   // the 64 -> 64 channel bf16 layer (full-resolution conv2 and its dgrad) has a persistent kernel with register-resident weights
-  const bool c64 = asr_tuning("C64", 1) != 0;
-  if (c64 && dtype == ASR_BF16 && Cin == 64 && Cout == 64 && (int64_t)B * H * W * 128 < ((int64_t)1 << 32) && !p.ablate) {
+  if (dtype == ASR_BF16 && Cin == 64 && Cout == 64 && (int64_t)B * H * W * 128 < ((int64_t)1 << 32) && !ablate) {
     C64Args a{};
     a.x = static_cast<const bf16_t*>(x); a.wk = static_cast<const bf16_t*>(wk); a.bias = bias;
     a.mask = static_cast<const bf16_t*>(mask_src); a.y = static_cast<bf16_t*>(y);
@@ -1314,7 +1303,7 @@ extern "C" int asr_conv3x3_igemm(const void* x, const void* wk, const float* bia
   // 64 -> 128 channels without a mask (conv.5 forward) in ONE pass: the weight-stationary kernel of conv_ws.hip with 64 input channels
   // (a wave keeps 32 of the 128 output channels x 9 x 64 in 144 registers, two workgroups per CU, 4-row tiles; round 5).  WS64 = 0
   // (tuning): the two-pass form below
-  if (dtype == ASR_BF16 && Cin == 64 && Cout == 128 && !mask_src && !p.ablate && asr_tuning("WS64", 1) != 0) {
+  if (dtype == ASR_BF16 && Cin == 64 && Cout == 128 && !mask_src && !ablate && asr_tuning("WS64", 1) != 0) {
     WsArgs a{};
     a.x = static_cast<const bf16_t*>(x); a.wk = static_cast<const bf16_t*>(wk); a.bias = bias; a.y = static_cast<bf16_t*>(y);
     a.B = B; a.H = H; a.W = W; a.Cin = 64; a.Cout = Cout; a.relu = relu;
@@ -1322,9 +1311,8 @@ extern "C" int asr_conv3x3_igemm(const void* x, const void* wk, const float* bia
     if (rc != ASR_EUNSUPPORTED) return rc;
   }
   // 64 -> 128 channels without a mask (conv.5 forward): the same kernel once per half of the output channels -- each half's 72 KB of
-  // weights sits in registers, the 64-channel input is read twice (the second time from L2 / MALL); 0 = the generic implicit GEMM
-  if (c64 && dtype == ASR_BF16 && Cin == 64 && Cout == 128 && !mask_src && (int64_t)B * H * W * 256 < ((int64_t)1 << 32) && !p.ablate &&
-      asr_tuning("C64_SPLIT", 1) != 0) {
+  // weights sits in registers, the 64-channel input is read twice (the second time from L2 / MALL)
+  if (dtype == ASR_BF16 && Cin == 64 && Cout == 128 && !mask_src && (int64_t)B * H * W * 256 < ((int64_t)1 << 32) && !ablate) {
     for (int half = 0; half < 2; ++half) {
       C64Args a{};
       a.x = static_cast<const bf16_t*>(x); a.wk = static_cast<const bf16_t*>(wk) + (size_t)half * 64 * 9 * 64;
@@ -1338,7 +1326,7 @@ extern "C" int asr_conv3x3_igemm(const void* x, const void* wk, const float* bia
   }
   // 128 input channels in bf16 (conv.7's data gradient with conv.5's ReLU mask, conv.5's data gradient): the persistent
   // weight-stationary kernel of conv_ws.hip; WS128 = 0 (tuning) or a shape outside its domain -> the generic implicit GEMM
-  if (dtype == ASR_BF16 && Cin == 128 && !p.ablate && asr_tuning("WS128", 1) != 0) {
+  if (dtype == ASR_BF16 && Cin == 128 && !ablate && asr_tuning("WS128", 1) != 0) {
     WsArgs a{};
     a.x = static_cast<const bf16_t*>(x); a.wk = static_cast<const bf16_t*>(wk); a.bias = bias;
     a.mask = static_cast<const bf16_t*>(mask_src); a.y = static_cast<bf16_t*>(y);
@@ -1364,7 +1352,6 @@ extern "C" int asr_conv3x3_igemm_bits(const void* x, const void* wk, const float
   if (dtype != ASR_BF16 || !aligned16(x) || !aligned16(wk) || !aligned16(y) || ((uintptr_t)bits_in & 3) || ((uintptr_t)bits_out & 3))
     return ASR_EUNSUPPORTED;
   if (bits_in ? (Cin != 128 || Cout != 128) : (Cin != 64 || Cout != 128 || !relu)) return ASR_EUNSUPPORTED;
-  if (asr_tuning("WS_BITS", 1) == 0) return ASR_EUNSUPPORTED;
   if (B == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_CONV_IGEMM, s);
   WsArgs a{};
@@ -1382,8 +1369,6 @@ extern "C" int asr_conv3x3_relu_pool(const void* x, const void* wk, const float*
   if (dtype != ASR_BF16 || Cin != 64 || Cout != 64 || !aligned16(x) || !aligned16(wk) || !aligned16(y) || !aligned16(pool) ||
       (int64_t)B * H * W * 128 >= ((int64_t)1 << 32))
     return ASR_EUNSUPPORTED;
-  const bool fused = asr_tuning("CONV_POOL", 1) != 0;
-  if (!fused) return ASR_EUNSUPPORTED;
   if (B == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_CONV_IGEMM, s);
   C64Args a{};
@@ -1401,7 +1386,7 @@ extern "C" int asr_conv3x3_relu_pool_code(const void* x, const void* wk, const f
   ASR_CHECK_ARG(x && wk && pool && code && B >= 0 && H > 0 && W > 0);
   ASR_CHECK_ARG(dtype == ASR_F32 || dtype == ASR_BF16);
   if (dtype != ASR_BF16 || Cin != 64 || Cout != 64 || !aligned16(x) || !aligned16(wk) || (y_or_null && !aligned16(y_or_null)) || !aligned16(pool) ||
-      (((uintptr_t)code) & 7) != 0 || (int64_t)B * H * W * 128 >= ((int64_t)1 << 32) || asr_tuning("CONV_POOL", 1) == 0)
+      (((uintptr_t)code) & 7) != 0 || (int64_t)B * H * W * 128 >= ((int64_t)1 << 32))
     return ASR_EUNSUPPORTED;
   if (B == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_CONV_IGEMM, s);
@@ -1422,7 +1407,7 @@ int conv3x3_relu_pool_tcf_code_impl(const void* x, const void* wk, const float* 
   ASR_CHECK_ARG(x && wk && pool && code && B >= 0 && H > 0 && W > 0);
   ASR_CHECK_ARG(dtype == ASR_F32 || dtype == ASR_BF16);
   if (dtype != ASR_BF16 || Cout != 128 || Cin % 64 != 0 || H % 8 != 0 || W % 16 != 0 || !aligned16(x) || !aligned16(wk) || !aligned16(pool) ||
-      (((uintptr_t)code) & 7) != 0 || asr_tuning("CONV_POOL", 1) == 0)
+      (((uintptr_t)code) & 7) != 0)
     return ASR_EUNSUPPORTED;
   if (B == 0) return ASR_OK;
   if (Cin == 128 && H % 8 == 0 && asr_tuning("WS128", 1) != 0) {        // conv.7 forward: persistent weight-stationary kernel (conv_ws.hip)
@@ -1435,7 +1420,7 @@ int conv3x3_relu_pool_tcf_code_impl(const void* x, const void* wk, const float* 
     if (rc != ASR_EUNSUPPORTED) return rc;
   }
   if (code_cl) return ASR_EUNSUPPORTED;        // channel-last selection bytes: the weight-stationary kernel only
-  if (H % 16 != 0 || asr_tuning("IGEMM_TH", 16) != 16) return ASR_EUNSUPPORTED;
+  if (H % 16 != 0) return ASR_EUNSUPPORTED;        // the pooled epilogue of the generic kernel: 16-row tiles
   ConvArgs p{};
   p.x = x; p.wk = wk; p.bias = bias; p.pool = pool; p.code = code;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
@@ -1636,8 +1621,9 @@ int conv3x3_wgrad_impl(const void* x, const void* dy, float* dw, float* db, floa
   p.tiles_h = (H + 7) / 8; p.tiles_w = (W + 15) / 16;
   p.npatch = B * p.tiles_h * p.tiles_w;
   p.nci = Cin / 64;
-  const int ablate = (int)asr_tuning("WGRAD_ABLATE", 0);
-  p.ablate = ablate;
+#ifdef ASR_TUNE_ABLATE
+  p.ablate = (int)asr_tuning("WGRAD_ABLATE", 0);
+#endif
   int wgx, blocks_y;
   asr_conv3x3_wgrad_grid(B, H, W, Cin, Cout, &wgx, &blocks_y, &p.patches_per_wg);
   p.ws = (workspace && workspace_floats >= (int64_t)wgx * blocks_y * 9 * 64 * 64 + (int64_t)wgx * Cout) ? workspace : nullptr;
@@ -1645,9 +1631,8 @@ int conv3x3_wgrad_impl(const void* x, const void* dy, float* dw, float* db, floa
   const size_t lds = (size_t)(180 + 128) * (64 * esz + 16);
   AsrProfScope prof(ASR_OP_CONV_WGRAD, s);
   // bf16 with a workspace: the LDS-DMA pipelined kernel (conv_wgrad_dma.hip); same grid, same partial-block layout
-  const bool dma = asr_tuning("WGRAD_DMA", 1) != 0;
   const int64_t cmax = Cin > Cout ? Cin : Cout;
-  if (dma && dtype == ASR_BF16 && p.ws && (int64_t)B * H * W * cmax * 2 < ((int64_t)1 << 32)) {
+  if (dtype == ASR_BF16 && p.ws && (int64_t)B * H * W * cmax * 2 < ((int64_t)1 << 32)) {
     WgdArgs q{};
     q.x = static_cast<const bf16_t*>(x); q.dy = static_cast<const bf16_t*>(dy); q.db = db; q.ws = p.ws;
     q.B = B; q.H = H; q.W = W; q.Cin = Cin; q.Cout = Cout; q.tiles_h = p.tiles_h; q.tiles_w = p.tiles_w;

@@ -5,7 +5,7 @@
 //   * persistent workgroups (default: TWO 4-wave workgroups per CU, which run out of phase so that one's address / epilogue work
 //     overlaps the other's MFMAs) walk tiles of 128 output pixels (8 x 16) x 64 co; wave (wm, wn) owns 4 pixel fragments x 2 co
 //     fragments and keeps its 32 co x 576 k weights in 144 VGPRs for the whole kernel: no weight traffic, no per-tap barrier
-//     (8-wave workgroups on 16 x 16 / 8 x 32 tiles remain as ASR_C64_SHAPE=1/2);
+//     (8-wave workgroups on 16 x 16 / 8 x 32 tiles remain behind the test hook C64_SHAPE = 1 / 2);
 //   * the halo patch of tile n+2 travels HBM -> LDS by the LDS-DMA into one of THREE patch buffers (two in the masked variant, where
 //     the mask stash needs the LDS) while tile n is contracted: one s_barrier per tile, the wait on the DMA counter sits after the
 //     MFMAs of a whole tile and is COUNTED (loads retire in order: "at most N outstanding" proves everything older has landed);
@@ -374,8 +374,7 @@ int launch_t(C64Args p, hipStream_t s) {
       return ASR_ELAUNCH;
     granted = true;
   }
-  const int pc = (int)asr_tuning("C64_PER_CU", 0);    // tuning: workgroups per CU (0 = what the occupancy query says)
-  const int64_t slots = (int64_t)cus * (pc > 0 ? pc : (per_cu > 0 ? per_cu : 1));
+  const int64_t slots = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
   const unsigned grid = (unsigned)(nt < slots ? nt : slots);
 #ifdef C64_TIMING
   static long long* dbg = nullptr;
@@ -406,8 +405,10 @@ int asr_conv3x3_c64_launch(const C64Args& a_, hipStream_t s) {
   C64Args a = a_;
   if (a.ypix == 0) a.ypix = 128;
   if (a.ypix != 128 && (a.mask || a.pool)) return ASR_EUNSUPPORTED;
+#ifdef ASR_TUNE_ABLATE
   a.ablate = (int)asr_tuning("C64_ABLATE", 0);
-  // shape (ASR_C64_SHAPE, tuning): 0 = two 4-wave workgroups per CU on 8 x 16 pixel tiles (default: the two workgroups are not in
+#endif
+  // shape (C64_SHAPE, test hook): 0 = two 4-wave workgroups per CU on 8 x 16 pixel tiles (default: the two workgroups are not in
   // phase, so one's address / epilogue VALU work overlaps the other's MFMAs); 1 / 2 = one 8-wave workgroup on 16 x 16 / 8 x 32 tiles
   const int shape = (int)asr_tuning("C64_SHAPE", 0);
   if (a.pool) {                      // pooled epilogue: forward with ReLU on the default shape only

@@ -244,7 +244,7 @@ int asr_conv3x3_wgrad_dma_launch(const WgdArgs& p, unsigned wgx, unsigned blocks
     granted = true;
   }
   WgdArgs q = p;
-  q.wgx = (int)wgx; q.blocks_y = (int)blocks_y; q.xcd_order = asr_tuning("WGRAD_XCD", 1) != 0;
+  q.wgx = (int)wgx; q.blocks_y = (int)blocks_y; q.xcd_order = 1;
   hipLaunchKernelGGL(conv3x3_wgrad_dma_kernel, dim3(wgx * blocks_y), dim3(256), lds, s, q);
   ASR_LAUNCH_CHECK();
   return ASR_OK;

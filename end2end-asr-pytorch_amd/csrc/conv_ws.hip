@@ -470,8 +470,8 @@ int ws_launch_t(WsArgs p, hipStream_t s) {
       return ASR_EUNSUPPORTED;
     granted = true;
   }
-  const int per_cu = CI == 64 ? (int)asr_tuning("WS64_PER_CU", 2) : 1;
-  const int64_t slots = (int64_t)cus * (per_cu > 0 ? per_cu : 1);         // 64 input channels: 144 registers of weights per wave, two workgroups per CU
+  constexpr int per_cu = CI == 64 ? 2 : 1;
+  const int64_t slots = (int64_t)cus * per_cu;         // 64 input channels: 144 registers of weights per wave, two workgroups per CU
   const int64_t items = EP == 2 ? nt / 2 : nt;
   const unsigned grid = (unsigned)(items < slots ? items : slots);
   hipLaunchKernelGGL((conv3x3_ws128_kernel<CI, TH, CO, MK, EP, TM>), dim3(grid), dim3(256), lds, s, p);

@@ -185,7 +185,7 @@ __device__ __forceinline__ void stage_glds(unsigned char* lds_stage, const unsig
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// NS LDS stages (default ONE; 2 / 3 / 4 via ASR_GEMM_NS), NS-1 K steps of LDS-DMA in flight.  A deeper pipeline needs counted
+// NS LDS stages (ONE, or the three-stage ring of launch_fast on bf16 64 x 64 tiles), NS-1 K steps of LDS-DMA in flight.  A deeper pipeline needs counted
 // s_waitcnt vmcnt(N), a RAW s_barrier (__syncthreads() carries a fence that drains every pending LDS-DMA write) and operand
 // reads the compiler cannot see (see the asm block below).  Measured (profiles/r01_microbench_v4.txt, MI355X): with all of that
 // in place, MORE stages are SLOWER on every shape of this model -- 6400x2048x512: 33.0 / 39.6 / 44 / 55 us for 1 / 2 / 3 / 4
@@ -444,12 +444,10 @@ int launch_fast(const GemmArgs& a, int splits, hipStream_t s) {
   // LDS stages: ONE wherever several workgroups share a CU (they cover each other's load latency: the measurement in front of
   // gemm_glds_kernel); a launch of at most NT_RING 64 x 64 blocks leaves a CU with one workgroup or two, and there the private
   // three-stage ring wins (the decoder's 3200 x 512 projections over K = 2048: 32 -> ~14 us; profiles/r03_gemm_nn_ring_ab.txt)
-  const int64_t blocks = ceil_div64(a.M, BM) * ceil_div64(a.N, BN) * splits;
-  const bool ring = BM == 64 && BN == 64 && sizeof(T) == 2 && a.K >= 256 && blocks <= asr_tuning("NT_RING", 512);
-  const int ns = (int)asr_tuning("GEMM_NS", ring ? 3 : 1);
-  if (ns == 2) return launch_fast_ns<T, TO, BM, BN, 2>(a, splits, s);
-  if (ns == 3) return launch_fast_ns<T, TO, BM, BN, 3>(a, splits, s);
-  if (ns == 4) return launch_fast_ns<T, TO, BM, BN, 4>(a, splits, s);
+  if constexpr (BM == 64 && BN == 64 && sizeof(T) == 2) {
+    const int64_t blocks = ceil_div64(a.M, BM) * ceil_div64(a.N, BN) * splits;
+    if (a.K >= 256 && blocks <= asr_tuning("NT_RING", 512)) return launch_fast_ns<T, TO, BM, BN, 3>(a, splits, s);
+  }
   return launch_fast_ns<T, TO, BM, BN, 1>(a, splits, s);
 }
 
@@ -741,128 +739,17 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
 // Same contraction for the larger weight gradients.  The 64x64-tile kernel above moves 32 flop per byte through L2 (12 TB/s
 // on the 2048x512 FFN gradient): this one owns a 128 x 128 block of dW per workgroup (64 flop per byte), waves in a 2 x 2 grid
 // of 64 x 64 quadrants (each wave contracts EVERY row of a stage: no cross-wave reduction, the partial block goes from the
-// accumulators straight to the workspace / C), 64 rows of m per stage (one LDS stage of 32 KB).
+// accumulators straight to the workspace / C).  (Its single-stage form, 64 rows of m per stage with compiler-issued loads, lost
+// to the pipelined one below at every shape the dispatch sends here and is gone: profiles/r02_microbench_tn.txt.)
 struct Tn128Args {
   const void* A; const void* B; float* C; float* colsum; float* ws;
   int64_t lda, ldb, ldc;
   int M, N, K, m_per_split, tiles_k, ntiles;
 };
 
-__device__ __forceinline__ uint4 tn128_pack(const unsigned char* tile, int m0, int lr, int g, int c0) {
-  // 8 consecutive rows m0 + 8g .. +7 of column c0 + lr of a [64][128] bf16 tile (256-byte rows, chunk c of row r in slot
-  // c ^ (r & 7): the XOR permutes the low 3 bits of the 4-bit chunk index)
-  const int row = m0 + 8 * g + (lr >> 2), col = c0 + 4 * (lr & 3);
-  const int chunk = col >> 3, half = (col >> 2) & 1;
-  const uint2 lo = asr_lds_read_tr16(tile + row * 256 + ((chunk ^ (row & 7)) << 4) + half * 8);
-  const uint2 hi = asr_lds_read_tr16(tile + (row + 4) * 256 + ((chunk ^ ((row + 4) & 7)) << 4) + half * 8);
-  return make_uint4(lo.x, lo.y, hi.x, hi.y);
-}
-
-template <int RM>
-__global__ __launch_bounds__(256) void gemm_tn128_kernel(Tn128Args p) {
-  constexpr int ROWB = 256, TILEB = RM * ROWB;               // one operand tile of a stage: 16 KB (RM = 64) / 32 KB (128)
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wn = wave >> 1, wk = wave & 1;
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, qn = nwg >> 3, rn = nwg & 7;
-  const int wid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
-  const int split = wid / p.ntiles, tile = wid % p.ntiles;
-  const int n0 = (tile / p.tiles_k) * 128, k0 = (tile % p.tiles_k) * 128;
-  const int m_beg = split * p.m_per_split, m_end = min(p.M, m_beg + p.m_per_split);
-  const int nstage = (m_end - m_beg + RM - 1) / RM;
-  const unsigned char* A = static_cast<const unsigned char*>(p.A);
-  const unsigned char* B = static_cast<const unsigned char*>(p.B);
-  const int a_chunks = (int)(p.lda * 2 / 16), b_chunks = (int)((p.ldb >= p.K ? p.ldb : (int64_t)((p.K + 7) / 8 * 8)) * 2 / 16);
-
-  f32x4_t acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-  const bool do_colsum = p.colsum != nullptr && k0 == 0 && wk == 0;
-
-  for (int st = 0; st < nstage; ++st) {
-    if (st > 0) __syncthreads();                 // everybody is done reading the previous stage
-    const int64_t mrow = m_beg + (int64_t)st * RM;
-#pragma unroll
-    for (int i = 0; i < RM * 16 / 256; ++i) {
-      const int c = i * 256 + tid, row = c >> 4, slot = (c & 15) ^ (row & 7);
-      int ca = n0 * 2 / 16 + slot; ca = ca < a_chunks ? ca : a_chunks - 1;       // columns past N / K are never stored
-      int cb = k0 * 2 / 16 + slot; cb = cb < b_chunks ? cb : b_chunks - 1;
-      const int64_t gr = mrow + row < p.M ? mrow + row : (int64_t)p.M - 1;       // rows past M: see the zero fill below
-      unsigned char* d = smem + (i * 256 + wave * 64) * 16;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A + gr * p.lda * 2 + (int64_t)ca * 16),
-                                       (__attribute__((address_space(3))) void*)d, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(B + gr * p.ldb * 2 + (int64_t)cb * 16),
-                                       (__attribute__((address_space(3))) void*)(d + TILEB), 16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int valid = m_end - (m_beg + st * RM);
-    if (valid < RM) {                            // partial last stage: zero the A rows that do not exist (B holds finite data)
-      for (int c = valid * 16 + tid; c < RM * 16; c += 256) *reinterpret_cast<uint4*>(smem + c * 16) = make_uint4(0u, 0u, 0u, 0u);
-      __syncthreads();
-    }
-    const unsigned char* sA = smem;
-    const unsigned char* sB = smem + TILEB;
-#pragma unroll
-    for (int ms = 0; ms < RM / 32; ++ms) {
-      uint4 a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = tn128_pack(sA, ms * 32, lr, g, wn * 64 + i * 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = tn128_pack(sB, ms * 32, lr, g, wk * 64 + j * 16);
-      if (do_colsum) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          Chunk<bf16_t> c; c.v = a[i];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) bsum[i] += bf16_to_f32(c.e[e]);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mma16<bf16_t>(acc[i][j], a[i], b[j]);
-    }
-  }
-
-  // ---- the wave's 64 x 64 quadrant: lane (lr, g) holds rows 4g..4g+3 of column lr of every fragment
-  const bool single = gridDim.x == (unsigned)p.ntiles;
-  float* part = p.ws ? p.ws + ((int64_t)split * p.ntiles + tile) * 16384 : nullptr;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = wn * 64 + i * 16 + g * 4 + r, gn = n0 + row;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int col = wk * 64 + j * 16 + lr, gk = k0 + col;
-        const float v = acc[i][j][r];
-        if (!single && part) part[row * 128 + col] = v;
-        else if (gn < p.N && gk < p.K) {
-          float* dst = p.C + (int64_t)gn * p.ldc + gk;
-          if (single) *dst += v; else atomicAdd(dst, v);
-        }
-      }
-    }
-  if (do_colsum) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float v = bsum[i];
-      v += __shfl_xor(v, 16, 64);
-      v += __shfl_xor(v, 32, 64);
-      const int gn = n0 + wn * 64 + i * 16 + lr;
-      if (g == 0 && gn < p.N) atomicAdd(p.colsum + gn, v);
-    }
-  }
-}
-
-// ---- pipelined variant: the same 128 x 128 block and wave layout, but RM = 32 rows of m per stage in an NST-deep LDS ring filled
+// ---- pipelined: the 128 x 128 block and wave layout above, RM = 32 rows of m per stage in an NST-deep LDS ring filled
 // by HAND-ISSUED LDS-DMA (inline asm: the compiler must not know a DMA is in flight, or it drains the VMEM counter in front of
-// every transposing read it can see -- the reason the single-stage kernel above cannot overlap its loads), counted
+// every transposing read it can see -- the reason the removed single-stage 128 x 128 kernel could not overlap its loads), counted
 // s_waitcnt vmcnt, raw s_barrier.  One barrier per stage; the DMA of stage st + NST - 1 is issued right behind the barrier of
 // stage st (the ring slot it overwrites was read at stage st - 1, which every wave has left).  A partial last stage reads the
 // missing rows of A from a 16-byte zero page (the DMA cannot zero fill).  64 KB of LDS at NST = 4: two workgroups per CU.
@@ -1903,8 +1790,7 @@ extern "C" int asr_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ld
     if (asr_gemm_big_nt(q, stream)) return ASR_OK;
   }
   // fast path: LDS-DMA staging needs whole 16-B chunks everywhere and whole 128-byte K steps
-  const bool fast = p.vecA && p.vecB && K > 0 && (K % bk == 0) && (kps % bk == 0) &&
-                    asr_tuning("GEMM_GENERIC", 0) == 0;
+  const bool fast = p.vecA && p.vecB && K > 0 && (K % bk == 0) && (kps % bk == 0);
   if (fast) {
     if (in_dtype == ASR_F32) return dispatch_fast<float, float>(p, splits, stream);
     if (out_dtype == ASR_BF16) return dispatch_fast<bf16_t, bf16_t>(p, splits, stream);
@@ -1919,7 +1805,7 @@ namespace {
 // slices over m: explicit, or automatic.  With a workspace the split costs one extra pass over splits*N*K floats, so the grid is
 // filled to ~2 workgroups per CU; without one the slices meet in fp32 atomics and are kept to the measured optimum (<= 4).
 int tn_splits(int M, int N, int K, int splits, int dtype, bool have_ws) {
-  const int ASR_TN_TARGET_WGS = (int)asr_tuning("TN_WGS", 512);
+  constexpr int ASR_TN_TARGET_WGS = 512;
   const int rm = dtype == ASR_F32 ? 64 : 128;
   const int ntiles = ((N + 63) / 64) * ((K + 63) / 64);
   const int stages = (M + rm - 1) / rm;
@@ -1943,26 +1829,20 @@ int tn_splits(int M, int N, int K, int splits, int dtype, bool have_ws) {
 namespace {
 // 128 x 128-tile kernel: bf16, automatic split, a workspace, and enough 128-blocks that ~512 workgroups of >= 4 stages exist.
 // Returns the number of m-slices (0 = use the 64 x 64-tile kernel).
-// LDS stages of the pipelined 128 x 128 kernel for an output of `nt` blocks, 0 = use the single-stage kernels.  Measured
-// (tools/microbench.py tn, profiles/r02_microbench_tn.txt): from 64 blocks on (2048 x 512 and larger) the pipelined kernel wins
+// LDS stages of the pipelined 128 x 128 kernel, and the number of blocks from which it replaces the single-stage 64 x 64 kernel.  Measured
+// (profiles/r02_microbench_tn.txt): from 64 blocks on (2048 x 512 and larger) the pipelined kernel wins
 // (512 x 2048 over 6400 rows: 38.9 -> 33.8 us; 2048 x 512 over 12720 rows: 58.8 -> 47.6 us), below that its m-slices are too
 // short to fill the ring and the 64 x 64 kernel's 8 workgroups per CU win (512 x 512: 19 vs 30 us).  3 stages (48 KB, 3
 // workgroups per CU) tie or beat 4.
-int tn_pipe_stages(int nt) {
-  const int pipe = (int)asr_tuning("TN_PIPE", 3);
-  return (pipe > 0 && nt >= (int)asr_tuning("TN_PIPE_MIN", 64)) ? pipe : 0;
-}
+constexpr int kTnPipe = 3, kTnPipeMin = 64;
 
 int tn128_splits(int M, int N, int K, int splits, int dtype) {
-  const int enabled = (int)asr_tuning("TN_128", 1);
-  const int min_tiles = (int)asr_tuning("TN_128_MIN", 128);      // measured: wins for 512x5120 (160 blocks), loses for 64-block outputs
-  if (!enabled || dtype != ASR_BF16 || splits > 0 || N < 128 || K < 128) return 0;
+  if (dtype != ASR_BF16 || splits > 0 || N < 128 || K < 128) return 0;
   const int nt = ((N + 127) / 128) * ((K + 127) / 128);
-  const int pipe = tn_pipe_stages(nt);
-  if (!pipe && nt < min_tiles) return 0;
-  const int stages = pipe ? (M + 31) / 32 : (M + 63) / 64;
+  if (nt < kTnPipeMin) return 0;      // (the single-stage 128 x 128 kernel's own threshold was 128 blocks: above kTnPipeMin, so it never ran)
+  const int stages = (M + 31) / 32;
   int sp = (512 + nt / 2) / nt;
-  if (sp > (pipe ? 32 : 16)) sp = pipe ? 32 : 16;
+  if (sp > 32) sp = 32;
   while (sp > 1 && stages / sp < 4) --sp;
   if (sp < 1) sp = 1;
   const int sps = (stages + sp - 1) / sp;
@@ -1999,26 +1879,15 @@ extern "C" int asr_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ld
       q.lda = lda; q.ldb = ldb; q.ldc = ldc; q.M = M; q.N = N; q.K = K;
       q.tiles_k = (K + 127) / 128;
       q.ntiles = ((N + 127) / 128) * q.tiles_k;
-      const int pipe = tn_pipe_stages(q.ntiles);
-      const int stages = pipe ? (M + 31) / 32 : (M + 63) / 64;
-      q.m_per_split = ((stages + s128 - 1) / s128) * (pipe ? 32 : 64);
+      const int stages = (M + 31) / 32;
+      q.m_per_split = ((stages + s128 - 1) / s128) * 32;
       AsrProfScope prof(ASR_OP_GEMM, stream);
-      const int rm128 = (int)asr_tuning("TN_128_RM", 64);
-      if (pipe) {
-        static bool granted = false;
-        if (!granted) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn128p_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 16384);
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn128p_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 16384);
-          granted = true;
-        }
-        if (pipe == 3) hipLaunchKernelGGL(gemm_tn128p_kernel<3>, dim3((unsigned)(q.ntiles * s128)), dim3(256), 3 * 16384, stream, q);
-        else hipLaunchKernelGGL(gemm_tn128p_kernel<4>, dim3((unsigned)(q.ntiles * s128)), dim3(256), 4 * 16384, stream, q);
-      } else if (rm128 == 128) {
-        static bool granted = false;
-        if (!granted) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn128_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * 256); granted = true; }
-        hipLaunchKernelGGL(gemm_tn128_kernel<128>, dim3((unsigned)(q.ntiles * s128)), dim3(256), 2 * 128 * 256, stream, q);
-      } else
-      hipLaunchKernelGGL(gemm_tn128_kernel<64>, dim3((unsigned)(q.ntiles * s128)), dim3(256), 2 * 64 * 256, stream, q);
+      static bool granted = false;
+      if (!granted) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn128p_kernel<kTnPipe>), hipFuncAttributeMaxDynamicSharedMemorySize, kTnPipe * 16384);
+        granted = true;
+      }
+      hipLaunchKernelGGL(gemm_tn128p_kernel<kTnPipe>, dim3((unsigned)(q.ntiles * s128)), dim3(256), kTnPipe * 16384, stream, q);
       ASR_LAUNCH_CHECK();
       if (q.ws) {
         hipLaunchKernelGGL(tn128_reduce_kernel, dim3((unsigned)(q.ntiles * 16)), dim3(256), 0, stream, q.ws, C, ldc, N, K, q.ntiles,
@@ -2044,20 +1913,18 @@ extern "C" int asr_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ld
   const int sps = (stages + splits - 1) / splits;
   p.m_per_split = sps * rm;
   p.ws = (have_ws && splits > 1) ? workspace : nullptr;
-  const int nbuf = (int)asr_tuning("TN_NBUF", 1);       // LDS stages (tuning hook)
-  const size_t lds_stage = (size_t)(nbuf == 2 ? 2 : 1) * 2 * rm * (64 * esz);
+  const size_t lds_stage = (size_t)2 * rm * (64 * esz);        // one LDS stage
   const size_t lds_epi = (size_t)2 * 64 * 64 * 4 + 4 * 64 * sizeof(float);
   const size_t lds = lds_stage > lds_epi ? lds_stage : lds_epi;
   AsrProfScope prof(ASR_OP_GEMM, stream);
   const dim3 grid((unsigned)(p.ntiles * splits));
-#define ASR_TN_LAUNCH(T_, NB_)                                                                                                  \
+#define ASR_TN_LAUNCH(T_)                                                                                                       \
   {                                                                                                                              \
     static bool granted = false;                                                                                                 \
-    if (!granted) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel<T_, NB_>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); granted = true; } \
-    hipLaunchKernelGGL((gemm_tn_kernel<T_, NB_>), grid, dim3(256), lds, stream, p);                                              \
+    if (!granted) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel<T_, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); granted = true; } \
+    hipLaunchKernelGGL((gemm_tn_kernel<T_, 1>), grid, dim3(256), lds, stream, p);                                                \
   }
-  if (dtype == ASR_F32) { if (nbuf == 2) ASR_TN_LAUNCH(float, 2) else ASR_TN_LAUNCH(float, 1) }
-  else { if (nbuf == 2) ASR_TN_LAUNCH(bf16_t, 2) else ASR_TN_LAUNCH(bf16_t, 1) }
+  if (dtype == ASR_F32) ASR_TN_LAUNCH(float) else ASR_TN_LAUNCH(bf16_t)
 #undef ASR_TN_LAUNCH
   ASR_LAUNCH_CHECK();
   if (p.ws) {
@@ -2185,14 +2052,14 @@ extern "C" int asr_gemm_tn_grouped(int n, const void* const* dy, const int64_t* 
   TnGroupArgs ga{};
   int total = 0;
   // Forms: 256 x 256 blocks (eight waves), one workgroup per CU, the launch's stages dealt out in equal pieces (gemm_tn256s_kernel);
-  // one workgroup per (block of dW, slice of <= TN_GROUP_MROWS rows), fp32 atomics where a block has more than one slice (A/B of the
+  // one workgroup per (block of dW, slice of <= mrows rows), fp32 atomics where a block has more than one slice (A/B of the
   // slice length: profiles/r03_grouped_wgrad_ab.txt); the 128 x 128 / four-wave form, one workgroup per whole contraction.  TN_GROUP_TILE:
-  // 0 (default): by the longest contraction of the group -- equal pieces up to TN_GROUP_SLICE_MIN rows, per-slice blocks from there on: with
+  // 0 (default): by the longest contraction of the group -- equal pieces up to slice_min rows, per-slice blocks from there on: with
   // >= 3 slices per block of dW the launch is several rounds of workgroups whatever the form, and the slices of one block run side by
   // side on one L2 (47 % hits against 7 %, profiles/r03_tn_group_l2.txt): configs[3] (12 720 rows) 13.16 -> 12.92 ms/step, while the
   // headline's 6 400 rows (2 slices: 1.2 rounds) keep the equal pieces.  1: equal pieces always; 256: per-slice always; 128.
   const int tmode = (int)asr_tuning("TN_GROUP_TILE", 0);
-  const int mrows = (int)asr_tuning("TN_GROUP_MROWS", 3200);
+  constexpr int mrows = 3200, slice_min = 9600;
   int max_m = 0;
   for (int j = 0; j < cnt; ++j) max_m = M[order[j]] > max_m ? M[order[j]] : max_m;
   // Round 5: tn256r_body, and ONE workgroup per block of dW over the WHOLE contraction, dispatched longest
@@ -2209,7 +2076,7 @@ extern "C" int asr_gemm_tn_grouped(int n, const void* const* dy, const int64_t* 
   int rot_splits[TN_GROUP_MAX];
   // where the whole blocks would leave CUs idle (tn_rot_plan), round 3's shared forms (equal pieces / slices) with the new loop
   const bool whole = rot && tn_rot_plan(cnt, order, M, N, K, rot_splits);
-  const bool sched = !whole && (tmode == 1 || (tmode == 0 && max_m < asr_tuning("TN_GROUP_SLICE_MIN", 9600)));
+  const bool sched = !whole && (tmode == 1 || (tmode == 0 && max_m < slice_min));
   if (whole) {
     int slice[TN_GROUP_MAX];
     for (int j = 0; j < cnt; ++j) {
@@ -2234,7 +2101,7 @@ extern "C" int asr_gemm_tn_grouped(int n, const void* const* dy, const int64_t* 
       continue;
     }
     int splits = whole ? rot_splits[i] : 1;
-    if (big && mrows > 0 && !whole) splits = (M[i] + mrows - 1) / mrows;
+    if (big && !whole) splits = (M[i] + mrows - 1) / mrows;
     if (splits < 1) splits = 1;
     q.m_per_split = ((M[i] + splits - 1) / splits + 31) / 32 * 32;
     splits = (M[i] + q.m_per_split - 1) / q.m_per_split;
@@ -2252,8 +2119,8 @@ extern "C" int asr_gemm_tn_grouped(int n, const void* const* dy, const int64_t* 
   }
   AsrProfScope prof(ASR_OP_GEMM, stream);
   if (sched) {
-    // one workgroup per CU (TN_GROUP_WGS), at least 16 stages each; pieces of equal length
-    int nwg = (int)asr_tuning("TN_GROUP_WGS", 256);
+    // one workgroup per CU, at least 16 stages each; pieces of equal length
+    int nwg = 256;
     if (nwg > total / 16) nwg = total / 16;
     if (nwg < 1) nwg = 1;
     const int per_wg = (total + nwg - 1) / nwg;
@@ -2279,6 +2146,7 @@ extern "C" int asr_gemm_tn_grouped(int n, const void* const* dy, const int64_t* 
   return ASR_OK;
 }
 
+constexpr int64_t kNnBig = 1700;      // data gradient (asr_gemm_nn, asr_gemm_nn_tn): 128x64 tiles from this many 64x64 tiles on
 extern "C" int asr_gemm_nn(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* relu_mask,
                            int M, int N, int K, float alpha, int flags, int in_dtype, int out_dtype, hipStream_t stream) {
   ASR_CHECK_ARG(A && B && C && M >= 0 && N >= 0 && K >= 0);
@@ -2303,8 +2171,7 @@ extern "C" int asr_gemm_nn(const void* A, int64_t lda, const void* B, int64_t ld
     if (asr_gemm_big_nn(q, stream)) return ASR_OK;
   }
   const int64_t t64 = ceil_div64(M, 64) * ceil_div64(N, 64);
-  const int64_t nn_big = asr_tuning("NN_BIG", 1700);      // 128x64 tiles from this many 64x64 tiles on
-  const bool big = t64 >= nn_big && M > 64;
+  const bool big = t64 >= kNnBig && M > 64;
   if (in_dtype == ASR_F32) return big ? launch_nn<float, float, 128>(p, stream) : launch_nn<float, float, 64>(p, stream);
   // a launch that leaves a CU with one workgroup or two and walks at least four K steps: the private three-stage ring (NN_RING: the
   // largest number of 64 x 64 blocks that takes it; 0 = never).  profiles/r03_gemm_nn_ring_ab.txt
@@ -2318,7 +2185,7 @@ extern "C" int asr_gemm_nn(const void* A, int64_t lda, const void* B, int64_t ld
 extern "C" int asr_gemm_nn_rowdot(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, const void* O, const float* O32,
                                   float* rowdot, int M, int N, int K, int T, int dtype, hipStream_t stream) {
   ASR_CHECK_ARG(A && B && C && (O || O32) && rowdot && M >= 0 && N >= 0 && K >= 0 && T > 0);
-  if (dtype != ASR_BF16 || N % 64 != 0 || M % T != 0 || asr_tuning("NN_ROWDOT", 1) == 0) return ASR_EUNSUPPORTED;
+  if (dtype != ASR_BF16 || N % 64 != 0 || M % T != 0) return ASR_EUNSUPPORTED;
   if (M == 0 || N == 0) return ASR_OK;
   if (K <= 0 || lda % 8 != 0 || ldb % 8 != 0 || !aligned16(A) || !aligned16(B) || !aligned16(C) || (O && !aligned16(O)) ||
       (O32 && !aligned16(O32)) || ldb < N || lda < (K + 63) / 64 * 64)
@@ -2360,8 +2227,8 @@ extern "C" int asr_gemm_nn_poolbwd(const void* A, int64_t lda, const void* Bp, i
 static int nn_tn_splits(int M, int splits, int* m_per_split) {
   const int stages = (M + 63) / 64;
   if (splits <= 0) {
-    const int per = (int)asr_tuning("NNTN_STAGES", 16);           // 64-row stages of one weight-gradient workgroup
-    splits = (stages + per - 1) / (per > 0 ? per : 16);
+    constexpr int per = 16;           // 64-row stages of one weight-gradient workgroup
+    splits = (stages + per - 1) / per;
   }
   splits = splits < 1 ? 1 : (splits > stages ? stages : splits);
   const int mps = ((stages + splits - 1) / splits) * 64;
@@ -2403,7 +2270,7 @@ extern "C" int asr_gemm_nn_tn(const void* dy, int64_t ld_dy, const void* w, int6
   p.vecC = ((((uintptr_t)dx) & 15) == 0) && (ld_dx % 4 == 0);
   p.tiles_n = (K + 63) / 64;
   const int64_t t64 = ceil_div64(M, 64) * p.tiles_n;
-  const bool big = t64 >= asr_tuning("NN_BIG", 1700) && M > 64;
+  const bool big = t64 >= kNnBig && M > 64;
   const int bm = big ? 128 : 64;
   p.ntiles = ((M + bm - 1) / bm) * p.tiles_n;
   const int n_tn = t.ntiles * splits;

@@ -77,17 +77,17 @@ extern "C" int asr_prof_collect(int op, double* total_ms, int64_t* launches) {
 }
 
 // ------------------------------------------------------------------------------------------------ tuning switches
-// The library reads NO environment variables: A/B switches are set through the ABI (asr_set_tuning) by the host layer
+// The library reads NO environment variables: its switches are set through the ABI (asr_set_tuning) by the host layer
 // (asr_hip/lib.py forwards ASR_<NAME> variables once, at load).  Unknown names are refused.
 namespace {
 const char* const kTuningNames[] = {
-    "ATTN_GENERIC", "IGEMM_TH", "IGEMM_TPS", "IGEMM_WBUF", "CONV1_WGRAD_MFMA", "IGEMM_ABLATE", "C64", "CONV_POOL", "WGRAD_ABLATE",
-    "WGRAD_DMA", "CONV1_WGRAD_WGS", "C64_PER_CU", "C64_ABLATE", "C64_SHAPE", "GEMM_NS", "GEMM_TILE", "GEMM_GENERIC", "TN_WGS",
-    "TN_128", "TN_128_MIN", "TN_128_RM", "TN_NBUF", "NN_BIG", "NN_RING", "TN_GROUP_SLICE_MIN", "GEMM_BIG_MIN", "NT_RING", "TN_PIPE", "TN_PIPE_MIN", "GEMM_ABLATE", "ATTN_SHORT", "ATTN_SHORT_BWD", "ATTN_BOTH", "NNTN_STAGES",
-    "ATTN_PP", "ATTN_PP_MIN", "ATTN_PP_TAIL", "ATTN_PP_PRIO", "ATTN_PP_STAGGER", "ATTN_PP_STAGGER_SEL", "TN_GROUP_TILE", "TN_GROUP_MROWS",
-    "TN_GROUP_WGS", "WGRAD_XCD", "IGEMM_XCD", "C64_SPLIT", "GEMM_BIG", "GEMM_BIG_NS", "GEMM_BIG_NN", "L0_WSPLIT", "WS128", "WS64", "WS64_PER_CU", "WS_PAIR", "WS_BITS", "NN_ROWDOT", "ATTN_BWD_FUSED",
+    // test hooks: each forces a path the dispatch takes at other shapes, so that a test can hold it bit for bit against the one it replaces
+    "GEMM_TILE", "GEMM_BIG", "GEMM_BIG_NS", "GEMM_BIG_NN", "NT_RING", "NN_RING", "TN_GROUP_TILE", "ATTN_BWD_FUSED", "WS64", "WS128", "WS_PAIR",
+    "L0_WSPLIT", "C64_SHAPE",
 #ifdef ASR_TUNE_ABLATE
-    "WS_DBG",          // development builds only: a device ADDRESS the timing instantiations of conv_ws.hip write through
+    // development builds only: kernels with parts of their work left out (timing), and WS_DBG, a device ADDRESS the timing
+    // instantiations of conv_ws.hip write through
+    "GEMM_ABLATE", "IGEMM_ABLATE", "C64_ABLATE", "WGRAD_ABLATE", "WS_DBG",
 #endif
 };
 constexpr int kNumTuning = (int)(sizeof(kTuningNames) / sizeof(kTuningNames[0]));

@@ -44,7 +44,7 @@ int asr_abi_version(void);   /* 4 since round 4: asr_gemm_nt_add_ln removed; the
 
 /* ---- tuning / A-B switches.  The library reads no environment variables and has no other mutable global state than
  * this table and the profiling slots below: a switch (names: the ASR_* list of DESIGN.md section 4 without the prefix,
- * e.g. "C64", "GEMM_TILE", "ATTN_GENERIC") keeps its built-in default until set here.  ASR_EINVAL for an unknown name.
+ * e.g. "GEMM_TILE", "WS128", "NN_RING") keeps its built-in default until set here.  ASR_EINVAL for an unknown name.
  * asr_clear_tuning(NULL) restores every default.                                                                */
 int asr_set_tuning(const char* name, int64_t value);
 int asr_clear_tuning(const char* name);

@@ -318,6 +318,53 @@ def test_library_reads_no_environment_and_tuning_goes_through_the_abi():
     assert h.asr_clear_tuning(None) == 0
 
 
+def _outside_ablate_blocks(text):
+    """The source as a shipped build sees it: without the `#ifdef ASR_TUNE_ABLATE` arms (an `#else` arm stays)."""
+    out, skip = [], None            # skip: the #if depth at which the dropped arm was opened
+    depth = 0
+    for line in text.split("\n"):
+        t = line.strip()
+        if t.startswith("#if"):
+            depth += 1
+            if skip is None and t.split()[:2] == ["#ifdef", "ASR_TUNE_ABLATE"]:
+                skip = depth
+                continue
+        elif t.startswith("#else") and skip == depth:
+            skip = -depth           # the #else arm of the block is live
+            continue
+        elif t.startswith("#endif"):
+            depth -= 1
+            if skip is not None and abs(skip) == depth + 1:
+                skip = None
+                continue
+        if skip is None or skip < 0:
+            out.append(line)
+    return "\n".join(out)
+
+
+def test_tuning_names_are_one_list():
+    """The switches of a shipped build are kept in three places that must agree: asr_hip/lib.py TUNING_NAMES (environment forwarding),
+    csrc/prof.hip kTuningNames (what asr_set_tuning accepts) and the asr_tuning("...") reads in csrc/ -- a name that is registered but
+    never read, or forwarded but refused, is a switch that silently does nothing."""
+    import glob
+    import re
+    from asr_hip import lib as L
+    csrc = os.path.join(ROOT, "end2end-asr-pytorch_amd", "csrc")
+    read = set()
+    for f in glob.glob(os.path.join(csrc, "*")):
+        read |= set(re.findall(r'asr_tuning\(\s*"([A-Za-z0-9_]+)"', _outside_ablate_blocks(open(f).read())))
+    prof = _outside_ablate_blocks(open(os.path.join(csrc, "prof.hip")).read())
+    table = re.search(r"kTuningNames\[\]\s*=\s*\{(.*?)\};", prof, re.S).group(1)
+    table = "\n".join(l.split("//")[0] for l in table.split("\n"))
+    registered = re.findall(r'"([A-Za-z0-9_]+)"', table)
+    assert len(registered) == len(set(registered)) and len(L.TUNING_NAMES) == len(set(L.TUNING_NAMES))
+    assert set(registered) == set(L.TUNING_NAMES) == read, (sorted(registered), sorted(L.TUNING_NAMES), sorted(read))
+    h = L.load()
+    for name in L.TUNING_NAMES:
+        assert h.asr_set_tuning(name.encode(), 1) == 0 and h.asr_clear_tuning(name.encode()) == 0, name
+    assert not set(L.ABLATE_NAMES) & set(L.TUNING_NAMES)            # (registered in -DASR_TUNE_ABLATE development builds only)
+
+
 def test_device_prefetcher_passes_batches_through_in_order():
     """utils/data_loader.DevicePrefetcher: same tuples in the same order (host path: pass-through; the H2D overlap itself is
     exercised by tests/test_gpu_train_cli.py, which trains through it)."""

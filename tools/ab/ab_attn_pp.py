@@ -1,9 +1,10 @@
-"""A/B + blind diagnostics of the long-sequence attention forward (csrc/attention_pp.hip) against the first-generation kernel
-(csrc/attention_fast.hip) and a torch fp32 reference.  Development tool:  python tools/ab/ab_attn_pp.py [diag|time|all]
+"""Blind diagnostics and timing of the long-sequence attention forward (csrc/attention_pp.hip: the dispatch sends it every non-causal
+shape of at least 384 keys) against a torch fp32 reference.  Development tool:  python tools/ab/ab_attn_pp.py [diag|time|all]
 
-diag: small shapes that isolate one mechanism each (one tile / several tiles / chunk mode / tail mode / ragged key length / dropout
-mask identity), error split by where it shows (lse = first contraction + softmax; O = second contraction) and by lane / block.
-time: the north-star shape and configs[3]'s shapes under ATTN_PP = 0 | 1, with the tail / priority switches."""
+diag: shapes that isolate one mechanism each (chunk mode / tail mode / ragged key length), error split by where it shows (lse =
+first contraction + softmax; O = second contraction) and by lane / block.
+time: the north-star shape and configs[3]'s shapes.  (The A/B against the first-generation kernel, the tail and the priority
+arms: profiles/r03_attention_pp_ab.txt.)"""
 import math
 import os
 import sys
@@ -12,7 +13,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "end2end-asr-pytorch_amd"))
-from asr_hip import lib as L  # noqa: E402
 from asr_hip import ops  # noqa: E402
 
 D = torch.device("cuda")
@@ -71,26 +71,14 @@ def diag_case(name, B, H, Tq, Tk, key_len=None):
 
 
 def diag():
-    print("== diagnostics, ATTN_PP = 1, ATTN_PP_MIN = 1 (every shape goes through attention_pp.hip)")
-    L.set_tuning("ATTN_PP", 1)
-    L.set_tuning("ATTN_PP_MIN", 1)
-    diag_case("tail  Tq=32  Tk=64  (1 tile)", 1, 1, 32, 64)
-    diag_case("tail  Tq=32  Tk=256 (4 tiles)", 1, 2, 32, 256)
+    print("== diagnostics (every shape has >= 384 keys: all of them go through attention_pp.hip)")
     diag_case("tail  Tq=32  Tk=832 (13 tiles)", 2, 2, 32, 832)
-    diag_case("chunk Tq=128 Tk=64  (1 tile)", 1, 1, 128, 64)
-    diag_case("chunk Tq=128 Tk=128 (2 tiles)", 1, 1, 128, 128)
-    diag_case("chunk Tq=128 Tk=192 (3 tiles)", 1, 2, 128, 192)
     diag_case("chunk Tq=128 Tk=448 (7 tiles)", 1, 2, 128, 448)
-    diag_case("chunk Tq=256 Tk=64  (1 tile)", 1, 1, 256, 64)
-    diag_case("chunk Tq=256 Tk=128 (2 tiles)", 1, 2, 256, 128)
-    diag_case("chunk Tq=256 Tk=256 (4 tiles)", 1, 2, 256, 256)
     diag_case("chunk Tq=256 Tk=800 ragged tile", 2, 8, 256, 800)
-    diag_case("tail  Tq=64  Tk=320 (2 blocks)", 1, 2, 64, 320)
-    diag_case("tail  Tq=40  Tk=320", 1, 2, 40, 320)
     diag_case("mixed Tq=800 Tk=800", 2, 8, 800, 800, key_len=[800, 613])
     diag_case("mixed Tq=795 Tk=795", 2, 8, 795, 795, key_len=[795, 402])
     diag_case("tails Tq=100 Tk=795", 2, 8, 100, 795, key_len=[700, 795])
-    diag_case("key_len 0 and 1", 2, 2, 160, 200, key_len=[0, 1])
+    diag_case("key_len 0 and 1", 2, 2, 160, 400, key_len=[0, 1])
     # spiked scores: the deferred reference must move (and move everything at the old reference exactly once)
     g = torch.Generator().manual_seed(5)
     B, H, Tq, Tk, d = 1, 2, 160, 512, 64
@@ -105,14 +93,6 @@ def diag():
     o, lse, _ = ops.attn_fwd(q, k, v, H, d, scale=0.125, o32=o32)
     ro, rl = ref(q, k, v, H, d, None)
     print("%-34s O32 err %.3e  lse err %.3e" % ("spiked keys (reference moves)", (o32 - ro).abs().max().item(), (lse.view(B, H, Tq) - rl).abs().max().item()))
-    # dropout: same mask as the first-generation kernel (same function of (seed, row, key)) and as the probability dump
-    q, k, v, kl, o1, lse1, o32a = run(2, 4, 288, 320, p=0.25, seed=3)
-    L.set_tuning("ATTN_PP", 0)
-    _, _, _, _, o0, lse0, o32b = run(2, 4, 288, 320, p=0.25, seed=3)
-    L.set_tuning("ATTN_PP", 1)
-    print("%-34s |O32(pp) - O32(v1)| %.3e   lse diff %.3e   (same dropout mask <=> small)" %
-          ("dropout p=0.25 vs first generation", (o32a - o32b).abs().max().item(), (lse1 - lse0).abs().max().item()))
-    L.set_tuning("ATTN_PP_MIN", None)
 
 
 def timeit(fn, n=30):
@@ -134,26 +114,16 @@ def timeit(fn, n=30):
 def time_all():
     print("== forward time (us), bf16 d=64; flop = 4 B H Tq Tk d; %% of the 2.5 PF dense bf16 peak")
     shapes = [(32, 8, 800, 800, 0.0), (32, 8, 800, 800, 0.1), (16, 8, 795, 795, 0.0), (16, 8, 795, 795, 0.1), (16, 8, 100, 795, 0.1),
-              (32, 8, 200, 200, 0.0), (32, 8, 200, 200, 0.1), (32, 8, 100, 200, 0.1), (32, 8, 512, 512, 0.0), (32, 8, 1024, 1024, 0.0),
+              (32, 8, 512, 512, 0.0), (32, 8, 1024, 1024, 0.0),
               (8, 8, 2048, 2048, 0.0)]
-    variants = [("v1", dict(ATTN_PP=0)), ("pp", dict(ATTN_PP=1)), ("pp no tails", dict(ATTN_PP=1, ATTN_PP_TAIL=0)),
-                ("pp prio1", dict(ATTN_PP=1, ATTN_PP_PRIO=1))]
     for B, H, Tq, Tk, p in shapes:
         q = torch.randn(B, Tq, H * 64, device=D).bfloat16()
         k = torch.randn(B, Tk, H * 64, device=D).bfloat16()
         v = torch.randn(B, Tk, H * 64, device=D).bfloat16()
         kl = torch.full((B,), Tk, device=D, dtype=torch.int32)
         fl = 4.0 * B * H * Tq * Tk * 64
-        row = []
-        for name, tv in variants:
-            for kk in ("ATTN_PP", "ATTN_PP_TAIL", "ATTN_PP_PRIO"):
-                L.set_tuning(kk, tv.get(kk))
-            L.set_tuning("ATTN_PP_MIN", 1)
-            us = timeit(lambda: ops.attn_fwd(q, k, v, H, 64, key_len=kl, scale=0.125, p=p, seed=5))
-            row.append("%s %6.1f us %4.1f%%" % (name, us, fl / us / 25e6))
-        print("  (%d,%d,%d,%d) p=%.1f : %s" % (B, H, Tq, Tk, p, " | ".join(row)))
-    for kk in ("ATTN_PP", "ATTN_PP_TAIL", "ATTN_PP_PRIO", "ATTN_PP_MIN"):
-        L.set_tuning(kk, None)
+        us = timeit(lambda: ops.attn_fwd(q, k, v, H, 64, key_len=kl, scale=0.125, p=p, seed=5))
+        print("  (%d,%d,%d,%d) p=%.1f : %6.1f us %4.1f%%" % (B, H, Tq, Tk, p, us, fl / us / 25e6))
 
 
 if __name__ == "__main__":

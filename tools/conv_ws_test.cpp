@@ -261,7 +261,6 @@ static int run_bits(int B, int H, int W, bool timing) {
 }
 
 int main(int argc, char** argv) {
-  if (const char* e = getenv("WS64_PER_CU")) AK(asr_set_tuning("WS64_PER_CU", atoi(e)));
   const bool timing = argc < 2 || strcmp(argv[1], "parity") != 0;
   const bool parity = argc < 2 || strcmp(argv[1], "time") != 0;
   int fails = 0;

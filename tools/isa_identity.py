@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Proves that a host-side refactor left the device code alone.
+
+  tools/isa_identity.py dump OUT_DIR [--tree TREE]    compile the device side of every csrc/*.hip of TREE (default: this tree) to
+                                                      gfx950 assembly with the flags of asr_hip/build.py (as tests/test_isa_static.py does)
+  tools/isa_identity.py compare BEFORE_DIR AFTER_DIR  per file: kernels before / after, the names removed, and how many surviving kernels
+                                                      differ in instruction text or in their .amdhsa_* block (exit status 1 if any does,
+                                                      or if AFTER has a kernel BEFORE has not)
+
+Kernels are split at their `_Z...:` labels.  The function index in local labels (.LBB<n>_<m>, .Lfunc_end<n>, ...) shifts when a
+neighbour is deleted, so it is normalised before the comparison."""
+import argparse
+import importlib.util
+import os
+import re
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "end2end-asr-pytorch_amd"
+
+
+def _build_module(tree):
+    spec = importlib.util.spec_from_file_location("_asr_build", os.path.join(tree, PKG, "asr_hip", "build.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def dump(tree, out):
+    b = _build_module(tree)
+    os.makedirs(out, exist_ok=True)
+    hipcc = b._hipcc()
+    flags = [f for f in b.FLAGS if f != "-fPIC"]
+
+    def one(name):
+        cmd = [hipcc] + flags + b.PER_FILE_FLAGS.get(name, []) + ["--cuda-device-only", "-S", os.path.join(b.CSRC, name), "-o",
+                                                                 os.path.join(out, name + ".s")]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc failed for %s:\n%s" % (name, r.stderr[-4000:]))
+        print("assembled", name, flush=True)
+
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        list(ex.map(one, sorted(f for f in os.listdir(b.CSRC) if f.endswith(".hip"))))
+
+
+_LOCAL = re.compile(r"\.L([A-Za-z_]+?)(\d+)(_\d+)?\b")
+
+
+def _norm(line):
+    line = line.split(";")[0].rstrip()                     # comments carry source line numbers
+    return _LOCAL.sub(lambda m: ".L%sN%s" % (m.group(1), m.group(3) or ""), line)
+
+
+def kernels(path):
+    """{symbol: (instruction text, .amdhsa block)} of one assembly file."""
+    lines = open(path).read().split("\n")
+    starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)]
+    text = {}
+    for n, a in enumerate(starts):
+        sym = lines[a].split(":")[0]
+        end = starts[n + 1] if n + 1 < len(starts) else len(lines)
+        body = []
+        for l in lines[a + 1:end]:
+            if l.startswith("\t.section") or l.startswith("\t.rodata") or l.startswith("\t.amdgpu_metadata"):
+                break                                      # the kernel descriptor / metadata that follow the code
+            t = _norm(l).strip()
+            if not t or t.startswith(".") and not t.endswith(":"):
+                continue                                   # directives (.p2align, .loc, .size ...): not instructions
+            body.append(t)
+        text[sym] = body
+    hsa, cur = {}, None
+    for l in lines:
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l)
+        if m:
+            cur = m.group(1)
+            hsa[cur] = []
+        elif cur is not None:
+            if l.strip() == ".end_amdhsa_kernel":
+                cur = None
+            else:
+                hsa[cur].append(_norm(l).strip())
+    return {s: (text[s], hsa.get(s)) for s in text}         # a device function that was not inlined has no .amdhsa block: None
+
+
+def compare(before, after):
+    bad = 0
+    tb = ta = 0
+    for f in sorted(os.listdir(before)):
+        if not f.endswith(".s"):
+            continue
+        kb, ka = kernels(os.path.join(before, f)), kernels(os.path.join(after, f))
+        removed, added = sorted(set(kb) - set(ka)), sorted(set(ka) - set(kb))
+        differ = [s for s in sorted(set(ka) & set(kb)) if ka[s] != kb[s]]
+        tb, ta = tb + len(kb), ta + len(ka)
+        print("%s: kernels %d -> %d, removed %d, added %d, %d differing" % (f[:-2], len(kb), len(ka), len(removed), len(added), len(differ)))
+        for s in removed:
+            print("  removed  %s" % _demangle(s))
+        for s in added:
+            print("  ADDED    %s" % _demangle(s))
+        for s in differ:
+            what = [w for w, i in (("text", 0), ("amdhsa", 1)) if ka[s][i] != kb[s][i]]
+            print("  DIFFERS  %s (%s)" % (_demangle(s), ", ".join(what)))
+        bad += len(added) + len(differ)
+    print("total: kernels %d -> %d, %d added or differing" % (tb, ta, bad))
+    return 1 if bad else 0
+
+
+def _demangle(sym):
+    try:
+        r = subprocess.run(["c++filt", sym], capture_output=True, text=True)
+        return r.stdout.strip() or sym
+    except OSError:
+        return sym
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    d = sub.add_parser("dump")
+    d.add_argument("out")
+    d.add_argument("--tree", default=ROOT)
+    c = sub.add_parser("compare")
+    c.add_argument("before")
+    c.add_argument("after")
+    a = ap.parse_args()
+    if a.cmd == "dump":
+        dump(os.path.abspath(a.tree), a.out)
+    else:
+        sys.exit(compare(a.before, a.after))
