@@ -168,7 +168,7 @@ def flush_wgrads(final=False):
 
 
 def _tn_group_ok(e):
-    """The layout test of asr_gemm_tn_grouped (csrc/gemm.hip) for one problem."""
+    """The layout test of asr_gemm_tn_grouped (csrc/gemm_tn.hip) for one problem."""
     dy, x, dw, db, N, K = e
     if dy.shape[0] == 0 or N == 0 or K == 0:
         return True

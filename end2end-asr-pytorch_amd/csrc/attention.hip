@@ -524,11 +524,7 @@ int run_bwd(const AttnArgs& p, hipStream_t s) {
       hipLaunchKernelGGL((attn_delta_kernel<T>), dim3((unsigned)ceil_div64(rows, 16)), dim3(256), 0, s, p, HD);
     ASR_LAUNCH_CHECK();
   }
-  static bool granted = false;
-  if (l2 > 48 * 1024 && !granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<T, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-    granted = true;
-  }
+  if (l2 > 48 * 1024) (void)asr_grant_lds<attn_bwd_dkv_kernel<T, HD>>(l2);
   if (p.parts & ASR_ATTN_DQ) {
     hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD>), dim3((p.Tq + 63) / 64, p.B * p.H), dim3(256), l1, s, p);
     ASR_LAUNCH_CHECK();

@@ -21,11 +21,6 @@ constexpr float LOG2E = 1.4426950408889634f;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-
 // all-reduce over the 4 lane groups that share lane & 15, on the VALU (gfx950 lane-swap instructions) instead of two
 // ds_bpermute round trips: v_permlane16_swap(v, v) -> {rows 0,0,2,2} / {rows 1,1,3,3}; v_permlane32_swap(v, v) -> {lo,lo} / {hi,hi}
 __device__ __forceinline__ float group_max4(float v) {
@@ -43,30 +38,15 @@ __device__ __forceinline__ float group_sum4(float v) {
   return __uint_as_float(c[0]) + __uint_as_float(c[1]);
 }
 
-// XCD-aware linear workgroup id: consecutive ids run on the same XCD (hardware deals blockIdx round-robin over 8 XCDs)
-__device__ __forceinline__ int xcd_linear_id(int bid, int nwg) {
-  const int xcd = bid & 7, qn = nwg >> 3, rn = nwg & 7;
-  return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
-}
-__device__ __forceinline__ int xcd_linear_id() { return xcd_linear_id((int)blockIdx.x, (int)gridDim.x); }
+__device__ __forceinline__ int xcd_linear_id() { return asr_xcd_linear((int)blockIdx.x, (int)gridDim.x); }
 
-// 64 rows x 128 B of a (rows, 64) bf16 slice -> LDS, chunk c of row r stored at slot c ^ (r & 7).  Rows past `nrows`
-// re-read the last valid row (the LDS-DMA cannot zero-fill; such rows are masked / never stored by the callers).
-//
-// The LDS-DMA is issued BY HAND (inline asm).  Through the builtin the compiler counts these loads itself, and its waitcnt pass
-// cannot tell a DMA's LDS write from the tile a later ds_read wants: it put s_waitcnt vmcnt(0) in front of the first LDS read that
-// followed the prefetch of the next tile (the P.V operand reads) -- the "double buffering" only ever overlapped the softmax, and
-// every tile exposed most of a global-memory round trip.  Hand-issued, nothing waits until the explicit s_waitcnt vmcnt(0) in front
-// of the barrier at the end of the tile (every loop below has one); ordinary global loads issued while a DMA is in flight still
-// wait for it (vmcnt retires in order), so the loops issue those BEFORE the prefetch.
-__device__ __forceinline__ void lds_dma16(unsigned lds_wave_base, const void* src) {
-  unsigned keep;      // M0 saved and restored: neutral for whatever the compiler keeps there
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(src)
-               : "memory");
-}
-// 4 bytes per lane (a row of 64 floats per wave)
+// The attention tiles come in by asr_lds_dma16 (common.h), the LDS-DMA issued BY HAND.  Through the builtin the compiler counts these
+// loads itself, and its waitcnt pass cannot tell a DMA's LDS write from the tile a later ds_read wants: it put s_waitcnt vmcnt(0) in
+// front of the first LDS read that followed the prefetch of the next tile (the P.V operand reads) -- the "double buffering" only ever
+// overlapped the softmax, and every tile exposed most of a global-memory round trip.  Hand-issued, nothing waits until the explicit
+// s_waitcnt vmcnt(0) in front of the barrier at the end of the tile (every loop below has one); ordinary global loads issued while a
+// DMA is in flight still wait for it (vmcnt retires in order), so the loops issue those BEFORE the prefetch.
+// The same piece with 4 bytes per lane (a row of 64 floats per wave):
 __device__ __forceinline__ void lds_dma4(unsigned lds_wave_base, const void* src) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
@@ -74,16 +54,12 @@ __device__ __forceinline__ void lds_dma4(unsigned lds_wave_base, const void* src
                : "s"(lds_wave_base), "v"(src)
                : "memory");
 }
-// The same with a wave-uniform base address (SGPR pair) + a per-thread 32-bit byte offset that does not change from tile to tile:
-// the loops of the forward kernel hoist the offsets (tile_voff) and pay no vector instruction per prefetch (the per-tile 64-bit
-// row * stride arithmetic was 24 of the 245 vector instructions of a forward tile).
-__device__ __forceinline__ void lds_dma16_s(unsigned lds_wave_base, unsigned voff, const void* sbase) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(voff), "s"(sbase)
-               : "memory");
-}
+
+// 64 rows x 128 B of a (rows, 64) bf16 slice -> LDS, chunk c of row r stored at slot c ^ (r & 7).  Rows past `nrows`
+// re-read the last valid row (the LDS-DMA cannot zero-fill; such rows are masked / never stored by the callers).
+// Full tiles go by a wave-uniform base address + per-thread byte offsets that do not change from tile to tile: the loops of the forward
+// kernel hoist the offsets (tile_voff) and pay no vector instruction per prefetch (the per-tile 64-bit row * stride arithmetic was 24 of
+// the 245 vector instructions of a forward tile).
 // byte offset of this thread's i-th chunk of a tile relative to the tile's first row (row stride st elements; fast_ok(): < 2^22)
 __device__ __forceinline__ unsigned tile_voff(int64_t st, int tid, int i) {
   const int c = i * 256 + tid, row = c >> 3, slot = c & 7;
@@ -97,7 +73,7 @@ __device__ __forceinline__ void stage_tile_h(unsigned char* lds, const bf16_t* g
     const unsigned base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
     const bf16_t* gb = g + (int64_t)r0 * st;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) lds_dma16_s(base + (unsigned)((i * 256 + wave * 64) * 16), voff[i], gb);
+    for (int i = 0; i < 2; ++i) asr_lds_dma16(base + (unsigned)((i * 256 + wave * 64) * 16), gb, voff[i]);
   } else {
     stage_tile(lds, g, st, r0, nrows, tid, wave);
   }
@@ -110,7 +86,7 @@ __device__ __forceinline__ void stage_tile(unsigned char* lds, const bf16_t* g, 
     int gr = r0 + row;
     gr = gr < nrows ? gr : nrows - 1;
     const bf16_t* src = g + (int64_t)gr * st + ((slot ^ (row & 7)) << 3);
-    lds_dma16(base + (unsigned)((i * 256 + wave * 64) * 16), src);
+    asr_lds_dma16(base + (unsigned)((i * 256 + wave * 64) * 16), src);
   }
 }
 // A-operand pack (one row, 8 consecutive d) from a natural tile: row, macro step ds over d, lane group g
@@ -1056,8 +1032,8 @@ __global__ __launch_bounds__(256, N == 1 ? 4 : 2) void attn_bwd_both_bf16_d64_ke
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * TILE];
   __shared__ float s_stat[2][2][64];
   const int bid = (int)blockIdx.x;
-  if (bid < n_dq) attn_bwd_dq_body<N>(p, xcd_linear_id(bid, n_dq), smem);
-  else attn_bwd_dkv_body<N>(p, xcd_linear_id(bid - n_dq, (int)gridDim.x - n_dq), smem, s_stat);
+  if (bid < n_dq) attn_bwd_dq_body<N>(p, asr_xcd_linear(bid, n_dq), smem);
+  else attn_bwd_dkv_body<N>(p, asr_xcd_linear(bid - n_dq, (int)gridDim.x - n_dq), smem, s_stat);
 }
 
 __global__ __launch_bounds__(256) void attn_delta_bf16_d64_kernel(AttnArgs p) {
@@ -1125,12 +1101,8 @@ int attn_fast_bwd(const AttnArgs& p, int d, int dtype, hipStream_t s) {
   }
   // short key sequences: the whole backward of a (batch, head) in one workgroup, one pass over the scores (attn_bwd_fused_body)
   if ((p.parts & ASR_ATTN_DQ) && (p.parts & ASR_ATTN_DKV) && p.Tk <= 256 && asr_tuning("ATTN_BWD_FUSED", 1) != 0) {
-    static bool granted = false;
-    if (!granted) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_bf16_d64_kernel<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_BWD_LDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_fused_bf16_d64_kernel<2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_BWD_LDS);
-      granted = true;
-    }
+    (void)asr_grant_lds<attn_bwd_fused_bf16_d64_kernel<1, 8>>(FUSED_BWD_LDS);
+    (void)asr_grant_lds<attn_bwd_fused_bf16_d64_kernel<2, 8>>(FUSED_BWD_LDS);
     // 8 waves x 16 keys up to 128 keys, x 32 keys up to 256
     if (p.Tk <= 128) attn_bwd_fused_bf16_d64_kernel<1, 8><<<dim3((unsigned)(p.B * p.H)), dim3(512), FUSED_BWD_LDS, s>>>(p);
     else attn_bwd_fused_bf16_d64_kernel<2, 8><<<dim3((unsigned)(p.B * p.H)), dim3(512), FUSED_BWD_LDS, s>>>(p);

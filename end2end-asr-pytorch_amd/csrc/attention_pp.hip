@@ -40,10 +40,6 @@ typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) unsigned short u16x2_t;
 
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
 __device__ __forceinline__ float max_halves(float v) {
   const uint32_t u = __float_as_uint(v);
   auto c = __builtin_amdgcn_permlane32_swap(u, u, false, false);
@@ -54,29 +50,10 @@ __device__ __forceinline__ float sum_halves(float v) {
   auto c = __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return __uint_as_float(c[0]) + __uint_as_float(c[1]);
 }
-__device__ __forceinline__ int xcd_linear(int bid, int nwg) {
-  const int xcd = bid & 7, qn = nwg >> 3, rn = nwg & 7;
-  return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
-}
 __device__ __forceinline__ void mma32(f32x16_t& acc, const uint4& a, const uint4& b) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
 }
 
-// LDS-DMA, hand issued (the compiler must not count it: see attention_fast.hip lds_dma16)
-__device__ __forceinline__ void dma16(unsigned lds_wave_base, const void* src) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(src)
-               : "memory");
-}
-__device__ __forceinline__ void dma16_s(unsigned lds_wave_base, unsigned voff, const void* sbase) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(voff), "s"(sbase)
-               : "memory");
-}
 
 // LDS image of a 64-key tile: row = key, 8 chunks of 16 B, chunk c of row r stored at slot c ^ key(r).
 //   K: key(r) = (r >> 1) & 7  -- ds_read_b128 by 32 lanes = 32 consecutive rows at one logical chunk: conflict free with two rows
@@ -110,16 +87,16 @@ struct Stager {          // this thread's share of a tile: 512 / (64 NW) 16-byte
     const bf16_t* vb = Vb + (int64_t)k0 * v_st;
     if (k0 + KT <= Tk) {
 #pragma unroll
-      for (int i = 0; i < NC; ++i) dma16_s(stage + piece + i * NW * 1024, voK[i], kb);
+      for (int i = 0; i < NC; ++i) asr_lds_dma16(stage + piece + i * NW * 1024, kb, voK[i]);
 #pragma unroll
-      for (int i = 0; i < NC; ++i) dma16_s(stage + TILE + piece + i * NW * 1024, voV[i], vb);
+      for (int i = 0; i < NC; ++i) asr_lds_dma16(stage + TILE + piece + i * NW * 1024, vb, voV[i]);
     } else {
       const int last = Tk - 1 - k0;
 #pragma unroll
       for (int i = 0; i < NC; ++i) {
         const int c = i * 64 * NW + tid, row = c >> 3, slot = c & 7, gr = row < last ? row : last;
-        dma16_s(stage + piece + i * NW * 1024, (unsigned)(gr * k_st * 2 + ((slot ^ swz_k(row)) << 4)), kb);
-        dma16_s(stage + TILE + piece + i * NW * 1024, (unsigned)(gr * v_st * 2 + ((slot ^ swz_v(row)) << 4)), vb);
+        asr_lds_dma16(stage + piece + i * NW * 1024, kb, (unsigned)(gr * k_st * 2 + ((slot ^ swz_k(row)) << 4)));
+        asr_lds_dma16(stage + TILE + piece + i * NW * 1024, vb, (unsigned)(gr * v_st * 2 + ((slot ^ swz_v(row)) << 4)));
       }
     }
   }
@@ -474,11 +451,11 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pp_bf16_d64_kernel(AttnAr
     prio &= 0xff;
   }
   if (bid < n_main) {
-    const int vid = xcd_linear(bid, n_main);
+    const int vid = asr_xcd_linear(bid, n_main);
     const int bh = vid / n_full;
     attn_fwd_pp_body<DROP, false, NW>(p, smem, bh, (vid - bh * n_full) * (32 * NW) + wave * 32, prio);
   } else {
-    const int vid = xcd_linear(bid - n_main, n_tail * BH);
+    const int vid = asr_xcd_linear(bid - n_main, n_tail * BH);
     const int bh = vid / n_tail;
     attn_fwd_pp_body<DROP, true, NW>(p, smem, bh, n_full * (32 * NW) + (vid - bh * n_tail) * 32, prio);
   }

@@ -51,6 +51,13 @@ template <typename T> union Chunk {
   T e[16 / sizeof(T)];
 };
 
+typedef __attribute__((ext_vector_type(2))) float asr_f32x2_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 asr_bf16x2_t;
+__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {      // (bf16(b) << 16) | bf16(a): one v_cvt_pk_bf16_f32
+  const asr_f32x2_t v = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, asr_bf16x2_t));
+}
+
 // ---------------------------------------------------------------------------------------------- MFMA wrapper
 // acc += A_pack (x) B_pack for one 16x16 fragment over one macro step.
 template <typename T> __device__ __forceinline__ void mma16(f32x4_t& acc, const uint4& a, const uint4& b);
@@ -93,6 +100,37 @@ __device__ __forceinline__ void asr_sum8_bf16(float& acc, const bf16x8_t& v) {
   asm("v_dot2c_f32_bf16 %0, %1, %2\n\tv_dot2c_f32_bf16 %0, %1, %3\n\tv_dot2c_f32_bf16 %0, %1, %4\n\tv_dot2c_f32_bf16 %0, %1, %5\n\ts_nop 3"
       : "+v"(acc) : "s"(0x3F803F80u), "v"(u[0]), "v"(u[1]), "v"(u[2]), "v"(u[3]));
 }
+
+// ---------------------------------------------------------------------------------------------- workgroup order, LDS-DMA
+// XCD-aware linear workgroup id: the hardware deals blockIdx round-robin over the 8 XCDs (each with its own L2), so blocks b, b + 8,
+// b + 16 ... run on one XCD; this gives them consecutive ids (0 .. nwg - 1, a bijection), and neighbours in the id share that L2.
+__device__ __forceinline__ int asr_xcd_linear(int bid, int nwg) {
+  const int xcd = bid & 7, qn = nwg >> 3, rn = nwg & 7;
+  return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
+}
+
+// One LDS-DMA piece issued BY HAND: lane l's 16 bytes at src go to LDS byte lds_wave_base + 16 l (the base is wave-uniform, in M0, which
+// is saved and restored: neutral for whatever the compiler keeps there).  Through the builtin the compiler counts the load itself and,
+// unable to tell the DMA's LDS write from the tile a later ds_read wants, drains vmcnt in front of every LDS read it can see; hand
+// issued, nothing waits until the caller's own asr_wait_vmcnt (csrc/attention_fast.hip has the measurement).  Ordinary global loads
+// issued while a piece is in flight still wait for it: vmcnt retires in order.
+__device__ __forceinline__ void asr_lds_dma16(unsigned lds_wave_base, const void* src) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "s"(lds_wave_base), "v"(src)
+               : "memory");
+}
+// The same with a wave-uniform base address (SGPR pair) + a per-thread 32-bit byte offset: offsets that do not change from tile to
+// tile are hoisted out of the loop, and a piece costs no vector instruction.
+__device__ __forceinline__ void asr_lds_dma16(unsigned lds_wave_base, const void* sbase, unsigned voff) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "s"(lds_wave_base), "v"(voff), "s"(sbase)
+               : "memory");
+}
+template <int N> __device__ __forceinline__ void asr_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // ---------------------------------------------------------------------------------------------- reductions
 __device__ __forceinline__ float wave_sum(float v) {
@@ -146,6 +184,19 @@ static inline uint32_t asr_drop_threshold(float p) {
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// Raises the dynamic-LDS limit of Kernel to `bytes` unless an earlier call granted as much.  One flag per KERNEL (a non-type template
+// parameter: kernels that share a signature do not share it).  hipFuncSetAttribute must not run inside a stream capture: the first
+// (eager / warm-up) launch of a kernel gets here.  A refused grant is reported by the return value, not left behind for the next
+// launch check, and is asked for again by the next call.
+template <auto Kernel> hipError_t asr_grant_lds(size_t bytes) {
+  static size_t granted = 0;
+  if (bytes <= granted) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) granted = bytes;
+  else (void)hipGetLastError();
+  return e;
+}
 
 // tuning switch set through asr_set_tuning (prof.hip), or `dflt`; the library itself reads no environment variables
 int64_t asr_tuning(const char* name, int64_t dflt);

@@ -300,8 +300,7 @@ __global__ __launch_bounds__(256) void conv3x3_igemm_kernel(ConvArgs p) {
   if (PT || p.xcd_order) {
     // consecutive tile ids on ONE XCD (blockIdx is dealt round-robin over the 8 XCDs, each with its own L2): neighbouring tiles share
     // their halo rows / columns in that L2 (PMC, conv.7 forward: 167.5 -> 131.1 MB fetched)
-    const int nwg = gridDim.x, xcd = t & 7, qn = nwg >> 3, rn = nwg & 7;
-    t = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (t >> 3);
+    t = asr_xcd_linear(t, (int)gridDim.x);
   }
   if constexpr (PT) {
     // pooled epilogue: the five row tiles of a column strip each write 16 bytes of every 80-byte (column, channel) run of the encoder
@@ -1159,15 +1158,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   dst[0] += acc.x; dst[9] += acc.y; dst[18] += acc.z; dst[27] += acc.w;
 }
 
-// once per kernel instantiation (never during a stream capture: the first eager/warm-up launch does it)
-template <typename K> void allow_big_lds(K kernel, size_t lds) {
-  static size_t granted = 0;      // one static per template instantiation = per kernel
-  if (lds > 48 * 1024 && lds > granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    granted = lds;
-  }
-}
-
 template <typename T, int NCO, int TH, int TPS, int WBUF, bool PT = false>
 int launch_igemm_t(const ConvArgs& a, hipStream_t s) {
   ConvArgs p = a;
@@ -1175,7 +1165,7 @@ int launch_igemm_t(const ConvArgs& a, hipStream_t s) {
   p.tiles_w = (p.W + 15) / 16;
   p.xcd_order = 1;
   size_t lds = (size_t)((TH + 2) * 18 + WBUF * TPS * NCO) * (64 * sizeof(T));      // (>= the 24 KB the pooled epilogue stages)
-  allow_big_lds(conv3x3_igemm_kernel<T, NCO, TH, TPS, WBUF, PT>, lds);
+  if (lds > 48 * 1024) (void)asr_grant_lds<conv3x3_igemm_kernel<T, NCO, TH, TPS, WBUF, PT>>(lds);
   hipLaunchKernelGGL((conv3x3_igemm_kernel<T, NCO, TH, TPS, WBUF, PT>), dim3((unsigned)(p.B * p.tiles_h * p.tiles_w)), dim3(256), lds, s, p);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
@@ -1448,11 +1438,11 @@ extern "C" int asr_maxpool_fwd(const void* x, void* y, int B, int H, int W, int 
     const size_t lds = (size_t)H2 * (C + 1) * sizeof(float);
     if (lds > 150 * 1024) return ASR_EUNSUPPORTED;
     if (C % epc == 0 && H2 % epc == 0 && aligned16(x) && aligned16(y)) {
-      if (dtype == ASR_F32) { allow_big_lds(pool_fwd_tcf_vec_kernel<float>, lds); hipLaunchKernelGGL((pool_fwd_tcf_vec_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (float*)y, B, H, W, C); }
-      else { allow_big_lds(pool_fwd_tcf_vec_kernel<bf16_t>, lds); hipLaunchKernelGGL((pool_fwd_tcf_vec_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, B, H, W, C); }
+      if (dtype == ASR_F32) { if (lds > 48 * 1024) (void)asr_grant_lds<pool_fwd_tcf_vec_kernel<float>>(lds); hipLaunchKernelGGL((pool_fwd_tcf_vec_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (float*)y, B, H, W, C); }
+      else { if (lds > 48 * 1024) (void)asr_grant_lds<pool_fwd_tcf_vec_kernel<bf16_t>>(lds); hipLaunchKernelGGL((pool_fwd_tcf_vec_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, B, H, W, C); }
     } else
-    if (dtype == ASR_F32) { allow_big_lds(pool_fwd_tcf_kernel<float>, lds); hipLaunchKernelGGL((pool_fwd_tcf_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (float*)y, B, H, W, C); }
-    else { allow_big_lds(pool_fwd_tcf_kernel<bf16_t>, lds); hipLaunchKernelGGL((pool_fwd_tcf_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, B, H, W, C); }
+    if (dtype == ASR_F32) { if (lds > 48 * 1024) (void)asr_grant_lds<pool_fwd_tcf_kernel<float>>(lds); hipLaunchKernelGGL((pool_fwd_tcf_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (float*)y, B, H, W, C); }
+    else { if (lds > 48 * 1024) (void)asr_grant_lds<pool_fwd_tcf_kernel<bf16_t>>(lds); hipLaunchKernelGGL((pool_fwd_tcf_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, B, H, W, C); }
   } else {
     if (C % epc != 0 || !aligned16(x) || !aligned16(y)) return ASR_EUNSUPPORTED;
     if ((int64_t)B * H2 > 65535) return ASR_EUNSUPPORTED;
@@ -1482,11 +1472,11 @@ extern "C" int asr_maxpool_bwd(const void* x, const void* dy, void* dx, int B, i
     if (lds > 150 * 1024) return ASR_EUNSUPPORTED;
     const int epc = dtype == ASR_F32 ? 4 : 8;
     if (C % epc == 0 && H2 % epc == 0 && aligned16(x) && aligned16(dy) && aligned16(dx)) {
-      if (dtype == ASR_F32) { allow_big_lds(pool_bwd_tcf_vec_kernel<float>, lds); hipLaunchKernelGGL((pool_bwd_tcf_vec_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (const float*)dy, (float*)dx, B, H, W, C); }
-      else { allow_big_lds(pool_bwd_tcf_vec_kernel<bf16_t>, lds); hipLaunchKernelGGL((pool_bwd_tcf_vec_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C); }
+      if (dtype == ASR_F32) { if (lds > 48 * 1024) (void)asr_grant_lds<pool_bwd_tcf_vec_kernel<float>>(lds); hipLaunchKernelGGL((pool_bwd_tcf_vec_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (const float*)dy, (float*)dx, B, H, W, C); }
+      else { if (lds > 48 * 1024) (void)asr_grant_lds<pool_bwd_tcf_vec_kernel<bf16_t>>(lds); hipLaunchKernelGGL((pool_bwd_tcf_vec_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C); }
     } else
-    if (dtype == ASR_F32) { allow_big_lds(pool_bwd_tcf_kernel<float>, lds); hipLaunchKernelGGL((pool_bwd_tcf_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (const float*)dy, (float*)dx, B, H, W, C); }
-    else { allow_big_lds(pool_bwd_tcf_kernel<bf16_t>, lds); hipLaunchKernelGGL((pool_bwd_tcf_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C); }
+    if (dtype == ASR_F32) { if (lds > 48 * 1024) (void)asr_grant_lds<pool_bwd_tcf_kernel<float>>(lds); hipLaunchKernelGGL((pool_bwd_tcf_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (const float*)dy, (float*)dx, B, H, W, C); }
+    else { if (lds > 48 * 1024) (void)asr_grant_lds<pool_bwd_tcf_kernel<bf16_t>>(lds); hipLaunchKernelGGL((pool_bwd_tcf_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C); }
   } else {
     const int epc = dtype == ASR_F32 ? 4 : 8;
     if (C % epc != 0 || !aligned16(x) || !aligned16(dy) || !aligned16(dx)) return ASR_EUNSUPPORTED;
@@ -1512,8 +1502,8 @@ extern "C" int asr_maxpool_fwd_code(const void* x, void* y, uint8_t* code, int B
   if (out_tcf) {
     const size_t lds = (size_t)H2 * (C + 1) * sizeof(float) + (size_t)H2 * (C + 4);
     if (lds > 150 * 1024 || H2 % epc != 0) return ASR_EUNSUPPORTED;
-    if (dtype == ASR_F32) { allow_big_lds(pool_fwd_tcf_code_kernel<float>, lds); hipLaunchKernelGGL((pool_fwd_tcf_code_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (float*)y, code, B, H, W, C); }
-    else { allow_big_lds(pool_fwd_tcf_code_kernel<bf16_t>, lds); hipLaunchKernelGGL((pool_fwd_tcf_code_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, code, B, H, W, C); }
+    if (dtype == ASR_F32) { if (lds > 48 * 1024) (void)asr_grant_lds<pool_fwd_tcf_code_kernel<float>>(lds); hipLaunchKernelGGL((pool_fwd_tcf_code_kernel<float>), dim3(B * W2), dim3(256), lds, s, (const float*)x, (float*)y, code, B, H, W, C); }
+    else { if (lds > 48 * 1024) (void)asr_grant_lds<pool_fwd_tcf_code_kernel<bf16_t>>(lds); hipLaunchKernelGGL((pool_fwd_tcf_code_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, code, B, H, W, C); }
   } else {
     if ((int64_t)B * H2 > 65535) return ASR_EUNSUPPORTED;
     const dim3 grid((unsigned)ceil_div64((int64_t)W2 * (C / epc), 256), (unsigned)(B * H2));
@@ -1543,8 +1533,8 @@ extern "C" int asr_maxpool_bwd_code(const uint8_t* code, const void* dy, void* d
   }
   if (in_tcf) {
     const size_t lds = (size_t)H2 * (C + 1) * sizeof(float) + (size_t)H2 * (C + 4);
-    if (dtype == ASR_F32) { allow_big_lds(pool_bwd_tcf_code_kernel<float>, lds); hipLaunchKernelGGL((pool_bwd_tcf_code_kernel<float>), dim3(B * W2), dim3(256), lds, s, code, (const float*)dy, (float*)dx, B, H, W, C); }
-    else { allow_big_lds(pool_bwd_tcf_code_kernel<bf16_t>, lds); hipLaunchKernelGGL((pool_bwd_tcf_code_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, code, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C); }
+    if (dtype == ASR_F32) { if (lds > 48 * 1024) (void)asr_grant_lds<pool_bwd_tcf_code_kernel<float>>(lds); hipLaunchKernelGGL((pool_bwd_tcf_code_kernel<float>), dim3(B * W2), dim3(256), lds, s, code, (const float*)dy, (float*)dx, B, H, W, C); }
+    else { if (lds > 48 * 1024) (void)asr_grant_lds<pool_bwd_tcf_code_kernel<bf16_t>>(lds); hipLaunchKernelGGL((pool_bwd_tcf_code_kernel<bf16_t>), dim3(B * W2), dim3(256), lds, s, code, (const bf16_t*)dy, (bf16_t*)dx, B, H, W, C); }
   } else {
     const dim3 grid((unsigned)ceil_div64((int64_t)W2 * (C / epc), 256), (unsigned)(B * H2));
     if (dtype == ASR_F32) hipLaunchKernelGGL((pool_bwd_nhwc_code_kernel<float>), grid, dim3(256), 0, s, code, (const float*)dy, (float*)dx, B, H, W, C);
@@ -1640,8 +1630,8 @@ int conv3x3_wgrad_impl(const void* x, const void* dy, float* dw, float* db, floa
     const int rc = asr_conv3x3_wgrad_dma_launch(q, (unsigned)wgx, (unsigned)blocks_y, s);
     if (rc != ASR_OK) return rc;
   } else
-  if (dtype == ASR_F32) { allow_big_lds(conv3x3_wgrad_nhwc_kernel<float>, lds); hipLaunchKernelGGL((conv3x3_wgrad_nhwc_kernel<float>), dim3((unsigned)wgx, (unsigned)blocks_y), dim3(256), lds, s, p); }
-  else { allow_big_lds(conv3x3_wgrad_nhwc_kernel<bf16_t>, lds); hipLaunchKernelGGL((conv3x3_wgrad_nhwc_kernel<bf16_t>), dim3((unsigned)wgx, (unsigned)blocks_y), dim3(256), lds, s, p); }
+  if (dtype == ASR_F32) { if (lds > 48 * 1024) (void)asr_grant_lds<conv3x3_wgrad_nhwc_kernel<float>>(lds); hipLaunchKernelGGL((conv3x3_wgrad_nhwc_kernel<float>), dim3((unsigned)wgx, (unsigned)blocks_y), dim3(256), lds, s, p); }
+  else { if (lds > 48 * 1024) (void)asr_grant_lds<conv3x3_wgrad_nhwc_kernel<bf16_t>>(lds); hipLaunchKernelGGL((conv3x3_wgrad_nhwc_kernel<bf16_t>), dim3((unsigned)wgx, (unsigned)blocks_y), dim3(256), lds, s, p); }
   ASR_LAUNCH_CHECK();
   if (p.ws && reduce) {
       hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(9 * 64 * 64 / 256 + (db ? 1 : 0), (unsigned)blocks_y), dim3(256), 0, s, p.ws, dw, db, wgx,

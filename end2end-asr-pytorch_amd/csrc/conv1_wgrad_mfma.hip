@@ -27,13 +27,6 @@ __device__ __forceinline__ uint32_t c1w_pack(float a, float b) {      // one v_c
 }
 
 // hand-issued LDS-DMA piece (see conv_wgrad_dma.hip: the compiler must not see a DMA in flight, and does not count it)
-__device__ __forceinline__ void c1w_dma(unsigned lds_wave_base, const unsigned char* src) {
-  unsigned keep;      // M0 is saved and restored: the statement is neutral for whatever the compiler keeps there
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(src)
-               : "memory");
-}
 
 // 4 bytes per lane (the fp32 input rows: only dword alignment is guaranteed)
 __device__ __forceinline__ void c1w_dma4(unsigned lds_wave_base, const unsigned char* src) {
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_mfma_kernel(const float* __re
     for (int i = 0; i < DYB / 4096; ++i) {
       const int c = tid + i * 256, px = c >> 3, ch = (c & 7) ^ (px & 7);
       const unsigned char* src = x0 + px < W ? DY + ((rowpix + x0 + px) * 128 + ch * 16) : zero;
-      c1w_dma(wave_lds + (unsigned)(buf * STAGE + i * 4096), src);
+      asr_lds_dma16(wave_lds + (unsigned)(buf * STAGE + i * 4096), src);
     }
   };
   // the three input rows of the tile (columns x0 - 4 .. x0 + TILE + 3, fp32) by 4-byte DMA pieces: element e of the 3 x XW block sits
@@ -183,13 +176,7 @@ int asr_conv1_wgrad_mfma_launch(const float* x, const bf16_t* dy, float* dw, flo
   const int64_t nt = (int64_t)B * H * tiles_w;
   if (nt >= ((int64_t)1 << 31)) return ASR_EUNSUPPORTED;
   const size_t lds = (size_t)C1W_STAGES * STAGE;
-  static bool granted = false;          // the first (eager / warm-up) launch does it, never a captured one
-  if (!granted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_wgrad_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-      return ASR_ELAUNCH;
-    granted = true;
-  }
+  if (asr_grant_lds<conv1_wgrad_mfma_kernel>(lds) != hipSuccess) return ASR_ELAUNCH;
   constexpr int per_cu = 2;
   const unsigned grid = (unsigned)(nt < 256 * per_cu ? nt : 256 * per_cu);     // every workgroup ends with 640 atomics
   hipLaunchKernelGGL(conv1_wgrad_mfma_kernel, dim3(grid), dim3(256), lds, s, x, dy, dw, db, B, H, W, tiles_w, (int)nt);

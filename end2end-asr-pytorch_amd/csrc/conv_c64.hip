@@ -367,13 +367,7 @@ int launch_t(C64Args p, hipStream_t s) {
   constexpr int WM = TW * TH / 64;
   const size_t lds = (size_t)NBUF * (TH + 2) * (TW + 2) * 128 + (MASK ? WM * 2 * 4096 : 0) + 256;
   const int per_cu = (int)(163840 / lds) < 8 / (WM * 2) ? (int)(163840 / lds) : 8 / (WM * 2);   // LDS- and register-limited
-  static bool granted = false;          // per instantiation; the first (eager / warm-up) launch does it, never a captured one
-  if (!granted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<TW, TH, MASK, NBUF, POOL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ASR_ELAUNCH;
-    granted = true;
-  }
+  if (asr_grant_lds<conv3x3_c64_kernel<TW, TH, MASK, NBUF, POOL>>(lds) != hipSuccess) return ASR_ELAUNCH;
   const int64_t slots = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
   const unsigned grid = (unsigned)(nt < slots ? nt : slots);
 #ifdef C64_TIMING

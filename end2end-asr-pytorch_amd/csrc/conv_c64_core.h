@@ -10,13 +10,6 @@ namespace {
 
 __device__ const uint4 c64_zero_page = {0u, 0u, 0u, 0u};
 
-typedef __attribute__((ext_vector_type(2))) float c64_f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 c64_bf16x2_t;
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {      // one v_cvt_pk_bf16_f32
-  const c64_f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, c64_bf16x2_t));
-}
-
 __device__ __forceinline__ void lds_read16(u32x4_t& dst, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
 }

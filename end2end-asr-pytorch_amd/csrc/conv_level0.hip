@@ -55,11 +55,6 @@ __device__ __forceinline__ void l0_dma4(unsigned lds_wave_base, const void* src)
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "s"(lds_wave_base), "v"(src) : "memory");
 }
-__device__ __forceinline__ void l0_dma16(unsigned lds_wave_base, const void* src) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(lds_wave_base), "v"(src) : "memory");
-}
 
 // fp32 frame value -> (hi << 16) | lo, hi = the top 16 bits (a bf16, exact), lo = bf16(x - hi)
 __device__ __forceinline__ uint32_t l0_split(float x) {
@@ -438,7 +433,7 @@ __device__ __forceinline__ void l0_stage_pooled(const L0Args& p, const L0Org& o,
       const int ph = ph0 + qr, pw = pw0 + qc;
       const bool in = (unsigned)ph < (unsigned)H2 && (unsigned)pw < (unsigned)W2;
       const unsigned char* s = in ? reinterpret_cast<const unsigned char*>(p.dpool) + ((((int64_t)o.b * H2 + ph) * W2 + pw) * 64 + c * 8) * 2 : zero;
-      l0_dma16(pst_lds + (unsigned)(it * 4096) + (unsigned)wave_u * 1024u, s);
+      asr_lds_dma16(pst_lds + (unsigned)(it * 4096) + (unsigned)wave_u * 1024u, s);
     }
   }
   if (t < 240) {
@@ -446,7 +441,7 @@ __device__ __forceinline__ void l0_stage_pooled(const L0Args& p, const L0Org& o,
     const int ph = ph0 + qr, pw = pw0 + qc;
     const bool in = (unsigned)ph < (unsigned)H2 && (unsigned)pw < (unsigned)W2;
     const unsigned char* s = in ? p.code + (((int64_t)o.b * H2 + ph) * W2 + pw) * 64 + (t & 3) * 16 : zero;
-    l0_dma16(pst_lds + (unsigned)L0_PV + (unsigned)wave_u * 1024u, s);
+    asr_lds_dma16(pst_lds + (unsigned)L0_PV + (unsigned)wave_u * 1024u, s);
   }
 }
 
@@ -706,10 +701,7 @@ __global__ __launch_bounds__(256, 2) void vgg_level0_wgrad_kernel(L0Args p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, g = lane >> 4;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   int vid = (int)blockIdx.x;
-  {
-    const int nwg = (int)gridDim.x, xcd = vid & 7, qn = nwg >> 3, rn = nwg & 7;
-    vid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (vid >> 3);
-  }
+  vid = asr_xcd_linear(vid, (int)gridDim.x);
   const int npatch = p.ntiles;
   const int p_beg = vid * p.patches_per_wg, p_end = min(npatch, p_beg + p.patches_per_wg);
   const int np = p_end - p_beg;
@@ -936,19 +928,7 @@ int l0_cus() {
   }
   return cus;
 }
-// One flag per KERNEL (the six kernels share the type void (*)(L0Args): a template over the type would share one flag between them,
-// ADVICE r5); the first (eager / warm-up) launch does the grant, never a captured one.
-template <void (*Kern)(L0Args)> int l0_grant(size_t lds) {
-  static bool granted = false;
-  if (!granted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();          // a refused grant is reported by the return value, not left behind for the next launch check
-      return ASR_ELAUNCH;
-    }
-    granted = true;
-  }
-  return ASR_OK;
-}
+template <void (*Kern)(L0Args)> int l0_grant(size_t lds) { return asr_grant_lds<Kern>(lds) == hipSuccess ? ASR_OK : ASR_ELAUNCH; }
 bool l0_shape_ok(int B, int H, int W) {
   return B >= 0 && H >= 2 && W >= 2 && (int64_t)B * H * W * 128 < ((int64_t)1 << 32);
 }

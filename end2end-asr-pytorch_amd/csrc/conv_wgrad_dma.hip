@@ -29,20 +29,6 @@ constexpr int STAGE = XB + DB;
 // One 16-byte-per-lane LDS-DMA piece, issued by hand: the compiler must not know that a DMA is in flight, or it drains the
 // VMEM counter before every LDS read of the patch being contracted.  (It then also cannot count these loads: the kernel has no
 // compiler-visible vector memory loads while a DMA is outstanding, and the patch loop waits for vmcnt(0) by hand.)
-__device__ __forceinline__ void wgd_dma(unsigned lds_wave_base, const unsigned char* base, unsigned off) {
-  unsigned keep;      // M0 is saved and restored: the statement is neutral for whatever the compiler keeps there
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(off), "s"(base)
-               : "memory");
-}
-__device__ __forceinline__ void wgd_dma(unsigned lds_wave_base, const unsigned char* src) {
-  unsigned keep;      // M0 is saved and restored: the statement is neutral for whatever the compiler keeps there
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(src)
-               : "memory");
-}
 
 // transposed 8-pixel operand: two ds_read_b64_tr_b16 (pixels 0..3 and 4..7 of the lane group's 8)
 __device__ __forceinline__ bf16x8_t wgd_read(const unsigned char* lo, const unsigned char* hi) {
@@ -60,8 +46,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgdArgs p) {
   // comes from HBM once per XCD instead of once per sibling (a 2-D grid put the siblings wgx ids apart: on whatever XCDs).
   int vid = (int)blockIdx.x;
   if (p.xcd_order) {
-    const int nwg = (int)gridDim.x, xcd = vid & 7, qn = nwg >> 3, rn = nwg & 7;
-    vid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (vid >> 3);
+    vid = asr_xcd_linear(vid, (int)gridDim.x);
   }
   // (wave-uniform by construction; readfirstlane tells the compiler so: the DMA below takes its base pointers in scalar registers)
   const int by = __builtin_amdgcn_readfirstlane(p.xcd_order ? vid % p.blocks_y : vid / p.wgx);
@@ -105,9 +90,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgdArgs p) {
     if (inside) {
 #pragma unroll
       for (int i = 0; i < RX; ++i)
-        if (i < RX - 1 || tid + i * 256 < NXC) wgd_dma(sx + i * 4096, X, bx + (unsigned)relx[i]);
+        if (i < RX - 1 || tid + i * 256 < NXC) asr_lds_dma16(sx + i * 4096, X, bx + (unsigned)relx[i]);
 #pragma unroll
-      for (int i = 0; i < RD; ++i) wgd_dma(sx + XB + i * 4096, DY, bd + (unsigned)reld[i]);
+      for (int i = 0; i < RD; ++i) asr_lds_dma16(sx + XB + i * 4096, DY, bd + (unsigned)reld[i]);
     } else {
       // (everything from the laundered thread index `t_`: this arithmetic must stay inside the patch loop, not in 20 hoisted registers)
       const unsigned char* zero = reinterpret_cast<const unsigned char*>(&wgd_zero_page);
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgdArgs p) {
           const bool in = gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
           const unsigned off = (((unsigned)b * (unsigned)p.H + (unsigned)gy) * (unsigned)p.W + (unsigned)gx) * (unsigned)xrow +
                                (unsigned)(((c & 7) ^ wgd_key(col)) << 4);
-          wgd_dma(sx + i * 4096, in ? X + off : zero);
+          asr_lds_dma16(sx + i * 4096, in ? X + off : zero);
         }
       }
 #pragma unroll
@@ -128,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgdArgs p) {
         const bool in = gy < p.H && gx < p.W;
         const unsigned off = (((unsigned)b * (unsigned)p.H + (unsigned)gy) * (unsigned)p.W + (unsigned)gx) * (unsigned)drow +
                              (unsigned)(((c & 7) ^ wgd_key(col)) << 4);
-        wgd_dma(sx + XB + i * 4096, in ? DY + off : zero);
+        asr_lds_dma16(sx + XB + i * 4096, in ? DY + off : zero);
       }
     }
   };
@@ -236,13 +221,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgdArgs p) {
 
 int asr_conv3x3_wgrad_dma_launch(const WgdArgs& p, unsigned wgx, unsigned blocks_y, hipStream_t s) {
   const size_t lds = 2 * (size_t)STAGE;
-  static bool granted = false;          // the first (eager / warm-up) launch does it, never a captured one
-  if (!granted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wgrad_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-      return ASR_ELAUNCH;
-    granted = true;
-  }
+  if (asr_grant_lds<conv3x3_wgrad_dma_kernel>(lds) != hipSuccess) return ASR_ELAUNCH;
   WgdArgs q = p;
   q.wgx = (int)wgx; q.blocks_y = (int)blocks_y; q.xcd_order = 1;
   hipLaunchKernelGGL(conv3x3_wgrad_dma_kernel, dim3(wgx * blocks_y), dim3(256), lds, s, q);

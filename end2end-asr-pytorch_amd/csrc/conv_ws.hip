@@ -463,13 +463,7 @@ int ws_launch_t(WsArgs p, hipStream_t s) {
   }
   constexpr int FM = TH / (4 / (CO / 32));
   const size_t lds = (size_t)WS_NBUF * WS_PB + (MK == 1 ? 4 * FM * 1024 : 0) + CO * 4;
-  static bool granted = false;          // per instantiation; the first (eager / warm-up) launch does it, never a captured one
-  if (!granted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_ws128_kernel<CI, TH, CO, MK, EP, TM>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ASR_EUNSUPPORTED;
-    granted = true;
-  }
+  if (asr_grant_lds<conv3x3_ws128_kernel<CI, TH, CO, MK, EP, TM>>(lds) != hipSuccess) return ASR_EUNSUPPORTED;
   constexpr int per_cu = CI == 64 ? 2 : 1;
   const int64_t slots = (int64_t)cus * per_cu;         // 64 input channels: 144 registers of weights per wave, two workgroups per CU
   const int64_t items = EP == 2 ? nt / 2 : nt;

@@ -180,11 +180,7 @@ extern "C" int asr_ctc_fwd(const float* logits, int64_t ld, const int64_t* targe
   hipLaunchKernelGGL(ctc_lse_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, ld, rows, V, lse);
   ASR_LAUNCH_CHECK();
   const size_t lds = (size_t)3 * S * sizeof(float);
-  static bool granted = false;
-  if (lds > 48 * 1024 && !granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_lattice_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    granted = true;
-  }
+  if (lds > 48 * 1024) (void)asr_grant_lds<ctc_lattice_kernel>(64 * 1024);
   // both recursions in one launch (alpha and beta are independent): the backward pass only runs the gradient kernel
   hipLaunchKernelGGL(ctc_lattice_kernel, dim3(B, 2), dim3(256), lds, s, logits, ld, lse, targets, Lmax, input_lengths, target_lengths,
                      T, S, blank, alpha, beta, nll);
@@ -206,11 +202,7 @@ extern "C" int asr_ctc_bwd(const float* logits, int64_t ld, const int64_t* targe
   const float* alpha = lse + (int64_t)B * T;
   const float* beta = alpha + (int64_t)B * T * S;
   const float* nll = beta + (int64_t)B * T * S;
-  static bool granted = false;
-  if (lds > 48 * 1024 && !granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    granted = true;
-  }
+  if (lds > 48 * 1024) (void)asr_grant_lds<ctc_grad_kernel>(64 * 1024);
   AsrProfScope prof(ASR_OP_CE, s);
   hipLaunchKernelGGL(ctc_grad_kernel, dim3((unsigned)((int64_t)B * T)), dim3(256), lds, s, logits, ld, lse, targets, Lmax, input_lengths,
                      target_lengths, B, T, V, S, blank, alpha, beta, nll, grad_out, dlogits, ldo);

@@ -1,7 +1,7 @@
 // emb_cnn front end (reference: models/asr/transformer.py:33-40): Conv2d(1,32,(41,11),s=(2,2),p=(0,10)) + BatchNorm2d +
 // Hardtanh(0,20) + Conv2d(32,32,(21,11),s=(2,1)) + BatchNorm2d + Hardtanh(0,20).
 //
-// The two big-window strided convolutions are lowered to GEMMs on the existing MFMA kernels (gemm.hip):
+// The two big-window strided convolutions are lowered to GEMMs on the existing MFMA kernels (gemm_nt.hip, gemm_tn.hip):
 //   forward   y  = col  . W^T (+bias)          asr_gemm_nt     col = im2col(x), rows m = (b, oh, ow), k = (ky, kx, c)
 //   wgrad     dW += dy^T . col  (db fused)     asr_gemm_tn
 //   dgrad     dcol = dy . W ;  dx = col2im(dcol)   asr_gemm_nn + asr_col2im (gather form, no atomics)

@@ -1,13 +1,13 @@
 // Eight-wave GEMMs for the linear layers of the Transformer (reference: models/common_layers.py:136-142,181-198 nn.Linear /
 // Conv1d(k=1) through autograd): C = act(alpha A B^T + bias) ("NT", forward) and C (+)= (A B) [masked] ("NN", data gradient).
 //
-// Why a second family next to csrc/gemm.hip's four-wave kernels.  The model's contractions are SHORT (K = 512: 8 steps of 64) over
+// Why a second family next to the four-wave kernels of csrc/gemm_nt.hip / gemm_nn.hip.  The model's contractions are SHORT (K = 512: 8 steps of 64) over
 // 3200 - 6400 rows: a 64 x 64 or 128 x 64 block issues 64 - 128 MFMAs per wave in its whole life, so every launch is mostly
 // fill / drain (measured in the replayed step: 6400 x 2048 x 512 in 25 us = 530 TF/s, 3200 x 512 x 2048 in 31 us = 216 TF/s).
 // Here one 512-thread workgroup owns a 256 x 256 (or 128 x 128) block of C:
 //   * 8 waves as 2 (m) x 4 (n): a wave's quadrant is 128 x 64 (64 x 32), i.e. 64 (16) MFMAs per 64-deep step against 24 (12)
 //     16-byte operand reads -- two waves per SIMD, one reading while the other multiplies;
-//   * both operands come in by LDS-DMA (global_load_lds_dwordx4, hand-issued: csrc/gemm.hip tn_dma) in 128-byte rows, the
+//   * both operands come in by LDS-DMA (global_load_lds_dwordx4, hand-issued: asr_lds_dma16, csrc/common.h) in 128-byte rows, the
 //     16-byte slot XOR-ed with (row & 7) on the SOURCE side and again on the fragment read -- conflict-free ds_read_b128;
 //     NS stages in a ring with counted vmcnt, ONE s_barrier per step (the barrier that publishes step t also frees the
 //     buffer step t + NS - 1 is loaded into);
@@ -17,15 +17,6 @@
 #include "gemm_big.h"
 
 namespace {
-
-__device__ __forceinline__ void big_dma(unsigned lds_wave_base, const unsigned char* src) {
-  unsigned keep;      // M0 saved and restored: neutral for whatever the compiler keeps there
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "s"(lds_wave_base), "v"(src)
-               : "memory");
-}
-template <int N> __device__ __forceinline__ void big_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // One operand tile of R rows x 128 bytes: piece i of a thread = chunk c = i * 512 + tid -> (row c >> 3, slot c & 7); the source is
 // chunk slot ^ (row & 7) of global row (row0 + row), clamped to the last valid row (rows past the edge are never stored).
@@ -53,8 +44,8 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nt_kernel(BigGemmArgs p, int 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   // XCD-aware order: blocks b, b + 8, ... share an XCD (private L2) -> consecutive tiles (n fastest: they share their A rows)
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, qn = nwg >> 3, rn = nwg & 7;
-  const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int tile = asr_xcd_linear(bid, nwg);
   if (tile >= ntiles) return;
   const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
   const int nk = p.K / 64;
@@ -69,9 +60,9 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nt_kernel(BigGemmArgs p, int 
     const unsigned sl = wave_lds + (unsigned)((kt % NS) * STAGE);
     const int64_t kb = (int64_t)kt * 128;
 #pragma unroll
-    for (int i = 0; i < LA; ++i) big_dma(sl + i * 8192, srcA[i] + kb);
+    for (int i = 0; i < LA; ++i) asr_lds_dma16(sl + i * 8192, srcA[i] + kb);
 #pragma unroll
-    for (int i = 0; i < LB; ++i) big_dma(sl + TA + i * 8192, srcB[i] + kb);
+    for (int i = 0; i < LB; ++i) asr_lds_dma16(sl + TA + i * 8192, srcB[i] + kb);
   };
 
   f32x4_t acc[FM][FN];
@@ -90,9 +81,9 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nt_kernel(BigGemmArgs p, int 
   for (int kt = 0; kt < nk; ++kt) {
     // step kt has landed once at most the pieces of the later steps are outstanding (LPS per step and thread, retired in order)
     const int ahead = min(NS - 2, nk - 1 - kt);
-    if (NS >= 4 && ahead >= 2) big_wait_vmcnt<2 * LPS>();
-    else if (NS >= 3 && ahead >= 1) big_wait_vmcnt<LPS>();
-    else big_wait_vmcnt<0>();
+    if (NS >= 4 && ahead >= 2) asr_wait_vmcnt<2 * LPS>();
+    else if (NS >= 3 && ahead >= 1) asr_wait_vmcnt<LPS>();
+    else asr_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();              // step kt visible to every wave; every wave is done reading step kt - 1
     asm volatile("" ::: "memory");
     if (kt + NS - 1 < nk) stage(kt + NS - 1);   // into the buffer step kt - 1 used
@@ -184,11 +175,7 @@ void launch_nt(const BigGemmArgs& p, hipStream_t s) {
   constexpr int PASSES = (BM * OP > 140 * 1024) ? 2 : 1;
   constexpr size_t lds_stage = (size_t)NS * (BM + BN) * 128, lds_out = (size_t)(BM / PASSES) * OP;
   constexpr size_t lds = lds_stage > lds_out ? lds_stage : lds_out;
-  static bool granted = false;
-  if (!granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_nt_kernel<BM, BN, NS, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    granted = true;
-  }
+  (void)asr_grant_lds<gemm_big_nt_kernel<BM, BN, NS, TO>>(lds);
   const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN, ntiles = tiles_m * tiles_n;
   hipLaunchKernelGGL((gemm_big_nt_kernel<BM, BN, NS, TO>), dim3((unsigned)ntiles), dim3(512), lds, s, p, tiles_n, ntiles);
 }
@@ -210,8 +197,8 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
   const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, qn = nwg >> 3, rn = nwg & 7;
-  const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int tile = asr_xcd_linear(bid, nwg);
   if (tile >= ntiles) return;
   const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
   const int nk = p.K / 64;
@@ -233,9 +220,9 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
   auto stage = [&](int kt) __attribute__((always_inline)) {
     const unsigned sl = wave_lds + (unsigned)((kt % NS) * STAGE);
 #pragma unroll
-    for (int i = 0; i < LA; ++i) big_dma(sl + i * 8192, srcA[i] + (int64_t)kt * 128);
+    for (int i = 0; i < LA; ++i) asr_lds_dma16(sl + i * 8192, srcA[i] + (int64_t)kt * 128);
 #pragma unroll
-    for (int i = 0; i < LB; ++i) big_dma(sl + TA + i * 8192, srcB[i] + kt * stepB);
+    for (int i = 0; i < LB; ++i) asr_lds_dma16(sl + TA + i * 8192, srcB[i] + kt * stepB);
   };
 
   f32x4_t acc[FM][FN];
@@ -254,9 +241,9 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
     if (st < nk) stage(st);
   for (int kt = 0; kt < nk; ++kt) {
     const int ahead = min(NS - 2, nk - 1 - kt);
-    if (NS >= 4 && ahead >= 2) big_wait_vmcnt<2 * LPS>();
-    else if (NS >= 3 && ahead >= 1) big_wait_vmcnt<LPS>();
-    else big_wait_vmcnt<0>();
+    if (NS >= 4 && ahead >= 2) asr_wait_vmcnt<2 * LPS>();
+    else if (NS >= 3 && ahead >= 1) asr_wait_vmcnt<LPS>();
+    else asr_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (kt + NS - 1 < nk) stage(kt + NS - 1);
@@ -394,11 +381,7 @@ template <int NS>
 void launch_nn(const BigGemmArgs& p, hipStream_t s) {
   constexpr size_t lds_stage = (size_t)NS * (128 * 128 + 64 * 128 * 2), lds_out = (size_t)128 * (128 * 4 + 16);
   constexpr size_t lds = lds_stage > lds_out ? lds_stage : lds_out;
-  static bool granted = false;
-  if (!granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_nn_kernel<NS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    granted = true;
-  }
+  (void)asr_grant_lds<gemm_big_nn_kernel<NS>>(lds);
   const int tiles_m = (p.M + 127) / 128, tiles_n = (p.N + 127) / 128, ntiles = tiles_m * tiles_n;
   hipLaunchKernelGGL((gemm_big_nn_kernel<NS>), dim3((unsigned)ntiles), dim3(512), lds, s, p, tiles_n, ntiles);
 }
@@ -417,7 +400,7 @@ bool asr_gemm_big_nt(const BigGemmArgs& p, hipStream_t stream) {
   const int64_t t128 = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128);
   int tile = mode == 256 || mode == 128 ? mode : (p.out_f32 && p.N >= 2048 ? 256 : 128);
   constexpr int64_t kBigMin = 128;
-  if (tile == 128 && mode == 1 && t128 < (p.K >= 2048 ? 150 : kBigMin)) return false;      // too few blocks: 64 x 64 four-wave blocks (with their ring, gemm.hip launch_fast) fill the chip better -- 48 -> 128: headline 6.02 -> 5.98 ms
+  if (tile == 128 && mode == 1 && t128 < (p.K >= 2048 ? 150 : kBigMin)) return false;      // too few blocks: 64 x 64 four-wave blocks (with their ring, gemm_nt.hip launch_fast) fill the chip better -- 48 -> 128: headline 6.02 -> 5.98 ms
   if (tile == 256) {
     if (p.out_f32) launch_nt<256, 256, 2, float>(p, stream); else launch_nt<256, 256, 2, bf16_t>(p, stream);
   } else {

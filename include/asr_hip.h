@@ -109,7 +109,7 @@ int asr_permute_cols_tcf(const void* src, int64_t ld_src, void* dst, int64_t ld_
 /* What asr_gemm_tn_grouped would do with these n problems (host only, nothing is launched): returns 1 = one workgroup per WHOLE block of
  * dW, dispatched longest first, no atomics (splits[i] > 1: a block longer than a CU's share of the launch is cut into that many
  * slices of its rows), 0 = the shared-block forms of round 3 (equal pieces / slices, fp32 atomics) because whole blocks would leave
- * CUs idle; < 0 = error.  The dispatch is played through on 256 CUs for a few slice lengths (csrc/gemm.hip tn_rot_plan).        */
+ * CUs idle; < 0 = error.  The dispatch is played through on 256 CUs for a few slice lengths (csrc/gemm_tn.hip tn_rot_plan).        */
 int asr_gemm_tn_grouped_plan(int n, const int* M, const int* N, const int* K, int* splits);
 /* The data gradient that IS the attention backward's dO (the output projection's, models/common_layers.py:190-198 under autograd),
  * with the softmax backward's row term from the same epilogue: C (M, N) bf16 = A (M, K) . B (K, N) as asr_gemm_nn (alpha = 1, no mask,

@@ -48,12 +48,19 @@ def _ops(seg):
 
 @pytest.fixture(scope="module")
 def gemm_asm(tmp_path_factory):
-    return _asm(str(tmp_path_factory.mktemp("isa")), "gemm.hip")
+    """assembly of one of the GEMM translation units (gemm_nt.hip, gemm_nn.hip, gemm_tn.hip), assembled once per module"""
+    tmp, done = str(tmp_path_factory.mktemp("isa")), {}
+
+    def asm(name):
+        if name not in done:
+            done[name] = _asm(tmp, name)
+        return done[name]
+    return asm
 
 
 @pytest.mark.parametrize("kernel,pieces", [(r"gemm_nn_kernelIttLi64ELi3E", 4), (r"gemm_glds_kernelIttLi64ELi64ELi3E", 4)])
 def test_ring_kernels_keep_their_counted_waits(gemm_asm, kernel, pieces):
-    ops = _ops(_kernel(gemm_asm, kernel))
+    ops = _ops(_kernel(gemm_asm("gemm_nn.hip" if kernel.startswith("gemm_nn") else "gemm_nt.hip"), kernel))
     mf = [i for i, (o, _) in enumerate(ops) if o.startswith("v_mfma")]
     assert len(mf) == 8                                         # one 64-deep K step of a 32 x 32 quadrant: the loop is not unrolled
     # the main loop = everything up to the barrier that follows the last MFMA (the epilogue starts there)
@@ -68,12 +75,12 @@ def test_ring_kernels_keep_their_counted_waits(gemm_asm, kernel, pieces):
 
 @pytest.mark.parametrize("kernel", [r"gemm_tn256g_kernelILi3ELb1ELb1EE", r"gemm_tn256g_kernelILi3ELb1ELb0EE", r"gemm_tn256s_kernelILi3EE"])
 def test_grouped_weight_gradient_loop_reads_under_its_mfmas(gemm_asm, kernel):
-    """csrc/gemm.hip tn256r_body (round 5): the operand reads of stage s + 1 are hand-issued under the MFMAs of stage s with counted
+    """csrc/gemm_tn.hip tn256r_body (round 5): the operand reads of stage s + 1 are hand-issued under the MFMAs of stage s with counted
     s_waitcnt lgkmcnt.  That only holds while (a) nothing else uses lgkmcnt in the loop -- round 3's loop reloaded lda / ldb from the
     kernel arguments behind every barrier (s_load + s_waitcnt lgkmcnt(0)); (b) a fragment's registers are written by the reads and
     consumed by the MFMAs directly -- a compiler-inserted copy of a register whose read is still in flight would copy stale bits;
     (c) the ring position costs one add per fragment, not the three instructions per read of the old loop."""
-    ops = _ops(_kernel(gemm_asm, kernel))
+    ops = _ops(_kernel(gemm_asm("gemm_tn.hip"), kernel))
     mf = [i for i, (o, _) in enumerate(ops) if o.startswith("v_mfma")]
     assert len(mf) == 32                                            # one 32-row stage of a 64 x 128 quadrant, not unrolled
     # the stage loop (its basic blocks are not in source order: row 3 precedes the header): everything between the first and the last of

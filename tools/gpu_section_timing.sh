@@ -1,6 +1,6 @@
 #!/bin/bash
 # In-kernel section timing (s_memtime stamps of workgroup 0) of the level-0 forward kernel or of the grouped weight gradient.
-# asr_hip/libasr_hip_timing.so = the library with csrc/conv_level0.hip built -DL0_TIMING, or csrc/gemm.hip built -DTN_TIMING (by hand:
+# asr_hip/libasr_hip_timing.so = the library with csrc/conv_level0.hip built -DL0_TIMING, or csrc/gemm_tn.hip built -DTN_TIMING (by hand:
 # the other objects from asr_hip/_obj).  usage: tools/gpu_section_timing.sh <tag> level0|tn
 tag=${1:-sect}; what=${2:-level0}
 cd ${GRAFT_REPO_ROOT:-$(pwd)}; mkdir -p gpurun_out; export TMPDIR=/tmp

@@ -6,9 +6,16 @@
   tools/isa_identity.py compare BEFORE_DIR AFTER_DIR  per file: kernels before / after, the names removed, and how many surviving kernels
                                                       differ in instruction text or in their .amdhsa_* block (exit status 1 if any does,
                                                       or if AFTER has a kernel BEFORE has not)
+  tools/isa_identity.py compare --by-symbol BEFORE_DIR AFTER_DIR
+                                                      the same comparison over the union of the symbols of all files of each dump, for a
+                                                      change that moves kernels between files (same normalisation, same exit status rule,
+                                                      and a kernel that one dump defines in two files counts as differing)
 
 Kernels are split at their `_Z...:` labels.  The function index in local labels (.LBB<n>_<m>, .Lfunc_end<n>, ...) shifts when a
-neighbour is deleted, so it is normalised before the comparison."""
+neighbour is deleted, so it is normalised before the comparison.  hipcc gives a kernel in an anonymous namespace the same name
+(_ZN12_GLOBAL__N_1...) whatever file it is compiled in -- no per-file suffix is appended without -fgpu-rdc -- so --by-symbol matches
+the names as they are.  A __device__ variable in a header (a zero page) is a symbol of every file that uses it; identical copies are
+one symbol."""
 import argparse
 import importlib.util
 import os
@@ -108,6 +115,36 @@ def compare(before, after):
     return 1 if bad else 0
 
 
+def _union(d):
+    """({symbol: (text, amdhsa)} over all files of a dump, the symbols that two files define differently or as a kernel)."""
+    all_, twice = {}, set()
+    for f in sorted(os.listdir(d)):
+        if not f.endswith(".s"):
+            continue
+        for s, v in kernels(os.path.join(d, f)).items():
+            if s in all_ and (v[1] is not None or all_[s] != v):
+                twice.add(s)
+            all_[s] = v
+    return all_, twice
+
+
+def compare_by_symbol(before, after):
+    (kb, _), (ka, twice) = _union(before), _union(after)
+    removed, added = sorted(set(kb) - set(ka)), sorted(set(ka) - set(kb))
+    differ = [s for s in sorted(set(ka) & set(kb)) if ka[s] != kb[s] or s in twice]
+    for s in removed:
+        print("  removed  %s" % _demangle(s))
+    for s in added:
+        print("  ADDED    %s" % _demangle(s))
+    for s in differ:
+        what = [w for w, i in (("text", 0), ("amdhsa", 1)) if ka[s][i] != kb[s][i]] + (["defined in two files"] if s in twice else [])
+        print("  DIFFERS  %s (%s)" % (_demangle(s), ", ".join(what)))
+    nk = lambda k: sum(1 for v in k.values() if v[1] is not None)
+    print("all files: symbols %d -> %d (kernels %d -> %d), removed %d, added %d, %d differing" %
+          (len(kb), len(ka), nk(kb), nk(ka), len(removed), len(added), len(differ)))
+    return 1 if added or differ else 0
+
+
 def _demangle(sym):
     try:
         r = subprocess.run(["c++filt", sym], capture_output=True, text=True)
@@ -123,10 +160,11 @@ if __name__ == "__main__":
     d.add_argument("out")
     d.add_argument("--tree", default=ROOT)
     c = sub.add_parser("compare")
+    c.add_argument("--by-symbol", action="store_true")
     c.add_argument("before")
     c.add_argument("after")
     a = ap.parse_args()
     if a.cmd == "dump":
         dump(os.path.abspath(a.tree), a.out)
     else:
-        sys.exit(compare(a.before, a.after))
+        sys.exit((compare_by_symbol if a.by_symbol else compare)(a.before, a.after))

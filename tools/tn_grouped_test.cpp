@@ -1,4 +1,4 @@
-// Development harness for the grouped weight-gradient contraction (asr_gemm_tn_grouped; csrc/gemm.hip tn256_body / tn256r_body): the linear
+// Development harness for the grouped weight-gradient contraction (asr_gemm_tn_grouped; csrc/gemm_tn.hip tn256_body / tn256r_body): the linear
 // layers of configs[1] (4 + 4 layers, d_model 512, inner 2048, 6400 encoder / 3200 decoder rows) in the two launches the training step
 // issues, the equal-piece form (tuning TN_GROUP_TILE = 1; until round 6 also round 3's loop, removed since) against round 5's (operand reads of the next stage under the MFMAs): the same bits (the
 // accumulation order per element is the same), interleaved timing.  `big` adds configs[3]'s row counts (12 720 / 1600).
