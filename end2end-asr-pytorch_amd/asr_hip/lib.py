@@ -139,6 +139,16 @@ _SIGS = {
     "asr_lm_nll_chunks": (_I, [_I]),
     "asr_lm_nll_partials": (_I, [_P, _L, _P, _L, _P, _P, _I, _I, _I, _P, _P, _P]),
     "asr_lm_nll_finish": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "asr_lm_dropout": (_I, [_P, _L, _P, _P, _L, _I, _I, _F, _U64, _P]),
+    "asr_lstm_step_train": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _P, _P, _I, _I, _I, _L, _F, _U64, _P]),
+    "asr_lstm_bptt_step": (_I, [_P, _L, _P, _P, _L, _P, _L, _P, _P, _L, _P, _L, _I, _I, _I, _P]),
+    "asr_lm_train_loss": (_I, [_P, _I, _P, _I, _P, _P, _P]),
+    "asr_lm_dlogits": (_I, [_P, _L, _P, _L, _P, _P, _I, _I, _I, _F, _P, _L, _P]),
+    "asr_lm_sub_rows": (_I, [_P, _L, _P, _L, _P, _I, _I, _F, _P]),
+    "asr_lm_colsum": (_I, [_P, _L, _I, _I, _P, _P, _I, _P]),
+    "asr_lm_emb_grad": (_I, [_P, _L, _P, _P, _P, _I, _I, _F, _P, _L, _P]),
+    "asr_lm_sumsq_floats": (_I, []),
+    "asr_lm_sumsq": (_I, [_P, _L, _P, _P, _P]),
 }
 
 

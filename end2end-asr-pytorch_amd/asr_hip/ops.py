@@ -1391,6 +1391,71 @@ def lm_nll(h, w, bias, tgt, K, step_off, lens, per_token=False):
     return (nll_sum, nll_tok) if per_token else nll_sum
 
 
+# ------------------------------------------------------------------------------------------------ LSTM language model: training
+def lm_nll_train(h, w, bias, tgt, K):
+    """-> (loss device scalar = mean NLL over the M tokens, lse (M,)): asr_lm_nll_partials + a fixed-order finish."""
+    M, V = tgt.numel(), w.shape[0]
+    nchunk = L.load().asr_lm_nll_chunks(V)
+    part = torch.empty((M, nchunk, 2), device=h.device, dtype=torch.float32)
+    tgt_logit = torch.empty((M,), device=h.device, dtype=torch.float32)
+    L.call("asr_lm_nll_partials", L.ptr(h), h.stride(0), L.ptr(w), w.stride(0), L.ptr(bias), L.ptr(tgt), M, V, int(K), L.ptr(part),
+           L.ptr(tgt_logit), L.stream())
+    lse = torch.empty((M,), device=h.device, dtype=torch.float32)
+    loss = torch.empty((), device=h.device, dtype=torch.float32)
+    L.call("asr_lm_train_loss", L.ptr(part), nchunk, L.ptr(tgt_logit), M, L.ptr(lse), L.ptr(loss), L.stream())
+    return loss, lse
+
+
+def lm_dropout(x, out, C, p, seed, ids=None):
+    """out[:, :C] = dropout(x[ids] or x) by the counter hash of (seed, row * C + column); out may be x (a gradient, in place)."""
+    M = ids.numel() if ids is not None else x.shape[0]
+    L.call("asr_lm_dropout", L.ptr(x), x.stride(0), L.ptr(ids), L.ptr(out), out.stride(0), M, int(C), float(p), int(seed), L.stream())
+    return out
+
+
+def lstm_step_train(xproj, h_prev, whh, c_prev, c, h, gates, h_drop, h_next, n, n_next, H, row0, p, seed):
+    L.call("asr_lstm_step_train", L.ptr(xproj), xproj.stride(0), L.ptr(h_prev), 0 if h_prev is None else h_prev.stride(0), L.ptr(whh),
+           whh.stride(0), L.ptr(c_prev), L.ptr(c), c.stride(0), L.ptr(h), h.stride(0), L.ptr(gates), gates.stride(0), L.ptr(h_drop),
+           L.ptr(h_next), int(n), int(n_next), int(H), int(row0), float(p), int(seed), L.stream())
+
+
+def lstm_bptt_step(dh, dg_next, g, whh_t, c, c_prev, dc, n, n_next, H):
+    L.call("asr_lstm_bptt_step", L.ptr(dh), dh.stride(0), L.ptr(dg_next), L.ptr(g), g.stride(0), L.ptr(whh_t), whh_t.stride(0),
+           L.ptr(c), L.ptr(c_prev), c.stride(0), L.ptr(dc), dc.stride(0), int(n), int(n_next), int(H), L.stream())
+
+
+def lm_dlogits(h, w, bias, lse, K, inv_n, out):
+    """out = softmax(h w^T + bias) * inv_n for the tokens of h (the onehot half of the gradient: lm_sub_rows, lm_emb_grad)."""
+    L.call("asr_lm_dlogits", L.ptr(h), h.stride(0), L.ptr(w), w.stride(0), L.ptr(bias), L.ptr(lse), lse.numel(),
+           w.shape[0], int(K), float(inv_n), L.ptr(out), out.stride(0), L.stream())
+
+
+def lm_sub_rows(dh, w, tgt, C, inv_n):
+    L.call("asr_lm_sub_rows", L.ptr(dh), dh.stride(0), L.ptr(w), w.stride(0), L.ptr(tgt), tgt.numel(), int(C), float(inv_n), L.stream())
+
+
+def lm_colsum(x, N, out, out2=None, accumulate=False):
+    L.call("asr_lm_colsum", L.ptr(x), x.stride(0), x.shape[0], int(N), L.ptr(out), L.ptr(out2), int(accumulate), L.stream())
+
+
+def lm_emb_grad(dx, rows, seg_off, seg_word, E, demb, scale=1.0):
+    """demb[seg_word[k]] += scale * sum of dx[rows[seg_off[k] : seg_off[k + 1]]] (fixed order)."""
+    L.call("asr_lm_emb_grad", L.ptr(dx), dx.stride(0), L.ptr(rows), L.ptr(seg_off), L.ptr(seg_word), seg_word.numel(), int(E),
+           float(scale), L.ptr(demb), demb.stride(0), L.stream())
+
+
+def lm_sumsq(g, out):
+    part = torch.empty(L.load().asr_lm_sumsq_floats(), device=g.device, dtype=torch.float32)
+    L.call("asr_lm_sumsq", L.ptr(g), g.numel(), L.ptr(part), L.ptr(out), L.stream())
+
+
+def cast_weight_f32(src, dst=None, dst_t=None):
+    """fp32 (rows, cols) -> a copy with another leading dimension and / or the transpose (the LM's padded operand copies)."""
+    rows, cols = src.shape
+    L.call("asr_cast_weight", L.ptr(src), src.stride(0), L.ptr(dst), 0 if dst is None else dst.stride(0), L.ptr(dst_t),
+           0 if dst_t is None else dst_t.stride(0), rows, cols, L.F32, L.stream())
+
+
 # ------------------------------------------------------------------------------------------------ profiling
 def prof_enable(op, on=True):
     L.call("asr_prof_enable", int(op), int(on))

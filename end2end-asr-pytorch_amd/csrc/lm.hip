@@ -15,45 +15,11 @@
 //
 // The contraction operands have rows padded with zeros to a multiple of 16 floats (K16 16-wide steps) and 16-byte aligned
 // rows; row indices past the end of an operand are clamped (their results are discarded), so no load leaves the tensors.
-#include <math.h>
-
-#include "common.h"
+#include "lm_common.h"
 
 namespace {
 
 constexpr int LM_NLL_CHUNK = 256;     // vocabulary words per partial (one wave)
-
-// acc[i][j] += A[a0 + 16 i + (0..15)] . B[b0 + 16 j + (0..15)]^T over 16 * K16 columns.  D: row (A) = 4 (l >> 4) + reg,
-// column (B) = l & 15.  b_ids: B row r is b[b_ids[r]] (an embedding gather) when not null.
-template <int TM, int TN>
-__device__ __forceinline__ void lm_tile(const float* __restrict__ a, int64_t lda, int a_rows, int a0, const float* __restrict__ b,
-                                        int64_t ldb, const int32_t* __restrict__ b_ids, int b_rows, int b0, int K16,
-                                        f32x4_t (&acc)[TM][TN]) {
-  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-  const float* pa[TM];
-  const float* pb[TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) pa[i] = a + (int64_t)min(a0 + 16 * i + r, a_rows - 1) * lda + 4 * g;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    int row = min(b0 + 16 * j + r, b_rows - 1);
-    if (b_ids) row = b_ids[row];
-    pb[j] = b + (int64_t)row * ldb + 4 * g;
-  }
-  for (int kk = 0; kk < K16; ++kk) {
-    uint4 va[TM], vb[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) va[i] = *reinterpret_cast<const uint4*>(pa[i] + 16 * kk);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) vb[j] = *reinterpret_cast<const uint4*>(pb[j] + 16 * kk);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) mma16<float>(acc[i][j], va[i], vb[j]);
-  }
-}
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // 256 threads = 4 waves side by side along N; a wave owns 32 output columns x 64 tokens.
 __global__ __launch_bounds__(256) void lm_proj_kernel(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ ids,
@@ -188,8 +154,6 @@ __global__ __launch_bounds__(256) void lm_nll_finish_kernel(const float2* __rest
   acc = wave_sum(acc);
   if (lane == 0) nll_sum[s] = acc;
 }
-
-bool ok_rows(const void* p, int64_t ld) { return aligned16(p) && ld % 4 == 0; }
 
 }  // namespace
 

@@ -570,6 +570,53 @@ int asr_lm_nll_partials(const float* h, int64_t ldh, const float* w, int64_t ldw
 int asr_lm_nll_finish(const float* part, int nchunk, const float* tgt_logit, const int32_t* step_off, const int32_t* lens, int S,
                       float* nll_tok, float* nll_sum, asr_stream_t stream);
 
+/* ---- training of that language model (csrc/lm_train.hip; asr_hip/lm_train.py).  Same layouts and numerics.  No entry point below
+ * adds with atomics: every output element has one owner and a fixed summation order (a training step is reproducible to the bit).
+ * Dropout (RNNModel.forward's three sites): element (packed row m, column c) of a site with C columns survives, scaled by
+ * 1 / (1 - p), iff asr_keep(seed, m * C + c, threshold(p)); the caller gives every site and step its own seed.
+ *
+ * out (M, ldo)[:, :C] = dropout(x[ids[m]] or x[m]).  Forward of the embedding site; with ids == NULL and out == x the backward
+ * of any site, in place on the gradient.                                                                                    */
+int asr_lm_dropout(const float* x, int64_t ldx, const int32_t* ids, float* out, int64_t ldo, int M, int C, float p, uint64_t seed,
+                   asr_stream_t stream);
+/* asr_lstm_step that keeps what the backward needs.  c_prev / c: the cell states of the previous / this step (per-token storage,
+ * both ldc; c_prev == NULL with h_prev == NULL at the first step); gates (n, ldg): the ACTIVATED i f g o, unit-major;
+ * h_drop (ldh, optional): dropout(h) with index (row0 + m) * H + u; h_next (ldh, optional): h again for the rows < n_next, the caller
+ * pointing it at step t + 1 of a second buffer (row m of that buffer is then h_{t-1} of the sentence of packed row m).          */
+int asr_lstm_step_train(const float* xproj, int64_t ldx, const float* h_prev, int64_t ldhp, const float* whh, int64_t ldw,
+                        const float* c_prev, float* c, int64_t ldc, float* h, int64_t ldh, float* gates, int64_t ldg, float* h_drop,
+                        float* h_next, int n, int n_next, int H, int64_t row0, float p, uint64_t seed, asr_stream_t stream);
+/* One (layer, step) of back-propagation through time over the n rows running at step t, of which the first n_next run on:
+ * dh = dh_above (n, lddh) + [m < n_next] dg_next (n_next, ldg) W_hh, contracted over the 4H unit-major gate columns against
+ * whh_t = W_hh^T (H, ldwt), both zero-padded to 16 * ceil(4H / 16) columns; then dc = dh o (1 - tanh^2 c) + [m < n_next] dc[m],
+ * g (n, ldg) <- the gradients of the pre-activation gates (read as the activated gates of this step), dc[m] <- dc f.
+ * c_prev == NULL at t = 0.  One launch per step; no workgroup waits on another.                                              */
+int asr_lstm_bptt_step(const float* dh, int64_t lddh, const float* dg_next, float* g, int64_t ldg, const float* whh_t, int64_t ldwt,
+                       const float* c, const float* c_prev, int64_t ldc, float* dc, int64_t lddc, int n, int n_next, int H,
+                       asr_stream_t stream);
+/* From asr_lm_nll_partials' output: lse[m] = logsumexp(logits[m]) (chunks in index order, as asr_lm_nll_finish) and
+ * loss[0] = sum_m (lse[m] - tgt_logit[m]) / M in a fixed order.                                                              */
+int asr_lm_train_loss(const float* part, int nchunk, const float* tgt_logit, int M, float* lse, float* loss, asr_stream_t stream);
+/* The output layer's backward, softmax half: out (M, ldo >= 64 * ceil(V / 64)) = softmax(h W^T + bias) * inv_n for M tokens (a bounded
+ * chunk: the caller chooses M), the logits recomputed bit for bit as asr_lm_nll_partials computes them from lse = asr_lm_train_loss's;
+ * columns V .. 64 * ceil(V / 64) - 1 are zero.  The "- onehot(tgt)" half of the gradient is kept out of the GEMMs that follow (the V-long
+ * contraction of dh then adds terms of one magnitude): asr_lm_sub_rows for dh, asr_lm_emb_grad over the sorted targets with
+ * scale = -inv_n for the decoder weight (dx = h) and bias (dx = a column of ones, E = 1).                                     */
+int asr_lm_dlogits(const float* h, int64_t ldh, const float* w, int64_t ldw, const float* bias, const float* lse, int M, int V, int K,
+                   float inv_n, float* out, int64_t ldo, asr_stream_t stream);
+/* dh (M, ldd)[m, :C] -= w[tgt[m], :C] * inv_n                                                                                */
+int asr_lm_sub_rows(float* dh, int64_t ldd, const float* w, int64_t ldw, const int32_t* tgt, int M, int C, float inv_n,
+                    asr_stream_t stream);
+/* out[n] (+)= sum_m x[m * ld + n] in a fixed order; out2 (optional) receives the same values (bias_ih and bias_hh share one gradient) */
+int asr_lm_colsum(const float* x, int64_t ld, int M, int N, float* out, float* out2, int accumulate, asr_stream_t stream);
+/* Embedding gradient over token ids sorted by the host: segment k = the tokens rows[seg_off[k] .. seg_off[k + 1]) of word
+ * seg_word[k]; demb[seg_word[k]] += scale * (the sum of their dx rows in the order given).                                    */
+int asr_lm_emb_grad(const float* dx, int64_t ldx, const int32_t* rows, const int32_t* seg_off, const int32_t* seg_word, int nseg,
+                    int E, float scale, float* demb, int64_t ldd, asr_stream_t stream);
+/* out[0] = sum g^2 in a fixed order (asr_sumsq_acc adds its blocks with atomics); partials: asr_lm_sumsq_floats() floats.       */
+int asr_lm_sumsq_floats(void);
+int asr_lm_sumsq(const float* g, int64_t n, float* partials, float* out, asr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
