@@ -1,6 +1,8 @@
 """Per-kernel parity: every C-ABI entry point against the torch-CPU fp32 expression it replaces (seeded inputs).
 Tolerances: fp32 mode = fp32 round-off of a different summation order; bf16 mode = bf16 storage (8 mantissa bits) of
-inputs/outputs with fp32 accumulation.  Runs on the MI355X (`-m gpu`)."""
+inputs/outputs with fp32 accumulation.  Runs on the MI355X (`-m gpu`).
+What a tolerance cannot see in the GEMMs -- one dropped chunk on a tile edge, a bias one column off, a partial sum added twice -- is
+held by tests/test_gpu_gemm_exact.py: every arm of the GEMM dispatch on exact-integer data, bit for bit against float64."""
 import math
 
 import numpy as np

@@ -726,3 +726,22 @@ def test_train_cli_replays_graphs_by_default_for_vgg_cnn():
     assert resolved_for(["--feat_extractor", "", "--cuda"], _M("vgg_cnn")) == 64
     assert resolved_for(["--feat_extractor", "", "--cuda"], _Wrapped("emb_cnn")) == 64
     assert resolved_for(["--cuda", "--graph-buckets", "32"], _M("")) == 32
+
+
+def test_kernel_coverage_parser_counts_launches_per_symbol():
+    """tools/kernel_coverage.py (host only): a three-line kernel-trace CSV -- a mangled name with the `.kd` suffix and a demangled one
+    with a return type -- counted per symbol under either spelling; a symbol the trace does not name counts zero."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "tools", "kernel_coverage.py"))
+    kc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kc)
+    ring = "_ZN12_GLOBAL__N_116gemm_glds_kernelIttLi64ELi64ELi3EEEvNS_8GemmArgsE"
+    fold = "_ZN12_GLOBAL__N_116tn_reduce_kernelEPKfPfliiiii"
+    names = {ring: "void (anonymous namespace)::gemm_glds_kernel<unsigned short, unsigned short, 64, 64, 3>((anonymous namespace)::GemmArgs)",
+             fold: "(anonymous namespace)::tn_reduce_kernel(float const*, float*, long, int, int, int, int, int)"}
+    trace = ['"Kind","Agent_Id","Kernel_Id","Kernel_Name","Start_Timestamp","End_Timestamp"',
+             '"KERNEL_DISPATCH",4,7,"%s.kd",100,200' % ring,
+             '"KERNEL_DISPATCH",4,7,"void (anonymous namespace)::gemm_glds_kernel<unsigned short, unsigned short, 64, 64, 3>((anonymous namespace)::GemmArgs)",300,400']
+    counts = kc.launch_counts(trace)
+    assert sum(counts.values()) == 2
+    assert kc.coverage([ring, fold], names, counts) == {ring: 2, fold: 0}

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Which GEMM kernels does a test run launch?  (tests/test_gpu_gemm_exact.py pins every arm of the GEMM dispatch; this is the evidence.)
+
+  tools/kernel_coverage.py asm OUT_DIR                 compile the device side of the GEMM translation units (csrc/gemm_nt.hip, gemm_nn.hip,
+                                                       gemm_tn.hip, gemm_big.hip) to gfx950 assembly, as tools/isa_identity.py dump does for all
+  tools/kernel_coverage.py report ASM_DIR ALL.csv [--auto AUTO.csv] [--wall NAME=SECONDS ...]
+                                                       launches per GEMM kernel symbol (tools/isa_identity.py kernels() lists them per file) in
+                                                       the kernel-trace CSV of
+                                                         rocprofv3 --kernel-trace --stats -M -f csv -- python -m pytest tests/test_gpu_gemm_exact.py -q -m gpu
+                                                       and, with --auto, in the trace of the same command with `-k auto` (the cases that set
+                                                       no tuning hook); then the symbols never launched, and those launched only under a hook
+                                                       with the dispatch line that keeps them from the automatic choice.  Exit status 1 if a
+                                                       symbol was never launched.
+
+The trace is matched by mangled name (rocprofv3 -M; a trailing .kd is dropped) or, for a demangled trace, by the c++filt form with white
+space removed.  The counter run is a run of its own: no --pmc next to the tracing."""
+import argparse
+import collections
+import csv
+import os
+import re
+import subprocess
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import isa_identity  # noqa: E402
+
+GEMM_FILES = ("gemm_nt.hip", "gemm_nn.hip", "gemm_tn.hip", "gemm_big.hip")
+
+# kernels the automatic dispatch cannot choose: (substring of the demangled name, the line that decides)
+HOOK_ONLY = (
+    ("gemm_glds_kernel<float, float, 128, 128, 1>", "gemm_nt.hip dispatch_fast: 128 x 128 four-wave blocks only under GEMM_TILE = 0"),
+    ("gemm_glds_kernel<unsigned short, unsigned short, 128, 128, 1>", "gemm_nt.hip dispatch_fast: 128 x 128 four-wave blocks only under GEMM_TILE = 0"),
+    ("gemm_glds_kernel<unsigned short, float, 128, 128, 1>", "gemm_nt.hip dispatch_fast: 128 x 128 four-wave blocks only under GEMM_TILE = 0"),
+    ("gemm_glds_kernel<unsigned short, float, 128, 64, 1>", "gemm_nt.hip dispatch_fast: 128 x 64 needs sizeof(TO) == sizeof(T); else GEMM_TILE = 1"),
+    ("gemm_big_nt_kernel<256, 256, 2, unsigned short>", "gemm_big.hip asr_gemm_big_nt: 256 x 256 blocks for fp32 output only; bf16 under GEMM_BIG = 256"),
+    ("gemm_big_nt_kernel<128, 128, 3, unsigned short>", "gemm_big.hip asr_gemm_big_nt: ns is 2 or 4 unless GEMM_BIG_NS = 3"),
+    ("gemm_big_nn_kernel<3>", "gemm_big.hip asr_gemm_big_nn: ns is 2 or 4 unless GEMM_BIG_NS = 3"),
+    ("gemm_tn128g_kernel<3>", "gemm_tn.hip asr_gemm_tn_grouped: 128 x 128 grouped blocks only under TN_GROUP_TILE = 128"),
+)
+
+
+def dump_asm(out):
+    b = isa_identity._build_module(isa_identity.ROOT)
+    os.makedirs(out, exist_ok=True)
+    flags = [f for f in b.FLAGS if f != "-fPIC"]
+    for name in GEMM_FILES:
+        cmd = [b._hipcc()] + flags + b.PER_FILE_FLAGS.get(name, []) + ["--cuda-device-only", "-S", os.path.join(b.CSRC, name), "-o",
+                                                                      os.path.join(out, name + ".s")]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc failed for %s:\n%s" % (name, r.stderr[-4000:]))
+        print("assembled", name, flush=True)
+
+
+def gemm_kernels(asm_dir):
+    """[(file, mangled symbol)] of every __global__ kernel of the GEMM translation units (a symbol with an .amdhsa block)."""
+    out = []
+    for f in GEMM_FILES:
+        ks = isa_identity.kernels(os.path.join(asm_dir, f + ".s"))
+        out += [(f, s) for s in sorted(ks) if ks[s][1] is not None]
+    return out
+
+
+def demangle(symbols):
+    try:
+        r = subprocess.run(["c++filt"], input="\n".join(symbols), capture_output=True, text=True)
+        names = r.stdout.split("\n")[:len(symbols)]
+        if r.returncode == 0 and len(names) == len(symbols):
+            return dict(zip(symbols, names))
+    except OSError:
+        pass
+    return {s: s for s in symbols}
+
+
+def _key(name):
+    """What a kernel name is matched by: no `.kd` / clone suffix, no return type, no white space."""
+    name = re.sub(r"\s*\[clone [^\]]*\]$", "", name.strip())
+    name = re.sub(r"\.kd$", "", name)
+    if name.startswith("void "):
+        name = name[5:]
+    return re.sub(r"\s+", "", name)
+
+
+def launch_counts(lines):
+    """{matching key of a kernel name: dispatches} from the lines of a rocprofv3 kernel-trace CSV (an open file or a list of lines)."""
+    counts = collections.Counter()
+    for row in csv.DictReader(lines):
+        name = row.get("Kernel_Name") or row.get("KernelName") or row.get("Name")
+        if name:
+            counts[_key(name)] += 1
+    return counts
+
+
+def coverage(symbols, names, counts):
+    """{symbol: dispatches}: a symbol is counted under its mangled name and under its demangled one."""
+    out = {}
+    for s in symbols:
+        keys = {_key(s), _key(names.get(s, s))}
+        out[s] = sum(counts.get(k, 0) for k in keys)
+    return out
+
+
+def report(asm_dir, all_csv, auto_csv, walls):
+    ks = gemm_kernels(asm_dir)
+    syms = [s for _, s in ks]
+    names = demangle(syms)
+    with open(all_csv, newline="") as fh:
+        call = coverage(syms, names, launch_counts(fh))
+    cauto = None
+    if auto_csv:
+        with open(auto_csv, newline="") as fh:
+            cauto = coverage(syms, names, launch_counts(fh))
+    for w in walls:
+        print("wall time  %s s" % w.replace("=", "  "))
+    print("%-14s %9s %9s  kernel" % ("file", "launches", "no hook" if cauto is not None else ""))
+    for f, s in ks:
+        print("%-14s %9d %9s  %s" % (f, call[s], cauto[s] if cauto is not None else "", names[s]))
+    never = [s for s in syms if call[s] == 0]
+    print("\nGEMM kernel symbols: %d, launched: %d, never launched: %d" % (len(syms), len(syms) - len(never), len(never)))
+    for s in never:
+        print("  NEVER  %s" % names[s])
+    if cauto is not None:
+        hook = [s for s in syms if call[s] > 0 and cauto[s] == 0]
+        print("launched only with a tuning hook set: %d" % len(hook))
+        for s in hook:
+            why = [w for sub, w in HOOK_ONLY if sub in names[s]]
+            print("  HOOK   %s\n         %s" % (names[s], why[0] if why else "NOT EXPLAINED: a case without a hook should reach it"))
+    return 1 if never else 0
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    a_ = sub.add_parser("asm")
+    a_.add_argument("out")
+    r_ = sub.add_parser("report")
+    r_.add_argument("asm_dir")
+    r_.add_argument("all_csv")
+    r_.add_argument("--auto")
+    r_.add_argument("--wall", action="append", default=[])
+    a = ap.parse_args()
+    if a.cmd == "asm":
+        dump_asm(a.out)
+    else:
+        sys.exit(report(a.asm_dir, a.all_csv, a.auto, a.wall))
