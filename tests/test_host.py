@@ -745,3 +745,31 @@ def test_kernel_coverage_parser_counts_launches_per_symbol():
     counts = kc.launch_counts(trace)
     assert sum(counts.values()) == 2
     assert kc.coverage([ring, fold], names, counts) == {ring: 2, fold: 0}
+
+
+def test_kernel_coverage_attention_family_names_three_translation_units():
+    """tools/kernel_coverage.py --family attention (host only): the family is the three attention translation units; a trace row of a
+    kernel in a nested anonymous namespace (asr_attn::(anonymous namespace)::..., two int arguments after the struct) is counted under its
+    mangled and its demangled spelling; the kernels that only a one-part asr_attn_bwd call reaches are named in PARTS_ONLY."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "tools", "kernel_coverage.py"))
+    kc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kc)
+    assert kc.FAMILIES["attention"] == ("attention.hip", "attention_fast.hip", "attention_pp.hip") and kc.FAMILIES["gemm"] == kc.GEMM_FILES
+    for f in kc.FAMILIES["attention"]:
+        assert os.path.exists(os.path.join(ROOT, "end2end-asr-pytorch_amd", "csrc", f)), f
+    both = "_ZN8asr_attn12_GLOBAL__N_129attn_bwd_both_bf16_d64_kernelILi1EEEvNS_8AttnArgsEi"
+    dq = "_ZN8asr_attn12_GLOBAL__N_127attn_bwd_dq_bf16_d64_kernelILi1EEEvNS_8AttnArgsE"
+    pp = "_ZN8asr_attn12_GLOBAL__N_127attn_fwd_pp_bf16_d64_kernelILb1ELi4EEEvNS_8AttnArgsEiii"
+    names = {both: "void asr_attn::(anonymous namespace)::attn_bwd_both_bf16_d64_kernel<1>(asr_attn::AttnArgs, int)",
+             dq: "void asr_attn::(anonymous namespace)::attn_bwd_dq_bf16_d64_kernel<1>(asr_attn::AttnArgs)",
+             pp: "void asr_attn::(anonymous namespace)::attn_fwd_pp_bf16_d64_kernel<true, 4>(asr_attn::AttnArgs, int, int, int)"}
+    trace = ['"Kind","Agent_Id","Kernel_Id","Kernel_Name","Start_Timestamp","End_Timestamp"',
+             '"KERNEL_DISPATCH",4,7,"%s.kd",100,200' % both,
+             '"KERNEL_DISPATCH",4,8,"%s",300,400' % names[both],
+             '"KERNEL_DISPATCH",4,9,"void asr_attn::(anonymous namespace)::attn_fwd_pp_bf16_d64_kernel<true, 4>(asr_attn::AttnArgs, int, int, int) [clone .kd]",500,600',
+             '"KERNEL_DISPATCH",4,9,"void asr_attn::(anonymous namespace)::attn_fwd_pp_bf16_d64_kernel<false, 4>(asr_attn::AttnArgs, int, int, int)",700,800']
+    counts = kc.launch_counts(trace)
+    assert sum(counts.values()) == 4
+    assert kc.coverage([both, dq, pp], names, counts) == {both: 2, dq: 0, pp: 1}
+    assert any(sub in names[dq] for sub, _ in kc.PARTS_ONLY) and not any(sub in names[both] for sub, _ in kc.PARTS_ONLY)

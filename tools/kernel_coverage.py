@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Which GEMM kernels does a test run launch?  (tests/test_gpu_gemm_exact.py pins every arm of the GEMM dispatch; this is the evidence.)
+"""Which GEMM (or, with --family attention, attention) kernels does a test run launch?  (tests/test_gpu_gemm_exact.py pins every arm of the
+GEMM dispatch, tests/test_gpu_attention_arms.py every arm of the attention dispatch; this is the evidence.)
 
   tools/kernel_coverage.py asm OUT_DIR                 compile the device side of the GEMM translation units (csrc/gemm_nt.hip, gemm_nn.hip,
                                                        gemm_tn.hip, gemm_big.hip) to gfx950 assembly, as tools/isa_identity.py dump does for all
@@ -13,7 +14,9 @@
                                                        symbol was never launched.
 
 The trace is matched by mangled name (rocprofv3 -M; a trailing .kd is dropped) or, for a demangled trace, by the c++filt form with white
-space removed.  The counter run is a run of its own: no --pmc next to the tracing."""
+space removed.  With `--family attention` both commands cover csrc/attention.hip, attention_fast.hip and attention_pp.hip, and the trace is that
+of tests/test_gpu_attention_arms.py (no tuning hook selects an attention kernel there: PARTS_ONLY lists the kernels that only a call with one
+of ASR_ATTN_DQ / ASR_ATTN_DKV reaches).  The counter run is a run of its own: no --pmc next to the tracing."""
 import argparse
 import collections
 import csv
@@ -26,6 +29,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_identity  # noqa: E402
 
 GEMM_FILES = ("gemm_nt.hip", "gemm_nn.hip", "gemm_tn.hip", "gemm_big.hip")
+ATTENTION_FILES = ("attention.hip", "attention_fast.hip", "attention_pp.hip")
+FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES}
+LABEL = {"gemm": "GEMM", "attention": "attention"}
 
 # kernels the automatic dispatch cannot choose: (substring of the demangled name, the line that decides)
 HOOK_ONLY = (
@@ -39,12 +45,18 @@ HOOK_ONLY = (
     ("gemm_tn128g_kernel<3>", "gemm_tn.hip asr_gemm_tn_grouped: 128 x 128 grouped blocks only under TN_GROUP_TILE = 128"),
 )
 
+# attention kernels that ops.attn_bwd never chooses (it asks for dQ and dK / dV in one launch): reached by a direct asr_attn_bwd call with one part
+PARTS_ONLY = (
+    ("attn_bwd_dq_bf16_d64_kernel<1>", "attention_fast.hip attn_fast_bwd: dQ alone only when parts has ASR_ATTN_DQ without ASR_ATTN_DKV"),
+    ("attn_bwd_dkv_bf16_d64_kernel<1>", "attention_fast.hip attn_fast_bwd: dK / dV alone only when parts has ASR_ATTN_DKV without ASR_ATTN_DQ"),
+)
 
-def dump_asm(out):
+
+def dump_asm(out, files=GEMM_FILES):
     b = isa_identity._build_module(isa_identity.ROOT)
     os.makedirs(out, exist_ok=True)
     flags = [f for f in b.FLAGS if f != "-fPIC"]
-    for name in GEMM_FILES:
+    for name in files:
         cmd = [b._hipcc()] + flags + b.PER_FILE_FLAGS.get(name, []) + ["--cuda-device-only", "-S", os.path.join(b.CSRC, name), "-o",
                                                                       os.path.join(out, name + ".s")]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -53,10 +65,10 @@ def dump_asm(out):
         print("assembled", name, flush=True)
 
 
-def gemm_kernels(asm_dir):
-    """[(file, mangled symbol)] of every __global__ kernel of the GEMM translation units (a symbol with an .amdhsa block)."""
+def family_kernels(asm_dir, files=GEMM_FILES):
+    """[(file, mangled symbol)] of every __global__ kernel of the family's translation units (a symbol with an .amdhsa block)."""
     out = []
-    for f in GEMM_FILES:
+    for f in files:
         ks = isa_identity.kernels(os.path.join(asm_dir, f + ".s"))
         out += [(f, s) for s in sorted(ks) if ks[s][1] is not None]
     return out
@@ -101,8 +113,8 @@ def coverage(symbols, names, counts):
     return out
 
 
-def report(asm_dir, all_csv, auto_csv, walls):
-    ks = gemm_kernels(asm_dir)
+def report(asm_dir, all_csv, auto_csv, walls, family="gemm"):
+    ks = family_kernels(asm_dir, FAMILIES[family])
     syms = [s for _, s in ks]
     names = demangle(syms)
     with open(all_csv, newline="") as fh:
@@ -113,13 +125,18 @@ def report(asm_dir, all_csv, auto_csv, walls):
             cauto = coverage(syms, names, launch_counts(fh))
     for w in walls:
         print("wall time  %s s" % w.replace("=", "  "))
-    print("%-14s %9s %9s  kernel" % ("file", "launches", "no hook" if cauto is not None else ""))
+    print("%-18s %9s %9s  kernel" % ("file", "launches", "no hook" if cauto is not None else ""))
     for f, s in ks:
-        print("%-14s %9d %9s  %s" % (f, call[s], cauto[s] if cauto is not None else "", names[s]))
+        print("%-18s %9d %9s  %s" % (f, call[s], cauto[s] if cauto is not None else "", names[s]))
     never = [s for s in syms if call[s] == 0]
-    print("\nGEMM kernel symbols: %d, launched: %d, never launched: %d" % (len(syms), len(syms) - len(never), len(never)))
+    print("\n%s kernel symbols: %d, launched: %d, never launched: %d" % (LABEL[family], len(syms), len(syms) - len(never), len(never)))
     for s in never:
         print("  NEVER  %s" % names[s])
+    if family == "attention":
+        for sub, why in PARTS_ONLY:
+            for s in syms:
+                if sub in names[s]:
+                    print("  PARTS  %s: %d launches\n         %s" % (names[s], call[s], why))
     if cauto is not None:
         hook = [s for s in syms if call[s] > 0 and cauto[s] == 0]
         print("launched only with a tuning hook set: %d" % len(hook))
@@ -134,13 +151,15 @@ if __name__ == "__main__":
     sub = ap.add_subparsers(dest="cmd", required=True)
     a_ = sub.add_parser("asm")
     a_.add_argument("out")
+    a_.add_argument("--family", choices=sorted(FAMILIES), default="gemm")
     r_ = sub.add_parser("report")
     r_.add_argument("asm_dir")
     r_.add_argument("all_csv")
     r_.add_argument("--auto")
     r_.add_argument("--wall", action="append", default=[])
+    r_.add_argument("--family", choices=sorted(FAMILIES), default="gemm")
     a = ap.parse_args()
     if a.cmd == "asm":
-        dump_asm(a.out)
+        dump_asm(a.out, FAMILIES[a.family])
     else:
-        sys.exit(report(a.asm_dir, a.all_csv, a.auto, a.wall))
+        sys.exit(report(a.asm_dir, a.all_csv, a.auto, a.wall, a.family))
