@@ -285,7 +285,9 @@ void launch_bwd(const T* dout, const T* z, const float* mean, const float* rstd,
   int rpb = 8;
   int nblk = (M + rpb - 1) / rpb;
   if (!ws || ws_floats < (int64_t)nblk * 2 * D) { rpb = 32; nblk = (M + rpb - 1) / rpb; ws = nullptr; }
-  hipLaunchKernelGGL((add_ln_bwd_kernel<T, NCH>), dim3(nblk), dim3(256), (size_t)3 * 2 * D * sizeof(float), s, dout, z,
+  const size_t lds = (size_t)3 * 2 * D * sizeof(float);            // 96 KB at the widest bf16 row (D = 4096): above the default limit
+  if (lds > 48 * 1024) (void)asr_grant_lds<add_ln_bwd_kernel<T, NCH>>(lds);
+  hipLaunchKernelGGL((add_ln_bwd_kernel<T, NCH>), dim3(nblk), dim3(256), lds, s, dout, z,
                      mean, rstd, gamma, keep, d_res, d_y, dgamma, dbeta, ws, M, D, rpb, thr, inv, seed, seed_dev);
   if (ws && reduce) {
     const int slices = nblk >= 512 ? 64 : (nblk >= 64 ? 16 : 1);      // ~13 partial rows per thread
@@ -374,7 +376,9 @@ extern "C" int asr_add_ln_bwd_partials(const void* dout, const void* z, const fl
 
 extern "C" int asr_ln_reduce_multi(const float* const* workspaces, const int* rows, float* const* dgamma, float* const* dbeta, int n,
                                    int D, hipStream_t s) {
-  ASR_CHECK_ARG(n >= 0 && D > 0 && D % 2 == 0 && (n == 0 || (workspaces && rows && dgamma && dbeta)));     // (16-byte partial rows)
+  // D % 4: a thread adds four consecutive columns of [dgamma | dbeta] with 16-byte loads; a group must not straddle column D (it would
+  // run past the end of dgamma and miss dbeta[0 .. 1]), and the partial rows (2 * D floats) must stay 16-byte aligned
+  ASR_CHECK_ARG(n >= 0 && D > 0 && D % 4 == 0 && (n == 0 || (workspaces && rows && dgamma && dbeta)));
   for (int i0 = 0; i0 < n; i0 += LN_MULTI) {
     LnMultiArgs a{};
     const int cnt = n - i0 < LN_MULTI ? n - i0 : LN_MULTI;

@@ -175,7 +175,9 @@ int asr_add_ln_bwd(const void* dout, const void* z, const float* mean, const flo
 /* The same with the second stage postponed: asr_add_ln_bwd_partials leaves the per-block column partials in `workspace`
  * (required, asr_add_ln_bwd_workspace(M, D) floats, alive until the reduction), asr_ln_reduce_multi adds the partials of n layers
  * (rows[i] = that layer's M) into their dgamma / dbeta in ONE launch -- the parameter gradients are not on backward's critical
- * path, 21 seven-microsecond launches per step are (host arrays of n pointers; the kernel arguments carry them by value).   */
+ * path, 21 seven-microsecond launches per step are (host arrays of n pointers; the kernel arguments carry them by value).
+ * asr_ln_reduce_multi needs D % 4 == 0 (it adds four consecutive columns of [dgamma | dbeta] at a time) and refuses any other D
+ * with ASR_EINVAL.                                                                                                             */
 int asr_add_ln_bwd_partials(const void* dout, const void* z, const float* mean, const float* rstd, const float* gamma,
                             const uint8_t* row_keep, void* d_res, void* d_y, float* workspace, int64_t workspace_floats, int M,
                             int D, float dropout_p, uint64_t seed, const uint64_t* seed_dev, int dtype, asr_stream_t stream);
