@@ -256,3 +256,15 @@ def call(name, *args):
     rc = fn(*args)
     if rc != 0:
         check(rc, name)
+
+
+def call_or_none(name, *args):
+    """call() for an entry point that may decline a shape: False on ASR_EUNSUPPORTED (the caller returns None or takes its fallback),
+    True when it ran; any other error raises."""
+    fn = _fn_cache.get(name)
+    if fn is None:
+        fn = _fn_cache[name] = getattr(load(), name)
+    rc = fn(*args)
+    if rc != 0 and rc != EUNSUPPORTED:
+        check(rc, name)
+    return rc == 0

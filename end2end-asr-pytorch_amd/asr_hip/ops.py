@@ -190,16 +190,14 @@ def gemm_tn_grouped(grp):
             return
     n = len(grp)
     P_, L_, I_ = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
-    rc = L.load().asr_gemm_tn_grouped(
-        n, P_(*[e[0].data_ptr() for e in grp]), L_(*[e[0].stride(0) for e in grp]), P_(*[e[1].data_ptr() for e in grp]),
+    ok = L.call_or_none(
+        "asr_gemm_tn_grouped", n, P_(*[e[0].data_ptr() for e in grp]), L_(*[e[0].stride(0) for e in grp]), P_(*[e[1].data_ptr() for e in grp]),
         L_(*[e[1].stride(0) for e in grp]), P_(*[e[2].data_ptr() for e in grp]), L_(*[e[2].stride(0) for e in grp]),
         P_(*[(e[3].data_ptr() if e[3] is not None else None) for e in grp]), I_(*[e[0].shape[0] for e in grp]),
         I_(*[e[4] for e in grp]), I_(*[e[5] for e in grp]), L.dt(grp[0][0]), L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not ok:
         for dy, x, dw, db, N, K in grp:
             gemm_tn(dy, x, dw, colsum_acc=db, N=N, K=K)
-    else:
-        L.check(rc, "asr_gemm_tn_grouped")
 
 
 def join_deferred():
@@ -284,11 +282,9 @@ def gemm_nn_rowdot(dy, w, o, o32, T):
         return None
     dx = torch.empty((M, K), device=dy.device, dtype=dy.dtype)
     rowdot = torch.empty((M // T, K // 64, T), device=dy.device, dtype=torch.float32)
-    rc = L.load().asr_gemm_nn_rowdot(L.ptr(dy), dy.stride(0), L.ptr(w), w.stride(0), L.ptr(dx), L.ptr(o), L.ptr(o32), L.ptr(rowdot),
-                                     M, K, N, T, L.dt(dy), L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_gemm_nn_rowdot", L.ptr(dy), dy.stride(0), L.ptr(w), w.stride(0), L.ptr(dx), L.ptr(o), L.ptr(o32), L.ptr(rowdot), M,
+                          K, N, T, L.dt(dy), L.stream()):
         return None
-    L.check(rc, "asr_gemm_nn_rowdot")
     return dx, rowdot
 
 
@@ -964,11 +960,9 @@ def conv3x3_relu_bits(x, wk, bias, Cout):
         return None
     y = torch.empty((B, H, W, Cout), device=x.device, dtype=x.dtype)
     bits = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
-    rc = L.load().asr_conv3x3_igemm_bits(L.ptr(x), L.ptr(wk), L.ptr(bias), None, L.ptr(y), L.ptr(bits), B, H, W, Cin, Cout, 1, L.dt(x),
-                                         L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_conv3x3_igemm_bits", L.ptr(x), L.ptr(wk), L.ptr(bias), None, L.ptr(y), L.ptr(bits), B, H, W, Cin, Cout, 1, L.dt(x),
+                          L.stream()):
         return None
-    L.check(rc, "asr_conv3x3_igemm_bits")
     return y, bits
 
 
@@ -977,11 +971,9 @@ def conv3x3_masked_by_bits(x, wk, bias, Cout, bits, relu=False):
     B, H, W, Cin = x.shape
     assert x.is_contiguous()
     y = torch.empty((B, H, W, Cout), device=x.device, dtype=x.dtype)
-    rc = L.load().asr_conv3x3_igemm_bits(L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(bits), L.ptr(y), None, B, H, W, Cin, Cout, int(relu),
-                                         L.dt(x), L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_conv3x3_igemm_bits", L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(bits), L.ptr(y), None, B, H, W, Cin, Cout, int(relu),
+                          L.dt(x), L.stream()):
         return None
-    L.check(rc, "asr_conv3x3_igemm_bits")
     return y
 
 
@@ -992,12 +984,10 @@ def conv3x3_relu_pool(x, wk, bias, Cout):
     assert x.is_contiguous()
     y = torch.empty((B, H, W, Cout), device=x.device, dtype=x.dtype)
     pool = torch.empty((B, H // 2, W // 2, Cout), device=x.device, dtype=x.dtype)
-    rc = L.load().asr_conv3x3_relu_pool(L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(y), L.ptr(pool), B, H, W, Cin, Cout, L.dt(x),
-                                        L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_conv3x3_relu_pool", L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(y), L.ptr(pool), B, H, W, Cin, Cout, L.dt(x),
+                          L.stream()):
         y = conv3x3(x, wk, bias, Cout, relu=True)
         return y, maxpool_fwd(y)
-    L.check(rc, "asr_conv3x3_relu_pool")
     return y, pool
 
 
@@ -1010,11 +1000,9 @@ def conv3x3_relu_pool_code(x, wk, bias, Cout, keep_y=False):
     y = torch.empty((B, H, W, Cout), device=x.device, dtype=x.dtype) if keep_y else None
     pool = torch.empty((B, H // 2, W // 2, Cout), device=x.device, dtype=x.dtype)
     code = torch.empty((B, H // 2, W // 2, Cout), device=x.device, dtype=torch.uint8)
-    rc = L.load().asr_conv3x3_relu_pool_code(L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(y), L.ptr(pool), L.ptr(code), B, H, W, Cin, Cout,
-                                             L.dt(x), L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_conv3x3_relu_pool_code", L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(y), L.ptr(pool), L.ptr(code), B, H, W, Cin, Cout,
+                          L.dt(x), L.stream()):
         return None
-    L.check(rc, "asr_conv3x3_relu_pool_code")
     return y, pool, code
 
 
@@ -1027,10 +1015,9 @@ def vgg_level0_fwd(src, w0, b0, wk2, b2):
     B, H, W = src3.shape
     pool = torch.empty((B, H // 2, W // 2, 64), device=src.device, dtype=torch.bfloat16)
     code = torch.empty((B, H // 2, W // 2, 64), device=src.device, dtype=torch.uint8)
-    rc = L.load().asr_vgg_level0_fwd(L.ptr(src3), L.ptr(w0), L.ptr(b0), L.ptr(wk2), L.ptr(b2), L.ptr(pool), L.ptr(code), B, H, W, L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_vgg_level0_fwd", L.ptr(src3), L.ptr(w0), L.ptr(b0), L.ptr(wk2), L.ptr(b2), L.ptr(pool), L.ptr(code), B, H, W,
+                          L.stream()):
         return None
-    L.check(rc, "asr_vgg_level0_fwd")
     return pool, code
 
 
@@ -1069,11 +1056,9 @@ def conv3x3_relu_pool_tcf_code(x, wk, bias, Cout, code_cl=False):
     assert x.is_contiguous()
     pool = torch.empty((B, W // 2, Cout * (H // 2)), device=x.device, dtype=x.dtype)
     code = torch.empty((B, W // 2, H // 2, Cout) if code_cl else (B, W // 2, Cout * (H // 2)), device=x.device, dtype=torch.uint8)
-    fn = L.load().asr_conv3x3_relu_pool_tcf_codecl if code_cl else L.load().asr_conv3x3_relu_pool_tcf_code
-    rc = fn(L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(pool), L.ptr(code), B, H, W, Cin, Cout, L.dt(x), L.stream())
-    if rc == L.EUNSUPPORTED:
+    name = "asr_conv3x3_relu_pool_tcf_codecl" if code_cl else "asr_conv3x3_relu_pool_tcf_code"
+    if not L.call_or_none(name, L.ptr(x), L.ptr(wk), L.ptr(bias), L.ptr(pool), L.ptr(code), B, H, W, Cin, Cout, L.dt(x), L.stream()):
         return None
-    L.check(rc, "asr_conv3x3_relu_pool_tcf_code")
     return pool, code
 
 
@@ -1095,11 +1080,9 @@ def gemm_nn_poolbwd(dy2d, w_perm, code_cl, x_shape):
             w_perm.stride(1) != 1 or tuple(code_cl.shape) != (B, W2, H2, C) or not code_cl.is_contiguous()):
         return None
     dx = torch.empty(x_shape, device=dy2d.device, dtype=dy2d.dtype)
-    rc = L.load().asr_gemm_nn_poolbwd(L.ptr(dy2d), dy2d.stride(0), L.ptr(w_perm), w_perm.stride(0), L.ptr(code_cl), L.ptr(dx), M, K, H2, W2,
-                                      C, L.dt(dy2d), L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_gemm_nn_poolbwd", L.ptr(dy2d), dy2d.stride(0), L.ptr(w_perm), w_perm.stride(0), L.ptr(code_cl), L.ptr(dx), M, K, H2,
+                          W2, C, L.dt(dy2d), L.stream()):
         return None
-    L.check(rc, "asr_gemm_nn_poolbwd")
     return dx
 
 
@@ -1109,10 +1092,8 @@ def maxpool_fwd_code(x, tcf=False):
     shape = (B, W // 2, C * (H // 2)) if tcf else (B, H // 2, W // 2, C)
     y = torch.empty(shape, device=x.device, dtype=x.dtype)
     code = torch.empty(shape, device=x.device, dtype=torch.uint8)
-    rc = L.load().asr_maxpool_fwd_code(L.ptr(x), L.ptr(y), L.ptr(code), B, H, W, C, int(tcf), L.dt(x), L.stream())
-    if rc == L.EUNSUPPORTED:
+    if not L.call_or_none("asr_maxpool_fwd_code", L.ptr(x), L.ptr(y), L.ptr(code), B, H, W, C, int(tcf), L.dt(x), L.stream()):
         return None
-    L.check(rc, "asr_maxpool_fwd_code")
     return y, code
 
 

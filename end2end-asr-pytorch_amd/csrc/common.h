@@ -188,14 +188,30 @@ static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0;
 // Raises the dynamic-LDS limit of Kernel to `bytes` unless an earlier call granted as much.  One flag per KERNEL (a non-type template
 // parameter: kernels that share a signature do not share it).  hipFuncSetAttribute must not run inside a stream capture: the first
 // (eager / warm-up) launch of a kernel gets here.  A refused grant is reported by the return value, not left behind for the next
-// launch check, and is asked for again by the next call.
-template <auto Kernel> hipError_t asr_grant_lds(size_t bytes) {
+// launch check, and is asked for again by the next call.  (Hidden, like asr_launch: a kernel with external linkage would otherwise put
+// its instantiation and the flag among the library's exported symbols.)
+template <auto Kernel> __attribute__((visibility("hidden"))) hipError_t asr_grant_lds(size_t bytes) {
   static size_t granted = 0;
   if (bytes <= granted) return hipSuccess;
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e == hipSuccess) granted = bytes;
   else (void)hipGetLastError();
   return e;
+}
+
+// One launch: the dynamic-LDS grant when `lds` is above the 48 KB every kernel has (its result ignored: a refused grant shows as a
+// failed launch), the launch, the launch check.
+template <auto Kernel, class... A> __attribute__((visibility("hidden"))) int asr_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, A... a) {
+  if (lds > 48 * 1024) (void)asr_grant_lds<Kernel>(lds);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, a...);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
+}
+// f(T{}) with the storage type T of `dtype` (a tag: only its type is used, as `using T = decltype(tag)`); ASR_EINVAL for any other dtype
+template <class F> int asr_with_dtype(int dtype, F&& f) {
+  if (dtype == ASR_F32) return f(float{});
+  if (dtype == ASR_BF16) return f(bf16_t{});
+  return ASR_EINVAL;
 }
 
 // tuning switch set through asr_set_tuning (prof.hip), or `dflt`; the library itself reads no environment variables

@@ -1,4 +1,4 @@
-// Internal interface between conv.hip (asr_conv1_wgrad dispatch) and conv1_wgrad_mfma.hip (bf16 storage mode, 64 channels).
+// Internal interface between conv1.hip (asr_conv1_wgrad dispatch) and conv1_wgrad_mfma.hip (bf16 storage mode, 64 channels).
 #pragma once
 #include "common.h"
 

@@ -1,6 +1,6 @@
 // Weight / bias gradient of vgg_cnn's first layer (1 -> 64 channels, 3x3; reference: autograd of models/asr/transformer.py:43-44)
 // on the matrix cores, bf16 storage mode.  dW[co][tap] = sum_px dY[px][co] * x[px + tap] is a GEMM whose contraction index is the
-// PIXEL: M = 64 channels, N = taps, K = B*H*W.  The vector-ALU kernel of conv.hip spends 9 FMA per (pixel, channel) and runs at
+// PIXEL: M = 64 channels, N = taps, K = B*H*W.  The vector-ALU kernel of conv1.hip spends 9 FMA per (pixel, channel) and runs at
 // 2.1 TB/s of dY; here:
 //   * dY tiles (128 consecutive pixels of one image row = 16 KB) travel HBM -> LDS by hand-issued LDS-DMA, four stages, 16-byte
 //     chunk c of pixel p in slot c ^ (p & 7); the A operands (8 consecutive pixels per lane) are built by ds_read_b64_tr_b16;

@@ -1,6 +1,6 @@
 // 3x3 convolution, 64 -> 64 channels, bf16 NHWC: the full-resolution layer of vgg_cnn (reference: models/asr/transformer.py:44-47,
 // conv2 forward and its dgrad), the largest single kernel of the training step.  A persistent, software-pipelined variant of the
-// implicit GEMM of conv.hip, possible because ALL of the layer's weights (64 co x 9 taps x 64 ci = 72 KB) fit in the register
+// implicit GEMM of conv_igemm.hip, possible because ALL of the layer's weights (64 co x 9 taps x 64 ci = 72 KB) fit in the register
 // files of a workgroup:
 //   * persistent workgroups (default: TWO 4-wave workgroups per CU, which run out of phase so that one's address / epilogue work
 //     overlaps the other's MFMAs) walk tiles of 128 output pixels (8 x 16) x 64 co; wave (wm, wn) owns 4 pixel fragments x 2 co

@@ -32,7 +32,6 @@
 #include <type_traits>
 #include <utility>
 
-int asr_conv3x3_wgrad_fold(const float* workspace, float* dw, float* db, int B, int H, int W, int Cin, int Cout, hipStream_t s);   // conv.hip
 
 namespace {
 
@@ -914,7 +913,7 @@ __global__ __launch_bounds__(256, 2) void vgg_level0_wgrad_kernel(L0Args p) {
     float v = bsum;
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
-    // its slot after the partial dW blocks, folded in workgroup order with the reduce (conv.hip): no atomics, the same bits every run
+    // its slot after the partial dW blocks, folded in workgroup order with the reduce (conv_wgrad.hip): no atomics, the same bits every run
     if (g == 0) p.ws[(int64_t)gridDim.x * (9 * 64 * 64) + (int64_t)vid * 64 + wave * 16 + lr] = v;
   }
 }
@@ -932,7 +931,7 @@ template <void (*Kern)(L0Args)> int l0_grant(size_t lds) { return asr_grant_lds<
 bool l0_shape_ok(int B, int H, int W) {
   return B >= 0 && H >= 2 && W >= 2 && (int64_t)B * H * W * 128 < ((int64_t)1 << 32);
 }
-void l0_wgrad_grid(int B, int H, int W, int* wgx, int* ppw) {      // the grid conv.hip's reduce will fold (one 64 x 64 block)
+void l0_wgrad_grid(int B, int H, int W, int* wgx, int* ppw) {      // the grid conv_wgrad.hip's reduce will fold (one 64 x 64 block)
   int blocks_y = 0;
   asr_conv3x3_wgrad_grid(B, H, W, 64, 64, wgx, &blocks_y, ppw);
 }

@@ -1,4 +1,4 @@
-// 3x3 convolution weight gradient, bf16 NHWC, LDS-DMA pipelined variant of conv3x3_wgrad_nhwc_kernel (conv.hip; reference:
+// 3x3 convolution weight gradient, bf16 NHWC, LDS-DMA pipelined variant of conv3x3_wgrad_nhwc_kernel (conv_wgrad.hip; reference:
 // the autograd of models/asr/transformer.py:44-52).  Same decomposition -- a workgroup owns a 64 co x 64 ci x 9 tap block of dW
 // and walks 8 x 16 pixel patches, wave w holds the 9 x 4 accumulator fragments of ci slice w -- but the operands no longer pass
 // through registers on their way to LDS and the vector ALU no longer does per-patch address arithmetic:
@@ -10,7 +10,7 @@
 //     compiler would drain the DMA counter before every LDS read it can see -- with the (macro step, tap) part of the address in
 //     the instruction's immediate offset;
 //   * two 4-wave workgroups per CU, out of phase: one's DMA issue / epilogue overlaps the other's MFMAs.
-// Per-workgroup partial dW blocks go to the caller's workspace and are folded by wgrad_reduce_kernel (conv.hip).
+// Per-workgroup partial dW blocks go to the caller's workspace and are folded by wgrad_reduce_kernel (conv_wgrad.hip).
 #include "common.h"
 #include "conv_wgrad_dma.h"
 
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgdArgs p) {
     float v = bsum;
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
-    // its slot after the partial dW blocks, folded in workgroup order by wgrad_reduce_kernel (conv.hip): no atomics, the same bits every run
+    // its slot after the partial dW blocks, folded in workgroup order by wgrad_reduce_kernel (conv_wgrad.hip): no atomics, the same bits every run
     if (g == 0) p.ws[(int64_t)p.wgx * p.blocks_y * (9 * 64 * 64) + ((int64_t)(by / p.nci) * p.wgx + bx) * 64 + wave * 16 + lr] = v;
   }
 }

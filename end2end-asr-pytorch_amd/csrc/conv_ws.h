@@ -1,4 +1,4 @@
-// Internal interface between conv.hip (asr_conv3x3_igemm / asr_conv3x3_relu_pool_tcf_code dispatch) and conv_ws.hip (persistent,
+// Internal interface between conv_igemm.hip (asr_conv3x3_igemm / asr_conv3x3_relu_pool_tcf_code dispatch) and conv_ws.hip (persistent,
 // weight-stationary bf16 kernel for vgg_cnn's second level: the three launches with 128 input channels and conv.5's forward, 64 -> 128).
 #pragma once
 #include "common.h"

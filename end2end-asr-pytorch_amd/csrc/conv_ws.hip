@@ -3,7 +3,7 @@
 // (B, T', C F') view / transpose of :74-76, conv.7's data gradient with conv.5's ReLU mask, conv.5's data gradient).  The notes below
 // describe the 128-input-channel form; WsGeo<64, 4> is the same kernel with 144 registers of weights per wave and two workgroups per CU.
 //
-// The generic implicit GEMM (conv.hip) re-reads all 9 x 128 x Cout weights (295 KB at Cout = 128) from L2 for every 16 x 16-pixel
+// The generic implicit GEMM (conv_igemm.hip) re-reads all 9 x 128 x Cout weights (295 KB at Cout = 128) from L2 for every 16 x 16-pixel
 // workgroup tile, through registers into a single LDS buffer with two barriers per tap: its MFMA loop alone runs at 55 % of the peak,
 // the shipped kernel at 37 - 40 % (profiles/r04_igemm_ablation.txt).  Here the recipe of conv_c64.hip is taken to 128 input channels:
 //   * ONE persistent 4-wave workgroup per CU (one wave per SIMD, the whole 512-entry register file each).  Wave wn owns 32 output

@@ -350,11 +350,10 @@ extern "C" int asr_colsum_acc(const void* X, int64_t ld, int M, int N, float* ou
   if (M == 0 || N == 0) return ASR_OK;
   const int rpb = 256;
   dim3 grid((N + 63) / 64, (M + rpb - 1) / rpb);
-  if (dtype == ASR_F32) hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, s, (const float*)X, ld, M, N, out, rpb);
-  else if (dtype == ASR_BF16) hipLaunchKernelGGL((colsum_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)X, ld, M, N, out, rpb);
-  else return ASR_EINVAL;
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return asr_launch<colsum_kernel<T>>(grid, dim3(256), 0, s, (const T*)X, ld, M, N, out, rpb);
+  });
 }
 
 extern "C" int asr_embed_fwd(const int64_t* tok, const float* table, const float* pe, void* out, int B, int T, int D,
@@ -363,11 +362,10 @@ extern "C" int asr_embed_fwd(const int64_t* tok, const float* table, const float
   if (B == 0) return ASR_OK;
   const uint32_t thr = asr_drop_threshold(p);
   const float inv = 1.f / (1.f - p);
-  if (dtype == ASR_F32) hipLaunchKernelGGL((embed_fwd_kernel<float>), dim3(B * T), dim3(256), 0, s, tok, table, pe, (float*)out, T, D, scale, thr, inv, seed, seed_dev);
-  else if (dtype == ASR_BF16) hipLaunchKernelGGL((embed_fwd_kernel<bf16_t>), dim3(B * T), dim3(256), 0, s, tok, table, pe, (bf16_t*)out, T, D, scale, thr, inv, seed, seed_dev);
-  else return ASR_EINVAL;
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(dtype, [&](auto t) {
+    using E = decltype(t);
+    return asr_launch<embed_fwd_kernel<E>>(dim3(B * T), dim3(256), 0, s, tok, table, pe, (E*)out, T, D, scale, thr, inv, seed, seed_dev);
+  });
 }
 // ---- incremental decoding with a device-side position (one captured hipGraph serves every step) -----------------------
 // state[0] = position t of the token being fed.  pe_cur = pe[t]; key_len[b] = t + 1 (the self-attention of this step sees the
@@ -408,10 +406,11 @@ extern "C" int asr_kv_append(const void* k_src, const void* v_src, int64_t src_l
   ASR_CHECK_ARG(k_src && v_src && k_cache && v_cache && state && B >= 0 && ncols > 0 && max_len > 0);
   ASR_CHECK_ARG(dtype == ASR_F32 || dtype == ASR_BF16);
   if (B == 0) return ASR_OK;
-  if (dtype == ASR_F32) hipLaunchKernelGGL((kv_append_kernel<float>), dim3(B), dim3(256), 0, s, (const float*)k_src, (const float*)v_src, src_ld, (float*)k_cache, (float*)v_cache, ncols, max_len, state);
-  else hipLaunchKernelGGL((kv_append_kernel<bf16_t>), dim3(B), dim3(256), 0, s, (const bf16_t*)k_src, (const bf16_t*)v_src, src_ld, (bf16_t*)k_cache, (bf16_t*)v_cache, ncols, max_len, state);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return asr_launch<kv_append_kernel<T>>(dim3(B), dim3(256), 0, s, (const T*)k_src, (const T*)v_src, src_ld, (T*)k_cache, (T*)v_cache, ncols,
+                                           max_len, state);
+  });
 }
 
 extern "C" int asr_embed_bwd(const int64_t* tok, const void* dout, float* dtable, int B, int T, int D, float scale,
@@ -420,11 +419,10 @@ extern "C" int asr_embed_bwd(const int64_t* tok, const void* dout, float* dtable
   if (B == 0) return ASR_OK;
   const uint32_t thr = asr_drop_threshold(p);
   const float inv = 1.f / (1.f - p);
-  if (dtype == ASR_F32) hipLaunchKernelGGL((embed_bwd_kernel<float>), dim3(B * T), dim3(256), 0, s, tok, (const float*)dout, dtable, D, scale, thr, inv, seed, seed_dev, pad_id);
-  else if (dtype == ASR_BF16) hipLaunchKernelGGL((embed_bwd_kernel<bf16_t>), dim3(B * T), dim3(256), 0, s, tok, (const bf16_t*)dout, dtable, D, scale, thr, inv, seed, seed_dev, pad_id);
-  else return ASR_EINVAL;
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(dtype, [&](auto t) {
+    using E = decltype(t);
+    return asr_launch<embed_bwd_kernel<E>>(dim3(B * T), dim3(256), 0, s, tok, (const E*)dout, dtable, D, scale, thr, inv, seed, seed_dev, pad_id);
+  });
 }
 
 extern "C" int asr_decoder_preprocess(const int64_t* tgt, int B, int L, int Td, int64_t* seq_in, int64_t* seq_out,
@@ -564,10 +562,10 @@ extern "C" int asr_permute_cols_tcf(const void* src, int64_t ld_src, void* dst, 
   if (rows == 0) return ASR_OK;
   int64_t blocks = ceil_div64((int64_t)rows * H2 * (C / epc), 256);
   if (blocks > 4096) blocks = 4096;
-  if (dtype == ASR_F32) hipLaunchKernelGGL((permute_cols_tcf_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)src, ld_src, (float*)dst, ld_dst, rows, C, H2);
-  else hipLaunchKernelGGL((permute_cols_tcf_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)src, ld_src, (bf16_t*)dst, ld_dst, rows, C, H2);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return asr_launch<permute_cols_tcf_kernel<T>>(dim3((unsigned)blocks), dim3(256), 0, s, (const T*)src, ld_src, (T*)dst, ld_dst, rows, C, H2);
+  });
 }
 
 extern "C" int asr_cast_flat(const float* src, void* dst, int64_t n, int dtype, hipStream_t s) {
@@ -576,9 +574,8 @@ extern "C" int asr_cast_flat(const float* src, void* dst, int64_t n, int dtype, 
   int64_t blocks = ceil_div64(n, 1024 * 2);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  if (dtype == ASR_F32) hipLaunchKernelGGL((cast_flat_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, src, (float*)dst, n);
-  else if (dtype == ASR_BF16) hipLaunchKernelGGL((cast_flat_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, s, src, (bf16_t*)dst, n);
-  else return ASR_EINVAL;
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return asr_launch<cast_flat_kernel<T>>(dim3((unsigned)blocks), dim3(256), 0, s, src, (T*)dst, n);
+  });
 }

@@ -115,10 +115,10 @@ extern "C" int asr_quant_fp8(const void* x, int64_t ld, int M, int K, int dtype,
   ASR_CHECK_ARG(ldq >= Kp && ldq % 16 == 0 && aligned16(q));
   if (M == 0) return ASR_OK;
   const unsigned grid = (unsigned)((M + 3) / 4);
-  if (dtype == ASR_F32) hipLaunchKernelGGL((fp8_quant_rows_kernel<float>), dim3(grid), dim3(256), 0, s, (const float*)x, ld, M, K, Kp, q, ldq, scale);
-  else hipLaunchKernelGGL((fp8_quant_rows_kernel<bf16_t>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x, ld, M, K, Kp, q, ldq, scale);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return asr_launch<fp8_quant_rows_kernel<T>>(dim3(grid), dim3(256), 0, s, (const T*)x, ld, M, K, Kp, q, ldq, scale);
+  });
 }
 
 extern "C" int asr_gemm_nt_fp8(const uint8_t* A, int64_t lda, const float* scale_a, const uint8_t* B, int64_t ldb, const float* scale_b,
@@ -133,8 +133,5 @@ extern "C" int asr_gemm_nt_fp8(const uint8_t* A, int64_t lda, const float* scale
   p.tiles_n = (N + 63) / 64;
   const unsigned grid = (unsigned)(((M + 63) / 64) * p.tiles_n);
   AsrProfScope prof(ASR_OP_GEMM, s);
-  if (out_dtype == ASR_F32) hipLaunchKernelGGL((gemm_fp8_nt_kernel<float>), dim3(grid), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((gemm_fp8_nt_kernel<bf16_t>), dim3(grid), dim3(256), 0, s, p);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(out_dtype, [&](auto t) { return asr_launch<gemm_fp8_nt_kernel<decltype(t)>>(dim3(grid), dim3(256), 0, s, p); });
 }

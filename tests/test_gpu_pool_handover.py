@@ -102,7 +102,7 @@ def test_whole_step_with_and_without_the_hand_over(golden_dir):
     (l1, g1), (l0, g0) = grads[True], grads[False]
     # (bit for bit since the loss statistics are added in a fixed order, asr_ce_finish: with fp32 atomics one ulp was seen once in ~15 runs)
     assert l1 == l0, (l1, l0)
-    # (the conv bias gradients too: their per-workgroup partials are folded in a fixed order, csrc/conv.hip wgrad_bias_fold)
+    # (the conv bias gradients too: their per-workgroup partials are folded in a fixed order, csrc/conv_wgrad.hip wgrad_bias_fold)
     for k in g1:
         assert torch.equal(g1[k], g0[k]), (k, float((g1[k] - g0[k]).abs().max()))
     assert float(g1["conv.7.weight"].abs().max()) > 0 and float(g1["conv.0.weight"].abs().max()) > 0
