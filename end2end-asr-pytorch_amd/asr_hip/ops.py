@@ -1264,11 +1264,53 @@ def _stft_constants(n_fft, device, window="hamming"):
     return c
 
 
-def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="hamming"):
+SPEC_PARAMS, SPEC_MAX_MASKS = 40, 8          # ASR_SPEC_AUGMENT_PARAMS: {n, c, w, nF, nT, 0, 0, 0, 8 x (f0, fw), 8 x (t0, tw)} int32
+
+
+def _spec_params(params, B, T_out, device):
+    """The (B, 40) int32 SpecAugment rows, checked on the host (the kernel clamps what it reads; a row it would have to clamp is a
+    caller's mistake and is refused here), on `device`."""
+    P = torch.as_tensor(params).cpu()
+    if P.dtype not in (torch.int32, torch.int64) or tuple(P.shape) != (B, SPEC_PARAMS):
+        raise ValueError("spec_augment: params must be integers of shape (%d, %d), got %s %s" % (B, SPEC_PARAMS, P.dtype, tuple(P.shape)))
+    if B:
+        n, nF, nT = P[:, 0], P[:, 3], P[:, 4]
+        if (n < 0).any() or (n > T_out).any():
+            raise ValueError("spec_augment: kept frames outside [0, %d]" % T_out)
+        if (nF < 0).any() or (nF > SPEC_MAX_MASKS).any() or (nT < 0).any() or (nT > SPEC_MAX_MASKS).any():
+            raise ValueError("spec_augment: at most %d masks per axis" % SPEC_MAX_MASKS)
+        if (P[:, 8:] < 0).any():
+            raise ValueError("spec_augment: negative mask start or width")
+    return P.to(torch.int32).contiguous().to(device)
+
+
+def spec_augment(x, params):
+    """SpecAugment (asr_spec_augment) of normalised log-spectrograms x (B, 1, F, T) or (B, F, T) fp32 on the
+    device, T contiguous and the (b, f) rows evenly strided (a [..., :T] cut of a contiguous tensor qualifies; anything else is
+    copied).  params: (B, 40) integers {n, c, w, nF, nT, 0, 0, 0, 8 x (f0, fw), 8 x (t0, tw)} as the loader draws them, expected ON
+    THE HOST (they are checked there before the upload; rows on the device cost a synchronising copy back).  Returns a
+    new contiguous tensor of x's shape: warped, masked rows / frames and the frames t >= n zero."""
+    assert x.dim() in (3, 4) and x.dtype == torch.float32 and (x.dim() == 3 or x.shape[1] == 1)
+    B, F, T = x.shape[0], x.shape[-2], x.shape[-1]
+    ld = x.stride(-2) if F > 1 else (x.stride(0) if B > 1 else T)
+    if T and (x.stride(-1) != 1 or ld < T or (B > 1 and F > 1 and x.stride(0) != F * ld)):
+        x = x.contiguous()
+        ld = T
+    prm = _spec_params(params, B, T, x.device)
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    L.call("asr_spec_augment", L.ptr(x), max(ld, T), L.ptr(out), T, L.ptr(prm), B, F, T, L.stream())
+    return out
+
+
+def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="hamming", spec=None, max_frames=None, stats=None):
     """Padded waveforms wav (B, L) fp32 + lengths (B) int32 (samples), both on the device -> (spect (B, 1, n_fft/2+1, Tmax)
     fp32 zero padded along T, n_frames (B) int32): log1p(|STFT|) normalised per utterance, the reference loader's features
     (utils/data_loader.py:72-89) computed on the GPU: framing kernel -> fp32 MFMA GEMM against the DFT basis -> magnitude /
-    log1p / mean / unbiased std kernels.  window: --window (hamming, hann, blackman, bartlett; symmetric)."""
+    log1p / mean / unbiased std kernels.  window: --window (hamming, hann, blackman, bartlett; symmetric).
+    spec: (B, 40) SpecAugment rows (spec_augment) -- the normalisation, the cut to max_frames frames and the augmentation are then
+    one launch (asr_spect_finish_aug) and the result is (B, 1, F, min(Tmax, max_frames)) with n_frames clamped to it (host rows,
+    as for spec_augment).  stats: a dict that receives what that launch normalised with -- "raw" (B, 1, F, Tmax) log-magnitudes and
+    "sums", "sqdev" (B) -- for tests and diagnostics: the reductions add with float atomics, so another launch may see other bits."""
     assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1 and lengths.dtype == torch.int32
     B, Lmax = wav.shape
     F = n_fft // 2 + 1
@@ -1282,10 +1324,21 @@ def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="ha
     gemm_nt(frames, basis, out=reim[:, :2 * F])
     spect = torch.empty((B, 1, F, Tmax), device=wav.device, dtype=torch.float32)
     scratch = torch.zeros((2, B), device=wav.device, dtype=torch.float32)
+    n_frames = (1 + torch.clamp(lengths, min=2) // hop).to(torch.int32)
+    if spec is not None:
+        if not normalize:
+            raise ValueError("log_spectrogram: SpecAugment is defined on the normalised features")
+        T_out = Tmax if max_frames is None else min(Tmax, int(max_frames))
+        prm = _spec_params(spec, B, T_out, wav.device)
+        out = torch.empty((B, 1, F, T_out), device=wav.device, dtype=torch.float32)
+        L.call("asr_spect_finish_aug", L.ptr(reim), ld, L.ptr(lengths), L.ptr(spect), L.ptr(scratch[0]), L.ptr(scratch[1]),
+               L.ptr(out), L.ptr(prm), B, F, Tmax, T_out, hop, L.stream())
+        if stats is not None:
+            stats.update(raw=spect, sums=scratch[0], sqdev=scratch[1])
+        return out, torch.clamp(n_frames, max=T_out)
     L.call("asr_spect_finish", L.ptr(reim), ld, L.ptr(lengths), L.ptr(spect), L.ptr(scratch[0]), L.ptr(scratch[1]), B, F, Tmax,
            hop, int(normalize), L.stream())
-    n_frames = 1 + torch.clamp(lengths, min=2) // hop
-    return spect, n_frames.to(torch.int32)
+    return spect, n_frames
 
 
 def augment_wave(wav, lens, params, bank, sample_rate=16000, offsets=False):

@@ -9,7 +9,9 @@
 //                       data_loader.py:196-209: zero padded along T) + per-utterance sum
 //   asr_spect_sqdev   : per-utterance sum of squared deviations from the mean (two-pass variance)
 //   asr_spect_normalize: in place (x - mean) * rstd on the valid frames
-#include "common.h"
+// asr_spect_finish_aug ends with the SpecAugment pass of csrc/spec_augment.hip instead, which normalises on load with the same
+// expressions (spec_augment.h) and writes the features already cut to T_out frames.
+#include "spec_augment.h"
 
 namespace {
 
@@ -101,11 +103,9 @@ __global__ __launch_bounds__(256) void spect_normalize_kernel(float* __restrict_
   const int t = tblk * 256 + threadIdx.x;
   const int nfr = 1 + max(lengths[b], 2) / hop;
   if (t >= nfr || t >= Tmax) return;
-  const float n = (float)nfr * (float)F;
-  const float mean = sums[b] / n;
-  const float rstd = rsqrtf(sq[b] / (n - 1.f));       // unbiased, as torch.Tensor.std() (data_loader.py:87-88)
+  const SpectNorm nm = spect_norm_of(sums, sq, b, nfr, F);
   float* p = spect + ((int64_t)b * F + f) * Tmax + t;
-  *p = (*p - mean) * rstd;
+  *p = spect_norm_apply(*p, nm);
 }
 
 }  // namespace
@@ -136,4 +136,18 @@ extern "C" int asr_spect_finish(const float* reim, int64_t ld, const int32_t* le
     ASR_LAUNCH_CHECK();
   }
   return ASR_OK;
+}
+
+extern "C" int asr_spect_finish_aug(const float* reim, int64_t ld, const int32_t* lengths, float* raw, float* sums, float* sqdev, float* out,
+                                    const int32_t* params, int B, int F, int Tmax, int T_out, int hop, hipStream_t stream) {
+  ASR_CHECK_ARG(reim && lengths && raw && sums && sqdev && out && params && B >= 0 && F > 0 && Tmax >= 0 && hop > 0 && ld >= 2 * F);
+  ASR_CHECK_ARG(T_out >= 0 && T_out <= Tmax && raw != out);
+  if (B == 0 || Tmax == 0) return ASR_OK;
+  AsrProfScope prof(ASR_OP_LAYOUT, stream);
+  const unsigned grid = (unsigned)((int64_t)B * F * ((Tmax + 255) / 256));
+  spect_logmag_kernel<<<grid, 256, 0, stream>>>(reim, ld, lengths, raw, sums, B, F, Tmax, hop);
+  ASR_LAUNCH_CHECK();
+  spect_sqdev_kernel<<<grid, 256, 0, stream>>>(raw, lengths, sums, sqdev, B, F, Tmax, hop);
+  ASR_LAUNCH_CHECK();
+  return spec_augment_launch(raw, Tmax, out, T_out, params, lengths, sums, sqdev, hop, B, F, T_out, stream);
 }

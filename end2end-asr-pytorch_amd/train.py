@@ -31,6 +31,16 @@ def build_labels(path):
     return label2id, id2label
 
 
+def build_datasets(args, audio_conf, label2id):
+    """(training dataset, [validation datasets]): tempo / gain draws and SpecAugment belong to the training dataset alone."""
+    from utils.data_loader import SpectrogramDataset, spec_policy
+    train_data = SpectrogramDataset(audio_conf, manifest_filepath_list=args.train_manifest_list, label2id=label2id,
+                                    normalize=True, augment=args.augment, spec_augment=spec_policy(args))
+    valid = [SpectrogramDataset(audio_conf, manifest_filepath_list=[m], label2id=label2id, normalize=True, augment=False)
+             for m in args.valid_manifest_list or []]
+    return train_data, valid
+
+
 DEFAULT_GRAPH_BUCKET = 64
 
 
@@ -58,7 +68,7 @@ def resolve_graph_buckets(args, explicit, model=None):
 
 def main():
     from trainer.asr.trainer import Trainer
-    from utils.data_loader import AudioDataLoader, BucketingSampler, SpectrogramDataset
+    from utils.data_loader import AudioDataLoader, BucketingSampler
     from utils.functions import init_optimizer, init_transformer_model, load_model
 
     args = constant.args
@@ -88,22 +98,20 @@ def main():
                       window=args.window, noise_dir=args.noise_dir, noise_prob=args.noise_prob,
                       noise_levels=(args.noise_min, args.noise_max))
     logging.info(audio_conf)
-    if (args.augment or args.noise_dir is not None) and args.cuda and not args.gpu_frontend:
-        # tempo / gain augmentation and noise injection run between the host-to-device copy and the STFT (csrc/augment.hip)
+    if (args.augment or args.noise_dir is not None or args.spec_augment) and args.cuda and not args.gpu_frontend:
+        # tempo / gain augmentation and noise injection run between the host-to-device copy and the STFT (csrc/augment.hip),
+        # SpecAugment in the front end's last pass (csrc/spec_augment.hip)
         args.gpu_frontend = True
-        logging.info("--augment / --noise-dir: --gpu-frontend turned on")
+        logging.info("--augment / --noise-dir / --spec-augment: --gpu-frontend turned on")
         if rank0:
-            print("--augment / --noise-dir: tempo, gain and noise run on the GPU front end (--gpu-frontend turned on)")
+            print("--augment / --noise-dir / --spec-augment: tempo, gain, noise and SpecAugment run on the GPU front end "
+                  "(--gpu-frontend turned on)")
     label2id, id2label = build_labels(args.labels_path)
 
-    train_data = SpectrogramDataset(audio_conf, manifest_filepath_list=args.train_manifest_list, label2id=label2id,
-                                    normalize=True, augment=args.augment)
+    train_data, valid_datas = build_datasets(args, audio_conf, label2id)
     train_sampler = BucketingSampler(train_data, batch_size=args.batch_size)
     train_loader = AudioDataLoader(train_data, num_workers=args.num_workers, batch_sampler=train_sampler)
-    valid_loader_list = []
-    for m in args.valid_manifest_list or []:
-        valid_data = SpectrogramDataset(audio_conf, manifest_filepath_list=[m], label2id=label2id, normalize=True, augment=False)
-        valid_loader_list.append(AudioDataLoader(valid_data, num_workers=args.num_workers, batch_size=args.batch_size))
+    valid_loader_list = [AudioDataLoader(v, num_workers=args.num_workers, batch_size=args.batch_size) for v in valid_datas]
 
     start_epoch, metrics = 0, None
     if args.continue_from != "":

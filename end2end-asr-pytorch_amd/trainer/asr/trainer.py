@@ -202,12 +202,13 @@ class Trainer():
     def _run_batch(self, model, data, smoothing, loss_type, id2label, opt=None):
         src, tgt, src_percentages, src_lengths, tgt_lengths = data[:5]
         aug = data[5] if len(data) > 5 else None          # tempo / gain / noise draws (utils/data_loader.py)
+        spec = data[6] if len(data) > 6 else None         # SpecAugment rows
         if constant.USE_CUDA:
             src, tgt = src.cuda(non_blocking=True), tgt.cuda(non_blocking=True)
         if getattr(constant.args, "gpu_frontend", False):
             a = constant.args
             src, src_lengths = gpu_front_end(src, src_lengths, a.sample_rate, a.window_size, a.window_stride, a.src_max_len,
-                                             window=a.window, aug=aug, noise_dir=a.noise_dir)
+                                             window=a.window, aug=aug, noise_dir=a.noise_dir, spec=spec)
         if opt is not None and loss_type == "ce" and getattr(constant.args, "graph_buckets", 0) > 0 and src.is_cuda:
             r = self._graph_step(model, opt, src, src_lengths, tgt, smoothing)
             if r is not None:

@@ -173,15 +173,23 @@ def noise_bank(noise_dir, sample_rate, device):
     return bank
 
 
+def spec_frames(samples, hop, src_max_len=None):
+    """Frames the front end keeps of an utterance of `samples` samples: min(1 + max(samples, 2) // hop, --src-max-len)."""
+    n = 1 + max(int(samples), 2) // int(hop)
+    return n if src_max_len is None else min(n, int(src_max_len))
+
+
 def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, window_stride=0.01, src_max_len=None, window="hamming",
-                  aug=None, noise_dir=None):
+                  aug=None, noise_dir=None, spec=None):
     """--gpu-frontend: `inputs` (B,1,1,Lmax) are the loader's zero padded WAVEFORMS and `input_sizes` (B) their sample
     counts (the collate function is unchanged: a waveform is a 1-bin "spectrogram").  Returns what the host path would have
     put in the batch: log-spectrograms (B,1,F,T) normalised per utterance, cut to --src-max-len frames AFTER the
     normalisation (data_loader.py:49-53), and the frame counts.
     aug: the loader's (B, 6) float64 draws {input samples, tempo (0: none), gain dB, noise clip (-1: none), noise start s, level}
     (utils/data_loader.py); they are applied on the device first (ops.augment_wave) and `input_sizes` are then the samples after
-    the tempo change.  noise_dir: the directory the clip indices refer to."""
+    the tempo change.  noise_dir: the directory the clip indices refer to.
+    spec: the loader's (B, 40) int32 SpecAugment rows; their n must be the kept frame counts of this batch.
+    Normalisation, cut and SpecAugment are then one launch (asr_spect_finish_aug)."""
     import torch
     from asr_hip import ops
     n_fft, hop = int(sample_rate * window_size), int(sample_rate * window_stride)
@@ -195,6 +203,14 @@ def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, wind
             raise ValueError("input_sizes are not the post-tempo sample counts of the draws")
     else:
         lens = torch.as_tensor(input_sizes).to(device=wav.device, dtype=torch.int32)
+    if spec is not None:
+        spec = torch.as_tensor(spec)
+        kept = [spec_frames(s, hop, src_max_len) for s in torch.as_tensor(input_sizes).tolist()]
+        if spec.dim() != 2 or spec[:, 0].tolist() != kept:
+            raise ValueError("the SpecAugment rows' frame counts are not the kept frames of input_sizes")
+        spect, n_frames = ops.log_spectrogram(wav, lens, n_fft=n_fft, hop=hop, normalize=True, window=window, spec=spec,
+                                              max_frames=src_max_len)
+        return spect, n_frames.cpu()
     spect, n_frames = ops.log_spectrogram(wav, lens, n_fft=n_fft, hop=hop, normalize=True, window=window)
     if src_max_len is not None and spect.shape[-1] > src_max_len:
         spect = spect[..., :src_max_len].contiguous()

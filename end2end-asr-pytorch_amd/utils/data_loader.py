@@ -5,7 +5,9 @@
              input_percentages f32 (B), input_sizes i32 (B), target_sizes i32 (B))   (:182-214);
   * with tempo / gain augmentation or noise injection (GPU front end only) a 6th element: the (B, 6) float64 draws
     {input samples, tempo (0: none), gain dB, noise clip (-1: none), noise start s, noise level}, and the batch is sorted by, and
-    input_sizes / input_percentages count, the samples AFTER the tempo change (utils.audio.gpu_front_end applies the draws).
+    input_sizes / input_percentages count, the samples AFTER the tempo change (utils.audio.gpu_front_end applies the draws);
+  * with SpecAugment (training dataset, GPU front end only) a 7th element: the (B, 40) int32 rows {n, c, w, nF, nT, 0, 0, 0,
+    8 x (f0, fw), 8 x (t0, tw)} of DESIGN.md section 7; the 6th element is then the wave draws or None.
 BucketingSampler keeps the reference's consecutive bins and additionally shards them over data-parallel ranks.
 """
 import random
@@ -17,13 +19,23 @@ from torch.utils.data.sampler import Sampler
 
 from asr_hip.ddp import rank_shard
 from utils import constant
-from utils.audio import load_audio, log_spectrogram, noise_files, resolve_window, tempo_length
+from utils.audio import load_audio, log_spectrogram, noise_files, resolve_window, spec_frames, tempo_length
 
 TEMPO_RANGE, GAIN_RANGE = (0.85, 1.15), (-6, 8)          # reference: utils/audio.py:54
+SPEC_PARAMS, SPEC_MAX_MASKS = 40, 8                      # one SpecAugment row (include/asr_hip.h, ASR_SPEC_AUGMENT_PARAMS)
+SPEC_POLICY_KEYS = ("time_warp", "freq_mask", "freq_masks", "time_mask", "time_masks", "time_mask_ratio")
+
+
+def spec_policy(args):
+    """The SpecAugment policy of a command line (--spec-augment and its --spec-* parameters) as the dict SpectrogramDataset takes,
+    or None with the flag off."""
+    if not getattr(args, "spec_augment", False):
+        return None
+    return {k: getattr(args, "spec_" + k) for k in SPEC_POLICY_KEYS}
 
 
 class SpectrogramParser(object):
-    def __init__(self, audio_conf, normalize=False, augment=False):
+    def __init__(self, audio_conf, normalize=False, augment=False, spec_augment=None):
         self.window_stride = audio_conf['window_stride']
         self.window_size = audio_conf['window_size']
         self.sample_rate = audio_conf['sample_rate']
@@ -34,6 +46,17 @@ class SpectrogramParser(object):
         if (augment or self.noise_dir is not None) and not getattr(constant.args, "gpu_frontend", False):
             raise NotImplementedError("tempo/gain augmentation (--augment) and noise injection (--noise-dir) run on the GPU front end "
                                       "only: use --cuda (it turns on --gpu-frontend)")
+        self.spec = None
+        if spec_augment is not None:
+            if not getattr(constant.args, "gpu_frontend", False):
+                raise NotImplementedError("SpecAugment (--spec-augment) runs on the GPU front end only: use --cuda (it turns on "
+                                          "--gpu-frontend)")
+            pol = {k: spec_augment[k] for k in SPEC_POLICY_KEYS}
+            if pol["freq_masks"] > SPEC_MAX_MASKS or pol["time_masks"] > SPEC_MAX_MASKS:
+                raise ValueError("--spec-freq-masks / --spec-time-masks: at most %d masks per axis" % SPEC_MAX_MASKS)
+            if min(pol.values()) < 0 or pol["time_mask_ratio"] > 1:
+                raise ValueError("--spec-* parameters must not be negative, --spec-time-mask-ratio at most 1: %s" % pol)
+            self.spec = pol
         self.noise_paths = None
         if self.noise_dir is not None:
             self.noise_paths, self.noise_lens = noise_files(self.noise_dir, self.sample_rate)
@@ -59,6 +82,26 @@ class SpectrogramParser(object):
             start_s = float(np.random.rand() * (self.noise_lens[clip] / self.sample_rate - data_len))
         return (n, tempo, gain, clip, start_s, level, n_out)
 
+    def draw_spec(self, samples):
+        """The SpecAugment row of an utterance of `samples` samples (after the tempo change), on the global np.random after the
+        utterance's wave draws: warp centre and target, then (width, start) per frequency mask, then per time mask."""
+        hop, n_fft = int(self.sample_rate * self.window_stride), int(self.sample_rate * self.window_size)
+        n, F, p = spec_frames(samples, hop, constant.args.src_max_len), n_fft // 2 + 1, self.spec
+        row = [0] * SPEC_PARAMS
+        row[0], row[3], row[4] = n, p["freq_masks"], p["time_masks"]
+        W = p["time_warp"]
+        if n > 2 * W:
+            row[1] = int(np.random.randint(W, n - W))
+            row[2] = row[1] + int(np.random.randint(-W, W + 1))
+        for k in range(p["freq_masks"]):
+            fw = int(np.random.randint(0, min(p["freq_mask"], F) + 1))
+            row[8 + 2 * k], row[9 + 2 * k] = int(np.random.randint(0, F - fw + 1)), fw
+        t_cap = min(p["time_mask"], int(np.floor(p["time_mask_ratio"] * n)))
+        for k in range(p["time_masks"]):
+            tw = int(np.random.randint(0, t_cap + 1))
+            row[8 + 2 * SPEC_MAX_MASKS + 2 * k], row[9 + 2 * SPEC_MAX_MASKS + 2 * k] = int(np.random.randint(0, n - tw + 1)), tw
+        return row
+
     @property
     def augmenting(self):
         return self.augment or self.noise_paths is not None
@@ -74,7 +117,7 @@ class SpectrogramParser(object):
 
 
 class SpectrogramDataset(Dataset, SpectrogramParser):
-    def __init__(self, audio_conf, manifest_filepath_list, label2id, normalize=False, augment=False):
+    def __init__(self, audio_conf, manifest_filepath_list, label2id, normalize=False, augment=False, spec_augment=None):
         self.ids_list = []
         self.max_size = 0
         for path in manifest_filepath_list:
@@ -84,7 +127,7 @@ class SpectrogramDataset(Dataset, SpectrogramParser):
             self.max_size = max(self.max_size, len(ids))
         self.manifest_filepath_list = manifest_filepath_list
         self.label2id = label2id
-        SpectrogramParser.__init__(self, audio_conf, normalize, augment)
+        SpectrogramParser.__init__(self, audio_conf, normalize, augment, spec_augment)
 
     def __getitem__(self, index):
         ids = self.ids_list[random.randint(0, len(self.ids_list) - 1)]      # one manifest at random, as the reference
@@ -92,6 +135,10 @@ class SpectrogramDataset(Dataset, SpectrogramParser):
         spect = self.parse_audio(audio_path)
         if not getattr(constant.args, "gpu_frontend", False):
             spect = spect[:, :constant.args.src_max_len]
+        if self.spec is not None:
+            draws = self.draw(spect.size(1)) if self.augmenting else None
+            return (spect, self.parse_transcript(transcript_path), draws,
+                    self.draw_spec(draws[6] if draws is not None else spect.size(1)))
         if self.augmenting:
             return spect, self.parse_transcript(transcript_path), self.draw(spect.size(1))
         return spect, self.parse_transcript(transcript_path)
@@ -106,7 +153,8 @@ class SpectrogramDataset(Dataset, SpectrogramParser):
 
 
 def _collate_fn(batch):
-    aug = len(batch[0]) > 2
+    aug = len(batch[0]) > 2 and batch[0][2] is not None
+    spec_rows = len(batch[0]) > 3
     size = (lambda s: s[2][6]) if aug else (lambda s: s[0].size(1))      # augmented: samples after the tempo change
     batch = sorted(batch, key=size, reverse=True)
     B = len(batch)
@@ -127,8 +175,10 @@ def _collate_fn(batch):
         input_percentages[i] = size(s) / float(n_max)
         target_sizes[i] = len(tgt)
         targets[i, :len(tgt)] = torch.tensor(tgt, dtype=torch.int64)
+    draws = torch.tensor([s[2][:6] for s in batch], dtype=torch.float64) if aug else None
+    if spec_rows:
+        return inputs, targets, input_percentages, input_sizes, target_sizes, draws, torch.tensor([s[3] for s in batch], dtype=torch.int32)
     if aug:
-        draws = torch.tensor([s[2][:6] for s in batch], dtype=torch.float64)
         return inputs, targets, input_percentages, input_sizes, target_sizes, draws
     return inputs, targets, input_percentages, input_sizes, target_sizes
 

@@ -543,6 +543,26 @@ int asr_augment_wave(const float* wav, int64_t wav_stride, const int32_t* lens, 
                      const int64_t* bank_off, const int64_t* bank_len, int nclips, float* out, int64_t out_stride, int32_t* offsets,
                      int64_t off_stride, int B, int S, int search, int O, asr_stream_t stream);
 
+/* ---- SpecAugment of the normalised log-spectrogram (no counterpart in the reference; Park et al. 2019, arXiv:1904.08779: time warp,
+ * frequency masks, time masks; definition in DESIGN.md section 7).  params (B, ASR_SPEC_AUGMENT_PARAMS) int32 on the device, one row
+ * per utterance: {n, c, w, nF, nT, 0, 0, 0, 8 x (f0, fw), 8 x (t0, tw)}.  n: kept frames (clamped to [0, T_out]); the warp moves frame c
+ * to frame w by linear interpolation of [0, c) -> [0, w) and [c, n) -> [w, n) (half-pixel centres, integer quotient / remainder, one
+ * fmaf) and applies when 0 < c < n and 0 <= w < n (c = w = 0: none; c == w: the identity bit for bit); then rows f0 <= f < f0 + fw of
+ * the first nF pairs and frames t0 <= t < t0 + tw of the first nT pairs (at most 8 each, a count outside [0, 8] is clamped) become
+ * +0.0, the utterance mean, as do the frames t >= n whatever the input holds there.  Masks may overlap; a width <= 0 masks nothing.
+ * The warp's integers are 32-bit for n <= 16384 and 64-bit above: no limit on n beyond T_out <= 2^30.
+ * x (B, F, >= T_out) fp32, already normalised, (b, f) rows ldx_row floats apart; out (B, F, T_out), rows ldo_row floats apart, out
+ * != x (the warp gathers).  16-byte stores when out is 16-byte aligned and ldo_row and T_out are multiples of 4.                  */
+#define ASR_SPEC_AUGMENT_PARAMS 40
+int asr_spec_augment(const float* x, int64_t ldx_row, float* out, int64_t ldo_row, const int32_t* params, int B, int F, int T_out,
+                     asr_stream_t stream);
+/* asr_spect_finish with normalize != 0 followed by asr_spec_augment of its first T_out <= Tmax frames, in three launches instead of
+ * four and without the cut's copy: log1p(|.|) and the two reductions into raw (B, F, Tmax) as asr_spect_finish does, then one pass
+ * that normalises each value it loads (the expressions of asr_spect_finish: bitwise the separate result) and writes out (B, F,
+ * T_out) contiguous.  n of a params row is additionally clamped to the utterance's 1 + max(len, 2) / hop frames.             */
+int asr_spect_finish_aug(const float* reim, int64_t ld, const int32_t* lengths, float* raw, float* sums, float* sqdev, float* out,
+                         const int32_t* params, int B, int F, int Tmax, int T_out, int hop, asr_stream_t stream);
+
 /* ---- LSTM language model for beam-search rescoring (reference: utils/lstm_utils.py LM.evaluate, RNNModel.forward; nn.LSTM gate
  * order i, f, g, o).  fp32 storage and f32-input MFMA (v_mfma_f32_16x16x4_f32) whatever the ASR model's precision.
  * Contraction operands: rows 16-byte aligned, leading dimensions multiples of 4 floats, and the K columns zero-padded to a multiple
