@@ -123,7 +123,9 @@ _SIGS = {
     "asr_augment_wave": (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
     "asr_spec_augment": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _P]),
     "asr_spect_finish_aug": (_I, [_P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "asr_im2col": (_I, [_P, _P] + [_I] * 12 + [_L, _L, _I, _I, _P]),
+    "asr_fbank_finish": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P]),
+    "asr_fbank_finish_aug": (_I, [_P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P]),
+    "asr_im2col":(_I, [_P, _P] + [_I] * 12 + [_L, _L, _I, _I, _P]),
     "asr_col2im": (_I, [_P, _P] + [_I] * 12 + [_L, _I, _P]),
     "asr_window_sum": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
     "asr_bn_stats": (_I, [_P, _L, _L, _I, _P, _P, _I, _I, _P]),

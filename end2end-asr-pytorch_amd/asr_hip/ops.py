@@ -3,6 +3,7 @@
 Everything here launches HIP kernels from libasr_hip.so on torch's current stream.  torch is used for device
 memory (torch.empty / zeros) and nothing else.
 """
+import collections
 import math
 import os
 
@@ -1302,7 +1303,62 @@ def spec_augment(x, params):
     return out
 
 
-def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="hamming", spec=None, max_frames=None, stats=None):
+FBANK_FLOOR = 1e-10                          # log-mel features: log(max(energy, FBANK_FLOOR))
+FbankDevice = collections.namedtuple("FbankDevice", "first count weights n_bins")
+
+
+def fbank_upload(bank, device):
+    """A sparse mel filter bank (utils.audio.mel_filterbank: first, count int arrays of M filters, flat fp32 weights, n_bins = K) checked
+    on the host -- the kernel clamps what it reads; a bank it would have to clamp is a caller's mistake and is refused here -- and
+    uploaded to `device`.  An FbankDevice is passed through."""
+    if isinstance(bank, FbankDevice):
+        return bank
+    first, count, weights, K = bank
+    first, count = torch.as_tensor(first).cpu().long().reshape(-1), torch.as_tensor(count).cpu().long().reshape(-1)
+    weights = torch.as_tensor(weights).cpu().reshape(-1)
+    if weights.dtype != torch.float32 or first.numel() == 0 or first.numel() != count.numel():
+        raise ValueError("fbank: the bank is (first (M), count (M), float32 weights, n_bins) with M > 0")
+    if (first < 0).any() or (count < 0).any() or (first + count > int(K)).any() or int(count.sum()) != weights.numel():
+        raise ValueError("fbank: a filter reaches outside the %d bins, or the counts do not add up to the %d weights" % (K, weights.numel()))
+    return FbankDevice(first.to(torch.int32).to(device), count.to(torch.int32).to(device), weights.contiguous().to(device), int(K))
+
+
+def fbank_finish(reim, lengths, bank, hop, normalize=True, spec=None, max_frames=None, stats=None, floor=FBANK_FLOOR):
+    """Log-mel filterbank features (asr_fbank_finish) of caller-supplied DFT rows: reim (B * Tmax, >= 2 K) fp32 on
+    the device, [re (K) | im (K)] per frame, rows evenly strided; lengths (B) int32 samples; bank: utils.audio.mel_filterbank's arrays
+    (host) or an fbank_upload of them.  Returns (feat (B, 1, M, Tmax), n_frames (B) int32) as log_spectrogram does, frames past an
+    utterance's 1 + max(len, 2) // hop zero.  normalize / spec / max_frames: as log_spectrogram; stats also without spec (then "raw" is
+    None when normalize overwrote it)."""
+    assert reim.dim() == 2 and reim.dtype == torch.float32 and reim.stride(1) == 1 and lengths.dtype == torch.int32
+    bank = fbank_upload(bank, reim.device)
+    B, K, M = lengths.numel(), bank.n_bins, bank.first.numel()
+    if B == 0 or reim.shape[0] % B or reim.shape[1] < 2 * K:
+        raise ValueError("fbank_finish: reim must hold B * Tmax rows of at least %d columns, got %s for B = %d" % (2 * K, tuple(reim.shape), B))
+    Tmax, ld = reim.shape[0] // B, reim.stride(0)
+    feat = torch.empty((B, 1, M, Tmax), device=reim.device, dtype=torch.float32)
+    scratch = torch.zeros((2, B), device=reim.device, dtype=torch.float32)
+    n_frames = torch.clamp(1 + torch.clamp(lengths, min=2) // hop, max=Tmax).to(torch.int32)
+    tail = (L.ptr(bank.first), L.ptr(bank.count), L.ptr(bank.weights), bank.weights.numel(), float(floor), L.stream())
+    if spec is not None:
+        if not normalize:
+            raise ValueError("fbank_finish: SpecAugment is defined on the normalised features")
+        T_out = Tmax if max_frames is None else min(Tmax, int(max_frames))
+        prm = _spec_params(spec, B, T_out, reim.device)
+        out = torch.empty((B, 1, M, T_out), device=reim.device, dtype=torch.float32)
+        L.call("asr_fbank_finish_aug", L.ptr(reim), ld, L.ptr(lengths), L.ptr(feat), L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(out),
+               L.ptr(prm), B, K, M, Tmax, T_out, hop, *tail)
+        if stats is not None:
+            stats.update(raw=feat, sums=scratch[0], sqdev=scratch[1])
+        return out, torch.clamp(n_frames, max=T_out)
+    L.call("asr_fbank_finish", L.ptr(reim), ld, L.ptr(lengths), L.ptr(feat), L.ptr(scratch[0]), L.ptr(scratch[1]), B, K, M, Tmax, hop,
+           int(normalize), *tail)
+    if stats is not None:               # the normalisation is in place: the raw values survive only without it
+        stats.update(raw=None if normalize else feat, sums=scratch[0], sqdev=scratch[1])
+    return feat, n_frames
+
+
+def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="hamming", spec=None, max_frames=None, stats=None,
+                    features="spect", mel=None):
     """Padded waveforms wav (B, L) fp32 + lengths (B) int32 (samples), both on the device -> (spect (B, 1, n_fft/2+1, Tmax)
     fp32 zero padded along T, n_frames (B) int32): log1p(|STFT|) normalised per utterance, the reference loader's features
     (utils/data_loader.py:72-89) computed on the GPU: framing kernel -> fp32 MFMA GEMM against the DFT basis -> magnitude /
@@ -1310,7 +1366,11 @@ def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="ha
     spec: (B, 40) SpecAugment rows (spec_augment) -- the normalisation, the cut to max_frames frames and the augmentation are then
     one launch (asr_spect_finish_aug) and the result is (B, 1, F, min(Tmax, max_frames)) with n_frames clamped to it (host rows,
     as for spec_augment).  stats: a dict that receives what that launch normalised with -- "raw" (B, 1, F, Tmax) log-magnitudes and
-    "sums", "sqdev" (B) -- for tests and diagnostics: the reductions add with float atomics, so another launch may see other bits."""
+    "sums", "sqdev" (B) -- for tests and diagnostics: the reductions add with float atomics, so another launch may see other bits.
+    features: "spect" (the above) or "fbank": log-mel filterbank features (B, 1, M, Tmax) of the same DFT through the bank `mel`
+    (fbank_finish)."""
+    if features not in ("spect", "fbank") or (features == "fbank") != (mel is not None):
+        raise ValueError("log_spectrogram: features is 'spect', or 'fbank' with its filter bank mel=")
     assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1 and lengths.dtype == torch.int32
     B, Lmax = wav.shape
     F = n_fft // 2 + 1
@@ -1322,6 +1382,11 @@ def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="ha
     ld = (2 * F + 3) // 4 * 4
     reim = torch.empty((B * Tmax, ld), device=wav.device, dtype=torch.float32)
     gemm_nt(frames, basis, out=reim[:, :2 * F])
+    if mel is not None:
+        mel = fbank_upload(mel, wav.device)
+        if mel.n_bins != F:
+            raise ValueError("log_spectrogram: the filter bank is not one of %d bins" % F)
+        return fbank_finish(reim, lengths, mel, hop, normalize=normalize, spec=spec, max_frames=max_frames, stats=stats)
     spect = torch.empty((B, 1, F, Tmax), device=wav.device, dtype=torch.float32)
     scratch = torch.zeros((2, B), device=wav.device, dtype=torch.float32)
     n_frames = (1 + torch.clamp(lengths, min=2) // hop).to(torch.int32)

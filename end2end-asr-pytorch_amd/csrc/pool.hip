@@ -262,6 +262,15 @@ __global__ __launch_bounds__(256) void pool_bwd_tcf_code_kernel(const uint8_t* _
   uint8_t* sc = reinterpret_cast<uint8_t*>(sp + H2 * (C + 1));
   const int ow = blockIdx.x % W2, b = blockIdx.x / W2;
   const int64_t o0 = ((int64_t)b * W2 + ow) * (int64_t)C * H2;
+  // H2 % EPC != 0 (pooled heights 20 and 10 of 80 and 40 feature rows): a channel's H2 values are no whole 16-byte chunks, so the pixel's
+  // C * H2 gradients and codes are read one element per thread, still consecutive along the row; the stores below are unchanged
+  if (H2 % EPC != 0)
+    for (int i = threadIdx.x; i < C * H2; i += 256) {
+      const int c = i / H2, oh = i % H2;
+      sp[oh * (C + 1) + c] = DT<T>::from(dy[o0 + i]);
+      sc[oh * (C + 4) + c] = code[o0 + i];
+    }
+  else
   for (int i = threadIdx.x; i < C * hg; i += 256) {
     const int c = i / hg, oh0 = (i % hg) * EPC;
     Chunk<T> g;
@@ -465,7 +474,7 @@ extern "C" int asr_maxpool_bwd_code(const uint8_t* code, const void* dy, void* d
   const int H2 = H / 2, W2 = W / 2;
   const size_t lds = pool_tcf_lds(H2, C, true);
   if (C % epc != 0 || !aligned16(dy) || !aligned16(dx) || (((uintptr_t)code) & 3) != 0) return ASR_EUNSUPPORTED;
-  if (in_tcf && (H2 % epc != 0 || lds > 150 * 1024)) return ASR_EUNSUPPORTED;
+  if (in_tcf && lds > 150 * 1024) return ASR_EUNSUPPORTED;      // any H2: whole 16-byte chunks along H2 when H2 % epc == 0, else by element
   if (!in_tcf && (int64_t)B * H2 > 65535) return ASR_EUNSUPPORTED;
   if (B == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_POOL, s);

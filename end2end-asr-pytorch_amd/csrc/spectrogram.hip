@@ -11,6 +11,9 @@
 //   asr_spect_normalize: in place (x - mean) * rstd on the valid frames
 // asr_spect_finish_aug ends with the SpecAugment pass of csrc/spec_augment.hip instead, which normalises on load with the same
 // expressions (spec_augment.h) and writes the features already cut to T_out frames.
+// asr_fbank_finish / asr_fbank_finish_aug (--features fbank) replace only the first pass: fbank_logmel_kernel
+// turns the same (re, im) rows into log-mel filterbank features (B, M, T) + per-utterance sum; the passes after it are the ones above
+// with F := M.
 #include "spec_augment.h"
 
 namespace {
@@ -108,6 +111,83 @@ __global__ __launch_bounds__(256) void spect_normalize_kernel(float* __restrict_
   *p = spect_norm_apply(*p, nm);
 }
 
+// Log-mel first pass.  One workgroup per (utterance, tile of 64 frames): the tile's (re, im) rows are read ALONG the row (a wave per
+// row, 256 contiguous bytes per load) and their power spectrum is staged in LDS as 64 x K fp32 with an odd row stride S = K | 1, so
+// that in the second half, where each lane owns a frame and reads its own row, the 32 lanes of an LDS access fall on 32 banks.  Each
+// wave then walks every fourth filter: first / count / weights are wave-uniform (scalar loads), the store is 256 contiguous bytes
+// along T.  Filters are clamped to the K bins and the nw weights: nothing outside the staged tile or the arrays is read.
+constexpr int kFbankTile = 64;
+
+__global__ __launch_bounds__(256) void fbank_logmel_kernel(const float* __restrict__ reim, int64_t ld, const int32_t* __restrict__ lengths,
+                                                           const int32_t* __restrict__ first, const int32_t* __restrict__ count,
+                                                           const float* __restrict__ wts, int nw, float floor_v, float* __restrict__ feat,
+                                                           float* __restrict__ sums, int B, int K, int M, int Tmax, int hop) {
+  extern __shared__ __attribute__((aligned(16))) float fbank_lds[];
+  __shared__ float red[4];
+  const int S = K | 1;
+  float* pw = fbank_lds;                                                  // kFbankTile x S power spectrum
+  int* offs = reinterpret_cast<int*>(fbank_lds + kFbankTile * S);         // M: start of each filter's weights
+  const int tiles = (Tmax + kFbankTile - 1) / kFbankTile;
+  const int b = blockIdx.x / tiles, t0 = (blockIdx.x % tiles) * kFbankTile;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nfr = 1 + max(lengths[b], 2) / hop;
+  const int nv = min(min(nfr, Tmax) - t0, kFbankTile);                    // frames of this tile that belong to the utterance
+  const int t = t0 + lane;
+  float* out = feat + (int64_t)b * M * Tmax + t;
+  if (nv <= 0) {                                                          // whole tile past the utterance's end: zeros, nothing to add
+    if (t < Tmax)
+      for (int m = wave; m < M; m += 4) out[(int64_t)m * Tmax] = 0.f;
+    return;
+  }
+  if (wave == 0) {                                                        // exclusive prefix sum of the counts
+    int carry = 0;
+    for (int m0 = 0; m0 < M; m0 += 64) {
+      const int m = m0 + lane;
+      const int c = m < M ? min(max(count[m], 0), K) : 0;
+      int incl = c;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += u;
+      }
+      if (m < M) offs[m] = carry + incl - c;
+      carry += __shfl(incl, 63, 64);
+    }
+  }
+  for (int r = wave; r < nv; r += 4) {
+    const float* row = reim + ((int64_t)b * Tmax + t0 + r) * ld;
+    for (int k = lane; k < K; k += 64) {
+      const float re = row[k], im = row[K + k];
+      pw[r * S + k] = re * re + im * im;
+    }
+  }
+  __syncthreads();
+  const bool valid = lane < nv;
+  const float* p = pw + lane * S;
+  float part = 0.f;
+  for (int m = wave; m < M; m += 4) {
+    const int o = __builtin_amdgcn_readfirstlane(offs[m]);
+    const int f0 = min(max(__builtin_amdgcn_readfirstlane(first[m]), 0), K);
+    const int c = max(min(min(__builtin_amdgcn_readfirstlane(count[m]), K - f0), nw - o), 0);
+    float acc = 0.f;
+    for (int j = 0; j < c; ++j) acc = fmaf(wts[o + j], p[f0 + j], acc);
+    const float v = valid ? logf(fmaxf(acc, floor_v)) : 0.f;
+    if (t < Tmax) out[(int64_t)m * Tmax] = v;
+    part += v;
+  }
+  const float s = block_sum(part, red);
+  if (threadIdx.x == 0) atomicAdd(sums + b, s);
+}
+
+int fbank_first_pass(const float* reim, int64_t ld, const int32_t* lengths, float* feat, float* sums, int B, int K, int M, int Tmax, int hop,
+                     const int32_t* first, const int32_t* count, const float* weights, int nw, float floor_v, hipStream_t stream) {
+  const size_t lds = ((size_t)kFbankTile * (K | 1) + M) * sizeof(float);
+  if (lds > 160 * 1024) return ASR_EUNSUPPORTED;
+  const unsigned grid = (unsigned)((int64_t)B * ((Tmax + kFbankTile - 1) / kFbankTile));
+  return asr_launch<fbank_logmel_kernel>(dim3(grid), dim3(256), lds, stream, reim, ld, lengths, first, count, weights, nw, floor_v, feat,
+                                         sums, B, K, M, Tmax, hop);
+}
+
 }  // namespace
 
 extern "C" int asr_stft_frames(const float* wav, int64_t wav_stride, const int32_t* lengths, const float* window, float* frames, int B,
@@ -150,4 +230,40 @@ extern "C" int asr_spect_finish_aug(const float* reim, int64_t ld, const int32_t
   spect_sqdev_kernel<<<grid, 256, 0, stream>>>(raw, lengths, sums, sqdev, B, F, Tmax, hop);
   ASR_LAUNCH_CHECK();
   return spec_augment_launch(raw, Tmax, out, T_out, params, lengths, sums, sqdev, hop, B, F, T_out, stream);
+}
+
+#define ASR_FBANK_CHECK_ARGS()                                                                                                          \
+  ASR_CHECK_ARG(reim && lengths && sums && sqdev && first && count && weights && B >= 0 && K > 0 && M > 0 && Tmax >= 0 && hop > 0 && \
+                nw >= 0 && ld >= 2 * (int64_t)K && floor > 0.f)
+
+extern "C" int asr_fbank_finish(const float* reim, int64_t ld, const int32_t* lengths, float* feat, float* sums, float* sqdev, int B, int K,
+                                int M, int Tmax, int hop, int normalize, const int32_t* first, const int32_t* count, const float* weights,
+                                int nw, float floor, hipStream_t stream) {
+  ASR_FBANK_CHECK_ARGS();
+  ASR_CHECK_ARG(feat);
+  if (B == 0 || Tmax == 0) return ASR_OK;
+  AsrProfScope prof(ASR_OP_LAYOUT, stream);
+  const int rc = fbank_first_pass(reim, ld, lengths, feat, sums, B, K, M, Tmax, hop, first, count, weights, nw, floor, stream);
+  if (rc != ASR_OK || !normalize) return rc;
+  const unsigned grid = (unsigned)((int64_t)B * M * ((Tmax + 255) / 256));
+  spect_sqdev_kernel<<<grid, 256, 0, stream>>>(feat, lengths, sums, sqdev, B, M, Tmax, hop);
+  ASR_LAUNCH_CHECK();
+  spect_normalize_kernel<<<grid, 256, 0, stream>>>(feat, lengths, sums, sqdev, B, M, Tmax, hop);
+  ASR_LAUNCH_CHECK();
+  return ASR_OK;
+}
+
+extern "C" int asr_fbank_finish_aug(const float* reim, int64_t ld, const int32_t* lengths, float* raw, float* sums, float* sqdev, float* out,
+                                    const int32_t* params, int B, int K, int M, int Tmax, int T_out, int hop, const int32_t* first,
+                                    const int32_t* count, const float* weights, int nw, float floor, hipStream_t stream) {
+  ASR_FBANK_CHECK_ARGS();
+  ASR_CHECK_ARG(raw && out && params && T_out >= 0 && T_out <= Tmax && raw != out);
+  if (B == 0 || Tmax == 0) return ASR_OK;
+  AsrProfScope prof(ASR_OP_LAYOUT, stream);
+  const int rc = fbank_first_pass(reim, ld, lengths, raw, sums, B, K, M, Tmax, hop, first, count, weights, nw, floor, stream);
+  if (rc != ASR_OK) return rc;
+  const unsigned grid = (unsigned)((int64_t)B * M * ((Tmax + 255) / 256));
+  spect_sqdev_kernel<<<grid, 256, 0, stream>>>(raw, lengths, sums, sqdev, B, M, Tmax, hop);
+  ASR_LAUNCH_CHECK();
+  return spec_augment_launch(raw, Tmax, out, T_out, params, lengths, sums, sqdev, hop, B, M, T_out, stream);
 }

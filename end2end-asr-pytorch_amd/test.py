@@ -24,7 +24,9 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
                 from utils.audio import gpu_front_end
                 src, src_lengths = gpu_front_end(src, src_lengths, args.sample_rate, args.window_size, args.window_stride,
                                                  args.src_max_len, window=getattr(args, "window", "hamming"), aug=aug,
-                                                 noise_dir=noise_dir)
+                                                 noise_dir=noise_dir, features=getattr(args, "features", "spect"),
+                                                 num_mel_bins=getattr(args, "num_mel_bins", 80),
+                                                 mel_fmin=getattr(args, "mel_fmin", 20.0))
             _, strs_hyps, strs_gold = model.evaluate(src, src_lengths, tgt, beam_search=args.beam_search,
                                                      beam_width=args.beam_width, beam_nbest=args.beam_nbest, lm=lm,
                                                      lm_rescoring=args.lm_rescoring, lm_weight=args.lm_weight,
@@ -44,6 +46,17 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
     return total_cer / max(1, total_char), total_wer / max(1, total_word)
 
 
+def feature_conf(loaded_args):
+    """The audio_conf of a checkpoint's run: the features the model was trained on (its window and --features settings; load_model has
+    filled in `spect` for a checkpoint from before --features and copied the three settings into constant.args for evaluate())."""
+    from utils.audio import feature_settings
+    features, num_mel_bins, mel_fmin = feature_settings(loaded_args)
+    return dict(sample_rate=loaded_args.sample_rate, window_size=loaded_args.window_size, window_stride=loaded_args.window_stride,
+                window=getattr(loaded_args, "window", "hamming"), noise_dir=loaded_args.noise_dir, noise_prob=loaded_args.noise_prob,
+                noise_levels=(loaded_args.noise_min, loaded_args.noise_max), features=features, num_mel_bins=num_mel_bins,
+                mel_fmin=mel_fmin)
+
+
 if __name__ == '__main__':
     from utils.data_loader import AudioDataLoader, BucketingSampler, SpectrogramDataset
     from utils.functions import load_model
@@ -58,9 +71,7 @@ if __name__ == '__main__':
         args.gpu_frontend = True                # noise injection runs on the GPU front end (utils/audio.py)
         print("--noise-dir of the checkpoint: noise injection on the GPU front end (--gpu-frontend turned on)")
     args.window = getattr(loaded_args, "window", "hamming")      # the features the model was trained on
-    audio_conf = dict(sample_rate=loaded_args.sample_rate, window_size=loaded_args.window_size,
-                      window_stride=loaded_args.window_stride, window=loaded_args.window, noise_dir=loaded_args.noise_dir,
-                      noise_prob=loaded_args.noise_prob, noise_levels=(loaded_args.noise_min, loaded_args.noise_max))
+    audio_conf = feature_conf(loaded_args)
     test_data = SpectrogramDataset(audio_conf=audio_conf, manifest_filepath_list=args.test_manifest_list, label2id=label2id,
                                    normalize=True, augment=False)
     test_sampler = BucketingSampler(test_data, batch_size=args.batch_size)

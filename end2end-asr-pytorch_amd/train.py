@@ -94,9 +94,15 @@ def main():
         print("=" * 50)
     os.makedirs("./log", exist_ok=True)
     logging.basicConfig(filename="log/" + args.name, filemode='w+', format='%(asctime)s - %(message)s', level=logging.INFO)
+    resumed = None
+    if args.continue_from != "":
+        # before the datasets are built: the checkpoint decides the feature type of a resumed run (load_model writes it into args)
+        logging.info("Continue from checkpoint: " + args.continue_from)
+        resumed = load_model(args.continue_from)
     audio_conf = dict(sample_rate=args.sample_rate, window_size=args.window_size, window_stride=args.window_stride,
                       window=args.window, noise_dir=args.noise_dir, noise_prob=args.noise_prob,
-                      noise_levels=(args.noise_min, args.noise_max))
+                      noise_levels=(args.noise_min, args.noise_max), features=args.features, num_mel_bins=args.num_mel_bins,
+                      mel_fmin=args.mel_fmin)
     logging.info(audio_conf)
     if (args.augment or args.noise_dir is not None or args.spec_augment) and args.cuda and not args.gpu_frontend:
         # tempo / gain augmentation and noise injection run between the host-to-device copy and the STFT (csrc/augment.hip),
@@ -114,9 +120,8 @@ def main():
     valid_loader_list = [AudioDataLoader(v, num_workers=args.num_workers, batch_size=args.batch_size) for v in valid_datas]
 
     start_epoch, metrics = 0, None
-    if args.continue_from != "":
-        logging.info("Continue from checkpoint: " + args.continue_from)
-        model, opt, start_epoch, metrics, loaded_args, label2id, id2label = load_model(args.continue_from)
+    if resumed is not None:
+        model, opt, start_epoch, metrics, loaded_args, label2id, id2label = resumed
     elif args.model == "TRFS":
         model = init_transformer_model(args, label2id, id2label)
         opt = init_optimizer(args, model, "noam")

@@ -208,7 +208,9 @@ class Trainer():
         if getattr(constant.args, "gpu_frontend", False):
             a = constant.args
             src, src_lengths = gpu_front_end(src, src_lengths, a.sample_rate, a.window_size, a.window_stride, a.src_max_len,
-                                             window=a.window, aug=aug, noise_dir=a.noise_dir, spec=spec)
+                                             window=a.window, aug=aug, noise_dir=a.noise_dir, spec=spec,
+                                             features=getattr(a, "features", "spect"), num_mel_bins=getattr(a, "num_mel_bins", 80),
+                                             mel_fmin=getattr(a, "mel_fmin", 20.0))
         if opt is not None and loss_type == "ce" and getattr(constant.args, "graph_buckets", 0) > 0 and src.is_cuda:
             r = self._graph_step(model, opt, src, src_lengths, tgt, smoothing)
             if r is not None:

@@ -3,7 +3,10 @@ utils/data_loader.py:60-91).  Own implementation on numpy only: the reference's 
 are not part of this build.  The reference's sox-based tempo/gain augmentation and noise injection (audio.py:17-61,
 data_loader.py:145-179) run on the GPU instead (asr_augment_wave, csrc/augment.hip; definition in DESIGN.md section 7): the host
 keeps the random draws (utils/data_loader.py), gpu_front_end applies them to the batch before the STFT.
+--features fbank (no counterpart in the reference): log-mel filterbank features of the same STFT (mel_filterbank, log_mel_fbank;
+definition in DESIGN.md section 7).
 """
+import collections
 import glob
 import logging
 import os
@@ -67,12 +70,9 @@ def window_function(name, n):
     return w.astype(np.float32)
 
 
-def log_spectrogram(y, sample_rate=16000, window_size=0.02, window_stride=0.01, normalize=True, window="hamming"):
-    """float waveform -> (n_fft/2+1, frames) log1p(|STFT|), optionally (x-mean)/std over the whole utterance with the
-    unbiased std torch uses (data_loader.py:72-89).  STFT convention: n_fft = win_length = sr*window_size (320),
-    hop = sr*window_stride (160), centred frames with reflect padding (librosa's default of that era)."""
-    n_fft = int(sample_rate * window_size)
-    hop = int(sample_rate * window_stride)
+def _windowed_frames(y, n_fft, hop, window):
+    """float waveform -> (frames, n_fft) float32 windowed frames: centred, reflect padded (zero padded when the signal is no longer
+    than n_fft / 2), a signal shorter than 2 samples padded to 2.  The framing both feature types share."""
     y = np.asarray(y, dtype=np.float32)
     if y.size < 2:
         y = np.pad(y, (0, 2 - y.size))
@@ -80,14 +80,114 @@ def log_spectrogram(y, sample_rate=16000, window_size=0.02, window_stride=0.01, 
     yp = np.pad(y, (pad, pad), mode="reflect") if y.size > pad else np.pad(y, (pad, pad), mode="constant")
     n_frames = 1 + (yp.size - n_fft) // hop
     idx = np.arange(n_fft)[None, :] + hop * np.arange(n_frames)[:, None]
-    frames = yp[idx] * window_function(window, n_fft)[None, :]
+    return yp[idx] * window_function(window, n_fft)[None, :]
+
+
+def _normalized(x):
+    """(x - mean) / unbiased std over the whole utterance (data_loader.py:87-88)."""
+    mean = x.mean()
+    std = x.std(ddof=1)
+    return (x - mean) / std
+
+
+def log_spectrogram(y, sample_rate=16000, window_size=0.02, window_stride=0.01, normalize=True, window="hamming"):
+    """float waveform -> (n_fft/2+1, frames) log1p(|STFT|), optionally (x-mean)/std over the whole utterance with the
+    unbiased std torch uses (data_loader.py:72-89).  STFT convention: n_fft = win_length = sr*window_size (320),
+    hop = sr*window_stride (160), centred frames with reflect padding (librosa's default of that era)."""
+    n_fft = int(sample_rate * window_size)
+    hop = int(sample_rate * window_stride)
+    frames = _windowed_frames(y, n_fft, hop, window)
     spec = np.abs(np.fft.rfft(frames, n=n_fft, axis=1)).T.astype(np.float32)        # (bins, frames)
     spec = np.log1p(spec)
     if normalize:
-        mean = spec.mean()
-        std = spec.std(ddof=1)
-        spec = (spec - mean) / std
+        spec = _normalized(spec)
     return spec
+
+
+# ------------------------------------------------------------------------------------------------ log-mel filterbank features
+FEATURES = ("spect", "fbank")
+FBANK_FLOOR = 1e-10
+# first[m], count[m]: the bins filter m weighs; weights: every filter's count[m] float32 weights one after the other; n_bins = K
+MelBank = collections.namedtuple("MelBank", "first count weights n_bins")
+
+
+def mel_filterbank(M=80, n_fft=320, sample_rate=16000, f_min=20.0, f_max=None):
+    """The sparse bank of M triangular filters on the K = n_fft/2 + 1 bins f_k = k sr / n_fft: M + 2 points
+    equally spaced on the HTK mel scale 2595 log10(1 + f/700) between f_min and f_max (default sr/2), mapped back to Hz as c_0 ..
+    c_{M+1}; w[m][k] = max(0, min((f_k - c_m) / (c_{m+1} - c_m), (c_{m+2} - f_k) / (c_{m+2} - c_{m+1}))), no area normalisation,
+    computed in float64 and stored as float32.  Refuses a bank with a filter that weighs no bin (its feature row would be the
+    constant log floor)."""
+    M, n_fft = int(M), int(n_fft)
+    f_max = sample_rate / 2.0 if f_max is None else float(f_max)
+    if M < 1 or not 0 <= f_min < f_max <= sample_rate / 2.0:
+        raise ValueError("--num-mel-bins %d, --mel-fmin %g: need at least one filter and 0 <= f_min < f_max = %g <= sample rate / 2"
+                         % (M, f_min, f_max))
+    K = n_fft // 2 + 1
+    f = np.arange(K, dtype=np.float64) * sample_rate / n_fft
+    mel = np.linspace(2595.0 * np.log10(1.0 + f_min / 700.0), 2595.0 * np.log10(1.0 + f_max / 700.0), M + 2)
+    c = 700.0 * (10.0 ** (mel / 2595.0) - 1.0)
+    c[0], c[-1] = f_min, f_max                # the end points map back exactly: no rounding residue as a weight on the bin at f_max
+    up = (f[None, :] - c[:M, None]) / (c[1:M + 1] - c[:M])[:, None]
+    down = (c[2:, None] - f[None, :]) / (c[2:] - c[1:M + 1])[:, None]
+    w = np.maximum(0.0, np.minimum(up, down)).astype(np.float32)                   # (M, K)
+    first, count, weights, empty = [], [], [], []
+    for m in range(M):
+        nz = np.nonzero(w[m])[0]
+        if nz.size == 0:
+            empty.append(m)
+            continue
+        first.append(int(nz[0]))
+        count.append(int(nz[-1] - nz[0] + 1))
+        weights.append(w[m, nz[0]:nz[-1] + 1])
+    if empty:
+        raise ValueError("--num-mel-bins %d with --mel-fmin %g on the %d bins of a %d-point STFT at --sample-rate %d: filter(s) %s lie "
+                         "between two bins and weigh none -- use fewer mel bins, a higher --mel-fmin or a longer --window-size"
+                         % (M, f_min, K, n_fft, sample_rate, empty))
+    return MelBank(np.array(first, dtype=np.int32), np.array(count, dtype=np.int32), np.concatenate(weights).astype(np.float32), K)
+
+
+_mel_banks = {}
+
+
+def _mel_bank_cached(M, n_fft, sample_rate, f_min):
+    key = (int(M), int(n_fft), int(sample_rate), float(f_min))
+    bank = _mel_banks.get(key)
+    if bank is None:
+        bank = _mel_banks[key] = mel_filterbank(*key)
+    return bank
+
+
+def log_mel_fbank(y, sample_rate=16000, window_size=0.02, window_stride=0.01, normalize=True, window="hamming", num_mel_bins=80,
+                  f_min=20.0):
+    """float waveform -> (num_mel_bins, frames) log(max(mel energies of the power spectrum, 1e-10)) of log_spectrogram's STFT (the
+    same framing), optionally normalised over the whole utterance as log_spectrogram does.  The host path of --features fbank."""
+    n_fft = int(sample_rate * window_size)
+    hop = int(sample_rate * window_stride)
+    bank = _mel_bank_cached(num_mel_bins, n_fft, sample_rate, f_min)
+    z = np.fft.rfft(_windowed_frames(y, n_fft, hop, window).astype(np.float64), n=n_fft, axis=1)
+    power = z.real ** 2 + z.imag ** 2                                               # (frames, bins)
+    x = np.empty((bank.first.size, power.shape[0]), dtype=np.float64)
+    o = 0
+    for m, (k0, n) in enumerate(zip(bank.first, bank.count)):
+        x[m] = power[:, k0:k0 + n] @ bank.weights[o:o + n].astype(np.float64)
+        o += n
+    x = np.log(np.maximum(x, FBANK_FLOOR)).astype(np.float32)
+    return _normalized(x) if normalize else x
+
+
+def feature_settings(args):
+    """(features, num_mel_bins, mel_fmin) of a Namespace; one written before --features existed is `spect`."""
+    return (getattr(args, "features", "spect"), int(getattr(args, "num_mel_bins", 80)), float(getattr(args, "mel_fmin", 20.0)))
+
+
+def feature_bins(args):
+    """Rows of the features the model sees: n_fft/2 + 1 (161) for --features spect, --num-mel-bins for fbank."""
+    features, M, _ = feature_settings(args)
+    if features == "fbank":
+        return M
+    if features != "spect":
+        raise ValueError("--features %r: one of %s" % (features, FEATURES))
+    return int(np.floor((args.sample_rate * args.window_size) / 2) + 1)
 
 
 # ------------------------------------------------------------------------------------------------ tempo / gain / noise
@@ -179,8 +279,21 @@ def spec_frames(samples, hop, src_max_len=None):
     return n if src_max_len is None else min(n, int(src_max_len))
 
 
+_device_mel_banks = {}
+
+
+def _device_mel_bank(M, n_fft, sample_rate, f_min, device):
+    """The filter bank on the device, uploaded once per (M, n_fft, sample rate, f_min, device), like the STFT constants."""
+    from asr_hip import ops
+    key = (int(M), int(n_fft), int(sample_rate), float(f_min), str(device))
+    bank = _device_mel_banks.get(key)
+    if bank is None:
+        bank = _device_mel_banks[key] = ops.fbank_upload(_mel_bank_cached(*key[:4]), device)
+    return bank
+
+
 def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, window_stride=0.01, src_max_len=None, window="hamming",
-                  aug=None, noise_dir=None, spec=None):
+                  aug=None, noise_dir=None, spec=None, features="spect", num_mel_bins=80, mel_fmin=20.0):
     """--gpu-frontend: `inputs` (B,1,1,Lmax) are the loader's zero padded WAVEFORMS and `input_sizes` (B) their sample
     counts (the collate function is unchanged: a waveform is a 1-bin "spectrogram").  Returns what the host path would have
     put in the batch: log-spectrograms (B,1,F,T) normalised per utterance, cut to --src-max-len frames AFTER the
@@ -189,10 +302,16 @@ def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, wind
     (utils/data_loader.py); they are applied on the device first (ops.augment_wave) and `input_sizes` are then the samples after
     the tempo change.  noise_dir: the directory the clip indices refer to.
     spec: the loader's (B, 40) int32 SpecAugment rows; their n must be the kept frame counts of this batch.
-    Normalisation, cut and SpecAugment are then one launch (asr_spect_finish_aug)."""
+    Normalisation, cut and SpecAugment are then one launch (asr_spect_finish_aug).
+    features="fbank": (B,1,num_mel_bins,T) log-mel filterbank features instead (log_mel_fbank's; asr_fbank_finish[_aug])."""
     import torch
     from asr_hip import ops
     n_fft, hop = int(sample_rate * window_size), int(sample_rate * window_stride)
+    if features not in FEATURES:
+        raise ValueError("features %r: one of %s" % (features, FEATURES))
+    kind = {}
+    if features == "fbank":
+        kind = dict(features="fbank", mel=_device_mel_bank(num_mel_bins, n_fft, sample_rate, mel_fmin, inputs.device))
     wav = inputs.reshape(inputs.shape[0], inputs.shape[-1]).float().contiguous()
     if aug is not None:
         aug = torch.as_tensor(aug, dtype=torch.float64)
@@ -209,9 +328,9 @@ def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, wind
         if spec.dim() != 2 or spec[:, 0].tolist() != kept:
             raise ValueError("the SpecAugment rows' frame counts are not the kept frames of input_sizes")
         spect, n_frames = ops.log_spectrogram(wav, lens, n_fft=n_fft, hop=hop, normalize=True, window=window, spec=spec,
-                                              max_frames=src_max_len)
+                                              max_frames=src_max_len, **kind)
         return spect, n_frames.cpu()
-    spect, n_frames = ops.log_spectrogram(wav, lens, n_fft=n_fft, hop=hop, normalize=True, window=window)
+    spect, n_frames = ops.log_spectrogram(wav, lens, n_fft=n_fft, hop=hop, normalize=True, window=window, **kind)
     if src_max_len is not None and spect.shape[-1] > src_max_len:
         spect = spect[..., :src_max_len].contiguous()
         n_frames = torch.clamp(n_frames, max=src_max_len)

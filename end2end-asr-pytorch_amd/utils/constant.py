@@ -12,7 +12,9 @@ Differences that do not change old command lines:
   * `--gpu-frontend`: the loader ships padded waveforms and the log-spectrogram is computed on the GPU (asr_stft_frames +
     fp32 MFMA DFT + asr_spect_finish) instead of on the host in the DataLoader workers;
   * `--spec-augment` (+ `--spec-time-warp/-freq-mask/-freq-masks/-time-mask/-time-masks/-time-mask-ratio`): SpecAugment of the
-    training batches on the GPU front end.
+    training batches on the GPU front end;
+  * `--features {spect,fbank}` (+ `--num-mel-bins`, `--mel-fmin`): the reference's 161 linear log1p(|STFT|) bins (default) or log-mel
+    filterbank features of the same STFT, on the host path and on the GPU front end alike.
 """
 import argparse
 import os
@@ -44,11 +46,14 @@ _FLAGS = [
     (("--noise-prob",), dict(default=0.4)), (("--noise-min",), dict(default=0.0, type=_F)),
     (("--noise-max",), dict(default=0.5, type=_F)),
     # SpecAugment on the GPU front end; defaults: the LibriSpeech "LD" policy of arXiv:1904.08779 (W 80, F 27,
-    # mF 2, T 100, p 1.0, mT 2) -- on the 161 linear bins of these features, not the paper's 80 mel bins
+    # mF 2, T 100, p 1.0, mT 2) -- on the 161 linear bins of --features spect; --features fbank gives the paper's 80 mel bins
     (("--spec-augment",), dict(action="store_true")), (("--spec-time-warp",), dict(default=80, type=_I)),
     (("--spec-freq-mask",), dict(default=27, type=_I)), (("--spec-freq-masks",), dict(default=2, type=_I)),
     (("--spec-time-mask",), dict(default=100, type=_I)), (("--spec-time-masks",), dict(default=2, type=_I)),
     (("--spec-time-mask-ratio",), dict(default=1.0, type=_F)),
+    # feature type: spect = the reference's linear bins; fbank = log-mel filterbank energies of the same STFT
+    (("--features",), dict(default="spect", choices=["spect", "fbank"])), (("--num-mel-bins",), dict(default=80, type=_I)),
+    (("--mel-fmin",), dict(default=20.0, type=_F)),
     # model
     (("--num-layers",), dict(default=3, type=_I)), (("--num-heads",), dict(default=5, type=_I)),
     (("--dim-model",), dict(default=512, type=_I)), (("--dim-key",), dict(default=64, type=_I)),

@@ -19,7 +19,8 @@ from torch.utils.data.sampler import Sampler
 
 from asr_hip.ddp import rank_shard
 from utils import constant
-from utils.audio import load_audio, log_spectrogram, noise_files, resolve_window, spec_frames, tempo_length
+from utils.audio import (FEATURES, load_audio, log_mel_fbank, log_spectrogram, mel_filterbank, noise_files, resolve_window, spec_frames,
+                         tempo_length)
 
 TEMPO_RANGE, GAIN_RANGE = (0.85, 1.15), (-6, 8)          # reference: utils/audio.py:54
 SPEC_PARAMS, SPEC_MAX_MASKS = 40, 8                      # one SpecAugment row (include/asr_hip.h, ASR_SPEC_AUGMENT_PARAMS)
@@ -42,6 +43,16 @@ class SpectrogramParser(object):
         self.window = resolve_window(audio_conf.get('window', 'hamming'))
         self.normalize = normalize
         self.augment = augment
+        # feature type (audio_conf of a run from before --features: spect); the filter bank is built here once, so that a bank with an
+        # empty filter is refused at start-up
+        self.features = audio_conf.get('features', 'spect')
+        self.num_mel_bins, self.mel_fmin = int(audio_conf.get('num_mel_bins', 80)), float(audio_conf.get('mel_fmin', 20.0))
+        if self.features not in FEATURES:
+            raise ValueError("--features %r: one of %s" % (self.features, FEATURES))
+        n_fft = int(self.sample_rate * self.window_size)
+        if self.features == "fbank":
+            mel_filterbank(self.num_mel_bins, n_fft, self.sample_rate, self.mel_fmin)
+        self.feature_bins = self.num_mel_bins if self.features == "fbank" else n_fft // 2 + 1
         self.noise_dir = audio_conf.get('noise_dir')
         if (augment or self.noise_dir is not None) and not getattr(constant.args, "gpu_frontend", False):
             raise NotImplementedError("tempo/gain augmentation (--augment) and noise injection (--noise-dir) run on the GPU front end "
@@ -85,8 +96,8 @@ class SpectrogramParser(object):
     def draw_spec(self, samples):
         """The SpecAugment row of an utterance of `samples` samples (after the tempo change), on the global np.random after the
         utterance's wave draws: warp centre and target, then (width, start) per frequency mask, then per time mask."""
-        hop, n_fft = int(self.sample_rate * self.window_stride), int(self.sample_rate * self.window_size)
-        n, F, p = spec_frames(samples, hop, constant.args.src_max_len), n_fft // 2 + 1, self.spec
+        hop = int(self.sample_rate * self.window_stride)
+        n, F, p = spec_frames(samples, hop, constant.args.src_max_len), self.feature_bins, self.spec
         row = [0] * SPEC_PARAMS
         row[0], row[3], row[4] = n, p["freq_masks"], p["time_masks"]
         W = p["time_warp"]
@@ -112,6 +123,9 @@ class SpectrogramParser(object):
             # ship the waveform as a 1-bin "spectrogram" (1, L): collate pads it like any other; utils.audio.gpu_front_end
             # turns the batch into log-spectrograms on the device
             return torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))[None, :]
+        if self.features == "fbank":
+            return torch.from_numpy(log_mel_fbank(y, self.sample_rate, self.window_size, self.window_stride, self.normalize,
+                                                  window=self.window, num_mel_bins=self.num_mel_bins, f_min=self.mel_fmin))
         return torch.from_numpy(log_spectrogram(y, self.sample_rate, self.window_size, self.window_stride, self.normalize,
                                                 window=self.window))
 

@@ -15,6 +15,7 @@ from asr_hip import params as P
 from asr_hip.ddp import HipDataParallel
 from models.asr.transformer import Decoder, Encoder, Transformer
 from utils import constant
+from utils.audio import feature_bins, feature_settings
 from utils.optimizer import AnnealingOpt, FusedAdam, NoamOpt
 
 
@@ -63,6 +64,16 @@ def load_model(load_path):
                                  getattr(cur, k), getattr(args, k))
                 setattr(args, k, getattr(cur, k))
         args.cuda = bool(getattr(args, "cuda", False) or getattr(cur, "cuda", False))
+        # the features the model was trained on are the checkpoint's (one written before --features existed: spect); typing another
+        # feature setting on the command line of a resumed run is an error, not an override
+        names = ("features", "num_mel_bins", "mel_fmin")
+        kept = feature_settings(args)
+        for k, v in zip(names, kept):
+            if k in getattr(constant, "explicit", ()) and hasattr(cur, k) and getattr(cur, k) != v:
+                raise ValueError("--%s %s on the command line, but %s was trained with --%s %s: the checkpoint's features cannot be "
+                                 "changed" % (k.replace("_", "-"), getattr(cur, k), load_path, k.replace("_", "-"), v))
+            setattr(args, k, v)
+            setattr(cur, k, v)          # the loaders and the GPU front end of this run read the process-global Namespace
     label2id, id2label = ckpt['label2id'], ckpt['id2label']
     model = init_transformer_model(args, label2id, id2label)
     sd = ckpt['model_state_dict']
@@ -105,8 +116,12 @@ def init_optimizer(args, model, opt_type="noam"):
 
 def init_transformer_model(args, label2id, id2label):
     """Builds Encoder / Decoder / Transformer from the flags; mutates args.dim_input exactly like the reference
-    (functions.py:116-162): 5120 for vgg_cnn, 672 for emb_cnn, unchanged (161) without a CNN."""
-    n_fft_bins = int(math.floor((args.sample_rate * args.window_size) / 2) + 1)       # 161
+    (functions.py:116-162): 5120 for vgg_cnn, 672 for emb_cnn, unchanged (161) without a CNN.  With --features fbank the bins are
+    --num-mel-bins instead of 161: 2560 for vgg_cnn at 80; emb_cnn needs 81 rows; without a CNN dim_input is the bin count."""
+    n_fft_bins = feature_bins(args)                                                   # 161, or --num-mel-bins with --features fbank
+    if args.feat_extractor == 'emb_cnn' and n_fft_bins < 81:
+        raise ValueError("--feat_extractor emb_cnn needs at least 81 feature rows (its 41- and 21-row strided kernels leave none of "
+                         "%d): use vgg_cnn with --features fbank --num-mel-bins %d" % (n_fft_bins, n_fft_bins))
     if args.feat_extractor == 'emb_cnn':
         h = int(math.floor(n_fft_bins - 41) / 2 + 1)
         h = int(math.floor(h - 21) / 2 + 1)
@@ -115,6 +130,11 @@ def init_transformer_model(args, label2id, id2label):
         args.dim_input = int(math.floor(int(math.floor(n_fft_bins) / 2) / 2)) * 128
     else:
         print("the model is initialized without feature extractor")
+        if feature_settings(args)[0] == "fbank":
+            if "dim_input" in getattr(constant, "explicit", ()) and args is constant.args and args.dim_input != n_fft_bins:
+                raise ValueError("--dim-input %d, but --features fbank --num-mel-bins %d gives the model %d rows"
+                                 % (args.dim_input, n_fft_bins, n_fft_bins))
+            args.dim_input = n_fft_bins
     ops.set_compute_dtype(torch.float32 if getattr(args, "precision", "bf16") == "fp32" else torch.bfloat16)
     ops.set_fp8(getattr(args, "precision", "bf16") == "fp8")
     encoder = Encoder(args.num_layers, num_heads=args.num_heads, dim_model=args.dim_model, dim_key=args.dim_key,

@@ -402,7 +402,9 @@ int asr_maxpool_bwd(const void* x, const void* dy, void* dx, int B, int H, int W
  * activations in backward: the forward writes one byte per pooled element, in the pooled tensor's layout -- 0: maximum <= 0 (no
  * gradient: ReLU'), 1 + k: the first maximum is window position k in scan order -- and the backward reads dy and the codes only
  * (first pool of the VGG front end: 0.72 GB moved instead of 1.19 GB, and the 527 MB un-pooled activation need not be kept).
- * ASR_EUNSUPPORTED for layouts without whole 16-byte chunks (callers use the pair above).                          */
+ * ASR_EUNSUPPORTED for layouts without whole 16-byte chunks (callers use the pair above); asr_maxpool_bwd_code with in_tcf takes any
+ * pooled height H/2 (the fused conv.7 epilogue below writes codes at heights it cannot hand to asr_gemm_nn_poolbwd: 20 and 10 pooled
+ * rows of 80 and 40 mel bins), reading by element where a channel's H/2 values are no whole chunks.                */
 int asr_maxpool_fwd_code(const void* x, void* y, uint8_t* code, int B, int H, int W, int C, int out_tcf, int dtype, asr_stream_t stream);
 int asr_maxpool_bwd_code(const uint8_t* code, const void* dy, void* dx, int B, int H, int W, int C, int in_tcf, int dtype,
                          asr_stream_t stream);
@@ -562,6 +564,21 @@ int asr_spec_augment(const float* x, int64_t ldx_row, float* out, int64_t ldo_ro
  * T_out) contiguous.  n of a params row is additionally clamped to the utterance's 1 + max(len, 2) / hop frames.             */
 int asr_spect_finish_aug(const float* reim, int64_t ld, const int32_t* lengths, float* raw, float* sums, float* sqdev, float* out,
                          const int32_t* params, int B, int F, int Tmax, int T_out, int hop, asr_stream_t stream);
+
+/* ---- log-mel filterbank features from the same reim rows (--features fbank; definition in DESIGN.md section 7).  The bank is sparse:
+ * filter m weighs the count[m] power-spectrum bins from first[m] on with the next count[m] entries of the flat fp32 array weights (nw
+ * entries; filter m's start is the sum of the counts before it):
+ *   feat (B, M, Tmax)[b][m][t] = logf(max(sum_j weights[.] (re^2 + im^2)[first[m] + j], floor)), zero past each utterance's frames,
+ * then the passes of asr_spect_finish / asr_spect_finish_aug with F := M (the same kernels: the normalised bits are theirs).
+ * K = n_fft/2 + 1 bins, ld >= 2 K; first, count (M) int32 and weights on the device.  A filter reaching outside [0, K) or past the nw
+ * weights is a caller's mistake that cannot be checked here without reading device memory back: the kernel clamps what it reads (the
+ * Python binding checks the bank on the host before the upload).  ASR_EUNSUPPORTED when 64 (K | 1) + M floats exceed 160 KB of LDS. */
+int asr_fbank_finish(const float* reim, int64_t ld, const int32_t* lengths, float* feat, float* sums, float* sqdev, int B, int K, int M,
+                     int Tmax, int hop, int normalize, const int32_t* first, const int32_t* count, const float* weights, int nw,
+                     float floor, asr_stream_t stream);
+int asr_fbank_finish_aug(const float* reim, int64_t ld, const int32_t* lengths, float* raw, float* sums, float* sqdev, float* out,
+                         const int32_t* params, int B, int K, int M, int Tmax, int T_out, int hop, const int32_t* first,
+                         const int32_t* count, const float* weights, int nw, float floor, asr_stream_t stream);
 
 /* ---- LSTM language model for beam-search rescoring (reference: utils/lstm_utils.py LM.evaluate, RNNModel.forward; nn.LSTM gate
  * order i, f, g, o).  fp32 storage and f32-input MFMA (v_mfma_f32_16x16x4_f32) whatever the ASR model's precision.
