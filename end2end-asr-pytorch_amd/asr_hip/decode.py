@@ -442,3 +442,45 @@ def greedy_search(decoder, encoder_padded_outputs, steps=300, check_every=16):
         if (i + 1) % check_every == 0 and bool(done.all()):
             break
     return torch.stack(out, dim=1)
+
+
+class CTCPrefixScorer:
+    """CTC prefix scores for joint CTC / attention beam search (csrc/ctc_prefix.hip): the scorer object of
+    Decoder._beam_search_hyps.  Holds lp = log-softmax of the encoder's CTC logits (B,T',V) and one (r_n, r_b) state (T',2) per
+    hypothesis row; row r belongs to utterance row_utt[r], whose true encoder frames are frames[row_utt[r]].  Everything stays on the
+    device: step() is one launch, select() one index_select."""
+
+    def __init__(self, ctc_logits, frames, row_utt):
+        dev = ctc_logits.device
+        logits = ctc_logits.detach()
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        B, T, V = logits.shape
+        if logits.stride(2) != 1 or logits.stride(0) != T * logits.stride(1):
+            logits = logits.contiguous()
+        self.frames = torch.as_tensor(frames).to(device=dev, dtype=torch.int32).contiguous()
+        self.row_utt = torch.as_tensor(row_utt).to(device=dev, dtype=torch.int32).contiguous()
+        assert self.frames.numel() == B
+        self.lp, self.state = ops.ctc_prefix_init(logits, self.frames, self.row_utt, constant.PAD_TOKEN)
+        R = self.row_utt.numel()
+        self._first = (torch.ones(R, device=dev, dtype=torch.int32), torch.zeros(R, device=dev, dtype=torch.int32))
+        self.steps = 0
+        self.new = None
+
+    @torch.no_grad()
+    def step(self, last, cand):
+        """last (R) int64 = every row's last token (SOS for the empty prefix: all rows of the search's first step), cand (R,K) int64 ->
+        psi (R,K) fp32 on the device; the K new states of every row wait for select()."""
+        first = self._first[0 if self.steps == 0 else 1]
+        psi, self.new = ops.ctc_prefix_step(self.lp, self.frames, self.state, self.row_utt, last, first, cand.contiguous(),
+                                            constant.PAD_TOKEN, constant.SOS_TOKEN, constant.EOS_TOKEN)
+        return psi
+
+    @torch.no_grad()
+    def select(self, flat):
+        """Row i of the new state continues (row, candidate) pair flat[i] = row * K + k of the last step."""
+        R, K, T, _ = self.new.shape
+        idx = torch.as_tensor(flat, device=self.new.device, dtype=torch.int64)
+        self.state = self.new.view(R * K, T, 2).index_select(0, idx)
+        self.new = None
+        self.steps += 1

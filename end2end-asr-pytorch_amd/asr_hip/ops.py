@@ -653,6 +653,37 @@ def ctc_bwd(logits, targets, input_lengths, target_lengths, ws, grad_out, blank=
     return dl
 
 
+def ctc_prefix_init(logits, frames, row_utt, blank=0):
+    """logits (B,T,V) fp32 (rows contiguous, any row stride), frames (B) int32, row_utt (R) int32 on the device ->
+    (lp (B,T,V) log-softmax, state (R,T,2) of the empty prefix): csrc/ctc_prefix.hip."""
+    B, T, V = logits.shape
+    R = row_utt.numel()
+    assert logits.dtype == torch.float32 and logits.stride(2) == 1 and logits.stride(0) == T * logits.stride(1)
+    assert frames.dtype == torch.int32 and frames.numel() == B and row_utt.dtype == torch.int32 and frames.is_contiguous()
+    lse = torch.empty(B * T, device=logits.device, dtype=torch.float32)
+    lp = torch.empty((B, T, V), device=logits.device, dtype=torch.float32)
+    state = torch.empty((R, T, 2), device=logits.device, dtype=torch.float32)
+    L.call("asr_ctc_prefix_init", L.ptr(logits), logits.stride(1), L.ptr(frames), L.ptr(row_utt), B, T, V, R, int(blank), L.ptr(lse),
+           L.ptr(lp), L.ptr(state), L.stream())
+    return lp, state
+
+
+def ctc_prefix_step(lp, frames, state, row_utt, last, first, cand, blank=0, sos=1, eos=2):
+    """One extension of every hypothesis row by each of its K candidates: state (R,T,2), last (R) int64, first (R) int32, cand (R,K)
+    int64 -> (psi (R,K) fp32, new_state (R,K,T,2)); frames >= T_b of new_state are left unwritten."""
+    B, T, V = lp.shape
+    R, K = cand.shape
+    assert lp.dtype == torch.float32 and lp.is_contiguous() and state.dtype == torch.float32 and state.is_contiguous()
+    assert tuple(state.shape) == (R, T, 2) and row_utt.dtype == torch.int32 and row_utt.numel() == R and first.dtype == torch.int32
+    assert first.numel() == R and last.dtype == torch.int64 and last.numel() == R and cand.dtype == torch.int64 and cand.is_contiguous()
+    assert frames.dtype == torch.int32 and frames.numel() == B
+    psi = torch.empty((R, K), device=lp.device, dtype=torch.float32)
+    new_state = torch.empty((R, K, T, 2), device=lp.device, dtype=torch.float32)
+    L.call("asr_ctc_prefix_step", L.ptr(lp), L.ptr(frames), L.ptr(state), L.ptr(row_utt), L.ptr(last), L.ptr(first), L.ptr(cand),
+           B, T, V, R, K, int(blank), int(sos), int(eos), L.ptr(psi), L.ptr(new_state), L.stream())
+    return psi, new_state
+
+
 def decode_prepare(pe, pe_cur, key_len, state):
     """pe (T,D) fp32, state (>=1) int64 on the device: pe_cur = pe[state[0]], key_len[:] = state[0] + 1."""
     assert pe.dtype == torch.float32 and pe.is_contiguous() and pe_cur.dtype == torch.float32 and key_len.dtype == torch.int32

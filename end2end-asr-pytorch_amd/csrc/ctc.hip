@@ -12,37 +12,14 @@
 // goes to a caller-owned workspace for the backward pass); everything else is row parallel.  Path probabilities through (t, s)
 // never exceed the total p(l|x), so exp(alpha + beta - lp + nll) lies in [0, 1]: the per-label sums of the gradient are
 // accumulated in linear space with LDS atomics, no second max pass.
-#include "common.h"
+#include "ctc_common.h"      // NEG_INF, lae2, ctc_lse_kernel (shared with ctc_prefix.hip)
 
 namespace {
 
-constexpr float NEG_INF = -INFINITY;
-
-__device__ __forceinline__ float lae2(float a, float b) {      // log(exp(a) + exp(b)), -inf safe
-  const float m = fmaxf(a, b);
-  if (m == NEG_INF) return NEG_INF;
-  return m + logf(expf(a - m) + expf(b - m));
-}
 __device__ __forceinline__ float lae3(float a, float b, float c) {
   const float m = fmaxf(fmaxf(a, b), c);
   if (m == NEG_INF) return NEG_INF;
   return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
-}
-
-// one wave per row: lse[row] = log sum_v exp(logits[row, v])
-__global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ logits, int64_t ld, int64_t rows, int V,
-                                                      float* __restrict__ lse) {
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float* x = logits + row * ld;
-  float m = NEG_INF;
-  for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
-  m = wave_max(m);
-  float s = 0.f;
-  for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
-  s = wave_sum(s);
-  if (lane == 0) lse[row] = m + logf(s);
 }
 
 // grid (B, 2): y = 0 the alpha recursion, y = 1 the beta recursion.  lat (B, T, S) fp32.

@@ -20,20 +20,45 @@ from models.common_layers import (LowRankMultiHeadAttention, LowRankPositionwise
 from utils import constant
 
 
+def frames_after_cnn(T, feat):
+    """Encoder positions produced by T input frames: vgg_cnn = two 2x2/2 max-pools behind same-padded 3x3 convolutions; emb_cnn = time
+    kernel 11 / stride 2 / padding 10, then kernel 11 / stride 1 / no padding; no front end: T."""
+    if feat == "vgg_cnn":
+        return (int(T) // 2) // 2
+    if feat == "emb_cnn":
+        return ((int(T) + 20 - 11) // 2 + 1) - 10
+    return int(T)
+
+
+def ctc_collapse(ids, length=None, blank=constant.PAD_TOKEN):
+    """Best-path CTC decoding of one utterance's frame-wise argmax ids: the first `length` frames, repeats merged, blanks dropped."""
+    out, prev = [], None
+    for x in ids[:len(ids) if length is None else max(0, int(length))]:
+        if x != prev and x != blank:
+            out.append(int(x))
+        prev = x
+    return out
+
+
 def _lengths_to_device(input_lengths, device):
     t = torch.as_tensor(input_lengths)
     return t.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
 
 
 class Transformer(nn.Module):
-    """Transformer(encoder, decoder, feat_extractor='vgg_cnn')   (reference: transformer.py:16-57)"""
+    """Transformer(encoder, decoder, feat_extractor='vgg_cnn')   (reference: transformer.py:16-57)
 
-    def __init__(self, encoder, decoder, feat_extractor='vgg_cnn'):
+    ctc_head=True (train.py --ctc-weight > 0) adds `ctc_linear`, a CTC output layer on the ENCODER output for joint
+    CTC / attention training and decoding (blank = PAD).  Without it the module, its parameters and its state_dict keys do not exist."""
+
+    def __init__(self, encoder, decoder, feat_extractor='vgg_cnn', ctc_head=False):
         super().__init__()
         self.encoder = encoder
         self.decoder = decoder
         self.id2label = decoder.id2label
         self.feat_extractor = feat_extractor
+        if ctc_head:
+            self.ctc_linear = nn.Linear(decoder.dim_model, decoder.num_trg_vocab)
         if feat_extractor == 'emb_cnn':
             self.conv = nn.Sequential(
                 nn.Conv2d(1, 32, kernel_size=(41, 11), stride=(2, 2), padding=(0, 10)), nn.BatchNorm2d(32),
@@ -65,25 +90,65 @@ class Transformer(nn.Module):
         b, c, f, t = padded_input.shape
         return padded_input.reshape(b, c * f, t).transpose(1, 2).contiguous().to(ops.compute_dtype())
 
-    def forward(self, padded_input, input_lengths, padded_target, verbose=False):
-        """-> (pred (B,Td,V) fp32, gold (B,Td), hyp_seq (B,Td), gold_seq)   (reference: transformer.py:59-85)"""
+    # -------------------------------------------------------------------------------------------- encoder CTC head
+    def ctc_frame_lengths(self, input_lengths, enc_frames):
+        """True encoder frames per utterance, min(T', frames_after_cnn(length)): the CTC input lengths.  (The PRE-CNN lengths the
+        encoder masks with are a reference quirk that stays where it is; CTC does not inherit it.)"""
+        return [min(int(enc_frames), frames_after_cnn(int(n), self.feat_extractor)) for n in torch.as_tensor(input_lengths).tolist()]
+
+    def ctc_logits(self, enc_out):
+        """(B,T',V) fp32 logits of the CTC head on the encoder output, through the project's linear autograd path."""
+        if not hasattr(self, "ctc_linear"):
+            raise ValueError("this model has no encoder CTC head (ctc_linear): it was trained with --ctc-weight 0")
+        # (called BEFORE the decoder: the fp32-logit hand-over slot of F_.linear belongs to the vocabulary projection that runs last)
+        return F_.linear(enc_out, self.ctc_linear.weight, self.ctc_linear.bias, True, True)
+
+    @torch.no_grad()
+    def ctc_greedy(self, enc_out, lengths):
+        """Best-path decoding from the CTC head alone: frame-wise argmax, repeats merged and blanks dropped inside each utterance's
+        true frames (`lengths`, encoder frames) -> strings.  The cheap way to see whether the head has learnt anything."""
+        logits = self.ctc_logits(enc_out)
+        B, T, V = logits.shape
+        ids = ops.argmax_rows(logits.reshape(B * T, V)).view(B, T).cpu().tolist()
+        return ["".join(self.id2label[x] for x in ctc_collapse(row, n)) for row, n in zip(ids, lengths)]
+
+    def forward(self, padded_input, input_lengths, padded_target, verbose=False, return_ctc=False):
+        """-> (pred (B,Td,V) fp32, gold (B,Td), hyp_seq (B,Td), gold_seq)   (reference: transformer.py:59-85); with return_ctc also
+        the CTC head's logits (B,T',V) fp32 on the encoder output."""
         feats = self._features(padded_input)
         enc_out, _ = self.encoder(feats, input_lengths)
+        ctc = self.ctc_logits(enc_out) if return_ctc else None
         pred, gold, *_ = self.decoder(padded_target, enc_out, input_lengths)
         hyp_seq = ops.argmax_rows(pred.detach().reshape(-1, pred.shape[-1])).view(pred.shape[0], pred.shape[1])
+        if return_ctc:
+            return pred, gold, hyp_seq, gold, ctc
         return pred, gold, hyp_seq, gold
 
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
-                 lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False):
-        """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124)"""
+                 lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
+                 ctc_candidates=0, ctc_greedy=False):
+        """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
+        scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
+        ctc_greedy: best-path decoding from the head alone."""
+        if ctc_weight > 0 and not beam_search:
+            raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % ctc_weight)
         feats = self._features(padded_input)
         enc_out, _ = self.encoder(feats, input_lengths)
         _, gold, *_ = self.decoder(padded_target, enc_out, input_lengths)
         gold_cpu = gold.cpu().tolist()
         strs_gold = ["".join(self.id2label[int(x)] for x in row) for row in gold_cpu]
-        if beam_search:
+        if ctc_weight > 0 or ctc_greedy:
+            if ctc_lengths is None:
+                ctc_lengths = self.ctc_frame_lengths(input_lengths, enc_out.shape[1])
+            if ctc_logits is None and not ctc_greedy:
+                with torch.no_grad():
+                    ctc_logits = self.ctc_logits(enc_out)
+        if ctc_greedy:
+            strs_hyps = self.ctc_greedy(enc_out, ctc_lengths)
+        elif beam_search:
             _, strs_hyps = self.decoder.beam_search(enc_out, beam_width=beam_width, nbest=1, lm=lm, lm_rescoring=lm_rescoring,
-                                                    lm_weight=lm_weight, c_weight=c_weight)
+                                                    lm_weight=lm_weight, c_weight=c_weight, ctc_logits=ctc_logits,
+                                                    ctc_lengths=ctc_lengths, ctc_weight=ctc_weight, ctc_candidates=ctc_candidates)
             if len(strs_hyps) != padded_input.shape[0]:
                 strs_hyps = self.decoder.greedy_search(enc_out)
         else:
@@ -291,19 +356,41 @@ class Decoder(nn.Module):
 
     @torch.no_grad()
     def beam_search(self, encoder_padded_outputs, beam_width=2, nbest=5, lm_rescoring=False, lm=None, lm_weight=0.1,
-                    c_weight=1, prob_weight=1.0, use_cache=True):
+                    c_weight=1, prob_weight=1.0, use_cache=True, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0, ctc_candidates=0):
         """Per-utterance beam search with the reference's scoring (transformer.py:396-517).  With
         use_cache the live hypotheses of an utterance are one batch of the KV-cached decoder (one step = one token per
         hypothesis); the candidate bookkeeping on the host is the reference's, including its in-loop re-sort (:460).
         With more than one utterance the cached search runs for all of them at once (_beam_search_batched);
         use_cache="per_utterance" keeps the utterance loop.  lm_rescoring=True with lm (utils/lstm_utils.LM) re-ranks the finished
-        hypotheses with the LM score (_rank_ended); the search itself prunes on the acoustic score alone, as in the reference."""
+        hypotheses with the LM score (_rank_ended); the search itself prunes on the acoustic score alone, as in the reference.
+        ctc_weight = mu > 0 with ctc_logits (B,T',V) fp32 (the encoder CTC head's) and ctc_lengths (true encoder frames): joint CTC /
+        attention scoring -- every step ranks the ctc_candidates (0: min(V, 16, 2 * beam_width)) best attention candidates of a
+        hypothesis by (1 - mu) * attention log-probability + mu * CTC prefix log-probability increment (csrc/ctc_prefix.hip) and keeps
+        the beam_width best; batched KV-cached search only."""
         if lm_rescoring and lm is None:
             raise ValueError("lm_rescoring=True needs lm (utils.lstm_utils.LM)")
         lm = lm if lm_rescoring else None
         from asr_hip.decode import DecoderKVCache
         if not self._kv_cache_supported():
             use_cache = False
+        if ctc_weight > 0:
+            if not 0.0 < ctc_weight <= 1.0:
+                raise ValueError("ctc_weight must lie in [0, 1], got %g" % ctc_weight)
+            if ctc_logits is None:
+                raise ValueError("ctc_weight %g needs ctc_logits (the encoder CTC head's output)" % ctc_weight)
+            if not use_cache or use_cache == "per_utterance":
+                raise NotImplementedError("joint CTC / attention scoring runs in the batched KV-cached beam search only (not the uncached "
+                                          "path, use_cache='per_utterance' or a low-rank / dim_key != dim_value model)")
+            from asr_hip.decode import CTCPrefixScorer
+            B, Te, V = ctc_logits.shape
+            K = int(ctc_candidates) if ctc_candidates else min(V, 16, 2 * beam_width)
+            if not beam_width <= K <= min(V, 16):
+                raise ValueError("ctc_candidates %d must lie in [beam_width %d, min(V, 16) = %d]" % (K, beam_width, min(V, 16)))
+            if ctc_lengths is None:
+                ctc_lengths = [Te] * B
+            scorer = CTCPrefixScorer(ctc_logits, ctc_lengths, [b for b in range(B) for _ in range(beam_width)])
+            ended = self._beam_search_hyps(encoder_padded_outputs, beam_width, ctc=(scorer, float(ctc_weight), K))
+            return self._rank_ended(ended, nbest, c_weight, lm, lm_weight)
         if use_cache and use_cache != "per_utterance" and encoder_padded_outputs.size(0) > 1:
             return self._beam_search_batched(encoder_padded_outputs, beam_width, nbest, c_weight, lm, lm_weight)
         all_ended = []
@@ -381,27 +468,54 @@ class Decoder(nn.Module):
         return hyp
 
     def _beam_search_batched(self, encoder_padded_outputs, beam_width, nbest, c_weight, lm=None, lm_weight=0.1):
+        return self._rank_ended(self._beam_search_hyps(encoder_padded_outputs, beam_width), nbest, c_weight, lm, lm_weight)
+
+    def _beam_search_hyps(self, encoder_padded_outputs, beam_width, ctc=None):
         """The same search for ALL utterances of the batch at once: utterance b owns decoder rows b * W .. b * W + W - 1 of ONE
         KV-cached decoder batch (its live hypotheses in the first rows, the others idle), so a step is one decoder step, one
         log-softmax / top-W launch and one device -> host copy for the whole batch instead of one of each per utterance.  The
         candidate bookkeeping per utterance is the reference's (transformer.py:437-497: the in-loop re-sort, forced EOS at the
-        last encoder frame, sqrt(words) * c_weight on finished hypotheses), so the strings are those of the per-utterance loop."""
+        last encoder frame, sqrt(words) * c_weight on finished hypotheses), so the strings are those of the per-utterance loop.
+        -> the finished hypotheses, one list per utterance (for _rank_ended).
+
+        ctc = (scorer, mu, K): joint CTC / attention scoring.  The step takes the top-K attention
+        log-probabilities per row instead of the top-W, the scorer (an object with step(last, cand) -> psi (R,K) and select(flat):
+        asr_hip.decode.CTCPrefixScorer, or a host restatement in the tests) gives the CTC prefix log-probability psi of every
+        candidate, and the W best of a hypothesis by joint = (1 - mu) * att + mu * (psi' - psi(g)) go into the unchanged bookkeeping.
+        'score' accumulates the joint increments ('att' the attention terms and 'psi' the prefix's CTC score alone); the CTC states are
+        selected with the rows of the KV cache.  psi reaches the host in the same copy as the top-K values and indices."""
         from asr_hip.decode import DecoderKVCache
         W = beam_width
         B, max_len = encoder_padded_outputs.size(0), encoder_padded_outputs.size(1)
         dev = encoder_padded_outputs.device
         cache = DecoderKVCache(self, encoder_padded_outputs.repeat_interleave(W, dim=0), max_len=300)
         hyps = [[{'score': 0.0, 'yseq': [constant.SOS_TOKEN]}] for _ in range(B)]
+        if ctc is not None:
+            scorer, mu, K = ctc
+            for b in range(B):
+                hyps[b][0].update(att=0.0, psi=0.0)
         ended = [[] for _ in range(B)]
         for i in range(300):
             last = [constant.SOS_TOKEN] * (B * W)
             for b in range(B):
                 for hi, h in enumerate(hyps[b]):
                     last[b * W + hi] = h['yseq'][-1]
-            logits = cache.step(torch.tensor(last, dtype=torch.int64, device=dev))
-            best_all, idx_all = ops.logsoftmax_topk(logits.float().contiguous(), W)
-            best_all, idx_all = best_all.tolist(), idx_all.tolist()
+            last = torch.tensor(last, dtype=torch.int64, device=dev)
+            logits = cache.step(last)
+            if ctc is None:
+                best_all, idx_all = ops.logsoftmax_topk(logits.float().contiguous(), W)
+                best_all, idx_all = best_all.tolist(), idx_all.tolist()
+            else:
+                best_all, idx_all = ops.logsoftmax_topk(logits.float().contiguous(), K)
+                psi_all = scorer.step(last, idx_all)
+                if psi_all.is_cuda:               # one device -> host copy per step (ids up to 2^24 are exact in fp32)
+                    packed = torch.cat([best_all, psi_all, idx_all.float()], dim=1).tolist()
+                    best_all, psi_all = [r[:K] for r in packed], [r[K:2 * K] for r in packed]
+                    idx_all = [[int(x) for x in r[2 * K:]] for r in packed]
+                else:
+                    best_all, idx_all, psi_all = best_all.tolist(), idx_all.tolist(), psi_all.tolist()
             rows = list(range(B * W))
+            slots = [0] * (B * W)                  # (ctc) the candidate slot k a surviving row continues: its state is (parent row, k)
             moved = False
             for b in range(B):
                 if not hyps[b]:
@@ -409,8 +523,16 @@ class Decoder(nn.Module):
                 cand = []
                 for hi, hyp in enumerate(hyps[b]):
                     best, idx = best_all[b * W + hi], idx_all[b * W + hi]
-                    for j in range(W):
-                        cand.append({'score': hyp['score'] + best[j], 'yseq': hyp['yseq'] + [idx[j]], 'parent': hi})
+                    if ctc is None:
+                        for j in range(W):
+                            cand.append({'score': hyp['score'] + best[j], 'yseq': hyp['yseq'] + [idx[j]], 'parent': hi})
+                    else:
+                        psi = psi_all[b * W + hi]
+                        # a candidate CTC rules out (blank, SOS, more labels than frames) scores -inf, never inf - inf
+                        joint = [((1.0 - mu) * best[j] + mu * (psi[j] - hyp['psi'])) if psi[j] > -math.inf else -math.inf for j in range(K)]
+                        for j in sorted(range(K), key=lambda j: joint[j], reverse=True)[:W]:      # stable: ties keep the attention order
+                            cand.append({'score': hyp['score'] + joint[j], 'yseq': hyp['yseq'] + [idx[j]], 'parent': hi, 'slot': j,
+                                         'att': hyp['att'] + best[j], 'psi': psi[j]})
                     cand = sorted(cand, key=lambda h: h['score'], reverse=True)[:W]      # the reference's in-loop re-sort (:460)
                 if i == max_len - 1:
                     for hyp in cand:
@@ -425,11 +547,14 @@ class Decoder(nn.Module):
                 for j, hyp in enumerate(alive):
                     moved |= hyp['parent'] != j
                     rows[b * W + j] = b * W + hyp['parent']
+                    slots[b * W + j] = hyp.get('slot', 0)
             if not any(hyps):
                 break
             if moved:
                 cache.select(rows, cross=False)           # parents stay inside their utterance: the cross keys / values do not move
-        return self._rank_ended(ended, nbest, c_weight, lm, lm_weight)
+            if ctc is not None:
+                scorer.select([r * K + k for r, k in zip(rows, slots)])
+        return ended
 
 
 class DecoderLayer(nn.Module):

@@ -30,7 +30,10 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
             _, strs_hyps, strs_gold = model.evaluate(src, src_lengths, tgt, beam_search=args.beam_search,
                                                      beam_width=args.beam_width, beam_nbest=args.beam_nbest, lm=lm,
                                                      lm_rescoring=args.lm_rescoring, lm_weight=args.lm_weight,
-                                                     c_weight=args.c_weight, verbose=args.verbose)
+                                                     c_weight=args.c_weight, verbose=args.verbose,
+                                                     ctc_weight=getattr(args, "ctc_decode_weight", 0.0),
+                                                     ctc_candidates=getattr(args, "ctc_candidates", 0),
+                                                     ctc_greedy=getattr(args, "ctc_greedy", False))
             for hyp, gold in zip(strs_hyps, strs_gold):
                 for ch in (constant.EOS_CHAR, constant.SOS_CHAR, constant.PAD_CHAR):
                     hyp, gold = hyp.replace(ch, ""), gold.replace(ch, "")
@@ -44,6 +47,19 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
                 total_cer * 100 / max(1, total_char), total_wer * 100 / max(1, total_word),
                 total_en_cer * 100 / max(1, total_en_char), total_zh_cer * 100 / max(1, total_zh_char)))
     return total_cer / max(1, total_char), total_wer / max(1, total_word)
+
+
+def check_ctc_decoding(args, model):
+    """--ctc-decode-weight / --ctc-greedy need the encoder CTC head of a model trained with --ctc-weight > 0; the weight lies in
+    [0, 1] and applies to --beam-search."""
+    w = float(getattr(args, "ctc_decode_weight", 0.0) or 0.0)
+    if not 0.0 <= w <= 1.0:
+        raise ValueError("--ctc-decode-weight must lie in [0, 1], got %g" % w)
+    if (w > 0 or getattr(args, "ctc_greedy", False)) and not hasattr(model, "ctc_linear"):
+        raise ValueError("--ctc-decode-weight / --ctc-greedy need a model with an encoder CTC head: this checkpoint was trained with "
+                         "--ctc-weight 0")
+    if w > 0 and not getattr(args, "beam_search", False):
+        raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % w)
 
 
 def feature_conf(loaded_args):
@@ -66,6 +82,7 @@ if __name__ == '__main__':
     if getattr(loaded_args, "parallel", False):
         print("unwrap data parallel")
         model = model.module
+    check_ctc_decoding(args, model)
     constant.args.tgt_max_len = max(constant.args.tgt_max_len, 301)      # greedy/beam search always run 300 steps
     if getattr(loaded_args, "noise_dir", None) is not None and args.cuda and not args.gpu_frontend:
         args.gpu_frontend = True                # noise injection runs on the GPU front end (utils/audio.py)

@@ -61,6 +61,8 @@ def resolve_graph_buckets(args, explicit, model=None):
     feat = getattr(core, "feat_extractor", None) if core is not None else None
     if feat is None:
         feat = getattr(args, "feat_extractor", "")
+    if getattr(args, "ctc_weight", 0.0) > 0:
+        return args.graph_buckets       # the hybrid CTC / attention step runs as eager launches (trainer/asr/trainer.py)
     if getattr(args, "cuda", False) and feat in ("vgg_cnn", "emb_cnn") and getattr(args, "loss", "ce") == "ce":
         args.graph_buckets = DEFAULT_GRAPH_BUCKET
     return args.graph_buckets
@@ -72,6 +74,8 @@ def main():
     from utils.functions import init_optimizer, init_transformer_model, load_model
 
     args = constant.args
+    from utils.functions import check_ctc_weight
+    check_ctc_weight(args.ctc_weight, args)          # at start-up, before any process group or dataset exists
     if "OMP_NUM_THREADS" not in os.environ:
         # the training process only issues kernel launches and small host tensor ops (collation runs in the loader's worker
         # processes): with torch's default of one intra-op thread per core, every host-side tensor op wakes a pool whose workers

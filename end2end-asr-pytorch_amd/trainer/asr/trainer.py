@@ -23,7 +23,7 @@ from utils.data_loader import DevicePrefetcher
 from utils.functions import save_model
 from asr_hip import ops
 from asr_hip.text import edit_distance_batch
-from utils.metrics import calculate_metrics
+from utils.metrics import calculate_joint_loss, calculate_metrics
 
 
 def _strings(id_rows, id2label):
@@ -98,11 +98,8 @@ class Trainer():
     def _frames_after_cnn(T, feat):
         """Encoder positions produced by T input frames (models/asr/transformer.py: vgg_cnn = two 2x2/2 max-pools behind same-padded
         3x3 convolutions; emb_cnn = time kernel 11 / stride 2 / padding 10, then kernel 11 / stride 1 / no padding)."""
-        if feat == "vgg_cnn":
-            return (int(T) // 2) // 2
-        if feat == "emb_cnn":
-            return ((int(T) + 20 - 11) // 2 + 1) - 10
-        return int(T)
+        from models.asr.transformer import frames_after_cnn
+        return frames_after_cnn(T, feat)
 
     def _graph_step(self, model, opt, src, src_lengths, tgt, smoothing):
         """--graph-buckets N: the training step as a captured hipGraph per (batch, padded frames) shape.  The batch is copied
@@ -211,15 +208,31 @@ class Trainer():
                                              window=a.window, aug=aug, noise_dir=a.noise_dir, spec=spec,
                                              features=getattr(a, "features", "spect"), num_mel_bins=getattr(a, "num_mel_bins", 80),
                                              mel_fmin=getattr(a, "mel_fmin", 20.0))
-        if opt is not None and loss_type == "ce" and getattr(constant.args, "graph_buckets", 0) > 0 and src.is_cuda:
+        # --ctc-weight > 0 (joint CTC / attention training): L = (1 - w) CE + w CTC on the encoder's CTC head.
+        # The hybrid step runs on the eager path; capturing it is a follow-up.
+        ctc_weight = float(getattr(constant.args, "ctc_weight", 0.0) or 0.0)
+        if ctc_weight > 0 and loss_type != "ce":
+            raise ValueError("--ctc-weight %g combines the encoder CTC loss with the cross-entropy loss: --loss %s is not supported with it"
+                             % (ctc_weight, loss_type))
+        if ctc_weight > 0 and opt is not None and not self.__dict__.get("_logged_ctc_eager"):
+            self._logged_ctc_eager = True
+            logging.info("--ctc-weight %g: the hybrid CTC / attention step runs as eager launches (no hipGraph replay)", ctc_weight)
+        if (opt is not None and loss_type == "ce" and getattr(constant.args, "graph_buckets", 0) > 0 and src.is_cuda
+                and ctc_weight == 0):
             r = self._graph_step(model, opt, src, src_lengths, tgt, smoothing)
             if r is not None:
                 loss, gold_seq, hyp_seq = r
                 return _Pending(gold_seq, hyp_seq, loss, id2label, graph_opt=opt)         # asynchronous D2H; no sync in this step
         if opt is not None:
             opt.zero_grad()
-        pred, gold, hyp_seq, gold_seq = model(src, src_lengths, tgt, verbose=False)
-        if loss_type == "ctc":
+        if ctc_weight > 0:
+            pred, gold, hyp_seq, gold_seq, ctc_logits = model(src, src_lengths, tgt, verbose=False, return_ctc=True)
+        else:
+            pred, gold, hyp_seq, gold_seq = model(src, src_lengths, tgt, verbose=False)
+        if ctc_weight > 0:
+            core = model.module if hasattr(model, "module") else model
+            loss, _, _ = calculate_joint_loss(core, pred, gold, ctc_logits, tgt, src_lengths, tgt_lengths, smoothing, ctc_weight)
+        elif loss_type == "ctc":
             # reference trainer.py:81-85: input lengths = source percentages x decoder positions, targets' true lengths
             sizes = (src_percentages.float() * int(pred.size(1))).int()
             loss, sums = calculate_metrics(pred, gold, input_lengths=sizes, target_lengths=tgt_lengths, loss_type="ctc")

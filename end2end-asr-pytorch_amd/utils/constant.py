@@ -69,6 +69,12 @@ _FLAGS = [
     (("--beam-nbest",), dict(default=5, type=_I)), (("--lm-rescoring",), dict(action="store_true")),
     (("--lm-path",), dict(type=_S, default="lm_model.pt")), (("--lm-weight",), dict(default=0.1, type=_F)),
     (("--c-weight",), dict(default=0.1, type=_F)), (("--prob-weight",), dict(default=1.0, type=_F)),
+    # joint CTC / attention.  --ctc-weight w (train.py): an encoder CTC head, L = (1 - w) CE + w CTC; 0 = no head.
+    # --ctc-decode-weight m (test.py --beam-search): beam candidates ranked by (1 - m) attention + m CTC prefix score, the
+    # --ctc-candidates (0: min(V, 16, 2 * beam width)) best attention candidates of a hypothesis scored; --ctc-greedy: best-path
+    # decoding from the CTC head alone
+    (("--ctc-weight",), dict(default=0.0, type=_F)), (("--ctc-decode-weight",), dict(default=0.0, type=_F)),
+    (("--ctc-candidates",), dict(default=0, type=_I)), (("--ctc-greedy",), dict(action="store_true")),
     # loss / regularisation
     (("--loss",), dict(type=_S, default="ce")), (("--clip",), dict(action="store_true")),
     (("--max-norm",), dict(default=400, type=_F)), (("--dropout",), dict(default=0.1, type=_F)),

@@ -74,6 +74,19 @@ def load_model(load_path):
                                  "changed" % (k.replace("_", "-"), getattr(cur, k), load_path, k.replace("_", "-"), v))
             setattr(args, k, v)
             setattr(cur, k, v)          # the loaders and the GPU front end of this run read the process-global Namespace
+        # the encoder CTC head (--ctc-weight) is part of the model: a run resumes with the checkpoint's weight (one written before the
+        # flag existed: 0, no head); an explicit --ctc-weight may replace a positive weight with another positive one (it only weighs
+        # the loss), but cannot add or drop the head
+        kept = float(getattr(args, "ctc_weight", 0.0) or 0.0)
+        if "ctc_weight" in getattr(constant, "explicit", ()) and hasattr(cur, "ctc_weight") and float(cur.ctc_weight) != kept:
+            check_ctc_weight(cur.ctc_weight)
+            if (float(cur.ctc_weight) > 0) != (kept > 0):
+                raise ValueError("--ctc-weight %g on the command line, but %s was trained with --ctc-weight %g: the encoder CTC head "
+                                 "cannot be added to or dropped from a checkpoint" % (cur.ctc_weight, load_path, kept))
+            logging.info("load_model: --ctc-weight %g from the command line replaces the checkpoint's %g", cur.ctc_weight, kept)
+            kept = float(cur.ctc_weight)
+        args.ctc_weight = kept
+        cur.ctc_weight = kept           # the trainer of this run reads the process-global Namespace
     label2id, id2label = ckpt['label2id'], ckpt['id2label']
     model = init_transformer_model(args, label2id, id2label)
     sd = ckpt['model_state_dict']
@@ -114,6 +127,23 @@ def init_optimizer(args, model, opt_type="noam"):
     return None
 
 
+def check_ctc_weight(w, args=None):
+    """--ctc-weight must lie in [0, 1]; a positive weight (joint CTC / attention training) excludes --parallel
+    (the token-mean CE and the utterance-mean CTC normalise differently under the gradient reducer's statistics slot) and --loss ctc
+    (the reference's CTC on the DECODER output)."""
+    w = float(w or 0.0)
+    if not 0.0 <= w <= 1.0:
+        raise ValueError("--ctc-weight must lie in [0, 1], got %g" % w)
+    if w > 0 and args is not None:
+        if getattr(args, "parallel", False):
+            raise ValueError("--ctc-weight %g with --parallel is not supported: the cross-entropy loss is a mean over tokens and the "
+                             "CTC loss a mean over utterances, and the data-parallel gradient reducer normalises by one of them" % w)
+        if getattr(args, "loss", "ce") != "ce":
+            raise ValueError("--ctc-weight %g with --loss %s is not supported: the weight combines the encoder CTC loss with the "
+                             "cross-entropy loss (--loss ce)" % (w, args.loss))
+    return w
+
+
 def init_transformer_model(args, label2id, id2label):
     """Builds Encoder / Decoder / Transformer from the flags; mutates args.dim_input exactly like the reference
     (functions.py:116-162): 5120 for vgg_cnn, 672 for emb_cnn, unchanged (161) without a CNN.  With --features fbank the bins are
@@ -144,7 +174,8 @@ def init_transformer_model(args, label2id, id2label):
                       num_heads=args.num_heads, dim_emb=args.dim_emb, dim_model=args.dim_model, dim_inner=args.dim_inner,
                       dim_key=args.dim_key, dim_value=args.dim_value, trg_max_length=args.tgt_max_len, dropout=args.dropout,
                       emb_trg_sharing=args.emb_trg_sharing, rank=getattr(args, "rank", 0))
-    model = Transformer(encoder, decoder, feat_extractor=args.feat_extractor)
+    ctc_weight = check_ctc_weight(getattr(args, "ctc_weight", 0.0), args)
+    model = Transformer(encoder, decoder, feat_extractor=args.feat_extractor, ctc_head=ctc_weight > 0)
     if args.parallel:
         model = HipDataParallel(model, device_ids=args.device_ids)
     return model

@@ -70,3 +70,16 @@ def calculate_metrics(pred, gold, input_lengths=None, target_lengths=None, smoot
     if with_argmax:
         return loss, sums, am.view(pred.shape[0], pred.shape[1])
     return loss, sums
+
+
+def calculate_joint_loss(model, pred, gold, ctc_logits, tgt, src_lengths, tgt_lengths, smoothing, ctc_weight):
+    """Joint CTC / attention loss (train.py --ctc-weight w) -> (L, CE, CTC), L = (1 - w) CE + w CTC.
+    CE is the label-smoothed loss of the attention decoder (calculate_loss); CTC is asr_ctc_fwd's loss (mean over utterances of
+    nll / target length) on the encoder CTC head's logits: blank = PAD, targets = the collated raw label ids `tgt` (no SOS / EOS)
+    with their true lengths, and the input length of an utterance is its TRUE number of encoder frames, model.ctc_frame_lengths --
+    not the pre-CNN length the encoder masks with.  An utterance with more labels than frames makes CTC, and so L, infinite (the
+    trainer skips such a batch)."""
+    ce, _ = calculate_metrics(pred, gold, smoothing=smoothing, loss_type="ce", sync=False)
+    frames = torch.tensor(model.ctc_frame_lengths(src_lengths, ctc_logits.shape[1]), dtype=torch.int32)
+    ctc = F_.CTCFn.apply(ctc_logits, tgt, frames, tgt_lengths, constant.PAD_TOKEN)
+    return (1.0 - ctc_weight) * ce + ctc_weight * ctc, ce, ctc

@@ -241,6 +241,21 @@ int asr_ctc_bwd(const float* logits, int64_t ld, const int64_t* targets, const i
                 const int32_t* target_lengths, int B, int T, int V, int Lmax, int blank, const float* workspace,
                 const float* grad_out, float* dlogits, int64_t ldo, asr_stream_t stream);
 
+/* ---- CTC prefix scorer for joint CTC / attention beam search (csrc/ctc_prefix.hip has the recursion; blank = `blank`).
+ * asr_ctc_prefix_init: logits (B,T,ld) fp32 = the encoder's CTC logits, frames (B) int32 = true frames T_b per utterance, row_utt (R)
+ *   int32 = utterance of every hypothesis row.  Writes lse (B*T) scratch, lp (B,T,V) = log-softmax, and state (R,T,2) fp32 = the
+ *   (r_n, r_b) pair per frame of the EMPTY prefix (frames >= T_b: -inf).
+ * asr_ctc_prefix_step: for every row r and candidate cand[r,k] (int64, the idx output of asr_logsoftmax_topk; K <= 16, else
+ *   ASR_EUNSUPPORTED) psi[r,k] = log p(prefix(r) . cand as a prefix) and new_state (R,K,T,2), from state (R,T,2), last (R) int64 = the
+ *   row's last label and first (R) int32 != 0 where the row's prefix is empty.  cand == eos: psi = log p(prefix(r) as the whole
+ *   sequence); blank, sos or an id outside [0,V): -inf; those leave an all -inf state.  Frames >= T_b of `state` are never read and
+ *   of `new_state` never written.  Survivors are gathered from new_state viewed as (R*K,T,2) by the caller, on the device.          */
+int asr_ctc_prefix_init(const float* logits, int64_t ld, const int32_t* frames, const int32_t* row_utt, int B, int T, int V, int R,
+                        int blank, float* lse, float* lp, float* state, asr_stream_t stream);
+int asr_ctc_prefix_step(const float* lp, const int32_t* frames, const float* state, const int32_t* row_utt, const int64_t* last,
+                        const int32_t* first, const int64_t* cand, int B, int T, int V, int R, int K, int blank, int sos, int eos,
+                        float* psi, float* new_state, asr_stream_t stream);
+
 /* ---- incremental (KV-cached) decoding with the position on the device: one captured hipGraph serves all 300 steps of
  * the reference's greedy loop (models/asr/transformer.py:316-394).  state[0] = position t of the token being fed.
  * asr_decode_prepare(advance=0): pe_cur[0..D) = pe[t], key_len[0..B) = t+1;  (advance=1): state[0] = t+1.
