@@ -12,6 +12,7 @@ Sub-layer -> reference code
   EmbCNNFn   models/asr/transformer.py:33-40, :70-76
   CEFn       utils/metrics.py:102-132
 """
+import collections
 import os
 import weakref
 
@@ -20,21 +21,6 @@ from torch.autograd import Function
 
 from . import ops
 from . import params as P
-
-
-def _wgrad_bias(dy2d, x2d, wparam, bparam):
-    """dW (N,K) += dy^T x and db (N) += column sums of dy, both accumulated in place into the fp32 gradient buffers.
-    Fast path: transpose-free TN kernel (natural layouts, bias gradient fused).  Fallback (rows not a multiple of the
-    kernel's stage, odd strides): explicit zero padded transposes + the NT kernel."""
-    N, K = wparam.shape[0], wparam.numel() // wparam.shape[0]
-    g = P.grad_of(wparam).view(N, K)
-    gb = P.grad_of(bparam) if bparam is not None else None
-    if ops.gemm_tn_supported(dy2d, x2d):
-        ops.gemm_tn(dy2d, x2d, g, colsum_acc=gb, N=N, K=K)
-        return
-    dy_t = ops.transpose_padded(dy2d[:, :N], gb)
-    x_t = ops.transpose_padded(x2d[:, :K])
-    ops.gemm_nt(dy_t, x_t, out=g, accumulate=True, splits=0)      # 0 = let the library choose split-K
 
 
 def _as_compute(dy2d):
@@ -65,41 +51,68 @@ def _linear_fwd(x2d, wparam, bparam, relu=False, out_dtype=None):
     return ops.gemm_nt(xp, W, bias=bparam.data if bparam is not None else None, relu=relu, out_dtype=out_dtype)
 
 
-def _dgrad(dy2d, wparam, dx_out=None, accumulate=False, relu_mask=None):
-    """dx (M,K) (+)= dy (M,N[p]) @ W (N,K).  Natural-layout weight + transposing LDS reads when the shape allows, else the
-    NT kernel on the padded W^T shadow."""
-    W = P.linear_weight(wparam)
-    if W.shape[1] == wparam.numel() // wparam.shape[0] and ops.gemm_nn_supported(dy2d, W):
-        return ops.gemm_nn(dy2d, W, out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
-    _, Wt = P.linear_shadow(wparam)
-    return ops.gemm_nt(_pad_cols(dy2d), Wt, out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
+# A linear layer as its backward sees it.  W: the weight in the compute dtype and natural (N,K) layout, or None where the NN kernels
+# cannot read it (the per-weight shadow is column padded when K is not a whole number of 16-byte chunks; nobody asked for dX);
+# wt(): W^T for the NT fallback; dw (N,K) / db (N) or None: the fp32 gradient buffers the launches accumulate into.
+_Lin = collections.namedtuple("_Lin", "W wt dw db N K")
+
+
+def _plain_lin(wparam, bparam, need_dx=True):
+    N, K = wparam.shape[0], wparam.numel() // wparam.shape[0]
+    W = P.linear_weight(wparam) if need_dx else None
+    return _Lin(W if W is not None and W.shape[1] == K else None, lambda: P.linear_shadow(wparam)[1],
+                P.grad_of(wparam).view(N, K), P.grad_of(bparam) if bparam is not None else None, N, K)
+
+
+def _wgrad_bias(lin, dy2d, x2d):
+    """dW (N,K) += dy^T x and db (N) += column sums of dy, both accumulated in place into the fp32 gradient buffers.
+    Fast path: transpose-free TN kernel (natural layouts, bias gradient fused).  Fallback (rows not a multiple of the
+    kernel's stage, odd strides): explicit zero padded transposes + the NT kernel."""
+    if ops.gemm_tn_supported(dy2d, x2d):
+        ops.gemm_tn(dy2d, x2d, lin.dw, colsum_acc=lin.db, N=lin.N, K=lin.K)
+        return
+    dy_t = ops.transpose_padded(dy2d[:, :lin.N], lin.db)
+    x_t = ops.transpose_padded(x2d[:, :lin.K])
+    ops.gemm_nt(dy_t, x_t, out=lin.dw, accumulate=True, splits=0)      # 0 = let the library choose split-K
+
+
+def _lin_bwd(lin, dy2d, x2d, dx_out=None, accumulate=False, need_dx=True, relu_mask=None, dgrad_now=None):
+    """THE linear backward: dy2d (M,N[p]) and x2d (M,K) in the compute dtype.  Accumulates dW / db, returns dx (M,K) (+)= dy W or None.
+    Four rungs, the first that applies: (1) data gradient now, weight gradient queued for the grouped launch; (2) dX and dW
+    workgroups in ONE launch; (3) dW / db on the second stream next to dX on this one; the transposing fallbacks inside (3).
+    dgrad_now(W), when given, is tried in place of rung 1's data-gradient launch and its result returned for dx (None from it:
+    the plain launch runs, the walk goes on from there)."""
+    W = lin.W
+    defer = ops.defer_wgrad_now(dy2d.dtype) and ops.gemm_tn_supported(dy2d, x2d) and x2d.dtype == dy2d.dtype
+    nn_ok = need_dx and W is not None and ops.gemm_nn_supported(dy2d, W)
+    if defer and (nn_ok or not need_dx):
+        # data gradient now (it is what the rest of backward waits for), weight gradient with the other layers' at the end
+        dx = None
+        if need_dx:
+            dx = dgrad_now(W) if dgrad_now is not None else None
+            if dx is None:
+                dx = ops.gemm_nn(dy2d, W, out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
+        ops.queue_wgrad(dy2d, x2d, lin.dw, lin.db, lin.N, lin.K)
+        return dx
+    if not need_dx:
+        _wgrad_bias(lin, dy2d, x2d)
+        return None
+    if W is not None and ops.gemm_nn_tn_supported(dy2d, W, x2d):      # graph capture, bf16: dX and dW workgroups in ONE launch
+        return ops.gemm_nn_tn(dy2d, W, x2d, lin.dw, lin.db, out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
+    f = ops.fork()
+    with f:                                   # dW / db on the second stream, next to dX on this one
+        _wgrad_bias(lin, dy2d, x2d)
+    if nn_ok:                                 # natural-layout weight + transposing LDS reads when the shape allows, else the NT kernel on W^T
+        dx = ops.gemm_nn(dy2d, W, out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
+    else:
+        dx = ops.gemm_nt(_pad_cols(dy2d), lin.wt(), out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
+    f.join()
+    return dx
 
 
 def _linear_bwd(dy2d, x2d, wparam, bparam, dx_out=None, accumulate=False, need_dx=True, relu_mask=None):
-    """dy2d (M,N[p]) and x2d (M,K) in the compute dtype.  Accumulates dW / db, returns dx = dy W (M,K) or None."""
-    N, K = wparam.shape[0], wparam.numel() // wparam.shape[0]
-    defer = ops.defer_wgrad_now(dy2d.dtype) and ops.gemm_tn_supported(dy2d, x2d) and x2d.dtype == dy2d.dtype
-    if not need_dx:
-        if defer:
-            ops.queue_wgrad(dy2d, x2d, P.grad_of(wparam).view(N, K), P.grad_of(bparam) if bparam is not None else None, N, K)
-        else:
-            _wgrad_bias(dy2d, x2d, wparam, bparam)
-        return None
-    W = P.linear_weight(wparam)
-    if defer and W.shape[1] == K and ops.gemm_nn_supported(dy2d, W):
-        # data gradient now (it is what the rest of backward waits for), weight gradient with the other layers' at the end
-        dx = ops.gemm_nn(dy2d, W, out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
-        ops.queue_wgrad(dy2d, x2d, P.grad_of(wparam).view(N, K), P.grad_of(bparam) if bparam is not None else None, N, K)
-        return dx
-    if W.shape[1] == K and ops.gemm_nn_tn_supported(dy2d, W, x2d):      # graph capture, bf16: dX and dW workgroups in ONE launch
-        return ops.gemm_nn_tn(dy2d, W, x2d, P.grad_of(wparam).view(N, K), P.grad_of(bparam) if bparam is not None else None,
-                              out=dx_out, accumulate=accumulate, relu_mask=relu_mask)
-    f = ops.fork()
-    with f:                                   # dW / db on the second stream, next to dX on this one
-        _wgrad_bias(dy2d, x2d, wparam, bparam)
-    dx = _dgrad(dy2d, wparam, dx_out, accumulate, relu_mask)
-    f.join()
-    return dx
+    """_lin_bwd of a plain layer: the weight's shadows and gradient buffers come from params."""
+    return _lin_bwd(_plain_lin(wparam, bparam, need_dx), dy2d, x2d, dx_out, accumulate, need_dx, relu_mask)
 
 
 # The output projection's data gradient IS the attention backward's dO: its epilogue also writes delta = rowsum(dO * O) per head
@@ -109,15 +122,10 @@ def _linear_bwd(dy2d, x2d, wparam, bparam, dx_out=None, accumulate=False, need_d
 
 def _out_proj_bwd(dy2d, o2d, o32, wparam, bparam, Tq, dk):
     """(dO, delta or None) for MHAFn.backward: _linear_bwd of the output projection, with delta from the same launch where possible."""
-    N, K = wparam.shape[0], wparam.numel() // wparam.shape[0]
-    if (dk == 64 and ops.defer_wgrad_now(dy2d.dtype) and ops.gemm_tn_supported(dy2d, o2d) and o2d.dtype == dy2d.dtype):
-        W = P.linear_weight(wparam)
-        if W.shape[1] == K and ops.gemm_nn_supported(dy2d, W):
-            got = ops.gemm_nn_rowdot(dy2d, W, o2d, o32.view(-1, K) if o32 is not None else None, Tq)
-            if got is not None:
-                ops.queue_wgrad(dy2d, o2d, P.grad_of(wparam).view(N, K), P.grad_of(bparam) if bparam is not None else None, N, K)
-                return got[0], got[1].view(-1, K // 64, Tq)
-    return _linear_bwd(dy2d, o2d, wparam, bparam), None
+    lin = _plain_lin(wparam, bparam)
+    o32 = o32.view(-1, lin.K) if o32 is not None else None
+    got = _lin_bwd(lin, dy2d, o2d, dgrad_now=(lambda W: ops.gemm_nn_rowdot(dy2d, W, o2d, o32, Tq)) if dk == 64 else None)
+    return (got[0], got[1].view(-1, lin.K // 64, Tq)) if isinstance(got, tuple) else (got, None)
 
 
 class _Fused:
@@ -147,49 +155,39 @@ class _Fused:
         return ops.gemm_nt(x2d, self.W, bias=self.b_master)
 
     def bwd(self, dy2d, x2d, dx_out=None, accumulate=False, need_dx=True):
-        g = self.w_grad.view(self.N, self.K)
-        if (ops.defer_wgrad_now(dy2d.dtype) and ops.gemm_tn_supported(dy2d, x2d) and x2d.dtype == dy2d.dtype and
-                (not need_dx or ops.gemm_nn_supported(dy2d, self.W))):
-            dx = ops.gemm_nn(dy2d, self.W, out=dx_out, accumulate=accumulate) if need_dx else None
-            ops.queue_wgrad(dy2d, x2d, g, self.b_grad, self.N, self.K)
-            return dx
-        if need_dx and ops.gemm_nn_tn_supported(dy2d, self.W, x2d):
-            return ops.gemm_nn_tn(dy2d, self.W, x2d, g, self.b_grad, out=dx_out, accumulate=accumulate)
-        f = ops.fork() if need_dx else None
-        if f is not None:
-            f.__enter__()
-        try:
-            if ops.gemm_tn_supported(dy2d, x2d):
-                ops.gemm_tn(dy2d, x2d, g, colsum_acc=self.b_grad, N=self.N, K=self.K)
-            else:
-                ops.gemm_nt(ops.transpose_padded(dy2d, self.b_grad), ops.transpose_padded(x2d), out=g, accumulate=True, splits=0)
-        finally:
-            if f is not None:
-                f.__exit__(None, None, None)
-        if not need_dx:
-            return None
-        if ops.gemm_nn_supported(dy2d, self.W):
-            dx = ops.gemm_nn(dy2d, self.W, out=dx_out, accumulate=accumulate)
-        else:
-            wt = ops.transpose_padded(self.W)
-            dx = ops.gemm_nt(_pad_cols(dy2d), wt, out=dx_out, accumulate=accumulate)
-        f.join()
-        return dx
+        lin = _Lin(self.W, lambda: ops.transpose_padded(self.W), self.w_grad.view(self.N, self.K), self.b_grad, self.N, self.K)
+        return _lin_bwd(lin, dy2d, x2d, dx_out, accumulate, need_dx)
 
 
 # ================================================================================================ plain linear
-_logit_handover = [None]              # (weakref to the latest fp32 logits, their data_ptr, numel, the producing LinearFn's box)
+class _Handover:
+    """One slot through which a producer's forward leaves a box for the consumer of its output: (weakref to the output, the
+    data_ptr and numel of its storage, the box).  The claim is made at FORWARD time and empties the slot: the association is by a
+    live weak reference to the producer's output tensor (while it is alive its memory cannot have been recycled) plus address and
+    size, never by an address alone, and it cannot outlive the forward that made it.  (slot[0] reads the slot.)"""
+
+    def __init__(self):
+        self.slot = None
+
+    def __getitem__(self, i):
+        return (self.slot,)[i]
+
+    def leave(self, out, storage, box):
+        self.slot = (weakref.ref(out), storage.data_ptr(), storage.numel(), box)
+
+    def clear(self):
+        self.slot = None
+
+    def claim(self, tensor):
+        """The box left by the forward that produced `tensor` (or a view of all of it), or None."""
+        slot, self.slot = self.slot, None
+        if slot is None or slot[0]() is None:
+            return None
+        return slot[3] if (slot[1] == tensor.data_ptr() and slot[2] == tensor.numel()) else None
+
+
+_logit_handover = _Handover()         # LinearFn (the latest fp32 logits) -> CEFn.forward
 _logit_handover_on = os.environ.get("ASR_LOGIT_HANDOVER", "1") != "0"
-
-
-def _claim_logit_handover(logits):
-    """CEFn.forward: the box of the LinearFn that produced `logits` (a view of them), or None.  The claim is made at FORWARD time and
-    empties the slot: the association is by a live weak reference to the producer's output tensor (while it is alive its memory
-    cannot have been recycled) plus address and size, never by an address alone, and it cannot outlive the forward that made it."""
-    slot, _logit_handover[0] = _logit_handover[0], None
-    if slot is None or slot[0]() is None:
-        return None
-    return slot[3] if (slot[1] == logits.data_ptr() and slot[2] == logits.numel()) else None
 
 
 _grad_mode = [False]      # torch.is_grad_enabled() at the call site of the running LinearFn (inside Function.forward it always reads False)
@@ -218,13 +216,13 @@ class LinearFn(Function):
         ctx.need_dx = x.requires_grad
         ctx.box = None
         out = y.view(*x.shape[:-1], weight.shape[0])
-        _logit_handover[0] = None              # one slot, and only for the forward that has just run (never across a no_grad forward)
+        _logit_handover.clear()                # one slot, and only for the forward that has just run (never across a no_grad forward)
         if out_fp32 and cd == torch.bfloat16 and _logit_handover_on and _grad_mode[0] and any(ctx.needs_input_grad):
             # fp32 logits of a bf16 model (the vocabulary projection): the loss's backward may leave ITS part of the gradient in the
             # compute dtype, zero padded to the data-gradient kernel's stage, in this box instead of an fp32 tensor that would be cast
             # and padded here (CEFn claims the box in its forward)
             ctx.box = {}
-            _logit_handover[0] = (weakref.ref(out), y.data_ptr(), y.numel(), ctx.box)
+            _logit_handover.leave(out, y, ctx.box)
         return out
 
     @staticmethod
@@ -492,18 +490,11 @@ class FFNFn(Function):
 # Hand-over between the conv front end and the encoder input projection (round 6).  The second max-pool's backward used to be a launch of
 # its own between the projection's data gradient and conv.7's backward (asr_maxpool_bwd_code: 58 us, 65 MB written by the GEMM, read
 # back with 33 MB of selection bytes, 262 MB written).  When VGGFn.forward produced its selection bytes channel last it leaves a slot
-# here; EncInFn.forward claims it if the features it is given ARE that output (live weak reference + address + size, never an address
-# alone; the claim empties the slot), and then its backward runs asr_gemm_nn_poolbwd -- the pooling backward in the data-gradient GEMM's
-# epilogue -- and leaves the un-pooled gradient in the box for VGGFn.backward, returning a stride-0 zero as the formal gradient.
-_pool_handover = [None]
+# here; EncInFn.forward claims it if the features it is given ARE that output (_Handover), and then its backward runs
+# asr_gemm_nn_poolbwd -- the pooling backward in the data-gradient GEMM's epilogue -- and leaves the un-pooled gradient in the box for
+# VGGFn.backward, returning a stride-0 zero as the formal gradient.
+_pool_handover = _Handover()          # VGGFn (the pooled features) -> EncInFn.forward
 _pool_handover_on = os.environ.get("ASR_POOL_HANDOVER", "1") != "0"
-
-
-def _claim_pool_handover(x):
-    slot, _pool_handover[0] = _pool_handover[0], None
-    if slot is None or slot[0]() is None:
-        return None
-    return slot[3] if (slot[1] == x.data_ptr() and slot[2] == x.numel()) else None
 
 
 class EncInFn(Function):
@@ -522,7 +513,7 @@ class EncInFn(Function):
         ctx.shape = (B, T, Din)
         ctx.need_dx = x.requires_grad
         ctx.in_dtype = x.dtype
-        ctx.pool_box = _claim_pool_handover(x) if (x.requires_grad and x.dtype == cd and x.is_contiguous()) else None
+        ctx.pool_box = _pool_handover.claim(x) if (x.requires_grad and x.dtype == cd and x.is_contiguous()) else None
         if ctx.pool_box is not None:
             ctx.pool_box["claimed"] = True
         return out.view(B, T, -1)
@@ -642,7 +633,9 @@ class VGGFn(Function):
         ctx.t = (src, y1, None if c1 is not None else y2, p1, y3, None if c4 is not None else y4, c1, c4, y4_shape, m3)
         ctx.params = (w0, b0, w2, b2, w5, b5, w7, b7)
         ctx.pool_box = box
-        _pool_handover[0] = (weakref.ref(out), out.data_ptr(), out.numel(), box) if box is not None else None
+        _pool_handover.clear()
+        if box is not None:
+            _pool_handover.leave(out, out, box)
         return out
 
     @staticmethod
@@ -1003,7 +996,7 @@ class CEFn(Function):
             count = global_count if global_count is not None else sums[1:2]
         ctx.t = (logits, g, lse, count)
         ctx.smoothing, ctx.pad_id, ctx.shape = smoothing, pad_id, pred.shape
-        ctx.handover = _claim_logit_handover(logits) if ctx.needs_input_grad[0] else None
+        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
         ctx.mark_non_differentiable(sums, am)
         return loss, sums, am
 

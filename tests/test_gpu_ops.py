@@ -413,6 +413,106 @@ def test_gemm_nn_partial_reduction_stage(ops, dtype, shape):
         close("nn_tn db partial tile", db, db0 + dy[:, :N].sum(0), torch.float32, scale=8)
 
 
+# what each rung of the linear backward launches, and how a test may select it: a predicate patched to False moves down the ladder,
+# defer_wgrad_now / deferral_ok patched to True stand for "inside a backward pass / a capture"; no layout predicate is ever forced to True
+LINEAR_RUNGS = {
+    "queued": (dict(defer_wgrad_now=True), ["asr_gemm_nn", "asr_gemm_tn_grouped"]),
+    "one_launch": (dict(defer_wgrad_now=False, deferral_ok=True), ["asr_gemm_nn_tn", "asr_tn_reduce_multi"]),
+    "pair": ({}, ["asr_gemm_tn", "asr_gemm_nn"]),
+    "transposed_wgrad": (dict(gemm_tn_supported=False), ["asr_transpose", "asr_transpose", "asr_gemm_nt", "asr_gemm_nn"]),
+    "nt_dgrad": ({}, ["asr_gemm_tn", "asr_gemm_nt"]),
+    "queued_no_dx": (dict(defer_wgrad_now=True), ["asr_gemm_tn_grouped"]),
+    "no_dx": ({}, ["asr_gemm_tn"]),
+}
+
+
+@pytest.mark.parametrize("form", ["plain", "fused"])
+def test_linear_backward_every_rung_gives_the_same_gradients(ops, monkeypatch, form):
+    """asr_hip/functions.py _linear_bwd / _Fused.bwd: whichever rung the ladder takes -- data gradient now + queued weight gradient,
+    the one-launch dX + dW, the pair, the transposing fallbacks, need_dx=False -- one layer gets the same dX, dW and db (reference:
+    autograd of nn.Linear, models/common_layers.py:136-142,181-187): the float64 products of the bf16-rounded operands, within the
+    bf16 GEMM tolerances of the kernel tests above.  M = 96 is not a multiple of the 64-row stage; N = 72 needs the zero columns of
+    _as_compute (plain form; the NT fallback is reached as the model reaches it, by a dy without room for them); fused: two adjacent
+    64 x 64 weights.  Each rung once storing dX (plain: under a ReLU mask) and once accumulating into dx_out."""
+    from asr_hip import functions as Fn
+    from asr_hip import lib as L
+    from asr_hip import params as P
+    bf = torch.bfloat16
+    D = dev()
+    M, K = 96, 64
+    N = 72 if form == "plain" else 128
+    g = torch.Generator().manual_seed(96 + N)
+    dy, x = q(torch.randn(M, N, generator=g), bf), q(torch.randn(M, K, generator=g), bf)
+    w = q(torch.randn(N, K, generator=g) / math.sqrt(N), bf)
+    base, mask = q(torch.randn(M, K, generator=g), bf), q(torch.randn(M, K, generator=g), bf)
+    dw0, db0 = torch.randn(N, K, generator=g), torch.randn(N, generator=g)
+    ref_dx = dy.double() @ w.double()
+    ref_dw, ref_db = dw0.double() + dy.double().t() @ x.double(), db0.double() + dy.double().sum(0)
+    seen = []
+
+    def spy(fn):
+        def f(name, *args):
+            seen.append(name)
+            return fn(name, *args)
+        return f
+
+    prev = ops.compute_dtype()
+    ops.set_compute_dtype(bf)
+    try:
+        xd = x.to(D, bf)
+        if form == "plain":
+            wp, bp = torch.nn.Parameter(w.to(D)), torch.nn.Parameter(torch.zeros(N, device=D))
+            wp.grad, bp.grad = torch.empty(N, K, device=D), torch.empty(N, device=D)
+            dw, db = wp.grad, bp.grad
+            P.linear_shadow(wp)                                               # the shadows' cast is the forward's launch, not the ladder's
+            dy_pad = Fn._as_compute(dy.to(D))
+            assert dy_pad.shape == (M, 128) and not ops.gemm_nn_supported(dy.to(D, bf), P.linear_weight(wp))
+
+            def bwd(rung, **kw):
+                return Fn._linear_bwd(dy.to(D, bf) if rung == "nt_dgrad" else dy_pad, xd, wp, bp, **kw)
+        else:
+            ws = [torch.nn.Parameter(w[:64].to(D)), torch.nn.Parameter(w[64:].to(D))]
+            bs = [torch.nn.Parameter(torch.zeros(64, device=D)) for _ in range(2)]
+            flat = P.FlatParams(ws + bs)
+            fused = Fn._Fused(ws, bs)
+            assert fused.ok and (fused.N, fused.K) == (N, K)
+            dw, db = fused.w_grad.view(N, K), fused.b_grad
+            dyd = dy.to(D, bf)
+
+            def bwd(rung, **kw):
+                kw.pop("relu_mask", None)                                     # the fused form takes none
+                return fused.bwd(dyd, xd, **kw)
+        monkeypatch.setattr(L, "call", spy(L.call))
+        monkeypatch.setattr(L, "call_or_none", spy(L.call_or_none))
+        for rung, (patches, launches) in LINEAR_RUNGS.items():
+            need_dx = not rung.endswith("no_dx")
+            if form == "fused" and rung == "nt_dgrad":
+                patches, launches = dict(gemm_nn_supported=False), ["asr_gemm_tn", "asr_transpose", "asr_gemm_nt"]
+            for variant in (("store", "accumulate") if need_dx else ("store",)):
+                dw.copy_(dw0.to(D)), db.copy_(db0.to(D))
+                out = base.to(D, bf) if variant == "accumulate" else None
+                masked = form == "plain" and variant == "store"
+                del seen[:]
+                with monkeypatch.context() as mp:
+                    for name, val in patches.items():
+                        mp.setattr(ops, name, lambda *a, _v=val, **k: _v)
+                    dx = bwd(rung, need_dx=need_dx, dx_out=out, accumulate=out is not None, relu_mask=mask.to(D, bf) if masked else None)
+                ops.join_deferred()
+                what = "%s %s %s" % (form, rung, variant)
+                assert seen == launches, what
+                if need_dx:
+                    want = ref_dx * (mask > 0) if masked else ref_dx + base.double() if out is not None else ref_dx
+                    assert out is None or dx is out, what
+                    close(what + " dX", dx, want, bf)
+                else:
+                    assert dx is None, what
+                close(what + " dW", dw, ref_dw, bf, scale=0.2)
+                close(what + " db", db, ref_db, torch.float32, scale=8)
+    finally:
+        ops.reset_pending()
+        ops.set_compute_dtype(prev)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_transpose_cast_colsum(ops, dtype):
     g = torch.Generator().manual_seed(3)
