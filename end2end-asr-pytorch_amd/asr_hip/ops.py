@@ -653,6 +653,28 @@ def ctc_bwd(logits, targets, input_lengths, target_lengths, ws, grad_out, blank=
     return dl
 
 
+def ctc_align(logits, targets, input_lengths, target_lengths, blank=0):
+    """Forced alignment (csrc/ctc_align.hip): logits (B,T,V) fp32 (rows contiguous, any row stride), targets (B,Lmax) int64, lengths (B)
+    int32 on the device -> dict(path (B,T) int32, start / end (B,Lmax) int32, lab_score (B,Lmax) fp32, score (B) fp32) on the device;
+    -1 / 0 / -inf for an utterance without a feasible alignment."""
+    B, T, V = logits.shape
+    Lmax = targets.shape[1]
+    assert logits.dtype == torch.float32 and logits.stride(2) == 1 and logits.stride(0) == T * logits.stride(1) and T >= 1
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape[0] == B and Lmax >= 1
+    assert input_lengths.dtype == torch.int32 and target_lengths.dtype == torch.int32
+    assert input_lengths.numel() == B and target_lengths.numel() == B and input_lengths.is_contiguous() and target_lengths.is_contiguous()
+    dev = logits.device
+    n = L.load().asr_ctc_align_workspace(B, T, Lmax)
+    ws = torch.empty(n, device=dev, dtype=torch.float32)
+    out = dict(path=torch.empty((B, T), device=dev, dtype=torch.int32), start=torch.empty((B, Lmax), device=dev, dtype=torch.int32),
+               end=torch.empty((B, Lmax), device=dev, dtype=torch.int32), lab_score=torch.empty((B, Lmax), device=dev, dtype=torch.float32),
+               score=torch.empty(B, device=dev, dtype=torch.float32))
+    L.call("asr_ctc_align", L.ptr(logits), logits.stride(1), L.ptr(targets), L.ptr(input_lengths), L.ptr(target_lengths), B, T, V, Lmax,
+           int(blank), L.ptr(ws), n, L.ptr(out["path"]), L.ptr(out["start"]), L.ptr(out["end"]), L.ptr(out["lab_score"]),
+           L.ptr(out["score"]), L.stream())
+    return out
+
+
 def ctc_prefix_init(logits, frames, row_utt, blank=0):
     """logits (B,T,V) fp32 (rows contiguous, any row stride), frames (B) int32, row_utt (R) int32 on the device ->
     (lp (B,T,V) log-softmax, state (R,T,2) of the empty prefix): csrc/ctc_prefix.hip."""

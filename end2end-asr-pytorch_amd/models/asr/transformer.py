@@ -30,6 +30,18 @@ def frames_after_cnn(T, feat):
     return int(T)
 
 
+def encoder_frame_span(j, feat):
+    """The input-frame interval [a, b) encoder frame j stands for (CTC alignment timestamps; seconds = frames * --window-stride).
+    vgg_cnn: the 4 frames under its two 2x2 pools; emb_cnn: the stride-2 cell at the centre of its receptive field [2j - 10, 2j + 20];
+    no front end: the frame itself.  The caller clamps b to the utterance's true input length."""
+    j = int(j)
+    if feat == "vgg_cnn":
+        return 4 * j, 4 * j + 4
+    if feat == "emb_cnn":
+        return 2 * j + 4, 2 * j + 6
+    return j, j + 1
+
+
 def ctc_collapse(ids, length=None, blank=constant.PAD_TOKEN):
     """Best-path CTC decoding of one utterance's frame-wise argmax ids: the first `length` frames, repeats merged, blanks dropped."""
     out, prev = [], None
@@ -37,6 +49,15 @@ def ctc_collapse(ids, length=None, blank=constant.PAD_TOKEN):
         if x != prev and x != blank:
             out.append(int(x))
         prev = x
+    return out
+
+
+def hypothesis_labels(ids):
+    """The label ids of a decoded hypothesis as a CTC target: SOS and EOS dropped, PAD dropped from the end.  A PAD (= the CTC blank)
+    left inside has no alignment, and the aligner reports it so."""
+    out = [int(x) for x in ids if int(x) not in (constant.SOS_TOKEN, constant.EOS_TOKEN)]
+    while out and out[-1] == constant.PAD_TOKEN:
+        out.pop()
     return out
 
 
@@ -104,13 +125,52 @@ class Transformer(nn.Module):
         return F_.linear(enc_out, self.ctc_linear.weight, self.ctc_linear.bias, True, True)
 
     @torch.no_grad()
-    def ctc_greedy(self, enc_out, lengths):
+    def ctc_greedy(self, enc_out, lengths, return_ids=False):
         """Best-path decoding from the CTC head alone: frame-wise argmax, repeats merged and blanks dropped inside each utterance's
-        true frames (`lengths`, encoder frames) -> strings.  The cheap way to see whether the head has learnt anything."""
+        true frames (`lengths`, encoder frames) -> strings (return_ids: (strings, label ids)).  The cheap way to see whether the head
+        has learnt anything."""
         logits = self.ctc_logits(enc_out)
         B, T, V = logits.shape
         ids = ops.argmax_rows(logits.reshape(B * T, V)).view(B, T).cpu().tolist()
-        return ["".join(self.id2label[x] for x in ctc_collapse(row, n)) for row, n in zip(ids, lengths)]
+        hyp_ids = [ctc_collapse(row, n) for row, n in zip(ids, lengths)]
+        strs = ["".join(self.id2label[x] for x in row) for row in hyp_ids]
+        return (strs, hyp_ids) if return_ids else strs
+
+    @torch.no_grad()
+    def ctc_align(self, enc_out, lengths, targets, target_lengths=None):
+        """Forced alignment of label ids against the CTC head (csrc/ctc_align.hip).  lengths: true encoder frames
+        per utterance (ctc_frame_lengths); targets: (B,L) int64 with target_lengths, or a list of id lists.  One device-to-host copy.
+        -> per utterance {"score": log-probability of the best path (-inf: no feasible alignment), "frames": T_b, "path": lattice state
+        per frame, "labels": [{"id", "label", "start_frame", "end_frame" (one past the last), "logp"}]} in encoder frames."""
+        logits = self.ctc_logits(enc_out)
+        B, T, V = logits.shape
+        dev = logits.device
+        if not torch.is_tensor(targets):
+            rows = [[int(x) for x in r] for r in targets]
+            target_lengths = [len(r) for r in rows]
+            tg = torch.zeros((B, max([1] + target_lengths)), dtype=torch.int64)
+            for b, r in enumerate(rows):
+                tg[b, :len(r)] = torch.tensor(r, dtype=torch.int64)
+            targets = tg
+        if targets.shape[1] == 0:
+            targets = torch.zeros((B, 1), dtype=torch.int64)
+        targets = targets.to(dev).contiguous()
+        out = ops.ctc_align(logits, targets, _lengths_to_device(lengths, dev), _lengths_to_device(target_lengths, dev),
+                            constant.PAD_TOKEN)
+        Lmax = targets.shape[1]
+        flat = torch.cat([out["path"].reshape(-1), out["start"].reshape(-1), out["end"].reshape(-1),
+                          out["lab_score"].view(torch.int32).reshape(-1), out["score"].view(torch.int32),
+                          targets.to(torch.int32).reshape(-1)]).cpu()
+        path, start, end, lab, score, tg = torch.split(flat, [B * T, B * Lmax, B * Lmax, B * Lmax, B, B * Lmax])
+        path, start, end = path.view(B, T).tolist(), start.view(B, Lmax).tolist(), end.view(B, Lmax).tolist()
+        lab, score, tg = lab.view(torch.float32).view(B, Lmax).tolist(), score.view(torch.float32).tolist(), tg.view(B, Lmax).tolist()
+        result = []
+        for b in range(B):
+            n = max(0, min(T, int(lengths[b])))
+            labels = [{"id": tg[b][l], "label": self.id2label[tg[b][l]], "start_frame": start[b][l], "end_frame": end[b][l],
+                       "logp": lab[b][l]} for l in range(Lmax) if start[b][l] >= 0]
+            result.append({"score": score[b], "frames": n, "path": path[b][:n] if score[b] > -math.inf else [], "labels": labels})
+        return result
 
     def forward(self, padded_input, input_lengths, padded_target, verbose=False, return_ctc=False):
         """-> (pred (B,Td,V) fp32, gold (B,Td), hyp_seq (B,Td), gold_seq)   (reference: transformer.py:59-85); with return_ctc also
@@ -126,37 +186,54 @@ class Transformer(nn.Module):
 
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
-                 ctc_candidates=0, ctc_greedy=False):
+                 ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
-        ctc_greedy: best-path decoding from the head alone."""
+        ctc_greedy: best-path decoding from the head alone.  align_source "gold" / "hyp": a fourth value, the forced alignment
+        (ctc_align) of padded_target with target_lengths, or of the label ids the decoder produced (SOS and EOS dropped; never a
+        re-tokenised string)."""
         if ctc_weight > 0 and not beam_search:
             raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % ctc_weight)
+        if align_source not in (None, "gold", "hyp"):
+            raise ValueError("align_source must be 'gold' or 'hyp', got %r" % (align_source,))
+        if align_source is not None and not hasattr(self, "ctc_linear"):
+            self.ctc_logits(None)                      # the "no encoder CTC head" ValueError, before any device work
+        if align_source == "gold" and target_lengths is None:
+            raise ValueError("align_source='gold' needs target_lengths (the true lengths of padded_target)")
         feats = self._features(padded_input)
         enc_out, _ = self.encoder(feats, input_lengths)
         _, gold, *_ = self.decoder(padded_target, enc_out, input_lengths)
         gold_cpu = gold.cpu().tolist()
         strs_gold = ["".join(self.id2label[int(x)] for x in row) for row in gold_cpu]
-        if ctc_weight > 0 or ctc_greedy:
+        if ctc_weight > 0 or ctc_greedy or align_source is not None:
             if ctc_lengths is None:
                 ctc_lengths = self.ctc_frame_lengths(input_lengths, enc_out.shape[1])
-            if ctc_logits is None and not ctc_greedy:
+            if ctc_logits is None and ctc_weight > 0 and not ctc_greedy:
                 with torch.no_grad():
                     ctc_logits = self.ctc_logits(enc_out)
         if ctc_greedy:
-            strs_hyps = self.ctc_greedy(enc_out, ctc_lengths)
+            strs_hyps, hyp_ids = self.ctc_greedy(enc_out, ctc_lengths, return_ids=True)
         elif beam_search:
-            _, strs_hyps = self.decoder.beam_search(enc_out, beam_width=beam_width, nbest=1, lm=lm, lm_rescoring=lm_rescoring,
-                                                    lm_weight=lm_weight, c_weight=c_weight, ctc_logits=ctc_logits,
-                                                    ctc_lengths=ctc_lengths, ctc_weight=ctc_weight, ctc_candidates=ctc_candidates)
+            hyp_ids, strs_hyps = self.decoder.beam_search(enc_out, beam_width=beam_width, nbest=1, lm=lm, lm_rescoring=lm_rescoring,
+                                                          lm_weight=lm_weight, c_weight=c_weight, ctc_logits=ctc_logits,
+                                                          ctc_lengths=ctc_lengths, ctc_weight=ctc_weight, ctc_candidates=ctc_candidates)
             if len(strs_hyps) != padded_input.shape[0]:
-                strs_hyps = self.decoder.greedy_search(enc_out)
+                strs_hyps, hyp_ids = self.decoder.greedy_search(enc_out, return_ids=True)
+        elif align_source == "hyp":
+            strs_hyps, hyp_ids = self.decoder.greedy_search(enc_out, return_ids=True)
         else:
             strs_hyps = self.decoder.greedy_search(enc_out)
         if verbose:
             print("GOLD", strs_gold)
             print("HYP", strs_hyps)
-        return _, strs_hyps, strs_gold
+        if align_source is None:
+            return _, strs_hyps, strs_gold
+        if align_source == "gold":
+            alignment = self.ctc_align(enc_out, ctc_lengths, padded_target, target_lengths)
+        else:
+            # (the ids of --ctc-greedy are CTC labels as they stand, feasible by construction; a decoder's carry SOS / EOS)
+            alignment = self.ctc_align(enc_out, ctc_lengths, hyp_ids if ctc_greedy else [hypothesis_labels(row) for row in hyp_ids])
+        return _, strs_hyps, strs_gold, alignment
 
 
 class Encoder(nn.Module):
@@ -314,13 +391,13 @@ class Decoder(nn.Module):
 
     @torch.no_grad()
     def greedy_search(self, encoder_padded_outputs, beam_width=2, lm_rescoring=False, lm=None, lm_weight=0.1, c_weight=1,
-                      use_cache=True):
+                      use_cache=True, return_ids=False):
         """1-best strings of the reference's 300-step greedy loop (transformer.py:316-394).  Needs --tgt-max-len >= 301.
         use_cache=True decodes incrementally with per-layer key/value caches, one captured hipGraph replayed per token
         (asr_hip/decode.py; in bf16 the step is the 30-launch one of csrc/decode.hip when the shapes allow it); "graph" the same
         with the kernel-per-op step; "eager" that step without the graph; False re-runs the full decoder over the prefix at
         every step like the reference -- "graph" / "eager" / False give the same tokens (tests/test_gpu_decode.py), the fused
-        step the same within the bf16 tolerance (tests/test_gpu_decode_fused.py)."""
+        step the same within the bf16 tolerance (tests/test_gpu_decode_fused.py).  return_ids: (strings, the label ids before EOS)."""
         if lm_rescoring:
             raise NotImplementedError("LM rescoring applies to beam search only: it re-ranks the finished beam hypotheses, and greedy "
                                       "decoding keeps one (the reference's greedy LM branch, transformer.py:357-372, cannot run: it "
@@ -344,15 +421,17 @@ class Decoder(nn.Module):
                 steps.append(nxt)
                 ys = torch.cat([ys, nxt.unsqueeze(1)], dim=1)
             toks = torch.stack(steps, dim=1).cpu().tolist()       # one D2H copy instead of per-token .item()
-        sents = []
+        sents, ids = [], []
         for row in toks:
-            st = ''
+            st, kept = '', []
             for t in row:
                 if t == constant.EOS_TOKEN:
                     break
                 st += self.id2label[t]
+                kept.append(t)
             sents.append(st)
-        return sents
+            ids.append(kept)
+        return (sents, ids) if return_ids else sents
 
     @torch.no_grad()
     def beam_search(self, encoder_padded_outputs, beam_width=2, nbest=5, lm_rescoring=False, lm=None, lm_weight=0.1,

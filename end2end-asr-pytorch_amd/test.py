@@ -1,5 +1,6 @@
 """Evaluation entry point -- same command line as the reference (reference: test.py): loads --continue-from, decodes
-every test utterance (greedy, or beam search with --beam-search) and reports CER / WER."""
+every test utterance (greedy, or beam search with --beam-search) and reports CER / WER.  --align-out PATH also writes label and word
+timestamps from the encoder CTC head (forced alignment of the transcript, or of the hypothesis with --align-source hyp)."""
 import torch
 from tqdm import tqdm
 
@@ -13,10 +14,16 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
     model.eval()
     total_word = total_char = total_cer = total_wer = 0
     total_en_cer = total_zh_cer = total_en_char = total_zh_char = 0
+    align_source = getattr(args, "align_source", "gold") if getattr(args, "align_out", None) else None
+    writer = None
+    if align_source is not None:      # --align-out: label and word timestamps from the CTC head, one JSON line per utterance
+        from utils.align import AlignmentWriter, utterance_record
+        check_ctc_decoding(args, model)
+        writer = AlignmentWriter(args.align_out)
     with torch.no_grad():
         pbar = tqdm(iter(test_loader), leave=True, total=len(test_loader))
         for data in pbar:
-            src, tgt, _, src_lengths, _ = data[:5]
+            src, tgt, _, src_lengths, tgt_lengths = data[:5]
             aug = data[5] if len(data) > 5 else None      # noise draws when the checkpoint's run injected noise
             if constant.USE_CUDA:
                 src, tgt = src.cuda(), tgt.cuda()
@@ -27,16 +34,20 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
                                                  noise_dir=noise_dir, features=getattr(args, "features", "spect"),
                                                  num_mel_bins=getattr(args, "num_mel_bins", 80),
                                                  mel_fmin=getattr(args, "mel_fmin", 20.0))
-            _, strs_hyps, strs_gold = model.evaluate(src, src_lengths, tgt, beam_search=args.beam_search,
-                                                     beam_width=args.beam_width, beam_nbest=args.beam_nbest, lm=lm,
-                                                     lm_rescoring=args.lm_rescoring, lm_weight=args.lm_weight,
-                                                     c_weight=args.c_weight, verbose=args.verbose,
-                                                     ctc_weight=getattr(args, "ctc_decode_weight", 0.0),
-                                                     ctc_candidates=getattr(args, "ctc_candidates", 0),
-                                                     ctc_greedy=getattr(args, "ctc_greedy", False))
-            for hyp, gold in zip(strs_hyps, strs_gold):
+            align = {} if writer is None else dict(align_source=align_source, target_lengths=tgt_lengths)
+            _, strs_hyps, strs_gold, *alignment = model.evaluate(src, src_lengths, tgt, beam_search=args.beam_search,
+                                                                 beam_width=args.beam_width, beam_nbest=args.beam_nbest, lm=lm,
+                                                                 lm_rescoring=args.lm_rescoring, lm_weight=args.lm_weight,
+                                                                 c_weight=args.c_weight, verbose=args.verbose,
+                                                                 ctc_weight=getattr(args, "ctc_decode_weight", 0.0),
+                                                                 ctc_candidates=getattr(args, "ctc_candidates", 0),
+                                                                 ctc_greedy=getattr(args, "ctc_greedy", False), **align)
+            for i, (hyp, gold) in enumerate(zip(strs_hyps, strs_gold)):
                 for ch in (constant.EOS_CHAR, constant.SOS_CHAR, constant.PAD_CHAR):
                     hyp, gold = hyp.replace(ch, ""), gold.replace(ch, "")
+                if writer is not None:
+                    writer.write(utterance_record(writer.count, gold if align_source == "gold" else hyp, alignment[0][i],
+                                                  model.feat_extractor, args.window_stride, int(src_lengths[i])))
                 total_wer += calculate_wer(hyp, gold)
                 total_cer += calculate_cer(hyp.strip(), gold.strip())
                 en_cer, zh_cer, n_en, n_zh = calculate_cer_en_zh(hyp, gold)
@@ -46,18 +57,20 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
             pbar.set_description("TEST CER:{:.2f}% WER:{:.2f}% CER_EN:{:.2f}% CER_ZH:{:.2f}%".format(
                 total_cer * 100 / max(1, total_char), total_wer * 100 / max(1, total_word),
                 total_en_cer * 100 / max(1, total_en_char), total_zh_cer * 100 / max(1, total_zh_char)))
+    if writer is not None:
+        writer.close()
     return total_cer / max(1, total_char), total_wer / max(1, total_word)
 
 
 def check_ctc_decoding(args, model):
-    """--ctc-decode-weight / --ctc-greedy need the encoder CTC head of a model trained with --ctc-weight > 0; the weight lies in
-    [0, 1] and applies to --beam-search."""
+    """--ctc-decode-weight / --ctc-greedy / --align-out need the encoder CTC head of a model trained with --ctc-weight > 0; the weight
+    lies in [0, 1] and applies to --beam-search."""
     w = float(getattr(args, "ctc_decode_weight", 0.0) or 0.0)
     if not 0.0 <= w <= 1.0:
         raise ValueError("--ctc-decode-weight must lie in [0, 1], got %g" % w)
-    if (w > 0 or getattr(args, "ctc_greedy", False)) and not hasattr(model, "ctc_linear"):
-        raise ValueError("--ctc-decode-weight / --ctc-greedy need a model with an encoder CTC head: this checkpoint was trained with "
-                         "--ctc-weight 0")
+    if (w > 0 or getattr(args, "ctc_greedy", False) or getattr(args, "align_out", None)) and not hasattr(model, "ctc_linear"):
+        raise ValueError("--ctc-decode-weight / --ctc-greedy / --align-out need a model with an encoder CTC head: this checkpoint was "
+                         "trained with --ctc-weight 0")
     if w > 0 and not getattr(args, "beam_search", False):
         raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % w)
 

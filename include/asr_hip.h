@@ -256,6 +256,26 @@ int asr_ctc_prefix_step(const float* lp, const int32_t* frames, const float* sta
                         const int32_t* first, const int64_t* cand, int B, int T, int V, int R, int K, int blank, int sos, int eos,
                         float* psi, float* new_state, asr_stream_t stream);
 
+/* ---- CTC forced alignment (csrc/ctc_align.hip has the recursion and its three rules): the best path of every target through the
+ * CTC head's posteriors.  Adds what asr_ctc_fwd does not keep: that kernel sums over the alignments, this one takes the maximum, leaves
+ * back-pointers and walks them.  Inputs as asr_ctc_fwd: logits (B,T,ld) fp32 with any row stride ld >= V, targets (B,Lmax) int64,
+ * lengths int32 on the device (clamped to [0,T] and [0,Lmax]).  Outputs on the device:
+ *   path (B,T) int32       lattice state s in [0, 2 L_b] at frame t (even: blank, odd: label (s-1)/2); -1 for t >= T_b
+ *   start, end (B,Lmax)    first frame and one past the last frame of label l (contiguous); -1 for l >= L_b
+ *   lab_score (B,Lmax)     sum over the label's frames of logit[t,label] - lse[t]; 0 where start is -1
+ *   score (B)              log-probability of the best path = its raw score - sum_{t<T_b} lse[t]
+ * An utterance without a feasible alignment (L_b > T_b, equal neighbours without a frame for the blank between them, a label that is
+ * `blank` or outside [0,V)) has path / start / end -1, lab_score 0 and score -inf; the other rows of the batch are unaffected.  L_b = 0:
+ * path all 0, score = the sum of the blank log-probabilities; T_b = 0: feasible for L_b = 0 only, score 0.  Frames >= T_b and targets
+ * >= L_b influence nothing.  The workspace (asr_ctc_align_workspace floats) holds the row log-sum-exp and, only when the packed
+ * back-pointers of an utterance do not fit into LDS, those; ASR_EUNSUPPORTED when even the working rows (20 (2 Lmax + 1) + T words)
+ * exceed the LDS of a CU.                                                                                                          */
+int64_t asr_ctc_align_workspace(int B, int T, int Lmax);
+int asr_ctc_align(const float* logits, int64_t ld, const int64_t* targets, const int32_t* input_lengths,
+                  const int32_t* target_lengths, int B, int T, int V, int Lmax, int blank, float* workspace,
+                  int64_t workspace_floats, int32_t* path, int32_t* start, int32_t* end, float* lab_score, float* score,
+                  asr_stream_t stream);
+
 /* ---- incremental (KV-cached) decoding with the position on the device: one captured hipGraph serves all 300 steps of
  * the reference's greedy loop (models/asr/transformer.py:316-394).  state[0] = position t of the token being fed.
  * asr_decode_prepare(advance=0): pe_cur[0..D) = pe[t], key_len[0..B) = t+1;  (advance=1): state[0] = t+1.
