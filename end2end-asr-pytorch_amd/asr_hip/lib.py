@@ -72,6 +72,8 @@ _SIGS = {
     "asr_ctc_bwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
     "asr_ctc_align_workspace": (_L, [_I, _I, _I]),
     "asr_ctc_align": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
+    "asr_ctc_beam_workspace": (_L, [_I, _I, _I, _I]),
+    "asr_ctc_beam_search": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
     "asr_ctc_prefix_init": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "asr_ctc_prefix_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "asr_decode_prepare": (_I, [_P, _I, _P, _P, _I, _P, _I, _P]),

@@ -675,6 +675,27 @@ def ctc_align(logits, targets, input_lengths, target_lengths, blank=0):
     return out
 
 
+def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0):
+    """CTC prefix beam search (csrc/ctc_beam.hip): logits (B,T,V) fp32 (rows contiguous, any row stride), lengths (B) int32 on the device
+    = true frames; beam_width W <= 16 prefixes kept per frame, candidates C <= 16 labels tried per frame (0: min(V, 16)), nbest <= W ->
+    dict(ids (B,nbest,T) int32, lengths (B,nbest) int32 (-1: no such hypothesis), scores (B,nbest) fp32) on the device, best first.
+    blank defaults to PAD (0).  The logits of the true frames must be finite."""
+    B, T, V = logits.shape
+    W, nbest = int(beam_width), int(nbest)
+    C = int(candidates) if candidates else min(V, 16)
+    assert logits.dtype == torch.float32 and logits.stride(2) == 1 and logits.stride(0) == T * logits.stride(1) and T >= 1
+    assert lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()
+    dev = logits.device
+    n = L.load().asr_ctc_beam_workspace(B, T, W, C)
+    ws = torch.empty(max(n, 1), device=dev, dtype=torch.float32)
+    rows = max(nbest, 1)
+    out = dict(ids=torch.empty((B, rows, T), device=dev, dtype=torch.int32), lengths=torch.empty((B, rows), device=dev, dtype=torch.int32),
+               scores=torch.empty((B, rows), device=dev, dtype=torch.float32))
+    L.call("asr_ctc_beam_search", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
+           L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.stream())
+    return out
+
+
 def ctc_prefix_init(logits, frames, row_utt, blank=0):
     """logits (B,T,V) fp32 (rows contiguous, any row stride), frames (B) int32, row_utt (R) int32 on the device ->
     (lp (B,T,V) log-softmax, state (R,T,2) of the empty prefix): csrc/ctc_prefix.hip."""

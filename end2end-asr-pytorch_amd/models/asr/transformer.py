@@ -137,6 +137,36 @@ class Transformer(nn.Module):
         return (strs, hyp_ids) if return_ids else strs
 
     @torch.no_grad()
+    def ctc_beam_search(self, enc_out, lengths, beam_width, nbest=1, candidates=0, lm=None, lm_weight=0.1, c_weight=1, return_ids=False):
+        """Prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): no decoder step.  lengths:
+        true encoder frames per utterance (ctc_frame_lengths); beam_width W in 1..16 prefixes kept per frame, candidates C (0: min(V, 16))
+        labels tried per frame.  One device-to-host copy.  The kernel's W hypotheses of an utterance, score = log-probability summed over
+        the alignments, are ranked like a decoder beam's (Decoder._rank_ended): score + sqrt(words) * c_weight, or with lm
+        (utils.lstm_utils.LM) score + lm_weight * (lm - 2 * oov) + sqrt(words) * c_weight, all utterances' hypotheses in ONE batched LM
+        call.  -> per utterance the min(nbest, found) best strings, best first (return_ids: (strings, label ids), same nesting); the ids
+        are CTC labels as they stand: no SOS, no EOS."""
+        W = int(beam_width)
+        if not 1 <= W <= 16:
+            raise ValueError("ctc_beam_search keeps beam_width prefixes per frame in the kernel's beam: 1..16, got %d" % W)
+        if nbest < 1:
+            raise ValueError("nbest must be at least 1, got %d" % nbest)
+        logits = self.ctc_logits(enc_out)
+        B, T, V = logits.shape
+        out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN)
+        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1), out["scores"].view(torch.int32).reshape(-1)]).cpu()
+        ids, lens, scores = torch.split(flat, [B * W * T, B * W, B * W])
+        ids, lens, scores = ids.view(B, W, T).tolist(), lens.view(B, W).tolist(), scores.view(torch.float32).view(B, W).tolist()
+        ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n]} for n in range(W) if lens[b][n] >= 0] for b in range(B)]
+        ranked, _ = self.decoder._rank_ended(ended, nbest, c_weight, lm, lm_weight)
+        hyp_ids, at = [], 0
+        for hs in ended:                                 # _rank_ended returns min(len, nbest) hypotheses per utterance, flat
+            n = min(len(hs), nbest)
+            hyp_ids.append(ranked[at:at + n])
+            at += n
+        strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
+        return (strs, hyp_ids) if return_ids else strs
+
+    @torch.no_grad()
     def ctc_align(self, enc_out, lengths, targets, target_lengths=None):
         """Forced alignment of label ids against the CTC head (csrc/ctc_align.hip).  lengths: true encoder frames
         per utterance (ctc_frame_lengths); targets: (B,L) int64 with target_lengths, or a list of id lists.  One device-to-host copy.
@@ -186,14 +216,22 @@ class Transformer(nn.Module):
 
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
-                 ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None):
+                 ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
-        ctc_greedy: best-path decoding from the head alone.  align_source "gold" / "hyp": a fourth value, the forced alignment
+        ctc_greedy: best-path decoding from the head alone; ctc_beam: prefix beam search over the head's posteriors alone
+        (ctc_beam_search: beam_width prefixes, ctc_candidates labels per frame, the beam_nbest best re-ranked with lm when lm_rescoring),
+        not together with beam_search, ctc_greedy or ctc_weight.  align_source "gold" / "hyp": a fourth value, the forced alignment
         (ctc_align) of padded_target with target_lengths, or of the label ids the decoder produced (SOS and EOS dropped; never a
         re-tokenised string)."""
         if ctc_weight > 0 and not beam_search:
             raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % ctc_weight)
+        if ctc_beam and (beam_search or ctc_greedy or ctc_weight > 0):
+            raise ValueError("ctc_beam decodes from the CTC head alone: not together with beam_search, ctc_greedy or ctc_weight")
+        if ctc_beam and not hasattr(self, "ctc_linear"):
+            self.ctc_logits(None)                      # the "no encoder CTC head" ValueError, before any device work
+        if lm_rescoring and ctc_beam and lm is None:
+            raise ValueError("lm_rescoring=True needs lm (utils.lstm_utils.LM)")
         if align_source not in (None, "gold", "hyp"):
             raise ValueError("align_source must be 'gold' or 'hyp', got %r" % (align_source,))
         if align_source is not None and not hasattr(self, "ctc_linear"):
@@ -205,7 +243,7 @@ class Transformer(nn.Module):
         _, gold, *_ = self.decoder(padded_target, enc_out, input_lengths)
         gold_cpu = gold.cpu().tolist()
         strs_gold = ["".join(self.id2label[int(x)] for x in row) for row in gold_cpu]
-        if ctc_weight > 0 or ctc_greedy or align_source is not None:
+        if ctc_weight > 0 or ctc_greedy or ctc_beam or align_source is not None:
             if ctc_lengths is None:
                 ctc_lengths = self.ctc_frame_lengths(input_lengths, enc_out.shape[1])
             if ctc_logits is None and ctc_weight > 0 and not ctc_greedy:
@@ -213,6 +251,11 @@ class Transformer(nn.Module):
                     ctc_logits = self.ctc_logits(enc_out)
         if ctc_greedy:
             strs_hyps, hyp_ids = self.ctc_greedy(enc_out, ctc_lengths, return_ids=True)
+        elif ctc_beam:
+            nbest_strs, nbest_ids = self.ctc_beam_search(enc_out, ctc_lengths, beam_width, nbest=max(1, int(beam_nbest)),
+                                                         candidates=ctc_candidates, lm=lm if lm_rescoring else None,
+                                                         lm_weight=lm_weight, c_weight=c_weight, return_ids=True)
+            strs_hyps, hyp_ids = [rows[0] if rows else "" for rows in nbest_strs], [rows[0] if rows else [] for rows in nbest_ids]
         elif beam_search:
             hyp_ids, strs_hyps = self.decoder.beam_search(enc_out, beam_width=beam_width, nbest=1, lm=lm, lm_rescoring=lm_rescoring,
                                                           lm_weight=lm_weight, c_weight=c_weight, ctc_logits=ctc_logits,
@@ -231,8 +274,9 @@ class Transformer(nn.Module):
         if align_source == "gold":
             alignment = self.ctc_align(enc_out, ctc_lengths, padded_target, target_lengths)
         else:
-            # (the ids of --ctc-greedy are CTC labels as they stand, feasible by construction; a decoder's carry SOS / EOS)
-            alignment = self.ctc_align(enc_out, ctc_lengths, hyp_ids if ctc_greedy else [hypothesis_labels(row) for row in hyp_ids])
+            # (the ids of --ctc-greedy and --ctc-beam-search are CTC labels as they stand, feasible by construction; a decoder's carry SOS / EOS)
+            alignment = self.ctc_align(enc_out, ctc_lengths,
+                                       hyp_ids if ctc_greedy or ctc_beam else [hypothesis_labels(row) for row in hyp_ids])
         return _, strs_hyps, strs_gold, alignment
 
 

@@ -1,5 +1,6 @@
 """Evaluation entry point -- same command line as the reference (reference: test.py): loads --continue-from, decodes
-every test utterance (greedy, or beam search with --beam-search) and reports CER / WER.  --align-out PATH also writes label and word
+every test utterance (greedy, beam search with --beam-search, or from the encoder CTC head alone with --ctc-greedy / --ctc-beam-search)
+and reports CER / WER.  --align-out PATH also writes label and word
 timestamps from the encoder CTC head (forced alignment of the transcript, or of the hypothesis with --align-source hyp)."""
 import torch
 from tqdm import tqdm
@@ -41,7 +42,8 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
                                                                  c_weight=args.c_weight, verbose=args.verbose,
                                                                  ctc_weight=getattr(args, "ctc_decode_weight", 0.0),
                                                                  ctc_candidates=getattr(args, "ctc_candidates", 0),
-                                                                 ctc_greedy=getattr(args, "ctc_greedy", False), **align)
+                                                                 ctc_greedy=getattr(args, "ctc_greedy", False),
+                                                                 ctc_beam=getattr(args, "ctc_beam_search", False), **align)
             for i, (hyp, gold) in enumerate(zip(strs_hyps, strs_gold)):
                 for ch in (constant.EOS_CHAR, constant.SOS_CHAR, constant.PAD_CHAR):
                     hyp, gold = hyp.replace(ch, ""), gold.replace(ch, "")
@@ -63,14 +65,28 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
 
 
 def check_ctc_decoding(args, model):
-    """--ctc-decode-weight / --ctc-greedy / --align-out need the encoder CTC head of a model trained with --ctc-weight > 0; the weight
-    lies in [0, 1] and applies to --beam-search."""
+    """--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need the encoder CTC head of a model trained with
+    --ctc-weight > 0; the weight lies in [0, 1] and applies to --beam-search.  --ctc-beam-search decodes from the head alone: it excludes
+    --beam-search, --ctc-greedy and a --ctc-decode-weight, and its --beam-width lies in 1..16."""
     w = float(getattr(args, "ctc_decode_weight", 0.0) or 0.0)
     if not 0.0 <= w <= 1.0:
         raise ValueError("--ctc-decode-weight must lie in [0, 1], got %g" % w)
-    if (w > 0 or getattr(args, "ctc_greedy", False) or getattr(args, "align_out", None)) and not hasattr(model, "ctc_linear"):
-        raise ValueError("--ctc-decode-weight / --ctc-greedy / --align-out need a model with an encoder CTC head: this checkpoint was "
-                         "trained with --ctc-weight 0")
+    ctc_beam = getattr(args, "ctc_beam_search", False)
+    if ((w > 0 or getattr(args, "ctc_greedy", False) or ctc_beam or getattr(args, "align_out", None))
+            and not hasattr(model, "ctc_linear")):
+        raise ValueError("--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need a model with an encoder CTC head: "
+                         "this checkpoint was trained with --ctc-weight 0")
+    if ctc_beam:
+        for flag, on in (("--beam-search", getattr(args, "beam_search", False)), ("--ctc-greedy", getattr(args, "ctc_greedy", False)),
+                         ("--ctc-decode-weight %g" % w, w > 0)):
+            if on:
+                raise ValueError("--ctc-beam-search decodes from the CTC head alone: it cannot be combined with %s" % flag)
+        if not 1 <= int(args.beam_width) <= 16:
+            raise ValueError("--ctc-beam-search keeps --beam-width prefixes per frame in the kernel's beam: 1..16, got %d"
+                             % int(args.beam_width))
+        c = int(getattr(args, "ctc_candidates", 0) or 0)
+        if not 0 <= c <= 16:
+            raise ValueError("--ctc-candidates must lie in 0..16 with --ctc-beam-search (0: min(V, 16)), got %d" % c)
     if w > 0 and not getattr(args, "beam_search", False):
         raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % w)
 

@@ -75,6 +75,9 @@ _FLAGS = [
     # decoding from the CTC head alone
     (("--ctc-weight",), dict(default=0.0, type=_F)), (("--ctc-decode-weight",), dict(default=0.0, type=_F)),
     (("--ctc-candidates",), dict(default=0, type=_I)), (("--ctc-greedy",), dict(action="store_true")),
+    # --ctc-beam-search (test.py): prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): --beam-width (1..16)
+    # prefixes kept per frame, --ctc-candidates (0: min(V, 16)) labels tried per frame, the n-best ranked like --beam-search's
+    (("--ctc-beam-search",), dict(action="store_true")),
     # CTC forced alignment (test.py): --align-out PATH writes one JSON line per test utterance with label and word
     # timestamps from the CTC head; --align-source gold aligns the transcript, hyp the label ids the decoder produced
     (("--align-out",), dict(default=None, type=_S)), (("--align-source",), dict(default="gold", choices=["gold", "hyp"])),

@@ -276,6 +276,22 @@ int asr_ctc_align(const float* logits, int64_t ld, const int64_t* targets, const
                   int64_t workspace_floats, int32_t* path, int32_t* start, int32_t* end, float* lab_score, float* score,
                   asr_stream_t stream);
 
+/* ---- CTC prefix beam search (csrc/ctc_beam.hip has the definition, slot by slot): the nbest label sequences of the CTC head's posteriors
+ * with the summed log-probability of all alignments of each, from the head alone.  Adds to asr_ctc_align what that kernel is given: the
+ * sequence.  logits (B,T,ld) fp32 with any row stride ld >= V, input_lengths (B) int32 on the device (clamped to [0,T]; frames >= T_b
+ * influence nothing).  W = beam width (prefixes kept per frame), C = candidate labels per frame (the C largest logits, the blank
+ * dropped); 1 <= C <= V.  W > 16, C > 16 or nbest > W: ASR_EUNSUPPORTED; a blank outside [0,V): ASR_EINVAL.  Outputs on the device:
+ *   ids (B,nbest,T) int32     the labels of hypothesis n of utterance b, best first; `blank` behind its length
+ *   lengths (B,nbest) int32   labels in it (0: the empty sequence); -1 where the beam held fewer than n + 1 prefixes
+ *   scores (B,nbest) fp32     log p(sequence | frames < T_b) within the beam: -inf where lengths is -1; T_b = 0: the empty sequence, 0
+ * Three launches: the row log-sum-exp, asr_logsoftmax_topk for the candidates, one workgroup per utterance for the search.  The
+ * workspace (asr_ctc_beam_workspace floats, 8-byte aligned) holds those two results and the prefix trie, 1 + T W (parent, label) pairs
+ * per utterance.  The result is a function of the inputs alone (no atomics).                                                        */
+int64_t asr_ctc_beam_workspace(int B, int T, int W, int C);
+int asr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C, int nbest,
+                        int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+                        asr_stream_t stream);
+
 /* ---- incremental (KV-cached) decoding with the position on the device: one captured hipGraph serves all 300 steps of
  * the reference's greedy loop (models/asr/transformer.py:316-394).  state[0] = position t of the token being fed.
  * asr_decode_prepare(advance=0): pe_cur[0..D) = pe[t], key_len[0..B) = t+1;  (advance=1): state[0] = t+1.
