@@ -5,6 +5,7 @@ by params.grad_of() (so the Functions return None for them) and reported to the 
 Sub-layer -> reference code
   MHAFn      models/common_layers.py:170-200 (+ :211-225) and the `*= non_pad_mask` that follows every call
   FFNFn      models/common_layers.py:135-142 (+ mask)
+  ConvModuleFn  (no reference code: the Conformer convolution module of --conv-module-kernel)
   EncInFn    models/asr/transformer.py:172-173
   EmbedFn    models/asr/transformer.py:292-293
   LinearFn   models/asr/transformer.py:302 (output_linear) and any plain nn.Linear
@@ -484,6 +485,44 @@ class FFNFn(Function):
         _linear_bwd(dh, x2, W1, b1, dx_out=d_res, accumulate=True)
         P.grad_ready(*ctx.params)
         return (d_res.view(B, T, D),) + (None,) * 7
+
+
+# ================================================================================================ convolution module
+class ConvModuleFn(Function):
+    """LN(dropout(W2 swish(dwconv(glu(W1 x)))) + x) * row_keep (csrc/convmod.hip has the definition): the two
+    pointwise layers on the linear path of every other sub-layer, the three launches of the module between them, FFNFn's epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, wd, bd, W2, b2, gamma, beta, cfg):
+        B, T, D = x.shape
+        K = wd.shape[-1]
+        lens = cfg["key_len"]
+        x2 = x.reshape(B * T, D).contiguous()
+        u = _linear_fwd(x2, W1, b1)
+        s, v = ops.convmod_fwd(u, wd.data, bd.data, lens, B, T, D, K)
+        y = _linear_fwd(v, W2, b2)
+        seed = P.next_seed()
+        out, mean, rstd = ops.add_ln_fwd(y, x2, gamma.data, beta.data, row_keep=cfg.get("row_keep"), p=cfg["p"], seed=seed)
+        ctx.t = (x2, u, s, v, y, mean, rstd, lens)
+        ctx.params = (W1, b1, wd, bd, W2, b2, gamma, beta)
+        ctx.cfg, ctx.seed, ctx.shape = cfg, seed, (B, T, D, K)
+        return out.view(B, T, D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, T, D, K = ctx.shape
+        x2, u, s, v, z, mean, rstd, lens = ctx.t
+        W1, b1, wd, bd, W2, b2, gamma, beta = ctx.params
+        cfg = ctx.cfg
+        dout2 = dout.reshape(B * T, D).contiguous()
+        d_res, d_y = ops.add_ln_bwd(dout2, z, mean, rstd, gamma.data, cfg.get("row_keep"), P.grad_of(gamma),
+                                    P.grad_of(beta), p=cfg["p"], seed=ctx.seed)
+        dv = _linear_bwd(d_y, v, W2, b2)
+        ops.convmod_bwd_weight(dv, s, u, lens, B, T, D, K, P.grad_of(wd), P.grad_of(bd))
+        du = ops.convmod_bwd_data(dv, s, u, wd.data, lens, B, T, D, K)
+        _linear_bwd(du, x2, W1, b1, dx_out=d_res, accumulate=True)
+        P.grad_ready(*ctx.params)
+        return (d_res.view(B, T, D),) + (None,) * 9
 
 
 # ================================================================================================ encoder input

@@ -696,6 +696,42 @@ def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0)
     return out
 
 
+# ------------------------------------------------------------------------------------------------ convolution module
+def _convmod_args(u, lens, B, T, D):
+    assert u.is_contiguous() and u.numel() == B * T * 2 * D and lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous()
+
+
+def convmod_fwd(u, wd, bd, lens, B, T, D, K):
+    """GLU -> depthwise convolution -> Swish (csrc/convmod.hip): u (B T, 2D) = [a | gate] in the compute dtype, wd (D,1,K) / bd (D) fp32,
+    lens (B) int32 on the device -> (s, v), both (B T, D) in u's dtype; frames t >= len_b are not read and v is zero there."""
+    _convmod_args(u, lens, B, T, D)
+    assert wd.dtype == torch.float32 and wd.is_contiguous() and wd.numel() == D * K and bd.dtype == torch.float32 and bd.numel() == D
+    s = torch.empty((B * T, D), device=u.device, dtype=u.dtype)
+    v = torch.empty((B * T, D), device=u.device, dtype=u.dtype)
+    L.call("asr_convmod_fwd", L.ptr(u), L.ptr(wd), L.ptr(bd), L.ptr(lens), B, T, D, K, L.dt(u), L.ptr(s), L.ptr(v), L.stream())
+    return s, v
+
+
+def convmod_bwd_data(dv, s, u, wd, lens, B, T, D, K):
+    """-> du (B T, 2D) in the compute dtype from dv, the saved s (both (B T, D)) and u: the operand of pointwise_1's backward."""
+    _convmod_args(u, lens, B, T, D)
+    assert dv.is_contiguous() and s.is_contiguous() and dv.dtype == u.dtype == s.dtype and dv.numel() == s.numel() == B * T * D
+    du = torch.empty((B * T, 2 * D), device=u.device, dtype=u.dtype)
+    L.call("asr_convmod_bwd_data", L.ptr(dv), L.ptr(s), L.ptr(u), L.ptr(wd), L.ptr(lens), B, T, D, K, L.dt(u), L.ptr(du), L.stream())
+    return du
+
+
+def convmod_bwd_weight(dv, s, u, lens, B, T, D, K, dwd, dbd):
+    """dwd (D K) += , dbd (D) += (fp32, accumulated in place; no atomics, the same bits for the same inputs)."""
+    _convmod_args(u, lens, B, T, D)
+    assert dv.is_contiguous() and s.is_contiguous() and dv.dtype == u.dtype == s.dtype and dv.numel() == s.numel() == B * T * D
+    assert dwd.dtype == torch.float32 and dbd.dtype == torch.float32 and dwd.numel() == D * K and dbd.numel() == D and dwd.is_contiguous()
+    n = L.load().asr_convmod_workspace(B, T, D, K)
+    ws = workspace("convmod_ws", (max(n, 1),), torch.float32, u.device, zero=False)      # every slab is written whole before it is read
+    L.call("asr_convmod_bwd_weight", L.ptr(dv), L.ptr(s), L.ptr(u), L.ptr(lens), B, T, D, K, L.dt(u), L.ptr(ws), n, L.ptr(dwd), L.ptr(dbd),
+           L.stream())
+
+
 def ctc_prefix_init(logits, frames, row_utt, blank=0):
     """logits (B,T,V) fp32 (rows contiguous, any row stride), frames (B) int32, row_utt (R) int32 on the device ->
     (lp (B,T,V) log-softmax, state (R,T,2) of the empty prefix): csrc/ctc_prefix.hip."""

@@ -15,8 +15,8 @@ import torch.nn as nn
 
 from asr_hip import functions as F_
 from asr_hip import ops
-from models.common_layers import (LowRankMultiHeadAttention, LowRankPositionwiseFeedForward, MultiHeadAttention,
-                                  PositionalEncoding, PositionwiseFeedForwardWithConv)
+from models.common_layers import (ConvolutionModule, LowRankMultiHeadAttention, LowRankPositionwiseFeedForward, MultiHeadAttention,
+                                  PositionalEncoding, PositionwiseFeedForwardWithConv, check_conv_module_kernel)
 from utils import constant
 
 
@@ -94,7 +94,7 @@ class Transformer(nn.Module):
                 nn.Conv2d(64, 128, 3, stride=1, padding=1), nn.ReLU(), nn.Conv2d(128, 128, 3, stride=1, padding=1),
                 nn.ReLU(), nn.MaxPool2d(2, stride=2))
         for p in self.parameters():            # reference: transformer.py:55-57 (overrides every earlier init)
-            if p.dim() > 1:
+            if p.dim() > 1 and not getattr(p, "_asr_keep_init", False):      # (a ConvolutionModule's depthwise taps keep Conv1d's init)
                 nn.init.xavier_uniform_(p)
 
     # -------------------------------------------------------------------------------------------- front end
@@ -282,11 +282,13 @@ class Transformer(nn.Module):
 
 class Encoder(nn.Module):
     """Encoder(num_layers, num_heads, dim_model, dim_key, dim_value, dim_input, dim_inner, dropout=0.1,
-    src_max_length=2500)   (reference: transformer.py:126-180)"""
+    src_max_length=2500)   (reference: transformer.py:126-180); conv_module_kernel K > 0 (--conv-module-kernel) gives every layer a
+    ConvolutionModule between its attention and feed-forward sub-layers."""
 
     def __init__(self, num_layers, num_heads, dim_model, dim_key, dim_value, dim_input, dim_inner, dropout=0.1,
-                 src_max_length=2500, rank=0):
+                 src_max_length=2500, rank=0, conv_module_kernel=0):
         super().__init__()
+        self.conv_module_kernel = check_conv_module_kernel(conv_module_kernel, dim_model, rank)
         self.dim_input, self.num_layers, self.num_heads = dim_input, num_layers, num_heads
         self.dim_model, self.dim_key, self.dim_value, self.dim_inner = dim_model, dim_key, dim_value, dim_inner
         self.src_max_length = src_max_length
@@ -295,8 +297,8 @@ class Encoder(nn.Module):
         self.input_linear = nn.Linear(dim_input, dim_model)
         self.layer_norm_input = nn.LayerNorm(dim_model)
         self.positional_encoding = PositionalEncoding(dim_model, src_max_length)
-        self.layers = nn.ModuleList([EncoderLayer(num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=dropout, rank=rank)
-                                     for _ in range(num_layers)])
+        self.layers = nn.ModuleList([EncoderLayer(num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=dropout, rank=rank,
+                                                  conv_module_kernel=self.conv_module_kernel) for _ in range(num_layers)])
 
     def forward(self, padded_input, input_lengths, need_attn=False):
         """padded_input (B,T,D_in), input_lengths (B) -> (output (B,T,D), [self_attn per layer])"""
@@ -317,13 +319,16 @@ class Encoder(nn.Module):
 class EncoderLayer(nn.Module):
     """EncoderLayer(num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=0.1)   (reference: transformer.py:183-203)"""
 
-    def __init__(self, num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=0.1, rank=0):
+    def __init__(self, num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=0.1, rank=0, conv_module_kernel=0):
         super().__init__()
+        conv_module_kernel = check_conv_module_kernel(conv_module_kernel, dim_model, rank)
         if rank > 0:          # Low-Rank Transformer (BASELINE configs[4]): every projection is V (out,r) . U (r,in)
             self.self_attn = LowRankMultiHeadAttention(num_heads, dim_model, dim_key, dim_value, rank, dropout=dropout)
             self.pos_ffn = LowRankPositionwiseFeedForward(dim_model, dim_inner, rank, dropout=dropout)
             return
         self.self_attn = MultiHeadAttention(num_heads, dim_model, dim_key, dim_value, dropout=dropout)
+        if conv_module_kernel:          # (registered between the two so that state_dict lists the sub-layers in the order they run)
+            self.conv_module = ConvolutionModule(dim_model, conv_module_kernel, dropout=dropout)
         self.pos_ffn = PositionwiseFeedForwardWithConv(dim_model, dim_inner, dropout=dropout)
 
     def forward(self, enc_input, non_pad_mask=None, self_attn_mask=None, row_keep=None, key_len=None, need_attn=False):
@@ -331,6 +336,8 @@ class EncoderLayer(nn.Module):
             row_keep = non_pad_mask.reshape(-1).ne(0).to(torch.uint8)
         out, attn = self.self_attn(enc_input, enc_input, enc_input, mask=self_attn_mask, key_len=key_len, row_keep=row_keep,
                                    need_attn=need_attn)
+        if hasattr(self, "conv_module"):
+            out = self.conv_module(out, key_len=key_len, row_keep=row_keep)
         out = self.pos_ffn(out, row_keep=row_keep)
         return out, attn
 

@@ -202,6 +202,54 @@ class PositionwiseFeedForwardWithConv(nn.Module):
                               self.layer_norm.weight, self.layer_norm.bias, cfg)
 
 
+CONV_MODULE_KERNELS = range(3, 32, 2)          # odd 3 .. 31: what csrc/convmod.hip keeps in registers per lane
+
+
+def check_conv_module_kernel(kernel_size, dim_model=None, rank=0):
+    """--conv-module-kernel K: 0 (no module) or odd with 3 <= K <= 31; the kernels take channels in whole 16-byte chunks (dim_model % 8 == 0);
+    the low-rank encoder (--rank) has no such module."""
+    K = int(kernel_size or 0)
+    if K == 0:
+        return 0
+    if K not in CONV_MODULE_KERNELS:
+        raise ValueError("--conv-module-kernel must be 0 (off) or odd with 3 <= K <= 31, got %d" % K)
+    if dim_model is not None and dim_model % 8 != 0:
+        raise ValueError("--conv-module-kernel %d needs --dim-model to be a multiple of 8, got %d" % (K, dim_model))
+    if rank and rank > 0:
+        raise ValueError("--conv-module-kernel %d with --rank %d is not supported: the Low-Rank Transformer's encoder layers have no "
+                         "convolution module" % (K, rank))
+    return K
+
+
+class ConvolutionModule(nn.Module):
+    """ConvolutionModule(dim_model, kernel_size, dropout): the convolution module of the Conformer (arXiv:2005.08100) as a post-LN
+    sub-layer, LN(dropout(W2 swish(dwconv_K(glu(W1 x)))) + x) * row_keep, without the paper's BatchNorm.  The
+    depthwise convolution sees zeros at and behind each utterance's length (`key_len`, the length the layer hands to attention).
+    No reference code: the reference has no such module."""
+
+    def __init__(self, dim_model, kernel_size, dropout=0.1):
+        super().__init__()
+        kernel_size = check_conv_module_kernel(kernel_size, dim_model)
+        if kernel_size == 0:
+            raise ValueError("ConvolutionModule needs a kernel size (odd, 3 <= K <= 31)")
+        self.dim_model, self.kernel_size = dim_model, kernel_size
+        self.pointwise_1 = nn.Linear(dim_model, 2 * dim_model)
+        self.depthwise = nn.Conv1d(dim_model, dim_model, kernel_size, padding=(kernel_size - 1) // 2, groups=dim_model)
+        self.pointwise_2 = nn.Linear(dim_model, dim_model)
+        self.dropout = nn.Dropout(dropout)
+        self.layer_norm = nn.LayerNorm(dim_model)
+        self.depthwise.weight._asr_keep_init = True       # (D,1,K) is no matrix: the model's closing xavier pass leaves it alone
+
+    def forward(self, x, key_len=None, row_keep=None):
+        B, T, _ = x.shape
+        if key_len is None:           # reference-style call with materialised masks: every frame is a frame
+            key_len = torch.full((B,), T, device=x.device, dtype=torch.int32)
+        cfg = dict(p=self.dropout.p if self.training else 0.0, row_keep=row_keep, key_len=key_len)
+        return F_.ConvModuleFn.apply(_to_compute(x), self.pointwise_1.weight, self.pointwise_1.bias, self.depthwise.weight,
+                                     self.depthwise.bias, self.pointwise_2.weight, self.pointwise_2.bias, self.layer_norm.weight,
+                                     self.layer_norm.bias, cfg)
+
+
 class PositionwiseFeedForward(nn.Module):
     """Linear variant (reference: common_layers.py:100-122; unused by the reference model, kept for the API)."""
 

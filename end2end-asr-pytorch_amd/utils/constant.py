@@ -14,7 +14,8 @@ Differences that do not change old command lines:
   * `--spec-augment` (+ `--spec-time-warp/-freq-mask/-freq-masks/-time-mask/-time-masks/-time-mask-ratio`): SpecAugment of the
     training batches on the GPU front end;
   * `--features {spect,fbank}` (+ `--num-mel-bins`, `--mel-fmin`): the reference's 161 linear log1p(|STFT|) bins (default) or log-mel
-    filterbank features of the same STFT, on the host path and on the GPU front end alike.
+    filterbank features of the same STFT (DESIGN.md section 7), on the host path and on the GPU front end alike;
+  * `--conv-module-kernel K` (odd, 3..31; 0 = off): a Conformer-style convolution module in every encoder layer.
 """
 import argparse
 import os
@@ -81,6 +82,9 @@ _FLAGS = [
     # CTC forced alignment (test.py): --align-out PATH writes one JSON line per test utterance with label and word
     # timestamps from the CTC head; --align-source gold aligns the transcript, hyp the label ids the decoder produced
     (("--align-out",), dict(default=None, type=_S)), (("--align-source",), dict(default="gold", choices=["gold", "hyp"])),
+    # Conformer-style convolution module: K odd in 3..31 gives every encoder layer a conv_module (GLU, depthwise
+    # convolution over K frames, Swish between two pointwise layers) between self_attn and pos_ffn; 0 = none.  Not with --rank
+    (("--conv-module-kernel",), dict(default=0, type=_I)),
     # loss / regularisation
     (("--loss",), dict(type=_S, default="ce")), (("--clip",), dict(action="store_true")),
     (("--max-norm",), dict(default=400, type=_F)), (("--dropout",), dict(default=0.1, type=_F)),

@@ -14,6 +14,7 @@ from asr_hip import ops
 from asr_hip import params as P
 from asr_hip.ddp import HipDataParallel
 from models.asr.transformer import Decoder, Encoder, Transformer
+from models.common_layers import check_conv_module_kernel
 from utils import constant
 from utils.audio import feature_bins, feature_settings
 from utils.optimizer import AnnealingOpt, FusedAdam, NoamOpt
@@ -87,6 +88,15 @@ def load_model(load_path):
             kept = float(cur.ctc_weight)
         args.ctc_weight = kept
         cur.ctc_weight = kept           # the trainer of this run reads the process-global Namespace
+        # the encoder's convolution modules (--conv-module-kernel) are part of the model too: the checkpoint's kernel size rebuilds them
+        # (one written before the flag existed: 0, none); typing a different size is an error, never an override
+        kept = int(getattr(args, "conv_module_kernel", 0) or 0)
+        if "conv_module_kernel" in getattr(constant, "explicit", ()) and int(getattr(cur, "conv_module_kernel", 0) or 0) != kept:
+            raise ValueError("--conv-module-kernel %d on the command line, but %s was trained with --conv-module-kernel %d: the encoder's "
+                             "convolution modules cannot be added to, dropped from or resized in a checkpoint"
+                             % (cur.conv_module_kernel, load_path, kept))
+        args.conv_module_kernel = kept
+        cur.conv_module_kernel = kept
     label2id, id2label = ckpt['label2id'], ckpt['id2label']
     model = init_transformer_model(args, label2id, id2label)
     sd = ckpt['model_state_dict']
@@ -165,11 +175,13 @@ def init_transformer_model(args, label2id, id2label):
                 raise ValueError("--dim-input %d, but --features fbank --num-mel-bins %d gives the model %d rows"
                                  % (args.dim_input, n_fft_bins, n_fft_bins))
             args.dim_input = n_fft_bins
+    conv_k = check_conv_module_kernel(getattr(args, "conv_module_kernel", 0), args.dim_model, getattr(args, "rank", 0))
     ops.set_compute_dtype(torch.float32 if getattr(args, "precision", "bf16") == "fp32" else torch.bfloat16)
     ops.set_fp8(getattr(args, "precision", "bf16") == "fp8")
     encoder = Encoder(args.num_layers, num_heads=args.num_heads, dim_model=args.dim_model, dim_key=args.dim_key,
                       dim_value=args.dim_value, dim_input=args.dim_input, dim_inner=args.dim_inner,
-                      src_max_length=args.src_max_len, dropout=args.dropout, rank=getattr(args, "rank", 0))
+                      src_max_length=args.src_max_len, dropout=args.dropout, rank=getattr(args, "rank", 0),
+                      conv_module_kernel=conv_k)
     decoder = Decoder(id2label, num_src_vocab=len(label2id), num_trg_vocab=len(label2id), num_layers=args.num_layers,
                       num_heads=args.num_heads, dim_emb=args.dim_emb, dim_model=args.dim_model, dim_inner=args.dim_inner,
                       dim_key=args.dim_key, dim_value=args.dim_value, trg_max_length=args.tgt_max_len, dropout=args.dropout,

@@ -292,6 +292,25 @@ int asr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* input_le
                         int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
                         asr_stream_t stream);
 
+/* ---- Conformer-style convolution module (csrc/convmod.hip has the definition): GLU -> depthwise convolution over time -> Swish between
+ * the module's two pointwise GEMMs, channel last.  u (B,T,2D) = [a | gate], s / v / dv (B,T,D), du (B,T,2D), all in `dtype` and
+ * contiguous; wd (D,K) and bd (D) fp32 (the layout of nn.Conv1d(D, D, K, padding=(K-1)/2, groups=D)); len (B) int32 on the device, clamped
+ * to [0,T]: frames t >= len_b are never read, g and v are zero there and so are ds and du.  All arithmetic fp32.
+ *   asr_convmod_fwd          s = bd + conv(g), v = s sigma(s)
+ *   asr_convmod_bwd_data     du from dv, the saved s and u
+ *   asr_convmod_bwd_weight   dwd (D,K) += , dbd (D) += : fp32, ACCUMULATED; ds and g are formed from (dv, s, u) in fp32.  No atomics: row
+ *                            slices leave partial slabs in the workspace (asr_convmod_workspace floats) and a finish launch adds
+ *                            them in index order, so the result is a function of the inputs alone.
+ * fp32 and bf16, D % 8 == 0, K odd in 3 .. 31, any B >= 1 and T >= 1 (T < K included); anything else: ASR_EUNSUPPORTED, nothing launched
+ * (asr_convmod_workspace: 0).  No allocation and no synchronisation: safe under stream capture.                                      */
+int64_t asr_convmod_workspace(int B, int T, int D, int K);
+int asr_convmod_fwd(const void* u, const float* wd, const float* bd, const int32_t* len, int B, int T, int D, int K, int dtype,
+                    void* s_out, void* v_out, asr_stream_t stream);
+int asr_convmod_bwd_data(const void* dv, const void* s, const void* u, const float* wd, const int32_t* len, int B, int T, int D, int K,
+                         int dtype, void* du_out, asr_stream_t stream);
+int asr_convmod_bwd_weight(const void* dv, const void* s, const void* u, const int32_t* len, int B, int T, int D, int K, int dtype,
+                           float* workspace, int64_t workspace_floats, float* dwd, float* dbd, asr_stream_t stream);
+
 /* ---- incremental (KV-cached) decoding with the position on the device: one captured hipGraph serves all 300 steps of
  * the reference's greedy loop (models/asr/transformer.py:316-394).  state[0] = position t of the token being fed.
  * asr_decode_prepare(advance=0): pe_cur[0..D) = pe[t], key_len[0..B) = t+1;  (advance=1): state[0] = t+1.
