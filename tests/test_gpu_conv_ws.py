@@ -8,36 +8,14 @@ comparison is equality:
   * against torch's float64 convolution (the reference's nn.Conv2d + ReLU (+ mask) (+ MaxPool2d + view / transpose) on the same data);
   * against the kernels it replaces (tuning WS128 / WS64 = 0: the generic implicit GEMM, the two-pass c64 form), incl. the pooled form's
     selection bytes and both forms of the pooled epilogue (vertical tile pairs at H % 16 == 0, single tiles otherwise).
-The same comparisons run without torch in tools/conv_ws_test.cpp (the development harness)."""
+The data and the float64 reference are those of tests/conv_reference.py (shared with tests/test_gpu_conv_arms.py, which holds every other
+convolution arm the same way).  The same comparisons run without torch in tools/conv_ws_test.cpp (the development harness)."""
 import pytest
 import torch
-import torch.nn.functional as F
+
+from conv_reference import conv_data as _data, conv_forward_ref as _reference, packed as _packed
 
 pytestmark = pytest.mark.gpu
-
-
-def _data(B, H, W, Cin, Cout, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-3, 4, (B, H, W, Cin), generator=g).float()
-    w = torch.randint(-2, 3, (Cout, Cin, 3, 3), generator=g).float()
-    bias = torch.randint(-8, 9, (Cout,), generator=g).float() * 0.5
-    mask = torch.randint(-1, 2, (B, H, W, Cout), generator=g).float()
-    return x, w, bias, mask
-
-
-def _packed(w):
-    """(Cout, 9 taps, Cin) bf16: the layout asr_conv_pack_weight produces (tap = ky * 3 + kx)."""
-    Cout, Cin = w.shape[:2]
-    return w.permute(0, 2, 3, 1).reshape(Cout, 9, Cin).contiguous().cuda().bfloat16()
-
-
-def _reference(x, w, bias, relu, mask):
-    y = F.conv2d(x.permute(0, 3, 1, 2).double(), w.double(), bias.double(), padding=1).permute(0, 2, 3, 1)
-    if relu:
-        y = y.clamp_min(0)
-    if mask is not None:
-        y = y * (mask > 0)
-    return y.float().bfloat16()          # exact fp32 value -> ONE round-to-nearest-even, as the kernels' v_cvt_pk_bf16_f32
 
 
 CASES = [  # B, H, W, Cin, Cout, relu, mask

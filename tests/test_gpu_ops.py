@@ -2,7 +2,9 @@
 Tolerances: fp32 mode = fp32 round-off of a different summation order; bf16 mode = bf16 storage (8 mantissa bits) of
 inputs/outputs with fp32 accumulation.  Runs on the MI355X (`-m gpu`).
 What a tolerance cannot see in the GEMMs -- one dropped chunk on a tile edge, a bias one column off, a partial sum added twice -- is
-held by tests/test_gpu_gemm_exact.py: every arm of the GEMM dispatch on exact-integer data, bit for bit against float64."""
+held by tests/test_gpu_gemm_exact.py: every arm of the GEMM dispatch on exact-integer data, bit for bit against float64.  The same for
+the convolutions and the pooling kernels -- a border row dropped from a weight gradient, a column lost at a patch seam, a tied maximum
+routed to the wrong window position -- is held by tests/test_gpu_conv_arms.py (every arm, torch.equal against tests/conv_reference.py)."""
 import math
 
 import numpy as np
@@ -1139,12 +1141,12 @@ def test_conv3x3_wgrad_two_stages_equal_one_launch(ops, cfg, dtype):
 
 @pytest.mark.parametrize("tw", ["0", "1", "2"])
 @pytest.mark.parametrize("cfg", [(3, 161, 232, True), (5, 97, 401, False), (1, 5, 7, True)])
-def test_conv3x3_c64_persistent(ops, tw, cfg, monkeypatch):
+def test_conv3x3_c64_persistent(ops, tw, cfg):
     """64 -> 64 channel bf16 layer on the persistent kernel (conv_c64.hip): more tiles than workgroups, so that the three-deep
     patch pipeline, both tile shapes, image borders and the masked (dgrad) epilogue all run; reference = fp32 conv of the same
-    bf16-rounded operands."""
+    bf16-rounded operands.  The tile shape is a switch of the library (lib.set_tuning; the library reads no environment)."""
+    from asr_hip import lib as L
     B, H, W, masked = cfg
-    monkeypatch.setenv("ASR_C64_SHAPE", tw)
     dtype = torch.bfloat16
     g = torch.Generator().manual_seed(H * W)
     x = q(torch.randn(B, 64, H, W, generator=g).relu(), dtype)
@@ -1154,13 +1156,17 @@ def test_conv3x3_c64_persistent(ops, tw, cfg, monkeypatch):
     wk = torch.empty(64, 9, 64, device=D, dtype=dtype); wd = torch.empty(64, 9, 64, device=D, dtype=dtype)
     ops.conv_pack_weight(w.to(D), wk, wd)
     ref = F.conv2d(x, q(w, dtype), b, padding=1)
-    if masked:
-        m = q(torch.randn(B, 64, H, W, generator=g), dtype)
-        y = ops.conv3x3(nhwc(x).to(D, dtype), wk, b.to(D), 64, relu=False, mask_src=nhwc(m).to(D, dtype))
-        close("c64 masked", y, nhwc(ref * (m > 0)), dtype, scale=2)
-    else:
-        y = ops.conv3x3(nhwc(x).to(D, dtype), wk, b.to(D), 64, relu=True)
-        close("c64 relu", y, nhwc(F.relu(ref)), dtype, scale=2)
+    try:
+        L.set_tuning("C64_SHAPE", int(tw))
+        if masked:
+            m = q(torch.randn(B, 64, H, W, generator=g), dtype)
+            y = ops.conv3x3(nhwc(x).to(D, dtype), wk, b.to(D), 64, relu=False, mask_src=nhwc(m).to(D, dtype))
+            close("c64 masked", y, nhwc(ref * (m > 0)), dtype, scale=2)
+        else:
+            y = ops.conv3x3(nhwc(x).to(D, dtype), wk, b.to(D), 64, relu=True)
+            close("c64 relu", y, nhwc(F.relu(ref)), dtype, scale=2)
+    finally:
+        L.set_tuning("C64_SHAPE", None)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

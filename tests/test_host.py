@@ -773,3 +773,24 @@ def test_kernel_coverage_attention_family_names_three_translation_units():
     assert sum(counts.values()) == 4
     assert kc.coverage([both, dq, pp], names, counts) == {both: 2, dq: 0, pp: 1}
     assert any(sub in names[dq] for sub, _ in kc.PARTS_ONLY) and not any(sub in names[both] for sub, _ in kc.PARTS_ONLY)
+
+
+def test_kernel_coverage_conv_family_names_nine_translation_units():
+    """tools/kernel_coverage.py --family conv (host only): the nine translation units of the convolution front end exist; the four 8-wave
+    c64 instantiations are explained as hook-only, the default one is not; a trace row of a c64 kernel counts under either spelling."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "tools", "kernel_coverage.py"))
+    kc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kc)
+    assert len(kc.FAMILIES["conv"]) == 9 and kc.HOOK_ONLY_OF["gemm"] is kc.HOOK_ONLY
+    for f in kc.FAMILIES["conv"]:
+        assert os.path.exists(os.path.join(ROOT, "end2end-asr-pytorch_amd", "csrc", f)), f
+    wide = "_ZN12_GLOBAL__N_118conv3x3_c64_kernelILi32ELi8ELb1ELi3ELb0EEEvNS_7C64ArgsE"
+    dflt = "_ZN12_GLOBAL__N_118conv3x3_c64_kernelILi16ELi8ELb0ELi3ELb0EEEvNS_7C64ArgsE"
+    names = {wide: "void (anonymous namespace)::conv3x3_c64_kernel<32, 8, true, 3, false>((anonymous namespace)::C64Args)",
+             dflt: "void (anonymous namespace)::conv3x3_c64_kernel<16, 8, false, 3, false>((anonymous namespace)::C64Args)"}
+    trace = ['"Kind","Agent_Id","Kernel_Id","Kernel_Name","Start_Timestamp","End_Timestamp"',
+             '"KERNEL_DISPATCH",4,7,"%s.kd",100,200' % wide, '"KERNEL_DISPATCH",4,8,"%s",300,400' % names[wide]]
+    assert kc.coverage([wide, dflt], names, kc.launch_counts(trace)) == {wide: 2, dflt: 0}
+    hooked = [sub for sub, _ in kc.HOOK_ONLY_OF["conv"]]
+    assert len(hooked) == 4 and any(sub in names[wide] for sub in hooked) and not any(sub in names[dflt] for sub in hooked)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Which GEMM (or, with --family attention, attention) kernels does a test run launch?  (tests/test_gpu_gemm_exact.py pins every arm of the
+"""Which GEMM (or, with --family attention / --family conv, attention / convolution and pooling) kernels does a test run launch?  (tests/test_gpu_gemm_exact.py pins every arm of the
 GEMM dispatch, tests/test_gpu_attention_arms.py every arm of the attention dispatch; this is the evidence.)
 
   tools/kernel_coverage.py asm OUT_DIR                 compile the device side of the GEMM translation units (csrc/gemm_nt.hip, gemm_nn.hip,
@@ -16,7 +16,11 @@ GEMM dispatch, tests/test_gpu_attention_arms.py every arm of the attention dispa
 The trace is matched by mangled name (rocprofv3 -M; a trailing .kd is dropped) or, for a demangled trace, by the c++filt form with white
 space removed.  With `--family attention` both commands cover csrc/attention.hip, attention_fast.hip and attention_pp.hip, and the trace is that
 of tests/test_gpu_attention_arms.py (no tuning hook selects an attention kernel there: PARTS_ONLY lists the kernels that only a call with one
-of ASR_ATTN_DQ / ASR_ATTN_DKV reaches).  The counter run is a run of its own: no --pmc next to the tracing."""
+of ASR_ATTN_DQ / ASR_ATTN_DKV reaches).  With `--family conv` they cover the nine translation units of the convolution front end (CONV_FILES)
+and the trace is that of tests/test_gpu_conv_arms.py; --auto is the trace of the same command with `-k "not hooked"` (the cases that set no
+tuning hook carry no "hooked" in their ids), CONV_HOOK_ONLY explains the symbols only a hook reaches and CONV_HOOK_FORMS lists the launch
+forms of a shared symbol that only a hook reaches.  Instantiations that exist only in -DASR_TUNE_ABLATE or C64_TIMING builds are not in a
+default build's assembly and so not in the report.  The counter run is a run of its own: no --pmc next to the tracing."""
 import argparse
 import collections
 import csv
@@ -30,8 +34,10 @@ import isa_identity  # noqa: E402
 
 GEMM_FILES = ("gemm_nt.hip", "gemm_nn.hip", "gemm_tn.hip", "gemm_big.hip")
 ATTENTION_FILES = ("attention.hip", "attention_fast.hip", "attention_pp.hip")
-FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES}
-LABEL = {"gemm": "GEMM", "attention": "attention"}
+CONV_FILES = ("conv1.hip", "conv1_wgrad_mfma.hip", "conv_igemm.hip", "conv_c64.hip", "conv_ws.hip", "conv_wgrad.hip", "conv_wgrad_dma.hip",
+              "conv_level0.hip", "pool.hip")
+FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES, "conv": CONV_FILES}
+LABEL = {"gemm": "GEMM", "attention": "attention", "conv": "convolution / pooling"}
 
 # kernels the automatic dispatch cannot choose: (substring of the demangled name, the line that decides)
 HOOK_ONLY = (
@@ -44,6 +50,29 @@ HOOK_ONLY = (
     ("gemm_big_nn_kernel<3>", "gemm_big.hip asr_gemm_big_nn: ns is 2 or 4 unless GEMM_BIG_NS = 3"),
     ("gemm_tn128g_kernel<3>", "gemm_tn.hip asr_gemm_tn_grouped: 128 x 128 grouped blocks only under TN_GROUP_TILE = 128"),
 )
+
+# convolution kernels the automatic dispatch cannot choose
+_C64_WHY = "conv_c64.hip asr_conv3x3_c64_launch: 8-wave workgroups on %s tiles only under C64_SHAPE = %d (default 0: 8 x 16, two 4-wave workgroups per CU)"
+CONV_HOOK_ONLY = (
+    ("conv3x3_c64_kernel<16, 16, true, 3, false>", _C64_WHY % ("16 x 16", 1)),
+    ("conv3x3_c64_kernel<16, 16, false, 3, false>", _C64_WHY % ("16 x 16", 1)),
+    ("conv3x3_c64_kernel<32, 8, true, 3, false>", _C64_WHY % ("8 x 32", 2)),
+    ("conv3x3_c64_kernel<32, 8, false, 3, false>", _C64_WHY % ("8 x 32", 2)),
+)
+# launch forms of a symbol that other shapes reach without a hook: (form, the line that decides)
+CONV_HOOK_FORMS = (
+    ("conv3x3_c64_kernel<16, 8, false, 3, false> twice with ypix = 256 (64 -> 128 in two passes)",
+     "conv_igemm.hip asr_conv3x3_igemm: bf16 64 -> 128 without a mask runs conv_ws.hip in one pass unless WS64 = 0"),
+    ("conv3x3_igemm_kernel<bf16, 64 | 128, 16, 1, 1, false> with 128 input channels",
+     "conv_igemm.hip asr_conv3x3_igemm: bf16 with Cin = 128 runs conv_ws.hip unless WS128 = 0 (Cin = 192 and 64 -> 128 with a mask reach the symbols)"),
+    ("conv3x3_igemm_kernel<bf16, 128, 16, 1, 1, true> with 128 input channels (pooled epilogue)",
+     "conv_igemm.hip conv3x3_relu_pool_tcf_code_impl: Cin = 128 runs conv_ws.hip unless WS128 = 0 (Cin = 64 reaches the symbol)"),
+    ("conv3x3_ws128_kernel<128, 8, 128, 0, 1> at H % 16 == 0 (single tiles)",
+     "conv_ws.hip asr_conv3x3_ws128_launch: vertical tile pairs at H % 16 == 0 unless WS_PAIR = 0 (H % 16 == 8 reaches the symbol)"),
+    ("vgg_level0_fwd / _dgrad / _wgrad_kernel with wsplit = 0",
+     "conv_level0.hip: conv.0 on split weights unless L0_WSPLIT = 0 (an argument of the same kernels)"),
+)
+HOOK_ONLY_OF = {"gemm": HOOK_ONLY, "attention": (), "conv": CONV_HOOK_ONLY}
 
 # attention kernels that ops.attn_bwd never chooses (it asks for dQ and dK / dV in one launch): reached by a direct asr_attn_bwd call with one part
 PARTS_ONLY = (
@@ -141,8 +170,12 @@ def report(asm_dir, all_csv, auto_csv, walls, family="gemm"):
         hook = [s for s in syms if call[s] > 0 and cauto[s] == 0]
         print("launched only with a tuning hook set: %d" % len(hook))
         for s in hook:
-            why = [w for sub, w in HOOK_ONLY if sub in names[s]]
+            why = [w for sub, w in HOOK_ONLY_OF[family] if sub in names[s]]
             print("  HOOK   %s\n         %s" % (names[s], why[0] if why else "NOT EXPLAINED: a case without a hook should reach it"))
+    if family == "conv":
+        print("launch forms of a shared symbol that only a tuning hook reaches: %d" % len(CONV_HOOK_FORMS))
+        for form, why in CONV_HOOK_FORMS:
+            print("  FORM   %s\n         %s" % (form, why))
     return 1 if never else 0
 
 
