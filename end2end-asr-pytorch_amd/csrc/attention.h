@@ -1,5 +1,6 @@
-// Shared declarations of the attention kernels (attention.hip: generic fp32/bf16 kernels for d in {16,32,64};
-// attention_fast.hip: the bf16 / d = 64 kernels used by the reference configurations).
+// Shared declarations of the attention translation units: the kernel arguments, the dropout mask, the key masks, and the launchers that
+// attention.hip (entry points and dispatch) calls in attention_generic.hip (fp32 / bf16, d in {16, 32, 64}), attention_d64_fwd.hip,
+// attention_d64_bwd.hip, attention_d64_bwd_fused.hip and attention_pp.hip (bf16, d = 64: the reference configurations).
 #pragma once
 #include "common.h"
 
@@ -58,15 +59,6 @@ __device__ __forceinline__ uint32_t drop_row(const AttnArgs& p, int b, int h, in
   return (uint32_t)((h * p.B + b) * p.Tq + q);
 }
 
-__device__ __forceinline__ float group_max(float v) {   // across the 4 lane groups that share lane&15
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float group_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-
 __device__ __forceinline__ bool key_masked(const AttnArgs& p, int b, int kg, int q, int kend) {
   if (kg >= kend) return true;
   if (p.key_pad && p.key_pad[(int64_t)b * p.m_sb + (int64_t)(q < p.Tq ? q : p.Tq - 1) * p.m_sq + kg]) return true;
@@ -80,10 +72,27 @@ __device__ __forceinline__ int key_end(const AttnArgs& p, int b) {
 }
 
 
-// fast path entry points (attention_fast.hip); return ASR_EUNSUPPORTED when the shape / layout is not theirs
-int attn_fast_fwd(const AttnArgs& p, int d, int dtype, hipStream_t s);
-int attn_fast_bwd(const AttnArgs& p, int d, int dtype, hipStream_t s);
-// long-sequence forward (attention_pp.hip): bf16, d = 64, no causal mask; the caller has checked fast_ok()
-int attn_pp_fwd(const AttnArgs& p, hipStream_t s);
+// Launchers between the translation units.  attention.hip chooses (attn_choose_fwd / attn_choose_bwd hold every eligibility condition);
+// these only launch what they are told to, and the caller has checked that the call is in the kernel's domain.  Hidden, like asr_launch:
+// they stay out of the library's dynamic symbol list.
+#define ASR_ATTN_LOCAL __attribute__((visibility("hidden")))
+// attention_generic.hip: fp32 / bf16, d in {16, 32, 64}; ASR_EUNSUPPORTED for any other d
+ASR_ATTN_LOCAL int attn_generic_fwd(const AttnArgs& p, int d, int dtype, hipStream_t s);
+ASR_ATTN_LOCAL int attn_generic_delta_bf16(const AttnArgs& p, int d, hipStream_t s);             // delta = rowsum(dO * O); built for bf16 only
+ASR_ATTN_LOCAL int attn_generic_delta_consistent_f32(const AttnArgs& p, int d, hipStream_t s);   // delta from the recomputed P; built for fp32 only
+ASR_ATTN_LOCAL int attn_generic_dq(const AttnArgs& p, int d, int dtype, hipStream_t s);
+ASR_ATTN_LOCAL int attn_generic_dkv(const AttnArgs& p, int d, int dtype, hipStream_t s);
+ASR_ATTN_LOCAL int attn_probs(const AttnArgs& p, int d, int dtype, hipStream_t s);                      // the (H B, Tq, Tk) probability dump, any d
+// bf16, d = 64 (fast_ok(), attention_d64.h).  attention_d64_fwd.hip: 64 nq queries per workgroup, nq = 1 or 2
+ASR_ATTN_LOCAL int attn_d64_fwd(const AttnArgs& p, int nq, hipStream_t s);
+// attention_pp.hip, the long-sequence forward: no causal mask, no key-padding bytes, 16-byte aligned Out / Out32 rows
+ASR_ATTN_LOCAL int attn_pp_fwd(const AttnArgs& p, hipStream_t s);
+// attention_d64_bwd.hip: dQ / dK / dV / O 16-byte aligned
+ASR_ATTN_LOCAL int attn_d64_delta(const AttnArgs& p, hipStream_t s);
+ASR_ATTN_LOCAL int attn_d64_bwd_both(const AttnArgs& p, hipStream_t s);       // dQ and dK / dV workgroups in one launch
+ASR_ATTN_LOCAL int attn_d64_bwd_dq(const AttnArgs& p, hipStream_t s);
+ASR_ATTN_LOCAL int attn_d64_bwd_dkv(const AttnArgs& p, hipStream_t s);
+// attention_d64_bwd_fused.hip: all three gradients in one pass, Tk <= 128 nk (nk = 1 or 2)
+ASR_ATTN_LOCAL int attn_d64_bwd_fused(const AttnArgs& p, int nk, hipStream_t s);
 
 }  // namespace asr_attn

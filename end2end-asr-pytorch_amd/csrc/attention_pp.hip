@@ -1,6 +1,6 @@
 // Long-sequence attention forward for bf16 / head dim 64 (models/common_layers.py:211-225 at dim_key = dim_value = 64; the encoder
 // self-attention of BASELINE.json's north-star shape B H = 256, T = 800 and of configs[3], T' = 795).  Round 3 redesign of
-// attention_fast.hip's forward kernel; what changed and why (MI355X_MICROARCH.md "Two waves per SIMD", measured split of the old
+// attention_d64_fwd.hip's forward kernel; what changed and why (MI355X_MICROARCH.md "Two waves per SIMD", measured split of the old
 // kernel in profiles/r02_attention_d64_pmc.txt: 8.6 vector instructions per 16x16x32 MFMA, 26 % of a wave's life parked at
 // s_waitcnt / s_barrier, 2.2 waves per SIMD):
 //   * v_mfma_f32_32x32x16_bf16 with swapped contractions S^T = K Q^T, O^T = V^T P^T: a lane owns ONE query column, its 32 scores of
@@ -21,24 +21,18 @@
 //   * work items: 128-query chunks; the queries left over after the last full chunk (800 = 6 x 128 + 32) run in TAIL workgroups
 //     whose four waves split the KEY range of one 32-query block and combine through LDS -- the launch is 3 full rounds of the
 //     512 workgroup slots plus short tails instead of 3.5 -> 4 rounds.
-#include "attention.h"
+#include "attention_d64.h"
 
 namespace asr_attn {
 namespace {
 
-constexpr int HD = 64;
-constexpr int ROWB = 128;                  // bytes per LDS row (64 bf16)
+// (HD, ROWB, TILE = one 64-key tile of 8 KB and LOG2E: attention_d64.h)
 constexpr int KT = 64;                     // keys per tile
-constexpr int TILE = KT * ROWB;            // 8 KB
 constexpr int NS = 3;                      // ring depth
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr float THR = 8.f;                 // deferred maximum: P <= 2^THR
 constexpr float M_INIT = -1e30f;
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) unsigned short u16x2_t;
 
 __device__ __forceinline__ float max_halves(float v) {
   const uint32_t u = __float_as_uint(v);
@@ -124,10 +118,6 @@ __device__ __forceinline__ void read_k(uint4 (&kf)[2][4], unsigned stage, const 
     }
   }
 }
-__device__ __forceinline__ uint2 lds_tr16(unsigned a) {
-  const asr_s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) asr_s16x4_t*)(uintptr_t)a);
-  return __builtin_bit_cast(uint2, v);
-}
 __device__ __forceinline__ void read_v(uint4 (&vf)[2][2][2], unsigned stage, const unsigned (&voff)[2]) {
 #pragma unroll
   for (int db = 0; db < 2; ++db) {
@@ -137,8 +127,8 @@ __device__ __forceinline__ void read_v(uint4 (&vf)[2][2][2], unsigned stage, con
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const uint2 lo = lds_tr16(a + stage + (kb * 32 + j * 16) * ROWB);
-        const uint2 hi = lds_tr16(a + stage + (kb * 32 + j * 16 + 8) * ROWB);
+        const uint2 lo = asr_lds_read_tr16(a + stage + (kb * 32 + j * 16) * ROWB);
+        const uint2 hi = asr_lds_read_tr16(a + stage + (kb * 32 + j * 16 + 8) * ROWB);
         vf[db][kb][j] = make_uint4(lo.x, lo.y, hi.x, hi.y);
       }
   }
@@ -157,11 +147,11 @@ __device__ __forceinline__ int key_of(int kb, int r, int half) { return kb * 32 
 //  the first-generation kernel and the reference are exact in fp32.  Not kept.)
 struct Soft {
   float ref, gate;
-  f32x2_t la, lb;     // four partial row sums (two independent packed chains)
+  asr_f32x2_t la, lb;     // four partial row sums (two independent packed chains)
   f32x16_t nref;
 };
 
-// key-length mask of the tile that holds the boundary (key padding BYTES are not this kernel's: attn_pp_fwd refuses them)
+// key-length mask of the tile that holds the boundary (key padding BYTES are not this kernel's: the dispatch of attention.hip keeps them away)
 __device__ __forceinline__ void mask_tile(f32x16_t (&s)[2], int k0, int half, int kend) {
   const int lim = kend - k0 - 4 * half;          // key_of(kb, r, 0) >= lim  <=>  key >= kend
 #pragma unroll
@@ -209,8 +199,8 @@ __device__ __forceinline__ void softmax_form(f32x16_t (&s)[2], Soft& st, uint4 (
   for (int r = 0; r < 16; r += 2) {
     const float a0 = __builtin_amdgcn_exp2f(s[0][r]), a1 = __builtin_amdgcn_exp2f(s[0][r + 1]);
     const float b0 = __builtin_amdgcn_exp2f(s[1][r]), b1 = __builtin_amdgcn_exp2f(s[1][r + 1]);
-    st.la += f32x2_t{a0, a1};                          // v_pk_add_f32, two independent chains
-    st.lb += f32x2_t{b0, b1};
+    st.la += asr_f32x2_t{a0, a1};                          // v_pk_add_f32, two independent chains
+    st.lb += asr_f32x2_t{b0, b1};
     s[0][r] = a0; s[0][r + 1] = a1;
     s[1][r] = b0; s[1][r + 1] = b1;
   }
@@ -333,7 +323,7 @@ __device__ __forceinline__ void attn_fwd_pp_body(const AttnArgs& p, unsigned cha
   const f32x16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   f32x16_t o[2] = {zero16, zero16}, s[2] = {zero16, zero16};
   Soft st;
-  st.ref = 0.f; st.la = f32x2_t{0.f, 0.f}; st.lb = st.la; st.gate = -3.0e38f; st.nref = zero16;
+  st.ref = 0.f; st.la = asr_f32x2_t{0.f, 0.f}; st.lb = st.la; st.gate = -3.0e38f; st.nref = zero16;
   Frags f;
   uint4 pk[2][2];
 
@@ -463,12 +453,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pp_bf16_d64_kernel(AttnAr
 
 }  // namespace
 
-// Entry: ASR_EUNSUPPORTED unless the long-sequence kernel applies (bf16, d = 64, no causal mask, no padding bytes -- key lengths only --, 16-byte aligned rows -- checked by
-// the caller's fast_ok() -- and at least `min_keys` keys).
+// Launch only: the dispatch of attention.hip has checked fast_ok(), no causal mask, no key-padding bytes (key lengths only) and 16-byte
+// aligned rows of Out / Out32.
 int attn_pp_fwd(const AttnArgs& p, hipStream_t s) {
-  if (p.causal || p.key_pad) return ASR_EUNSUPPORTED;
-  if ((((uintptr_t)p.Out) & 15) != 0 || p.o_st % 8 != 0 || p.o_sb % 8 != 0) return ASR_EUNSUPPORTED;
-  if (p.Out32 && (((uintptr_t)p.Out32) & 15) != 0) return ASR_EUNSUPPORTED;
   const int BH = p.B * p.H;
   constexpr int nw = 4;
   const int n_full = p.Tq / (32 * nw);
@@ -479,10 +466,8 @@ int attn_pp_fwd(const AttnArgs& p, hipStream_t s) {
   // shape from 71.8 to 65.8 us at p = 0 and changes nothing elsewhere
   constexpr int kPrio = 0, kStagger = 8, kStaggerSel = 1;
   constexpr int prio = kPrio | (kStagger << 8) | (kStaggerSel << 16);
-  if (p.thr) attn_fwd_pp_bf16_d64_kernel<true, nw><<<grid, dim3(64 * nw), 0, s>>>(p, nf, n_tail, prio);
-  else attn_fwd_pp_bf16_d64_kernel<false, nw><<<grid, dim3(64 * nw), 0, s>>>(p, nf, n_tail, prio);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  if (p.thr) return asr_launch<attn_fwd_pp_bf16_d64_kernel<true, nw>>(grid, dim3(64 * nw), 0, s, p, nf, n_tail, (int)prio);
+  return asr_launch<attn_fwd_pp_bf16_d64_kernel<false, nw>>(grid, dim3(64 * nw), 0, s, p, nf, n_tail, (int)prio);
 }
 
 }  // namespace asr_attn

@@ -80,6 +80,11 @@ __device__ __forceinline__ uint2 asr_lds_read_tr16(const unsigned char* p) {
   const asr_s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) asr_s16x4_t*)(uintptr_t)p);
   return __builtin_bit_cast(uint2, v);
 }
+// the same read at an LDS byte address (callers that keep their addresses as 32-bit offsets)
+__device__ __forceinline__ uint2 asr_lds_read_tr16(unsigned lds_addr) {
+  const asr_s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) asr_s16x4_t*)(uintptr_t)lds_addr);
+  return __builtin_bit_cast(uint2, v);
+}
 
 // Pixels 2 .. 9 of a run of 12 bf16 (r0 = 0 .. 3, r1 = 4 .. 7, r2 = 8 .. 11) as one MFMA operand: (r0.y, r1.x | r1.y, r2.x).  An operand must start
 // on an even register and r0.y never does, so the compiler spends four v_mov on it; v_pk_mov_b32 moves two dwords at once and picks a half of
@@ -112,7 +117,7 @@ __device__ __forceinline__ int asr_xcd_linear(int bid, int nwg) {
 // One LDS-DMA piece issued BY HAND: lane l's 16 bytes at src go to LDS byte lds_wave_base + 16 l (the base is wave-uniform, in M0, which
 // is saved and restored: neutral for whatever the compiler keeps there).  Through the builtin the compiler counts the load itself and,
 // unable to tell the DMA's LDS write from the tile a later ds_read wants, drains vmcnt in front of every LDS read it can see; hand
-// issued, nothing waits until the caller's own asr_wait_vmcnt (csrc/attention_fast.hip has the measurement).  Ordinary global loads
+// issued, nothing waits until the caller's own asr_wait_vmcnt (csrc/attention_d64.h has the measurement).  Ordinary global loads
 // issued while a piece is in flight still wait for it: vmcnt retires in order.
 __device__ __forceinline__ void asr_lds_dma16(unsigned lds_wave_base, const void* src) {
   unsigned keep;
@@ -184,6 +189,7 @@ static inline uint32_t asr_drop_threshold(float p) {
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+static inline bool aligned8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
 
 // Raises the dynamic-LDS limit of Kernel to `bytes` unless an earlier call granted as much.  One flag per KERNEL (a non-type template
 // parameter: kernels that share a signature do not share it).  hipFuncSetAttribute must not run inside a stream capture: the first

@@ -354,7 +354,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
       for (int e = 0; e < 8; ++e) o.e[e] = f32_to_bf16(v[e]);
       *reinterpret_cast<uint4*>(C + off) = o.v;
       if (p.dot_out) {
-        // the attention backward's delta = rowsum(dO * O) per head from the block that IS dO (csrc/attention_fast.hip
+        // the attention backward's delta = rowsum(dO * O) per head from the block that IS dO (csrc/attention_d64_bwd.hip
         // attn_delta_bf16_d64_kernel, same lanes per row, same order of additions: the same bits): 8 lanes = the 64 columns of a head
         const int64_t ooff = (int64_t)grow * p.N + gcol;
         float acc = 0.f;

@@ -155,7 +155,7 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
           if constexpr (sizeof(TO) == 2) {
             if (p.dot_out) {
               // the attention backward's delta = rowsum(dO * O) per head from the block that IS dO (asr_gemm_nn_rowdot; the lanes, the
-              // order of additions and therefore the bits of csrc/attention_fast.hip attn_delta_bf16_d64_kernel): 8 lanes = one head
+              // order of additions and therefore the bits of csrc/attention_d64_bwd.hip attn_delta_bf16_d64_kernel): 8 lanes = one head
               const int64_t ooff = (int64_t)gr * p.N + gc;
               float acc = 0.f;
               if (p.dot_o32) {

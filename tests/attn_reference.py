@@ -221,6 +221,9 @@ CASES = [
     _case("fwd1_fused1_100x128", 100, 128, "kv", key_len=[128, 77], arms="fwd<1> / fused<1> (Tk 128)", flip_seen=False),
     _case("fwd1_fused2_100x129", 100, 129, "kv", key_len=[129, 65], arms="fwd<1> / fused<2> (Tk 129)"),
     _case("fwd1_causal_65", 65, 65, "qkv", pad="tail", causal=True, arms="fwd<1> causal / fused<1>"),
+    # Tk >= 384 where the long-sequence kernel must be refused: it reads neither key-padding bytes nor a causal mask
+    _case("fwd1_pad_100x384", 100, 384, "kv", pad="tail", arms="fwd<1> (pp refused: padding bytes) / both", flip_seen=False),
+    _case("fwd2_causal_385", 385, 385, "qkv", key_len=[385, 300], causal=True, arms="fwd<2> (pp refused: causal) / both", flip_seen=False),
     # a batch entry without a single live key, once on each of pp, fwd<2>, fwd<1>, fused<1>, fused<2> and both
     _case("dead_pp_161x401", 161, 401, "kv", key_len=[401, 0], arms="fully masked entry: pp / both"),
     _case("dead_fwd2_300x383", 300, 383, "kv", key_len=[383, 0], arms="fully masked entry: fwd<2> / both", flip_seen=False),

@@ -133,7 +133,7 @@ def test_every_defect_breaks_the_bound_of_every_case(case):
     against the reference with one defect: a slice of O, dQ, dK or dV must leave the bound.  A defect that cannot act on a case (a mask
     defect without dropout, the diagonal without a causal mask, the key length under a 3-D mask) is not applied there.  The single-bit
     flip is applied where one bit moves the most (attn_reference.defective_reference); the same flip at an ordinary row (query Tq // 2) is
-    recorded per case (flip_seen in attn_reference.CASES): it moves a slice by 2e-6 .. 4e-2 and stays under the bound in six bf16 cases."""
+    recorded per case (flip_seen in attn_reference.CASES): it moves a slice by 2e-6 .. 4e-2 and stays under the bound in eight bf16 cases."""
     x = AR.make_inputs(case)
     mask, inv_keep = AR.keep_mask(AR.SEED, AR.B, AR.H, case["Tq"], case["Tk"], case["p"]) if case["p"] > 0 else (None, 1.0)
     ref = AR.cached_reference(case, x, mask, inv_keep)

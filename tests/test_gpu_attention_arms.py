@@ -1,6 +1,7 @@
-"""Every arm of the attention dispatch (csrc/attention.hip, attention_fast.hip, attention_pp.hip) against a float64 reference, forward AND
-backward, under dropout, in the layouts the model uses (asr_hip/functions.py: column slices of one Q|K|V buffer, of a K|V buffer, of the
-stacked K|V buffer of the decoder's cross attention), with the fp32 copy of O, and with a batch entry that has no live key.
+"""Every arm of the attention dispatch (attn_choose_fwd / attn_choose_bwd of csrc/attention.hip over the kernels of attention_generic.hip,
+attention_d64_*.hip and attention_pp.hip) against a float64 reference, forward AND backward, under dropout, in the layouts the model uses
+(asr_hip/functions.py: column slices of one Q|K|V buffer, of a K|V buffer, of the stacked K|V buffer of the decoder's cross attention),
+with the fp32 copy of O, and with a batch entry that has no live key.
 
 The dropout mask is known on the host (tests/attn_reference.py keep_mask restates csrc/attention.h), so the reference drops exactly what the
 kernels drop and dQ / dK / dV under dropout are compared with autograd, not with another kernel.  Every case asserts:
@@ -13,7 +14,7 @@ kernels drop and dQ / dK / dV under dropout are compared with autograd, not with
   5. a slice whose reference is zero is exactly zero; gradient columns outside the written slices keep their sentinel.
 tests/test_attention_reference_host.py shows on the CPU that this bound catches a lost key, an excluded diagonal, a rotated mask row, a
 missing rescale and a swapped (b, h) on the data of every case, and one flipped mask bit where a bit moves the most (at an ordinary row a
-single bit stays under the bound in six cases: flip_seen in attn_reference.CASES).  Measured figures: profiles/attention_arms_error.txt.
+single bit stays under the bound in eight cases: flip_seen in attn_reference.CASES).  Measured figures: profiles/attention_arms_error.txt.
 """
 import numpy as np
 import pytest

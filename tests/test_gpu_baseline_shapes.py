@@ -14,7 +14,7 @@
               T'=795 on the encoder axis): M = 12 720 rows -- per-slice grouped weight gradients, 256 x 256 blocks, the emb_cnn packet
               contractions at full height, the long-sequence attention kernels -- against the fp64 oracle, not only in op tests
 
-dk=64 + bf16 runs attention_fast.hip, the 128x64 / tn128 GEMM tiles and the V=4364 -> 4416 padded vocabulary GEMM
+dk=64 + bf16 runs attention_d64_*.hip, the 128x64 / tn128 GEMM tiles and the V=4364 -> 4416 padded vocabulary GEMM
 that the tiny goldens never reach.  Ragged lengths: source rows below T' and targets from 5 to 99 tokens.
 
 The truth is the oracle in FLOAT64 (same weights, same inputs, run on the GPU box's host cores).  Every fixture also holds,

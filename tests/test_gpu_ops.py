@@ -776,7 +776,7 @@ def test_attention_dropout_consistency(ops, dtype, d, T):
     (2, 2, 70, 256, False, "full", 0.25), (1, 8, 333, 131, False, None, 0.1), (2, 4, 64, 64, True, None, 0.0), (1, 2, 5, 3, False, None, 0.1)])
 def test_attention_backward_in_one_pass_equals_the_two_halves(ops, B, H, Tq, Tk, causal, mask, p):
     """Short key sequences (Tk <= 256, bf16, d = 64): the whole backward of a (batch, head) in one workgroup and one pass over the scores
-    (csrc/attention_fast.hip attn_bwd_fused_body; reference: autograd of models/common_layers.py:211-225) against the two-half launch it
+    (csrc/attention_d64_bwd_fused.hip attn_bwd_fused_body; reference: autograd of models/common_layers.py:211-225) against the two-half launch it
     replaces (tuning ATTN_BWD_FUSED = 0) on the same inputs, masks, dropout seed and delta: both form P, the dropout mask and dS from
     the same fp32 scores with the same instructions, so dK / dV (same contraction, same order) are EQUAL and dQ -- contracted over the
     keys from the bf16 dS^T through LDS instead of from fp32-accumulated per-wave fragments -- is within bf16 rounding of it."""

@@ -747,15 +747,48 @@ def test_kernel_coverage_parser_counts_launches_per_symbol():
     assert kc.coverage([ring, fold], names, counts) == {ring: 2, fold: 0}
 
 
-def test_kernel_coverage_attention_family_names_three_translation_units():
-    """tools/kernel_coverage.py --family attention (host only): the family is the three attention translation units; a trace row of a
-    kernel in a nested anonymous namespace (asr_attn::(anonymous namespace)::..., two int arguments after the struct) is counted under its
-    mangled and its demangled spelling; the kernels that only a one-part asr_attn_bwd call reaches are named in PARTS_ONLY."""
+def test_isa_identity_by_symbol_flags_a_kernel_two_files_define_unless_both_dumps_share_it(tmp_path):
+    """tools/isa_identity.py compare --by-symbol (host only, hand-written assembly): a kernel that moved to another file compares equal; one
+    that both dumps define in two files with identical copies (a kernel in a header) is one symbol; copies that differ from each other in
+    AFTER, a copy left behind in a second file of AFTER, and a changed instruction each count as differing."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("isa_identity", os.path.join(ROOT, "tools", "isa_identity.py"))
+    ii = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ii)
+
+    def asm(*kernels):
+        return "".join("%s:\n\t%s\n\ts_endpgm\n.Lfunc_end%d:\n\t.section .rodata\n\t.amdhsa_kernel %s\n\t\t.amdhsa_next_free_vgpr 8\n"
+                       "\t.end_amdhsa_kernel\n\t.text\n" % (k, ins, n, k) for n, (k, ins) in enumerate(kernels))
+
+    def dump(name, files):
+        d = os.path.join(str(tmp_path), name)
+        os.makedirs(d)
+        for f, ks in files.items():
+            with open(os.path.join(d, f + ".s"), "w") as fh:
+                fh.write(asm(*ks))
+        return d
+
+    a, b, h, h2 = ("_Z1av", "v_mov_b32 v0, 1"), ("_Z1bv", "v_mov_b32 v0, 2"), ("_Z1hv", "v_mov_b32 v0, 3"), ("_Z1hv", "v_mov_b32 v0, 4")
+    before = dump("before", {"one.hip": [a, b, h], "two.hip": [h]})
+    assert ii._union(before)[1:] == (set(), {"_Z1hv"})
+    assert ii.compare_by_symbol(before, dump("moved", {"x.hip": [h, a], "y.hip": [b, h]})) == 0
+    assert ii.compare_by_symbol(before, dump("diverged", {"x.hip": [a, h], "y.hip": [b, h2]})) == 1
+    assert ii.compare_by_symbol(before, dump("diverged_first", {"x.hip": [a, h2], "y.hip": [b, h]})) == 1
+    assert ii.compare_by_symbol(before, dump("left_behind", {"x.hip": [a, b, h], "y.hip": [b, h]})) == 1
+    assert ii.compare_by_symbol(before, dump("changed", {"x.hip": [a, ("_Z1bv", "v_mov_b32 v0, 5"), h], "y.hip": [h]})) == 1
+
+
+def test_kernel_coverage_attention_family_names_five_translation_units():
+    """tools/kernel_coverage.py --family attention (host only): the family is the five attention translation units that hold kernels; a
+    trace row of a kernel in a nested anonymous namespace (asr_attn::(anonymous namespace)::..., two int arguments after the struct) is
+    counted under its mangled and its demangled spelling; the kernels that only a one-part asr_attn_bwd call reaches are named in
+    PARTS_ONLY."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "tools", "kernel_coverage.py"))
     kc = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(kc)
-    assert kc.FAMILIES["attention"] == ("attention.hip", "attention_fast.hip", "attention_pp.hip") and kc.FAMILIES["gemm"] == kc.GEMM_FILES
+    assert kc.FAMILIES["attention"] == ("attention_generic.hip", "attention_d64_fwd.hip", "attention_d64_bwd.hip", "attention_d64_bwd_fused.hip",
+                                        "attention_pp.hip") and kc.FAMILIES["gemm"] == kc.GEMM_FILES
     for f in kc.FAMILIES["attention"]:
         assert os.path.exists(os.path.join(ROOT, "end2end-asr-pytorch_amd", "csrc", f)), f
     both = "_ZN8asr_attn12_GLOBAL__N_129attn_bwd_both_bf16_d64_kernelILi1EEEvNS_8AttnArgsEi"

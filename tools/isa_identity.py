@@ -9,7 +9,10 @@
   tools/isa_identity.py compare --by-symbol BEFORE_DIR AFTER_DIR
                                                       the same comparison over the union of the symbols of all files of each dump, for a
                                                       change that moves kernels between files (same normalisation, same exit status rule,
-                                                      and a kernel that one dump defines in two files counts as differing)
+                                                      a symbol whose copies in two files of AFTER differ from each other counts as
+                                                      differing, and so does a kernel that AFTER defines in two files unless BEFORE has
+                                                      it in two files too, with identical copies: a kernel shared through a header, as
+                                                      ctc_lse_kernel of ctc_common.h)
 
 Kernels are split at their `_Z...:` labels.  The function index in local labels (.LBB<n>_<m>, .Lfunc_end<n>, ...) shifts when a
 neighbour is deleted, so it is normalised before the comparison.  hipcc gives a kernel in an anonymous namespace the same name
@@ -116,20 +119,24 @@ def compare(before, after):
 
 
 def _union(d):
-    """({symbol: (text, amdhsa)} over all files of a dump, the symbols that two files define differently or as a kernel)."""
-    all_, twice = {}, set()
+    """({symbol: (text, amdhsa)} over all files of a dump, the symbols whose copies in two files differ, the kernels that two files define
+    with identical copies)."""
+    all_, diverging, shared = {}, set(), set()
     for f in sorted(os.listdir(d)):
         if not f.endswith(".s"):
             continue
         for s, v in kernels(os.path.join(d, f)).items():
-            if s in all_ and (v[1] is not None or all_[s] != v):
-                twice.add(s)
-            all_[s] = v
-    return all_, twice
+            if s in all_ and all_[s] != v:
+                diverging.add(s)
+            elif s in all_ and v[1] is not None:
+                shared.add(s)
+            all_.setdefault(s, v)
+    return all_, diverging, shared - diverging
 
 
 def compare_by_symbol(before, after):
-    (kb, _), (ka, twice) = _union(before), _union(after)
+    (kb, _, shared_before), (ka, diverging, shared) = _union(before), _union(after)
+    twice = diverging | (shared - shared_before)
     removed, added = sorted(set(kb) - set(ka)), sorted(set(ka) - set(kb))
     differ = [s for s in sorted(set(ka) & set(kb)) if ka[s] != kb[s] or s in twice]
     for s in removed:

@@ -14,7 +14,8 @@ GEMM dispatch, tests/test_gpu_attention_arms.py every arm of the attention dispa
                                                        symbol was never launched.
 
 The trace is matched by mangled name (rocprofv3 -M; a trailing .kd is dropped) or, for a demangled trace, by the c++filt form with white
-space removed.  With `--family attention` both commands cover csrc/attention.hip, attention_fast.hip and attention_pp.hip, and the trace is that
+space removed.  With `--family attention` both commands cover the five attention translation units that hold kernels (ATTENTION_FILES; csrc/attention.hip
+holds the entry points and the dispatch, no kernel), and the trace is that
 of tests/test_gpu_attention_arms.py (no tuning hook selects an attention kernel there: PARTS_ONLY lists the kernels that only a call with one
 of ASR_ATTN_DQ / ASR_ATTN_DKV reaches).  With `--family conv` they cover the nine translation units of the convolution front end (CONV_FILES)
 and the trace is that of tests/test_gpu_conv_arms.py; --auto is the trace of the same command with `-k "not hooked"` (the cases that set no
@@ -33,7 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_identity  # noqa: E402
 
 GEMM_FILES = ("gemm_nt.hip", "gemm_nn.hip", "gemm_tn.hip", "gemm_big.hip")
-ATTENTION_FILES = ("attention.hip", "attention_fast.hip", "attention_pp.hip")
+ATTENTION_FILES = ("attention_generic.hip", "attention_d64_fwd.hip", "attention_d64_bwd.hip", "attention_d64_bwd_fused.hip", "attention_pp.hip")
 CONV_FILES = ("conv1.hip", "conv1_wgrad_mfma.hip", "conv_igemm.hip", "conv_c64.hip", "conv_ws.hip", "conv_wgrad.hip", "conv_wgrad_dma.hip",
               "conv_level0.hip", "pool.hip")
 FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES, "conv": CONV_FILES}
@@ -76,8 +77,8 @@ HOOK_ONLY_OF = {"gemm": HOOK_ONLY, "attention": (), "conv": CONV_HOOK_ONLY}
 
 # attention kernels that ops.attn_bwd never chooses (it asks for dQ and dK / dV in one launch): reached by a direct asr_attn_bwd call with one part
 PARTS_ONLY = (
-    ("attn_bwd_dq_bf16_d64_kernel<1>", "attention_fast.hip attn_fast_bwd: dQ alone only when parts has ASR_ATTN_DQ without ASR_ATTN_DKV"),
-    ("attn_bwd_dkv_bf16_d64_kernel<1>", "attention_fast.hip attn_fast_bwd: dK / dV alone only when parts has ASR_ATTN_DKV without ASR_ATTN_DQ"),
+    ("attn_bwd_dq_bf16_d64_kernel<1>", "attention.hip attn_choose_bwd: dQ alone (attention_d64_bwd.hip) only when parts has ASR_ATTN_DQ without ASR_ATTN_DKV"),
+    ("attn_bwd_dkv_bf16_d64_kernel<1>", "attention.hip attn_choose_bwd: dK / dV alone (attention_d64_bwd.hip) only when parts has ASR_ATTN_DKV without ASR_ATTN_DQ"),
 )
 
 
