@@ -65,6 +65,19 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nt_kernel(BigGemmArgs p, int 
     for (int i = 0; i < LB; ++i) asr_lds_dma16(sl + TA + i * 8192, srcB[i] + kb);
   };
 
+  // the epilogue's bias values, requested before the first LDS-DMA piece: they do not depend on the accumulators, and loaded behind
+  // the K loop they were a round trip in front of the block's staging (vmcnt retires in order: the ring's counted waits only get
+  // more conservative, and its last step's vmcnt(0) drains these loads too)
+  float bv[FN][4];
+#pragma unroll
+  for (int j = 0; j < FN; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int col = n0 + wn * WN + j * 16 + g * 4 + r;
+      bv[j][r] = (p.bias != nullptr && col < p.N) ? p.bias[col] : 0.f;
+    }
+  asm volatile("" ::: "memory");
+
   f32x4_t acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -113,14 +126,6 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nt_kernel(BigGemmArgs p, int 
   // The MFMAs ran with the operands swapped (first = B rows, second = A rows), so lane (lr, g) holds C[m = lr][n = 4 g + r]: four
   // CONSECUTIVE columns of one row -- one 8-byte (bf16) or 16-byte (fp32) LDS write per fragment instead of four 2-byte ones.
   TO* C = static_cast<TO*>(p.C);
-  float bv[FN][4];
-#pragma unroll
-  for (int j = 0; j < FN; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int col = n0 + wn * WN + j * 16 + g * 4 + r;
-      bv[j][r] = (p.bias != nullptr && col < p.N) ? p.bias[col] : 0.f;
-    }
 #pragma unroll
   for (int pass = 0; pass < PASSES; ++pass) {
     if (PASSES == 1 || wm == pass) {
@@ -225,6 +230,43 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
     for (int i = 0; i < LB; ++i) asr_lds_dma16(sl + TA + i * 8192, srcB[i] + kt * stepB);
   };
 
+  // ---- the general epilogue's global operands, requested in the LAST K step, behind its barrier (`request()` in the loop below): none
+  // of them depends on the accumulators, and loaded inside the store loop they were 4 - 8 serialised round trips at the tail of every
+  // block (cold lines in the replayed step).  Now they are one round trip, under the last step's MFMAs and the staging of the block.
+  // Not earlier: vmcnt retires in order, so a request in front of the ring makes the FIRST counted wait wait for these cold lines (the
+  // latency only moves from the tail to the head: measured, profiles/nn_epilogue_operands_ab.txt), and one between two stages would
+  // need a third wait count.  Behind the last step's vmcnt(0) no LDS-DMA is in flight or follows, so nothing counts these loads but the
+  // compiler's own wait in front of their use.  Piece i of a thread = chunk c = tid + 512 i of the block (the epilogue's own mapping); a
+  // piece past M or N takes the clamped address big_src / srcB take (row M - 1, last whole chunk) and is never stored.  eop[0]: the ReLU
+  // mask piece, or O (bf16) / the first half of O32 of the row-dot; eop[1]: the `+=` base, or the second half of O32 -- the launcher
+  // makes mask / `+=` and the row-dot exclusive.
+  constexpr int CPR = BN / 8, EP = BM * CPR / 512;   // 16-byte pieces per row of C, pieces per thread
+  bf16_t* C = static_cast<bf16_t*>(p.C);
+  const bf16_t* Msk = static_cast<const bf16_t*>(p.mask);
+  uint4 eop[2][EP];
+  auto request = [&]() __attribute__((always_inline)) {
+    // one address computation and two wave-uniform tests on kernel arguments for every form: base 0 / base 1 = mask / C, O / none, O32 /
+    // O32 + 16 bytes; rows of ld elements of esz bytes
+    const bool dot = p.dot_out != nullptr, o32 = dot && p.dot_o32 != nullptr;
+    const unsigned char* b0 = static_cast<const unsigned char*>(dot ? (o32 ? (const void*)p.dot_o32 : p.dot_o) : (const void*)Msk);
+    const unsigned char* b1 = dot ? (o32 ? reinterpret_cast<const unsigned char*>(p.dot_o32) + 16 : nullptr)
+                                  : (p.accumulate ? static_cast<const unsigned char*>(p.C) : nullptr);
+    if (p.pool_code) b0 = b1 = nullptr;
+    const int64_t ld = dot ? (int64_t)p.N : p.ldc;
+    const int esz = o32 ? 4 : 2;
+#pragma unroll
+    for (int i = 0; i < EP; ++i) {
+      const int c = tid + 512 * i, row = c / CPR, pc = c % CPR;
+      int gr = m0 + row, gch = n0 / 8 + pc;
+      gr = gr < p.M ? gr : p.M - 1;
+      gch = gch < nchunks ? gch : nchunks - 1;
+      const int64_t eoff = ((int64_t)gr * ld + gch * 8) * esz;
+      if (b0) eop[0][i] = *reinterpret_cast<const uint4*>(b0 + eoff);
+      if (b1) eop[1][i] = *reinterpret_cast<const uint4*>(b1 + eoff);
+    }
+    asm volatile("" ::: "memory");                 // the loads stay where they are issued (tests/test_isa_epilogue_operands.py)
+  };
+
   f32x4_t acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -247,6 +289,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (kt + NS - 1 < nk) stage(kt + NS - 1);
+    if (kt == nk - 1) request();
     const unsigned char* s = smem + (kt % NS) * STAGE;
     const unsigned char* sB = s + TA;
 #pragma unroll
@@ -281,9 +324,6 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
           make_float4(acc[i][j][0] * p.alpha, acc[i][j][1] * p.alpha, acc[i][j][2] * p.alpha, acc[i][j][3] * p.alpha);
     }
   __syncthreads();
-  bf16_t* C = static_cast<bf16_t*>(p.C);
-  const bf16_t* Msk = static_cast<const bf16_t*>(p.mask);
-  constexpr int CPR = BN / 8;
   if (p.pool_code) {
     // The second max-pool's backward (asr_gemm_nn_poolbwd).  A piece = 8 channels of pooled pixel (h2, w2) of image b (row m = (b, w2),
     // column n = (h2, c)); it is routed by its 8 selection bytes to the 2 x 2 window, and all four positions are written.  The loop
@@ -330,8 +370,10 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
     }
     return;
   }
-  for (int c = tid; c < BM * CPR; c += 512) {
-    const int row = c / CPR, pc = c % CPR;
+  // (no global load below: the operands are the registers request() filled)
+#pragma unroll
+  for (int i = 0; i < EP; ++i) {
+    const int c = tid + 512 * i, row = c / CPR, pc = c % CPR;
     const int grow = m0 + row, gcol = n0 + pc * 8;
     if (grow < p.M && gcol < p.N) {
       const float4 v0 = *reinterpret_cast<const float4*>(smem + row * OP + pc * 32);
@@ -340,13 +382,13 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
       const int64_t off = (int64_t)grow * p.ldc + gcol;
       if (Msk) {
         Chunk<bf16_t> m;
-        m.v = *reinterpret_cast<const uint4*>(Msk + off);
+        m.v = eop[0][i];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = bf16_to_f32(m.e[e]) > 0.f ? v[e] : 0.f;
       }
       Chunk<bf16_t> o;
       if (p.accumulate) {
-        o.v = *reinterpret_cast<const uint4*>(C + off);
+        o.v = eop[1][i];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32(o.e[e]);
       }
@@ -356,15 +398,18 @@ __global__ __launch_bounds__(512, 2) void gemm_big_nn_kernel(BigGemmArgs p, int 
       if (p.dot_out) {
         // the attention backward's delta = rowsum(dO * O) per head from the block that IS dO (csrc/attention_d64_bwd.hip
         // attn_delta_bf16_d64_kernel, same lanes per row, same order of additions: the same bits): 8 lanes = the 64 columns of a head
-        const int64_t ooff = (int64_t)grow * p.N + gcol;
         float acc = 0.f;
         if (p.dot_o32) {
-          const f32x4_t o0 = *reinterpret_cast<const f32x4_t*>(p.dot_o32 + ooff), o1 = *reinterpret_cast<const f32x4_t*>(p.dot_o32 + ooff + 4);
+          const uint4 q0 = eop[0][i], q1 = eop[1][i];
+          const float o0[4] = {__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z), __uint_as_float(q0.w)};
+          const float o1[4] = {__uint_as_float(q1.x), __uint_as_float(q1.y), __uint_as_float(q1.z), __uint_as_float(q1.w)};
+          // which of the two products is rounded before the add is WRITTEN OUT: left to -ffp-contract the compiler picks it by the shape of
+          // the surrounding code, and delta changes in its last bit (exact-integer tests cannot see that; the dumped step can)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc += o0[e] * bf16_to_f32(o.e[e]) + o1[e] * bf16_to_f32(o.e[4 + e]);
+          for (int e = 0; e < 4; ++e) acc += __builtin_fmaf(o0[e], bf16_to_f32(o.e[e]), o1[e] * bf16_to_f32(o.e[4 + e]));
         } else {
           Chunk<bf16_t> f;
-          f.v = *reinterpret_cast<const uint4*>(static_cast<const bf16_t*>(p.dot_o) + ooff);
+          f.v = eop[0][i];
 #pragma unroll
           for (int e = 0; e < 8; ++e) acc += bf16_to_f32(f.e[e]) * bf16_to_f32(o.e[e]);
         }

@@ -31,6 +31,49 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
   const int nk = (p.K + BKR - 1) / BKR;          // a partial last stage: A's columns past K are zero (caller), B's rows are clamped
   const int b_chunks = (int)(p.ldb * ESZ / 16);
 
+  // ---- the storage-dtype epilogue's global operands (ReLU mask, `+=` base, O of the row-dot), requested all together BEFORE the
+  // store loop (`request()`): none depends on the accumulators, and loaded inside the store loop every trip was a round trip of its own
+  // at the tail of the block.  Piece i of a thread = chunk c = tid + 256 i of the tile (the epilogue's own mapping); a piece past M or N
+  // takes a clamped, valid address (row M - 1, last whole chunk) and is never stored.  eop[0]: mask, or O (bf16) / the first half of
+  // O32; eop[1]: the `+=` base, or the second half of O32 (the launchers make mask / `+=` and the row-dot exclusive).
+  // The ring form (one or two workgroups per CU by its launch condition) requests them in its LAST K step, behind that step's barrier:
+  // one round trip under the step's MFMAs and the staging of the tile.  Not earlier: vmcnt retires in order, so a request in front of
+  // the ring makes the first counted wait wait for these cold lines (measured: the latency moves from the tail to the head,
+  // profiles/nn_epilogue_operands_ab.txt); behind the last step's vmcnt(0) no LDS-DMA is in flight or follows.  The single-stage form
+  // lives on workgroups per CU (64 rows: 7 at 68 registers, 5 at the 82 that 16 registers held across a K step cost; fp32 has twice
+  // the pieces), so it requests them once the accumulators are staged, in front of the barrier that publishes the tile, in registers
+  // the K loop and the accumulators no longer need.
+  constexpr int EPCO = 16 / (int)sizeof(TO), CPRO = BN / EPCO, EP = BM * CPRO / 256;
+  const bool chunked = sizeof(TO) == sizeof(T) && p.vecC && p.N % EPCO == 0 && p.ldc % EPCO == 0;
+  const bool rowdot = sizeof(TO) == 2 && !p.accumulate && p.dot_out != nullptr;
+  const T* Msk = rowdot ? nullptr : static_cast<const T*>(p.mask);
+  uint4 eop[2][EP];
+  auto request = [&]() __attribute__((always_inline)) {
+    if constexpr (sizeof(TO) == sizeof(T)) {
+      // one address computation and two wave-uniform tests on kernel arguments for every form: base 0 / base 1 = mask / C, O / none,
+      // O32 / O32 + 16 bytes; rows of ld elements of esz bytes
+      const bool o32 = rowdot && p.dot_o32 != nullptr;
+      const unsigned char* b0 = static_cast<const unsigned char*>(rowdot ? (o32 ? (const void*)p.dot_o32 : p.dot_o) : (const void*)Msk);
+      const unsigned char* b1 = rowdot ? (o32 ? reinterpret_cast<const unsigned char*>(p.dot_o32) + 16 : nullptr)
+                                       : (p.accumulate ? static_cast<const unsigned char*>(p.C) : nullptr);
+      if (!chunked) b0 = b1 = nullptr;
+      const int64_t ld = rowdot ? (int64_t)p.N : p.ldc;
+      const int esz = o32 ? 4 : (int)sizeof(TO);
+      const int nch = p.N / EPCO;
+#pragma unroll
+      for (int i = 0; i < EP; ++i) {
+        const int c = tid + 256 * i, row = c / CPRO, pc = c % CPRO;
+        int gr = m0 + row, gch = n0 / EPCO + pc;
+        gr = gr < p.M ? gr : p.M - 1;
+        gch = gch < nch ? gch : nch - 1;
+        const int64_t eoff = ((int64_t)gr * ld + gch * EPCO) * esz;
+        if (b0) eop[0][i] = *reinterpret_cast<const uint4*>(b0 + eoff);
+        if (b1) eop[1][i] = *reinterpret_cast<const uint4*>(b1 + eoff);
+      }
+    }
+    asm volatile("" ::: "memory");                 // the loads stay where they are issued (tests/test_isa_epilogue_operands.py)
+  };
+
   f32x4_t acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -114,6 +157,7 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
       __builtin_amdgcn_s_barrier();                // step kt visible to every wave; every wave is done reading step kt - 1
       asm volatile("" ::: "memory");
       if (kt + NST - 1 < nk) stage_ring(kt + NST - 1);
+      if (kt == nk - 1) request();
       compute(smem + (kt % NST) * STAGE);
     }
   }
@@ -122,11 +166,8 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
   // ---- storage-dtype output in whole 16-byte chunks (every data-gradient GEMM of the model).  Plain store: the tile is staged
   // in the output dtype.  Accumulate (dX added into the residual gradient): staged in fp32 so that C + acc is rounded ONCE.
   if constexpr (sizeof(TO) == sizeof(T)) {
-    constexpr int EPCO = 16 / (int)sizeof(TO);
-    if (p.vecC && p.N % EPCO == 0 && p.ldc % EPCO == 0) {
+    if (chunked) {                                 // (no global load below: the operands are the registers request() filled)
       TO* C = static_cast<TO*>(p.C);
-      const T* Msk = static_cast<const T*>(p.mask);
-      constexpr int CPRO = BN / EPCO;
       if (!p.accumulate) {
         constexpr int OP = BN * (int)sizeof(TO) + 16;
 #pragma unroll
@@ -137,8 +178,11 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
             for (int r = 0; r < 4; ++r)
               *reinterpret_cast<TO*>(smem + (wm * WM + i * 16 + g * 4 + r) * OP + (wn * WN + j * 16 + lr) * sizeof(TO)) =
                   DT<TO>::to(acc[i][j][r] * p.alpha);
+        if constexpr (NST == 1) request();
         __syncthreads();
-        for (int c = tid; c < BM * CPRO; c += 256) {
+#pragma unroll
+        for (int i = 0; i < EP; ++i) {
+          const int c = tid + 256 * i;
           const int row = c / CPRO, col = (c % CPRO) * EPCO;
           const int gr = m0 + row, gc = n0 + col;
           if (gr >= p.M || gc >= p.N) continue;
@@ -146,25 +190,28 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
           o.v = *reinterpret_cast<const uint4*>(smem + row * OP + col * sizeof(TO));
           if (Msk) {
             Chunk<T> m;
-            m.v = *reinterpret_cast<const uint4*>(Msk + (int64_t)gr * p.ldc + gc);
+            m.v = eop[0][i];
 #pragma unroll
             for (int e = 0; e < EPCO; ++e)
               if (!(DT<T>::from(m.e[e]) > 0.f)) o.e[e] = DT<TO>::to(0.f);
           }
           *reinterpret_cast<uint4*>(C + (int64_t)gr * p.ldc + gc) = o.v;
           if constexpr (sizeof(TO) == 2) {
-            if (p.dot_out) {
+            if (rowdot) {
               // the attention backward's delta = rowsum(dO * O) per head from the block that IS dO (asr_gemm_nn_rowdot; the lanes, the
               // order of additions and therefore the bits of csrc/attention_d64_bwd.hip attn_delta_bf16_d64_kernel): 8 lanes = one head
-              const int64_t ooff = (int64_t)gr * p.N + gc;
               float acc = 0.f;
               if (p.dot_o32) {
-                const f32x4_t o0 = *reinterpret_cast<const f32x4_t*>(p.dot_o32 + ooff), o1 = *reinterpret_cast<const f32x4_t*>(p.dot_o32 + ooff + 4);
+                const uint4 q0 = eop[0][i], q1 = eop[1][i];
+                const float o0[4] = {__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z), __uint_as_float(q0.w)};
+                const float o1[4] = {__uint_as_float(q1.x), __uint_as_float(q1.y), __uint_as_float(q1.z), __uint_as_float(q1.w)};
+                // which of the two products is rounded before the add is WRITTEN OUT: left to -ffp-contract the compiler picks it by the shape of
+                // the surrounding code, and delta changes in its last bit (exact-integer tests cannot see that; the dumped step can)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc += o0[e] * bf16_to_f32(o.e[e]) + o1[e] * bf16_to_f32(o.e[4 + e]);
+                for (int e = 0; e < 4; ++e) acc += __builtin_fmaf(o0[e], bf16_to_f32(o.e[e]), o1[e] * bf16_to_f32(o.e[4 + e]));
               } else {
                 Chunk<bf16_t> f;
-                f.v = *reinterpret_cast<const uint4*>(static_cast<const bf16_t*>(p.dot_o) + ooff);
+                f.v = eop[0][i];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc += bf16_to_f32(f.e[e]) * bf16_to_f32(o.e[e]);
               }
@@ -183,16 +230,19 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
 #pragma unroll
             for (int r = 0; r < 4; ++r)
               *reinterpret_cast<float*>(smem + (wm * WM + i * 16 + g * 4 + r) * CPITCH + (wn * WN + j * 16 + lr) * 4) = acc[i][j][r] * p.alpha;
+        if constexpr (NST == 1) request();
         __syncthreads();
-        for (int c = tid; c < BM * CPRO; c += 256) {
+#pragma unroll
+        for (int i = 0; i < EP; ++i) {
+          const int c = tid + 256 * i;
           const int row = c / CPRO, col = (c % CPRO) * EPCO;
           const int gr = m0 + row, gc = n0 + col;
           if (gr >= p.M || gc >= p.N) continue;
           TO* dst = C + (int64_t)gr * p.ldc + gc;
           Chunk<TO> o, old;
-          old.v = *reinterpret_cast<const uint4*>(dst);
+          old.v = eop[1][i];
           Chunk<T> m;
-          if (Msk) m.v = *reinterpret_cast<const uint4*>(Msk + (int64_t)gr * p.ldc + gc);
+          if (Msk) m.v = eop[0][i];
 #pragma unroll
           for (int e = 0; e < EPCO; ++e) {
             float v = *reinterpret_cast<const float*>(smem + row * CPITCH + (col + e) * 4);
@@ -214,7 +264,6 @@ __device__ __forceinline__ void gemm_nn_body(const GemmArgs& p, const int bid, c
         *reinterpret_cast<float*>(smem + (wm * WM + i * 16 + g * 4 + r) * CPITCH + (wn * WN + j * 16 + lr) * 4) = acc[i][j][r] * p.alpha;
   __syncthreads();
   TO* C = static_cast<TO*>(p.C);
-  const T* Msk = static_cast<const T*>(p.mask);
   constexpr int CPR = BN / 4;
   for (int c = tid; c < BM * CPR; c += 256) {
     const int row = c / CPR, col = (c % CPR) * 4;

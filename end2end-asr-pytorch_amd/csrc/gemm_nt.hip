@@ -175,6 +175,20 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(GemmArgs p) {
   if (p.ablate & 16) nk = 0;
 #endif
 
+  // the chunked epilogue's bias values (one per fragment column of the lane), requested before the first operand piece: they do not
+  // depend on the accumulators, and loaded behind the K loop they were a round trip in front of the tile's staging
+  float bvj[FN];
+  if constexpr (sizeof(TO) == sizeof(T)) {
+    constexpr int EPCO = 16 / (int)sizeof(TO);
+    const bool add_bias = p.bias != nullptr && split == 0 && p.vecC && !p.atomic && !p.accumulate && p.N % EPCO == 0 && p.ldc % EPCO == 0;
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      const int col = n0 + wn * WN + j * 16 + lr;
+      bvj[j] = (add_bias && col < p.N) ? p.bias[col] : 0.f;
+    }
+  }
+  asm volatile("" ::: "memory");
+
   f32x4_t acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -278,11 +292,10 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(GemmArgs p) {
     constexpr int EPCO = 16 / (int)sizeof(TO);
     if (p.vecC && !p.atomic && !p.accumulate && p.N % EPCO == 0 && p.ldc % EPCO == 0) {     // (+= keeps the single rounding of the fp32 path)
       constexpr int OP = BN * (int)sizeof(TO) + 16;
-      const bool add_bias = p.bias != nullptr && split == 0;
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         const int col = wn * WN + j * 16 + lr;
-        const float bv = (add_bias && n0 + col < p.N) ? p.bias[n0 + col] : 0.f;
+        const float bv = bvj[j];
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
