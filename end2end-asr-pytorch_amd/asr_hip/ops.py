@@ -928,6 +928,22 @@ def logsoftmax_topk(logits, k):
     return vals, idx
 
 
+def seq_logprob(logits, tgt, seg_off):
+    """Sequence log-probabilities of a rescoring batch (csrc/seq_logprob.hip): logits (M,V) fp32 with unit column stride and any row
+    stride (a view of a wider buffer works; the columns behind V are never read), tgt (M) int64, seg_off (R+1) int32 on the device,
+    non-decreasing with seg_off[R] = M -> dict(tok (M,) fp32 = log_softmax(logits)[m, tgt[m]], score (R,) fp32 = the sum of tok over rows
+    seg_off[r] .. seg_off[r+1]-1 in row order; an empty segment 0).  A tgt outside [0,V) or a -inf target logit: -inf."""
+    M, V = logits.shape
+    R = seg_off.numel() - 1
+    assert logits.dtype == torch.float32 and (logits.stride(1) == 1 or V == 1 or M == 0)
+    assert tgt.dtype == torch.int64 and tgt.numel() == M and tgt.is_contiguous()
+    assert seg_off.dtype == torch.int32 and R >= 0 and seg_off.is_contiguous()
+    out = dict(tok=torch.empty((M,), device=logits.device, dtype=torch.float32),
+               score=torch.empty((R,), device=logits.device, dtype=torch.float32))
+    L.call("asr_seq_logprob", L.ptr(logits), logits.stride(0) if M else V, L.ptr(tgt), L.ptr(seg_off), R, M, V, L.ptr(out["tok"]), L.ptr(out["score"]), L.stream())
+    return out
+
+
 def ce_bwd(logits, gold, lse, smoothing, pad_id, grad_out, count, out_dtype=torch.float32, pad=8):
     """Returns dlogits as an (M,V) view of an (M, V rounded up to `pad`) buffer whose pad columns are zero; with a 64-column pad
     the WHOLE padded buffer is returned (the data-gradient GEMM contracts the padded width)."""

@@ -137,15 +137,22 @@ class Transformer(nn.Module):
         return (strs, hyp_ids) if return_ids else strs
 
     @torch.no_grad()
-    def ctc_beam_search(self, enc_out, lengths, beam_width, nbest=1, candidates=0, lm=None, lm_weight=0.1, c_weight=1, return_ids=False):
+    def ctc_beam_search(self, enc_out, lengths, beam_width, nbest=1, candidates=0, lm=None, lm_weight=0.1, c_weight=1, return_ids=False,
+                        rescoring_weight=0.0):
         """Prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): no decoder step.  lengths:
         true encoder frames per utterance (ctc_frame_lengths); beam_width W in 1..16 prefixes kept per frame, candidates C (0: min(V, 16))
         labels tried per frame.  One device-to-host copy.  The kernel's W hypotheses of an utterance, score = log-probability summed over
         the alignments, are ranked like a decoder beam's (Decoder._rank_ended): score + sqrt(words) * c_weight, or with lm
         (utils.lstm_utils.LM) score + lm_weight * (lm - 2 * oov) + sqrt(words) * c_weight, all utterances' hypotheses in ONE batched LM
         call.  -> per utterance the min(nbest, found) best strings, best first (return_ids: (strings, label ids), same nesting); the ids
-        are CTC labels as they stand: no SOS, no EOS."""
+        are CTC labels as they stand: no SOS, no EOS.
+        rescoring_weight = lambda in (0, 1]: attention rescoring.  ALL W hypotheses of every utterance get 'ctc_score' (the kernel's),
+        'att_score' (Decoder.score_hypotheses: one teacher-forced decoder pass, one more small device-to-host copy) and score =
+        (1 - lambda) * ctc_score + lambda * att_score before the ranking above; 0 makes no decoder launch."""
         W = int(beam_width)
+        lam = float(rescoring_weight)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError("rescoring_weight must lie in [0, 1], got %g" % lam)
         if not 1 <= W <= 16:
             raise ValueError("ctc_beam_search keeps beam_width prefixes per frame in the kernel's beam: 1..16, got %d" % W)
         if nbest < 1:
@@ -157,6 +164,12 @@ class Transformer(nn.Module):
         ids, lens, scores = torch.split(flat, [B * W * T, B * W, B * W])
         ids, lens, scores = ids.view(B, W, T).tolist(), lens.view(B, W).tolist(), scores.view(torch.float32).view(B, W).tolist()
         ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n]} for n in range(W) if lens[b][n] >= 0] for b in range(B)]
+        if lam > 0.0:
+            att = self.decoder.score_hypotheses(enc_out, [[h['yseq'] for h in hs] for hs in ended])
+            for hs, scores_b in zip(ended, att):
+                for h, a in zip(hs, scores_b):
+                    h['ctc_score'], h['att_score'] = h['score'], a
+                    h['score'] = (1.0 - lam) * h['ctc_score'] + lam * a
         ranked, _ = self.decoder._rank_ended(ended, nbest, c_weight, lm, lm_weight)
         hyp_ids, at = [], 0
         for hs in ended:                                 # _rank_ended returns min(len, nbest) hypotheses per utterance, flat
@@ -216,18 +229,26 @@ class Transformer(nn.Module):
 
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
-                 ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False):
+                 ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,
+                 attention_rescoring_weight=0.0):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
         ctc_greedy: best-path decoding from the head alone; ctc_beam: prefix beam search over the head's posteriors alone
         (ctc_beam_search: beam_width prefixes, ctc_candidates labels per frame, the beam_nbest best re-ranked with lm when lm_rescoring),
-        not together with beam_search, ctc_greedy or ctc_weight.  align_source "gold" / "hyp": a fourth value, the forced alignment
+        not together with beam_search, ctc_greedy or ctc_weight; attention_rescoring_weight = lambda in (0, 1] (ctc_beam only): all
+        beam_width hypotheses are rescored by the decoder in one teacher-forced pass and ranked by (1 - lambda) * CTC + lambda * attention
+        log-probability (ctc_beam_search's rescoring_weight).  align_source "gold" / "hyp": a fourth value, the forced alignment
         (ctc_align) of padded_target with target_lengths, or of the label ids the decoder produced (SOS and EOS dropped; never a
         re-tokenised string)."""
         if ctc_weight > 0 and not beam_search:
             raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % ctc_weight)
         if ctc_beam and (beam_search or ctc_greedy or ctc_weight > 0):
             raise ValueError("ctc_beam decodes from the CTC head alone: not together with beam_search, ctc_greedy or ctc_weight")
+        if not 0.0 <= attention_rescoring_weight <= 1.0:
+            raise ValueError("--attention-rescoring-weight must lie in [0, 1], got %g" % attention_rescoring_weight)
+        if attention_rescoring_weight > 0 and not ctc_beam:
+            raise ValueError("--attention-rescoring-weight %g needs --ctc-beam-search: the decoder rescores the CTC search's n-best"
+                             % attention_rescoring_weight)
         if ctc_beam and not hasattr(self, "ctc_linear"):
             self.ctc_logits(None)                      # the "no encoder CTC head" ValueError, before any device work
         if lm_rescoring and ctc_beam and lm is None:
@@ -254,7 +275,8 @@ class Transformer(nn.Module):
         elif ctc_beam:
             nbest_strs, nbest_ids = self.ctc_beam_search(enc_out, ctc_lengths, beam_width, nbest=max(1, int(beam_nbest)),
                                                          candidates=ctc_candidates, lm=lm if lm_rescoring else None,
-                                                         lm_weight=lm_weight, c_weight=c_weight, return_ids=True)
+                                                         lm_weight=lm_weight, c_weight=c_weight, return_ids=True,
+                                                         rescoring_weight=attention_rescoring_weight)
             strs_hyps, hyp_ids = [rows[0] if rows else "" for rows in nbest_strs], [rows[0] if rows else [] for rows in nbest_ids]
         elif beam_search:
             hyp_ids, strs_hyps = self.decoder.beam_search(enc_out, beam_width=beam_width, nbest=1, lm=lm, lm_rescoring=lm_rescoring,
@@ -431,6 +453,93 @@ class Decoder(nn.Module):
         for layer in self.layers:
             x, _, _ = layer(x, encoder_padded_outputs, causal_only=True)
         return F_.linear(x, self.output_linear.weight, None, True, False)
+
+    RESCORE_LOGIT_BYTES = 512 << 20          # fp32 logits of one score_hypotheses pass; a larger batch runs in chunks of whole utterances
+
+    @torch.no_grad()
+    def score_hypotheses(self, encoder_padded_outputs, hyps, return_tokens=False):
+        """Attention rescoring: log p(y_1..y_n, EOS | encoder output) under this decoder for every label sequence of
+        `hyps` (one list per utterance of label-id lists: CTC labels as they stand, no SOS, no EOS, possibly empty), in ONE teacher-forced
+        pass: input [SOS] + y, targets y + [EOS], n + 1 rows per hypothesis; the empty hypothesis scores log p(EOS | SOS).  Masks as in
+        _step_logits (causal only, no encoder-length mask): the quantity the attention beam search accumulates.  -> the same nesting of
+        floats (return_tokens: (scores, the n + 1 per-token terms)).
+
+        The W hypotheses of an utterance (fewer: padded with empty dummies) are a (B W, L, D) batch for self-attention and the SAME rows
+        viewed (B, W L, D) for cross-attention -- its queries do not interact, so the K | V projection of the encoder output runs on B
+        utterances, not B W copies.  Only the sum(n + 1) scored rows reach the vocabulary projection, and csrc/seq_logprob.hip turns their
+        logits into per-token and per-hypothesis log-probabilities.  Through the layer modules: low-rank and dim_key != dim_value models
+        work; the KV-cache kernels are not used."""
+        B = encoder_padded_outputs.size(0)
+        if len(hyps) != B:
+            raise ValueError("score_hypotheses needs one list of hypotheses per utterance: %d lists for %d utterances" % (len(hyps), B))
+        hyps = [[[int(t) for t in y] for y in hs] for hs in hyps]
+        limit = self.positional_encoding.pe.shape[1] - 1
+        longest = max([len(y) for hs in hyps for y in hs] + [0])
+        if longest > limit:
+            raise ValueError("score_hypotheses: a hypothesis has %d labels, the decoder's positional encoding reaches %d (trg_max_length "
+                             "%d minus the SOS position)" % (longest, limit, limit + 1))
+        row_bytes = 4 * self.num_trg_vocab
+        scores, tokens = [], []
+        b0 = 0
+        while b0 < B:                                  # whole utterances while their scored rows fit the cap (always at least one)
+            b1, rows = b0, 0
+            while b1 < B:
+                r = sum(len(y) + 1 for y in hyps[b1])
+                if b1 > b0 and (rows + r) * row_bytes > self.RESCORE_LOGIT_BYTES:
+                    break
+                rows, b1 = rows + r, b1 + 1
+            s, t = self._score_chunk(encoder_padded_outputs[b0:b1], hyps[b0:b1], return_tokens)
+            scores += s
+            tokens += t
+            b0 = b1
+        return (scores, tokens) if return_tokens else scores
+
+    def _score_chunk(self, enc, hyps, return_tokens):
+        """score_hypotheses for utterances whose logits fit one pass -> (scores, per-token terms or empty lists), nested per utterance."""
+        Bc = len(hyps)
+        flat = [y for hs in hyps for y in hs]
+        if not flat:
+            return [[] for _ in hyps], [[] for _ in hyps]
+        W = max(len(hs) for hs in hyps)
+        L = max(len(y) for y in flat) + 1
+        dev = enc.device
+        ys = [[constant.SOS_TOKEN] + [constant.PAD_TOKEN] * (L - 1) for _ in range(Bc * W)]       # (dummies: the empty sequence)
+        index, targets, seg_off = [], [], [0]
+        for b, hs in enumerate(hyps):
+            for w, y in enumerate(hs):
+                n, row = len(y), b * W + w
+                ys[row][1:n + 1] = y
+                index += range(row * L, row * L + n + 1)
+                targets += y + [constant.EOS_TOKEN]
+                seg_off.append(len(targets))
+        M = len(targets)
+        packed = torch.tensor([t for row in ys for t in row] + index + targets, dtype=torch.int64).to(dev, non_blocking=True)
+        ys_d, index_d, tgt_d = torch.split(packed, [Bc * W * L, M, M])
+        seg_d = torch.tensor(seg_off, dtype=torch.int32).to(dev, non_blocking=True)
+        p = self.dropout.p if self.training else 0.0
+        x = F_.EmbedFn.apply(ys_d.view(Bc * W, L), self.trg_embedding.weight, self.positional_encoding.pe[0], self.x_logit_scale, p,
+                             constant.PAD_TOKEN, True)
+        D = x.shape[-1]
+        kv_pre = F_.cross_kv_all(enc, self.layers) if len(self.layers) > 1 else None
+        for li, layer in enumerate(self.layers):           # DecoderLayer.forward's causal_only branch, on two views of the same rows
+            x = x.reshape(Bc * W, L, D)
+            x, _ = layer.self_attn(x, x, x, causal=True, need_attn=False)
+            q = x.reshape(Bc, W * L, D)
+            if kv_pre is not None:
+                x, _ = layer.encoder_attn(q, enc, enc, need_attn=False, kv_pre=(kv_pre[0][li], kv_pre[1], li))
+            else:
+                x, _ = layer.encoder_attn(q, enc, enc, need_attn=False)
+            x = layer.pos_ffn(x)
+        scored = x.reshape(Bc * W * L, D).index_select(0, index_d)
+        logits = F_.linear(scored, self.output_linear.weight, None, True, False)
+        out = ops.seq_logprob(logits, tgt_d.contiguous(), seg_d)
+        back = torch.cat([out["score"], out["tok"]] if return_tokens else [out["score"]]).cpu().tolist()
+        scores, tokens, at = [], [], 0
+        for hs in hyps:
+            scores.append(back[at:at + len(hs)])
+            tokens.append([back[len(flat) + seg_off[at + w]:len(flat) + seg_off[at + w + 1]] for w in range(len(hs))] if return_tokens else [])
+            at += len(hs)
+        return scores, tokens
 
     def _kv_cache_supported(self):
         """The incremental decoders (asr_hip/decode.py) read the full-rank projection weights of every layer; the Low-Rank

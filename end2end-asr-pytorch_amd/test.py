@@ -1,6 +1,6 @@
 """Evaluation entry point -- same command line as the reference (reference: test.py): loads --continue-from, decodes
-every test utterance (greedy, beam search with --beam-search, or from the encoder CTC head alone with --ctc-greedy / --ctc-beam-search)
-and reports CER / WER.  --align-out PATH also writes label and word
+every test utterance (greedy, beam search with --beam-search, or from the encoder CTC head alone with --ctc-greedy / --ctc-beam-search,
+the latter's n-best rescored by the decoder with --attention-rescoring-weight) and reports CER / WER.  --align-out PATH also writes label and word
 timestamps from the encoder CTC head (forced alignment of the transcript, or of the hypothesis with --align-source hyp)."""
 import torch
 from tqdm import tqdm
@@ -43,7 +43,9 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
                                                                  ctc_weight=getattr(args, "ctc_decode_weight", 0.0),
                                                                  ctc_candidates=getattr(args, "ctc_candidates", 0),
                                                                  ctc_greedy=getattr(args, "ctc_greedy", False),
-                                                                 ctc_beam=getattr(args, "ctc_beam_search", False), **align)
+                                                                 ctc_beam=getattr(args, "ctc_beam_search", False),
+                                                                 attention_rescoring_weight=getattr(args, "attention_rescoring_weight", 0.0),
+                                                                 **align)
             for i, (hyp, gold) in enumerate(zip(strs_hyps, strs_gold)):
                 for ch in (constant.EOS_CHAR, constant.SOS_CHAR, constant.PAD_CHAR):
                     hyp, gold = hyp.replace(ch, ""), gold.replace(ch, "")
@@ -67,11 +69,17 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
 def check_ctc_decoding(args, model):
     """--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need the encoder CTC head of a model trained with
     --ctc-weight > 0; the weight lies in [0, 1] and applies to --beam-search.  --ctc-beam-search decodes from the head alone: it excludes
-    --beam-search, --ctc-greedy and a --ctc-decode-weight, and its --beam-width lies in 1..16."""
+    --beam-search, --ctc-greedy and a --ctc-decode-weight, and its --beam-width lies in 1..16.  --attention-rescoring-weight lies in
+    [0, 1] and applies to --ctc-beam-search."""
     w = float(getattr(args, "ctc_decode_weight", 0.0) or 0.0)
     if not 0.0 <= w <= 1.0:
         raise ValueError("--ctc-decode-weight must lie in [0, 1], got %g" % w)
     ctc_beam = getattr(args, "ctc_beam_search", False)
+    lam = float(getattr(args, "attention_rescoring_weight", 0.0) or 0.0)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("--attention-rescoring-weight must lie in [0, 1], got %g" % lam)
+    if lam > 0 and not ctc_beam:
+        raise ValueError("--attention-rescoring-weight %g needs --ctc-beam-search: the decoder rescores the CTC search's n-best" % lam)
     if ((w > 0 or getattr(args, "ctc_greedy", False) or ctc_beam or getattr(args, "align_out", None))
             and not hasattr(model, "ctc_linear")):
         raise ValueError("--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need a model with an encoder CTC head: "

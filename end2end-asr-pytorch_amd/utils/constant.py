@@ -79,6 +79,9 @@ _FLAGS = [
     # --ctc-beam-search (test.py): prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): --beam-width (1..16)
     # prefixes kept per frame, --ctc-candidates (0: min(V, 16)) labels tried per frame, the n-best ranked like --beam-search's
     (("--ctc-beam-search",), dict(action="store_true")),
+    # --attention-rescoring-weight l (test.py --ctc-beam-search): the decoder scores all --beam-width hypotheses of the
+    # CTC search in one teacher-forced pass and they are ranked by (1 - l) CTC + l attention log-probability; 0 = off, no decoder pass
+    (("--attention-rescoring-weight",), dict(default=0.0, type=_F)),
     # CTC forced alignment (test.py): --align-out PATH writes one JSON line per test utterance with label and word
     # timestamps from the CTC head; --align-source gold aligns the transcript, hyp the label ids the decoder produced
     (("--align-out",), dict(default=None, type=_S)), (("--align-source",), dict(default="gold", choices=["gold", "hyp"])),

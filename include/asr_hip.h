@@ -384,6 +384,16 @@ int asr_edit_distance_batch(const int32_t* a, const int64_t* a_off, const int32_
 /* beam-search scoring (F.log_softmax + torch.topk per hypothesis, transformer.py:446-449): vals (M,k) = the k largest
  * log-probabilities of each row, best first, idx (M,k) their indices (lowest index first among equal values); k <= 16   */
 int asr_logsoftmax_topk(const float* logits, int64_t ld, int M, int V, int k, float* vals, int64_t* idx, asr_stream_t stream);
+/* attention rescoring of an n-best (csrc/seq_logprob.hip): replaces F.log_softmax + gather + a masked sum over a rescoring batch, without
+ * the (M,V) log-probability tensor.  logits: M rows of fp32 with row stride ld >= V (columns >= V are never read); tgt (M) int64;
+ * seg_off (R+1) int32 on the device, non-decreasing, seg_off[R] = M (clamped to [0,M] when read): segment r owns rows seg_off[r] ..
+ * seg_off[r+1]-1.  tok_lp[m] = logits[m,tgt[m]] - logsumexp(logits[m,:V]); -inf for a tgt outside [0,V) (nothing is read) and for a
+ * target logit of -inf.  score[r] = the sum of its rows' tok_lp, added in row order by one lane (no atomics: the bits are a function of
+ * the input alone); an empty segment scores exactly 0.  Every row needs one finite logit and none of +inf.  Each row is read once (16-byte
+ * loads where its base allows, the same bits where not).  M == 0 or R == 0: nothing is launched (score is zeroed for R > 0).
+ * V < 1, ld < V, R < 0 or M < 0: ASR_EINVAL.                                                                                            */
+int asr_seq_logprob(const float* logits, int64_t ld, const int64_t* tgt, const int32_t* seg_off, int R, int M, int V, float* tok_lp,
+                    float* score, asr_stream_t stream);
 /* dlogits[m,v] = coef * (softmax*sum_q - q), coef = *grad_out / *count (device scalars), 0 for PAD rows.
  * dlogits has leading dimension ldd >= V and dtype `out_dtype`; columns V..ldd-1 are zero-filled.              */
 int asr_ce_bwd(const float* logits, int64_t ld, const int64_t* gold, const float* row_lse, int M, int V,
