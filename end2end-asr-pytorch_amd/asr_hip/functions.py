@@ -4,6 +4,7 @@ by params.grad_of() (so the Functions return None for them) and reported to the 
 
 Sub-layer -> reference code
   MHAFn      models/common_layers.py:170-200 (+ :211-225) and the `*= non_pad_mask` that follows every call
+  RopeFn     (no reference code: rotary position embedding, --pos-encoding rope; MHAFn applies it through cfg["rope"])
   FFNFn      models/common_layers.py:135-142 (+ mask)
   ConvModuleFn  (no reference code: the Conformer convolution module of --conv-module-kernel)
   EncInFn    models/asr/transformer.py:172-173
@@ -350,6 +351,15 @@ class MHAFn(Function):
             Q = _linear_fwd(q2, Wq, bq).view(B, Tq, HD)
             K = _linear_fwd(kv2, Wk, bk).view(B, Tk, HD)
             V = _linear_fwd(kv2, Wv, bv).view(B, Tk, HD)
+        rope = cfg.get("rope")
+        if rope is not None:               # rotary position embedding (csrc/rope.hip): Q and K in place, V untouched; ctx keeps the rotated ones
+            if not self_attn or kv_pre is not None:
+                raise ValueError("cfg['rope'] is for self-attention only (kv_in is None, no kv_pre)")
+            if fused.ok:
+                ops.rope_(qkv[:, :, :2 * HD], rope, 2 * H, dk)
+            else:
+                ops.rope_(Q, rope, H, dk)
+                ops.rope_(K, rope, H, dk)
         p_att = cfg["p"]
         seed_a, seed_o = P.next_seed(), P.next_seed()
         scale = 1.0 / (dk ** 0.5)
@@ -415,6 +425,13 @@ class MHAFn(Function):
         ops.attn_bwd(Q, K, V, O, dO.view(B, Tq, HD), lse, H, dk, key_len=cfg.get("key_len"), key_pad=cfg.get("key_pad"),
                      causal=cfg.get("causal", False), scale=ctx.scale, p=cfg["p"], seed=seed_a, out=(dQ, dK, dV), o32=O32, delta=delta)
         d_kv = None
+        rope = cfg.get("rope")
+        if rope is not None:               # dQ and dK are gradients of the rotated Q and K: the transposed rotation takes them back
+            if fused.ok:
+                ops.rope_(dqkv[:, :, :2 * HD], rope, 2 * H, dk, inverse=True)
+            else:
+                ops.rope_(dQ, rope, H, dk, inverse=True)
+                ops.rope_(dK, rope, H, dk, inverse=True)
         # dq_in = d_res + dQ.Wq (+ dK.Wk + dV.Wv for self attention): accumulated straight into d_res
         if ctx.kv_pre:
             _linear_bwd(dQ.view(B * Tq, HD), q2, Wq, bq, dx_out=d_res, accumulate=True)
@@ -446,6 +463,22 @@ class MHAFn(Function):
             d_kv = d_kv.view(B, Tk, D)
         P.grad_ready(*ctx.params)
         return (d_res.view(B, Tq, D), d_kv) + (None,) * 12
+
+
+# ================================================================================================ rotary position embedding
+class RopeFn(Function):
+    """RopeFn.apply(x, cs, nheads, d) -> x (B, T, nheads d) rotated by the table cs (T, d/2, 2), out of place (ops.rope_ on a clone); the
+    gradient is the transposed rotation of the incoming one.  MHAFn rotates its own Q and K in place (cfg["rope"]); this is for callers
+    outside it."""
+
+    @staticmethod
+    def forward(ctx, x, cs, nheads, d):
+        ctx.cs, ctx.nheads, ctx.d = cs, nheads, d
+        return ops.rope_(x.clone(), cs, nheads, d)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.rope_(dy.clone(), ctx.cs, ctx.nheads, ctx.d, inverse=True), None, None, None
 
 
 # ================================================================================================ feed-forward sub-layer
@@ -546,7 +579,8 @@ class EncInFn(Function):
             x2 = x2.to(cd)
         x2 = x2.contiguous()
         y = _linear_fwd(x2, Win, bin_)
-        out, mean, rstd = ops.add_ln_fwd(y, None, gamma.data, beta.data, post_add=pe[:T].contiguous())
+        # (pe None: --pos-encoding rope, the encoder adds no absolute sinusoid)
+        out, mean, rstd = ops.add_ln_fwd(y, None, gamma.data, beta.data, post_add=None if pe is None else pe[:T].contiguous())
         ctx.t = (x2, y, mean, rstd)
         ctx.params = (Win, bin_, gamma, beta)
         ctx.shape = (B, T, Din)

@@ -78,6 +78,7 @@ _SIGS = {
     "asr_convmod_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "asr_convmod_bwd_data": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "asr_convmod_bwd_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P]),
+    "asr_rope": (_I, [_P, _L, _L, _I, _I, _I, _I, _P, _I, _I, _P]),
     "asr_ctc_prefix_init": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "asr_ctc_prefix_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "asr_decode_prepare": (_I, [_P, _I, _P, _P, _I, _P, _I, _P]),

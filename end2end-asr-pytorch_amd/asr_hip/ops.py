@@ -732,6 +732,28 @@ def convmod_bwd_weight(dv, s, u, lens, B, T, D, K, dwd, dbd):
            L.stream())
 
 
+# ------------------------------------------------------------------------------------------------ rotary position embedding
+def rope_table(n, d, base=10000.0, device=None):
+    """-> cs (n, d/2, 2) fp32 = [cos, sin] of the angle t * base^(-2i/d), t < n, i < d/2: computed in float64 on the host and cast once
+    (the one piece of arithmetic here: a table made once per model, not an op of the step)."""
+    assert d % 2 == 0 and n >= 0
+    t = torch.arange(n, dtype=torch.float64).unsqueeze(1)
+    inv = torch.pow(torch.tensor(float(base), dtype=torch.float64), -torch.arange(0, d, 2, dtype=torch.float64) / d)
+    ang = t * inv.unsqueeze(0)
+    cs = torch.stack((torch.cos(ang), torch.sin(ang)), dim=-1).to(torch.float32).contiguous()
+    return cs if device is None else cs.to(device)
+
+
+def rope_(x, cs, nheads, d, inverse=False):
+    """Rotates x (B, T, nheads d), a view with last-dimension stride 1 and any other strides, IN PLACE (csrc/rope.hip): pair
+    (x[2i], x[2i+1]) of every head of frame t by cs[t, i] = [cos, sin]; inverse=True applies the transpose (the backward).  -> x."""
+    assert x.dim() == 3 and x.stride(2) == 1 and x.shape[2] == nheads * d
+    assert cs.dtype == torch.float32 and cs.is_contiguous() and tuple(cs.shape) == (x.shape[1], d // 2, 2)
+    B, T, _ = x.shape
+    L.call("asr_rope", L.ptr(x), x.stride(0), x.stride(1), B, T, nheads, d, L.ptr(cs), 1 if inverse else 0, L.dt(x), L.stream())
+    return x
+
+
 def ctc_prefix_init(logits, frames, row_utt, blank=0):
     """logits (B,T,V) fp32 (rows contiguous, any row stride), frames (B) int32, row_utt (R) int32 on the device ->
     (lp (B,T,V) log-softmax, state (R,T,2) of the empty prefix): csrc/ctc_prefix.hip."""

@@ -16,7 +16,7 @@ import torch.nn as nn
 from asr_hip import functions as F_
 from asr_hip import ops
 from models.common_layers import (ConvolutionModule, LowRankMultiHeadAttention, LowRankPositionwiseFeedForward, MultiHeadAttention,
-                                  PositionalEncoding, PositionwiseFeedForwardWithConv, check_conv_module_kernel)
+                                  PositionalEncoding, PositionwiseFeedForwardWithConv, check_conv_module_kernel, check_pos_encoding)
 from utils import constant
 
 
@@ -305,12 +305,14 @@ class Transformer(nn.Module):
 class Encoder(nn.Module):
     """Encoder(num_layers, num_heads, dim_model, dim_key, dim_value, dim_input, dim_inner, dropout=0.1,
     src_max_length=2500)   (reference: transformer.py:126-180); conv_module_kernel K > 0 (--conv-module-kernel) gives every layer a
-    ConvolutionModule between its attention and feed-forward sub-layers."""
+    ConvolutionModule between its attention and feed-forward sub-layers; pos_encoding "rope" (--pos-encoding) rotates Q and K of every
+    layer's self-attention by the frame's position (asr_hip.ops.rope_) and leaves the absolute sinusoid out."""
 
     def __init__(self, num_layers, num_heads, dim_model, dim_key, dim_value, dim_input, dim_inner, dropout=0.1,
-                 src_max_length=2500, rank=0, conv_module_kernel=0):
+                 src_max_length=2500, rank=0, conv_module_kernel=0, pos_encoding="abs"):
         super().__init__()
         self.conv_module_kernel = check_conv_module_kernel(conv_module_kernel, dim_model, rank)
+        self.pos_encoding = check_pos_encoding(pos_encoding, dim_key, dim_value, rank)
         self.dim_input, self.num_layers, self.num_heads = dim_input, num_layers, num_heads
         self.dim_model, self.dim_key, self.dim_value, self.dim_inner = dim_model, dim_key, dim_value, dim_inner
         self.src_max_length = src_max_length
@@ -321,19 +323,27 @@ class Encoder(nn.Module):
         self.positional_encoding = PositionalEncoding(dim_model, src_max_length)
         self.layers = nn.ModuleList([EncoderLayer(num_heads, dim_model, dim_inner, dim_key, dim_value, dropout=dropout, rank=rank,
                                                   conv_module_kernel=self.conv_module_kernel) for _ in range(num_layers)])
+        if self.pos_encoding == "rope":
+            # not persistent: state_dict has the same keys in both modes (positional_encoding.pe stays in the checkpoint, unused)
+            self.register_buffer("rope_cs", ops.rope_table(src_max_length, dim_key), persistent=False)
 
     def forward(self, padded_input, input_lengths, need_attn=False):
         """padded_input (B,T,D_in), input_lengths (B) -> (output (B,T,D), [self_attn per layer])"""
         B, T, _ = padded_input.shape
         dev = padded_input.device
+        rope = None
+        if self.pos_encoding == "rope":          # one table row per frame, the same rows for every layer
+            if T > self.src_max_length:
+                raise ValueError("%d encoder frames, but the rotary table has --src-max-len %d rows" % (T, self.src_max_length))
+            rope = self.rope_cs[:T]
         lens = _lengths_to_device(input_lengths, dev)
         # row_keep[b,t] = t < len[b]   (reference: common_layers.py:33-38 via transformer.py:168)
         row_keep = ops.length_mask(lens, T)
         x = F_.EncInFn.apply(padded_input, self.input_linear.weight, self.input_linear.bias, self.layer_norm_input.weight,
-                             self.layer_norm_input.bias, self.positional_encoding.pe[0])
+                             self.layer_norm_input.bias, None if rope is not None else self.positional_encoding.pe[0])
         attns = []
         for layer in self.layers:
-            x, a = layer(x, row_keep=row_keep, key_len=lens, need_attn=need_attn)
+            x, a = layer(x, row_keep=row_keep, key_len=lens, need_attn=need_attn, rope=rope)
             attns.append(a)
         return x, attns
 
@@ -353,11 +363,12 @@ class EncoderLayer(nn.Module):
             self.conv_module = ConvolutionModule(dim_model, conv_module_kernel, dropout=dropout)
         self.pos_ffn = PositionwiseFeedForwardWithConv(dim_model, dim_inner, dropout=dropout)
 
-    def forward(self, enc_input, non_pad_mask=None, self_attn_mask=None, row_keep=None, key_len=None, need_attn=False):
+    def forward(self, enc_input, non_pad_mask=None, self_attn_mask=None, row_keep=None, key_len=None, need_attn=False, rope=None):
         if row_keep is None and non_pad_mask is not None:      # reference-style call with materialised masks
             row_keep = non_pad_mask.reshape(-1).ne(0).to(torch.uint8)
+        kw = {} if rope is None else {"rope": rope}          # (the Low-Rank attention takes no such argument: Encoder refuses rope with --rank)
         out, attn = self.self_attn(enc_input, enc_input, enc_input, mask=self_attn_mask, key_len=key_len, row_keep=row_keep,
-                                   need_attn=need_attn)
+                                   need_attn=need_attn, **kw)
         if hasattr(self, "conv_module"):
             out = self.conv_module(out, key_len=key_len, row_keep=row_keep)
         out = self.pos_ffn(out, row_keep=row_keep)

@@ -112,16 +112,23 @@ class MultiHeadAttention(nn.Module):
         self.query_linear.weight._asr_qkv = True      # hint for the flat-parameter layout: q/k/v weights adjacent
 
     def forward(self, query, key, value, mask=None, key_len=None, key_pad=None, causal=False, row_keep=None,
-                need_attn=True, kv_grad_box=None, kv_pre=None):
+                need_attn=True, kv_grad_box=None, kv_pre=None, rope=None):
         """kv_pre: (projections (B, Tk, 2 H dk) of `key` by this block's K | V weights, their shared gradient box, layer index) when the
-        decoder ran all its layers' cross-attention projections as one GEMM (asr_hip.functions.cross_kv_all); `key` is then only a shape."""
+        decoder ran all its layers' cross-attention projections as one GEMM (asr_hip.functions.cross_kv_all); `key` is then only a shape.
+        rope: the (Tq, dim_key / 2, 2) slice of an ops.rope_table that rotates Q and K (--pos-encoding rope); self-attention only."""
         if key is not value:
             raise NotImplementedError("key and value must be the same tensor (as everywhere in the reference model)")
         if self.dim_key != self.dim_value or self.dim_key not in _HEAD_WIDTHS:
+            if rope is not None:
+                raise ValueError("rope needs dim_key == dim_value in %s, got %d and %d" % (list(_HEAD_WIDTHS), self.dim_key, self.dim_value))
             return self._forward_padded(query, key, mask, key_len, key_pad, causal, row_keep, need_attn)
+        if rope is not None and (key is not query or kv_pre is not None):
+            raise ValueError("rope is for self-attention only (query, key and value the same tensor, no kv_pre)")
         cfg = dict(H=self.num_heads, dk=self.dim_key, p=self.dropout.p if self.training else 0.0, key_len=key_len,
                    key_pad=key_pad if key_pad is not None else _mask_to_u8(mask), causal=causal, row_keep=row_keep,
                    want_attn=need_attn, kv_grad_box=kv_grad_box)
+        if rope is not None:
+            cfg["rope"] = rope
         q = _to_compute(query)
         kv = None if key is query else _to_compute(key)
         pre = None
@@ -200,6 +207,28 @@ class PositionwiseFeedForwardWithConv(nn.Module):
         cfg = dict(p=self.dropout.p if self.training else 0.0, row_keep=row_keep)
         return F_.FFNFn.apply(_to_compute(x), self.conv_1.weight, self.conv_1.bias, self.conv_2.weight, self.conv_2.bias,
                               self.layer_norm.weight, self.layer_norm.bias, cfg)
+
+
+POS_ENCODINGS = ("abs", "rope")
+
+
+def check_pos_encoding(pos_encoding, dim_key=None, dim_value=None, rank=0):
+    """--pos-encoding: abs (the reference's sinusoid, added once after the input projection) or rope (rotary position embedding of Q and K
+    in every encoder self-attention, csrc/rope.hip).  rope rotates whole heads of the attention kernels' own widths, so it needs
+    --dim-key == --dim-value in {16, 32, 64} (not the padded compatibility path); the low-rank encoder (--rank) has no such hook."""
+    pe = "abs" if pos_encoding is None else str(pos_encoding)
+    if pe not in POS_ENCODINGS:
+        raise ValueError("--pos-encoding must be one of %s, got %r" % (", ".join(POS_ENCODINGS), pos_encoding))
+    if pe == "abs":
+        return pe
+    if rank and rank > 0:
+        raise ValueError("--pos-encoding rope with --rank %d is not supported: the Low-Rank Transformer's attention has no rotation of "
+                         "Q and K" % rank)
+    if dim_key is not None and dim_value is not None and dim_key != dim_value:
+        raise ValueError("--pos-encoding rope needs --dim-key == --dim-value, got --dim-key %d --dim-value %d" % (dim_key, dim_value))
+    if dim_key is not None and dim_key not in _HEAD_WIDTHS:
+        raise ValueError("--pos-encoding rope needs --dim-key in %s, got --dim-key %d" % (list(_HEAD_WIDTHS), dim_key))
+    return pe
 
 
 CONV_MODULE_KERNELS = range(3, 32, 2)          # odd 3 .. 31: what csrc/convmod.hip keeps in registers per lane

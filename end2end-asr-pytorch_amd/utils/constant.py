@@ -15,7 +15,9 @@ Differences that do not change old command lines:
     training batches on the GPU front end;
   * `--features {spect,fbank}` (+ `--num-mel-bins`, `--mel-fmin`): the reference's 161 linear log1p(|STFT|) bins (default) or log-mel
     filterbank features of the same STFT (DESIGN.md section 7), on the host path and on the GPU front end alike;
-  * `--conv-module-kernel K` (odd, 3..31; 0 = off): a Conformer-style convolution module in every encoder layer.
+  * `--conv-module-kernel K` (odd, 3..31; 0 = off): a Conformer-style convolution module in every encoder layer (DESIGN.md section 7);
+  * `--pos-encoding {abs,rope}`: the reference's absolute sinusoid (default) or rotary position embedding of Q and K in every encoder
+    self-attention; the decoder keeps its sinusoid.
 """
 import argparse
 import os
@@ -88,6 +90,9 @@ _FLAGS = [
     # Conformer-style convolution module: K odd in 3..31 gives every encoder layer a conv_module (GLU, depthwise
     # convolution over K frames, Swish between two pointwise layers) between self_attn and pos_ffn; 0 = none.  Not with --rank
     (("--conv-module-kernel",), dict(default=0, type=_I)),
+    # position signal of the encoder: abs = the reference's sinusoid added after the input projection; rope = rotary
+    # position embedding of Q and K in every encoder self-attention and no sinusoid.  Needs --dim-key == --dim-value in {16, 32, 64}; not with --rank
+    (("--pos-encoding",), dict(default="abs", choices=["abs", "rope"])),
     # loss / regularisation
     (("--loss",), dict(type=_S, default="ce")), (("--clip",), dict(action="store_true")),
     (("--max-norm",), dict(default=400, type=_F)), (("--dropout",), dict(default=0.1, type=_F)),

@@ -14,7 +14,7 @@ from asr_hip import ops
 from asr_hip import params as P
 from asr_hip.ddp import HipDataParallel
 from models.asr.transformer import Decoder, Encoder, Transformer
-from models.common_layers import check_conv_module_kernel
+from models.common_layers import check_conv_module_kernel, check_pos_encoding
 from utils import constant
 from utils.audio import feature_bins, feature_settings
 from utils.optimizer import AnnealingOpt, FusedAdam, NoamOpt
@@ -97,6 +97,14 @@ def load_model(load_path):
                              % (cur.conv_module_kernel, load_path, kept))
         args.conv_module_kernel = kept
         cur.conv_module_kernel = kept
+        # and so is the encoder's position signal (--pos-encoding): the weights were trained with one of them (a checkpoint written before
+        # the flag existed: abs)
+        kept = str(getattr(args, "pos_encoding", None) or "abs")
+        if "pos_encoding" in getattr(constant, "explicit", ()) and str(getattr(cur, "pos_encoding", None) or "abs") != kept:
+            raise ValueError("--pos-encoding %s on the command line, but %s was trained with --pos-encoding %s: a trained encoder "
+                             "cannot change its position signal" % (cur.pos_encoding, load_path, kept))
+        args.pos_encoding = kept
+        cur.pos_encoding = kept
     label2id, id2label = ckpt['label2id'], ckpt['id2label']
     model = init_transformer_model(args, label2id, id2label)
     sd = ckpt['model_state_dict']
@@ -176,12 +184,13 @@ def init_transformer_model(args, label2id, id2label):
                                  % (args.dim_input, n_fft_bins, n_fft_bins))
             args.dim_input = n_fft_bins
     conv_k = check_conv_module_kernel(getattr(args, "conv_module_kernel", 0), args.dim_model, getattr(args, "rank", 0))
+    pos_enc = check_pos_encoding(getattr(args, "pos_encoding", "abs"), args.dim_key, args.dim_value, getattr(args, "rank", 0))
     ops.set_compute_dtype(torch.float32 if getattr(args, "precision", "bf16") == "fp32" else torch.bfloat16)
     ops.set_fp8(getattr(args, "precision", "bf16") == "fp8")
     encoder = Encoder(args.num_layers, num_heads=args.num_heads, dim_model=args.dim_model, dim_key=args.dim_key,
                       dim_value=args.dim_value, dim_input=args.dim_input, dim_inner=args.dim_inner,
                       src_max_length=args.src_max_len, dropout=args.dropout, rank=getattr(args, "rank", 0),
-                      conv_module_kernel=conv_k)
+                      conv_module_kernel=conv_k, pos_encoding=pos_enc)
     decoder = Decoder(id2label, num_src_vocab=len(label2id), num_trg_vocab=len(label2id), num_layers=args.num_layers,
                       num_heads=args.num_heads, dim_emb=args.dim_emb, dim_model=args.dim_model, dim_inner=args.dim_inner,
                       dim_key=args.dim_key, dim_value=args.dim_value, trg_max_length=args.tgt_max_len, dropout=args.dropout,

@@ -311,6 +311,16 @@ int asr_convmod_bwd_data(const void* dv, const void* s, const void* u, const flo
 int asr_convmod_bwd_weight(const void* dv, const void* s, const void* u, const int32_t* len, int B, int T, int D, int K, int dtype,
                            float* workspace, int64_t workspace_floats, float* dwd, float* dbd, asr_stream_t stream);
 
+/* ---- rotary position embedding (csrc/rope.hip has the definition; RoPE, arXiv:2104.09864): x (B,T,nheads*d) in `dtype` with element
+ * strides (x_sb, x_st, 1) is rotated IN PLACE, pair (x[2i], x[2i+1]) of every head by the angle whose [cos, sin] is cs[t][i]; cs
+ * (T, d/2, 2) fp32, contiguous, row t for frame t of every batch entry and head (a table that starts at another position is a slice made
+ * by the caller).  inverse != 0 applies the transpose, which is the backward.  fp32 arithmetic, one rounding to `dtype`.
+ * d in {16, 32, 64}, fp32 and bf16, any nheads; B, T or nheads == 0: ASR_OK, nothing launched.  Another d or an odd stride:
+ * ASR_EUNSUPPORTED; a null pointer, x not aligned to a pair or cs not to 8 bytes: ASR_EINVAL.  16-byte accesses when x and cs are
+ * 16-byte aligned and both strides are multiples of 16 bytes, one pair per lane otherwise.  No allocation, no synchronisation.      */
+int asr_rope(void* x, int64_t x_sb, int64_t x_st, int B, int T, int nheads, int d, const float* cs, int inverse, int dtype,
+             asr_stream_t stream);
+
 /* ---- incremental (KV-cached) decoding with the position on the device: one captured hipGraph serves all 300 steps of
  * the reference's greedy loop (models/asr/transformer.py:316-394).  state[0] = position t of the token being fed.
  * asr_decode_prepare(advance=0): pe_cur[0..D) = pe[t], key_len[0..B) = t+1;  (advance=1): state[0] = t+1.
