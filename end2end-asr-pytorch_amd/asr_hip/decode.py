@@ -17,101 +17,105 @@ from . import ops
 from utils import constant
 
 
+def _ffn_linears(ff):
+    """The two feed-forward projections: 1x1 convolutions in the reference's module, plain linears in the low-rank one."""
+    return (ff.conv_1, ff.conv_2) if hasattr(ff, "conv_1") else (ff.linear_1, ff.linear_2)
+
+
 class DecoderKVCache:
-    def __init__(self, decoder, encoder_padded_outputs, max_len, batch=None):
-        """encoder_padded_outputs (Be,Te,D).  batch: number of decoder rows (hypotheses); with Be == 1 the cross-attention
-        keys/values are shared by every row (stride-0 batch axis)."""
+    def __init__(self, decoder, encoder_padded_outputs, max_len):
+        """encoder_padded_outputs (B,Te,D): one decoder row (sequence / hypothesis) per encoder row."""
         self.dec = decoder
-        cd = ops.compute_dtype()
-        enc = encoder_padded_outputs
-        if enc.dtype != cd:
-            enc = enc.to(cd)
-        enc = enc.contiguous()
-        Be, Te, D = enc.shape
-        self.B = Be if batch is None else batch
-        assert Be in (1, self.B)
+        self.B = encoder_padded_outputs.shape[0]
         self.H, self.dk = decoder.num_heads, decoder.dim_key
-        HD = self.H * self.dk
         self.max_len = max_len
         self.t = 0
-        dev = enc.device
-        self.cross, self.self_k, self.self_v = [], [], []
+        self.cross = self.project_cross(encoder_padded_outputs)
+        shape, dev = (self.B, max_len, self.H * self.dk), encoder_padded_outputs.device
+        self.self_k = [torch.empty(shape, device=dev, dtype=ops.compute_dtype()) for _ in decoder.layers]
+        self.self_v = [torch.empty(shape, device=dev, dtype=ops.compute_dtype()) for _ in decoder.layers]
+
+    def project_cross(self, encoder_padded_outputs, into=None):
+        """Every layer's cross-attention keys / values (B,Te,H*d) of the encoder output -> [(k, v)]; into: written in place over
+        such a list instead (a captured graph keeps its addresses)."""
+        enc = encoder_padded_outputs.to(ops.compute_dtype()).contiguous()
+        Be, Te, D = enc.shape
         enc2 = enc.view(Be * Te, D)
-        for layer in decoder.layers:
+        fresh = []
+        for i, layer in enumerate(self.dec.layers):
             a = layer.encoder_attn
-            k = F_._linear_fwd(enc2, a.key_linear.weight, a.key_linear.bias).view(Be, Te, HD)
-            v = F_._linear_fwd(enc2, a.value_linear.weight, a.value_linear.bias).view(Be, Te, HD)
-            if Be != self.B:
-                k, v = k.expand(self.B, Te, HD), v.expand(self.B, Te, HD)
-            self.cross.append((k, v))
-            self.self_k.append(torch.empty((self.B, max_len, HD), device=dev, dtype=cd))
-            self.self_v.append(torch.empty((self.B, max_len, HD), device=dev, dtype=cd))
+            kv = []
+            for j, lin in enumerate((a.key_linear, a.value_linear)):
+                y = F_._linear_fwd(enc2, lin.weight, lin.bias).view(Be, Te, -1)
+                kv.append(y if into is None else into[i][j].copy_(y))
+            fresh.append(tuple(kv))
+        return fresh
 
     # ------------------------------------------------------------------------------------------------ hypotheses
-    def select(self, rows, cross=True):
-        """Keep / duplicate / reorder decoder rows (beam search: row i of the new state continues old row rows[i]).
-        cross=False: the cross-attention keys / values stay where they are (the caller guarantees that rows[i] and i belong to
-        the same utterance, and len(rows) is the current batch)."""
+    def select(self, rows):
+        """Keep / duplicate / reorder decoder rows (beam search: row i of the new state continues old row rows[i]).  The
+        cross-attention keys / values stay where they are: the caller guarantees that rows[i] and i belong to the same utterance, and
+        len(rows) is the batch."""
+        assert len(rows) == self.B
         idx = torch.as_tensor(rows, device=self.self_k[0].device, dtype=torch.int64)
         t = self.t
         for i in range(len(self.self_k)):
-            nk = torch.empty((len(rows),) + tuple(self.self_k[i].shape[1:]), device=idx.device, dtype=self.self_k[i].dtype)
+            nk = torch.empty_like(self.self_k[i])
             nv = torch.empty_like(nk)
             nk[:, :t] = self.self_k[i][:, :t].index_select(0, idx)
             nv[:, :t] = self.self_v[i][:, :t].index_select(0, idx)
             self.self_k[i], self.self_v[i] = nk, nv
-            if not cross:
-                assert len(rows) == self.B
-                continue
-            k, v = self.cross[i]
-            if k.stride(0) == 0:
-                self.cross[i] = (k[:1].expand(len(rows), -1, -1), v[:1].expand(len(rows), -1, -1))
-            else:
-                self.cross[i] = (k.index_select(0, idx), v.index_select(0, idx))
-        self.B = len(rows)
 
     # ------------------------------------------------------------------------------------------------ one token
-    def _attend(self, attn_mod, x, q_in, k, v):
+    def _attend(self, attn_mod, x, q_in, k, v, key_len=None):
         """MultiHeadAttention on one query row per sequence: out = LN(W_o . attn(q, K, V) + b_o + x)."""
         B = x.shape[0]
         HD = self.H * self.dk
-        o, _, _ = ops.attn_fwd(q_in.view(B, 1, HD), k, v, self.H, self.dk, scale=1.0 / (self.dk ** 0.5))
+        o, _, _ = ops.attn_fwd(q_in.view(B, 1, HD), k, v, self.H, self.dk, key_len=key_len, scale=1.0 / (self.dk ** 0.5))
         y = F_._linear_fwd(o.view(B, HD), attn_mod.output_linear.weight, attn_mod.output_linear.bias)
         out, _, _ = ops.add_ln_fwd(y, x, attn_mod.layer_norm.weight.data, attn_mod.layer_norm.bias.data)
         return out
 
-    @torch.no_grad()
-    def step(self, tokens):
-        """tokens (B,) int64: the input token at position self.t -> logits (B,V) fp32 for position self.t."""
+    def walk(self, tokens, pe_row, put_kv, self_keys):
+        """The kernel-per-op decoder step: tokens (B,) int64 at one position, pe_row (1,D) that position's encoding -> logits (B,V)
+        fp32.  The two callers differ in where the position lives, and supply what follows from it: put_kv(i, x, self_attn) lands this
+        position's key / value rows of x in layer i's cache, self_keys(i) -> (keys, values, key_len) is what its self-attention sees."""
         dec = self.dec
-        t = self.t
-        if t >= self.max_len:
-            raise RuntimeError("decode position %d exceeds the cache length %d" % (t, self.max_len))
-        B = self.B
-        HD = self.H * self.dk
-        pe = dec.positional_encoding.pe[0]
-        x = ops.embed_fwd(tokens.view(B, 1).contiguous(), dec.trg_embedding.weight.data, pe[t:t + 1].contiguous(),
-                          dec.x_logit_scale, 0.0, 0, ops.compute_dtype()).view(B, -1)
+        x = ops.embed_fwd(tokens.view(self.B, 1).contiguous(), dec.trg_embedding.weight.data, pe_row, dec.x_logit_scale, 0.0, 0,
+                          ops.compute_dtype()).view(self.B, -1)
         for i, layer in enumerate(dec.layers):
             sa = layer.self_attn
             q = F_._linear_fwd(x, sa.query_linear.weight, sa.query_linear.bias)
-            # this position's key / value rows go straight into the cache (strided GEMM output)
-            kt, vt = self.self_k[i][:, t], self.self_v[i][:, t]
-            W, Wv = F_.P.linear_weight(sa.key_linear.weight), F_.P.linear_weight(sa.value_linear.weight)
-            xp = F_._pad_cols(x) if W.shape[1] != x.shape[1] else x
-            ops.gemm_nt(xp, W, bias=sa.key_linear.bias.data, out=kt)
-            ops.gemm_nt(xp, Wv, bias=sa.value_linear.bias.data, out=vt)
-            x = self._attend(sa, x, q, self.self_k[i][:, :t + 1], self.self_v[i][:, :t + 1])
+            put_kv(i, x, sa)
+            x = self._attend(sa, x, q, *self_keys(i))
             ca = layer.encoder_attn
             q = F_._linear_fwd(x, ca.query_linear.weight, ca.query_linear.bias)
             x = self._attend(ca, x, q, self.cross[i][0], self.cross[i][1])
             ff = layer.pos_ffn
-            w1, w2 = (ff.conv_1, ff.conv_2) if hasattr(ff, "conv_1") else (ff.linear_1, ff.linear_2)
+            w1, w2 = _ffn_linears(ff)
             h = F_._linear_fwd(x, w1.weight, w1.bias, relu=True)
             y = F_._linear_fwd(h, w2.weight, w2.bias)
             x, _, _ = ops.add_ln_fwd(y, x, ff.layer_norm.weight.data, ff.layer_norm.bias.data)
-        self.t = t + 1
         return F_._linear_fwd(x, dec.output_linear.weight, None, out_dtype=torch.float32)
+
+    @torch.no_grad()
+    def step(self, tokens):
+        """tokens (B,) int64: the input token at position self.t -> logits (B,V) fp32 for position self.t.  The position is a host
+        integer: the keys are the slice [:t + 1] of the cache."""
+        t = self.t
+        if t >= self.max_len:
+            raise RuntimeError("decode position %d exceeds the cache length %d" % (t, self.max_len))
+
+        def put_kv(i, x, sa):          # this position's key / value rows go straight into the cache (strided GEMM output)
+            W, Wv = F_.P.linear_weight(sa.key_linear.weight), F_.P.linear_weight(sa.value_linear.weight)
+            xp = F_._pad_cols(x) if W.shape[1] != x.shape[1] else x
+            ops.gemm_nt(xp, W, bias=sa.key_linear.bias.data, out=self.self_k[i][:, t])
+            ops.gemm_nt(xp, Wv, bias=sa.value_linear.bias.data, out=self.self_v[i][:, t])
+
+        logits = self.walk(tokens, self.dec.positional_encoding.pe[0][t:t + 1].contiguous(), put_kv,
+                           lambda i: (self.self_k[i][:, :t + 1], self.self_v[i][:, :t + 1]))
+        self.t = t + 1
+        return logits
 
 
 class GraphedGreedyDecoder:
@@ -123,11 +127,8 @@ class GraphedGreedyDecoder:
     token)."""
 
     def __init__(self, decoder, encoder_padded_outputs, max_len):
-        self.dec = decoder
-        self.cache = DecoderKVCache(decoder, encoder_padded_outputs, max_len)
-        c = self.cache
+        c = self.cache = DecoderKVCache(decoder, encoder_padded_outputs, max_len)
         dev = encoder_padded_outputs.device
-        self.B, self.max_len = c.B, max_len
         self.state = torch.zeros(2, dtype=torch.int64, device=dev)
         self.key_len = torch.zeros(c.B, dtype=torch.int32, device=dev)
         pe = decoder.positional_encoding.pe[0]
@@ -141,37 +142,16 @@ class GraphedGreedyDecoder:
             c.self_v[i].zero_()
         self.graph = None
 
-    def _attend(self, attn_mod, x, q_in, k, v, key_len):
-        c = self.cache
-        B = x.shape[0]
-        HD = c.H * c.dk
-        o, _, _ = ops.attn_fwd(q_in.view(B, 1, HD), k, v, c.H, c.dk, key_len=key_len, scale=1.0 / (c.dk ** 0.5))
-        y = F_._linear_fwd(o.view(B, HD), attn_mod.output_linear.weight, attn_mod.output_linear.bias)
-        out, _, _ = ops.add_ln_fwd(y, x, attn_mod.layer_norm.weight.data, attn_mod.layer_norm.bias.data)
-        return out
-
     def _step(self):
-        dec, c = self.dec, self.cache
-        B = self.B
+        c = self.cache
         ops.decode_prepare(self.pe, self.pe_cur, self.key_len, self.state)
-        x = ops.embed_fwd(self.tok.view(B, 1), dec.trg_embedding.weight.data, self.pe_cur, dec.x_logit_scale, 0.0, 0,
-                          ops.compute_dtype()).view(B, -1)
-        for i, layer in enumerate(dec.layers):
-            sa = layer.self_attn
-            q = F_._linear_fwd(x, sa.query_linear.weight, sa.query_linear.bias)
+
+        def put_kv(i, x, sa):
             kt = F_._linear_fwd(x, sa.key_linear.weight, sa.key_linear.bias)
             vt = F_._linear_fwd(x, sa.value_linear.weight, sa.value_linear.bias)
             ops.kv_append(kt, vt, c.self_k[i], c.self_v[i], self.state)
-            x = self._attend(sa, x, q, c.self_k[i], c.self_v[i], self.key_len)
-            ca = layer.encoder_attn
-            q = F_._linear_fwd(x, ca.query_linear.weight, ca.query_linear.bias)
-            x = self._attend(ca, x, q, c.cross[i][0], c.cross[i][1], None)
-            ff = layer.pos_ffn
-            w1, w2 = (ff.conv_1, ff.conv_2) if hasattr(ff, "conv_1") else (ff.linear_1, ff.linear_2)
-            h = F_._linear_fwd(x, w1.weight, w1.bias, relu=True)
-            y = F_._linear_fwd(h, w2.weight, w2.bias)
-            x, _, _ = ops.add_ln_fwd(y, x, ff.layer_norm.weight.data, ff.layer_norm.bias.data)
-        logits = F_._linear_fwd(x, dec.output_linear.weight, None, out_dtype=torch.float32)
+
+        logits = c.walk(self.tok, self.pe_cur, put_kv, lambda i: (c.self_k[i], c.self_v[i], self.key_len))
         ops.argmax_rows(logits, out=self.tok)
         self.done |= self.tok.eq(constant.EOS_TOKEN)
         ops.decode_advance(self.state)
@@ -226,7 +206,7 @@ def _dec_pack(decoder):
     layers = []
     for layer in decoder.layers:
         sa, ca, ff = layer.self_attn, layer.encoder_attn, layer.pos_ffn
-        w1, w2_ = (ff.conv_1, ff.conv_2) if hasattr(ff, "conv_1") else (ff.linear_1, ff.linear_2)
+        w1, w2_ = _ffn_linears(ff)
         layers.append(dict(
             wqkv=fr(torch.cat([w2(sa.query_linear), w2(sa.key_linear), w2(sa.value_linear)], 0)),
             wq_c_rm=w2(ca.query_linear),
@@ -254,8 +234,7 @@ def fused_decode_supported(decoder, encoder_padded_outputs, max_len):
         return False
     D = decoder.dim_model
     B, Te, _ = encoder_padded_outputs.shape
-    ff = decoder.layers[0].pos_ffn
-    w1 = ff.conv_1 if hasattr(ff, "conv_1") else ff.linear_1
+    w1, _ = _ffn_linears(decoder.layers[0].pos_ffn)
     return (B >= 1 and D % 64 == 0 and D <= 512 and decoder.dim_key == 64 and getattr(decoder, "dim_value", 64) == 64 and
             w1.weight.shape[0] % 64 == 0 and (decoder.num_heads * decoder.dim_key) % 64 == 0)
 
@@ -343,15 +322,8 @@ class FusedGreedyDecoder:
         """Start a new batch of the same shape: position 0, SOS tokens, fresh cross-attention keys / values (in place: the
         captured graph keeps its addresses)."""
         c = self.cache
-        cd = ops.compute_dtype()
-        enc = encoder_padded_outputs.to(cd).contiguous()
-        Be, Te, D = enc.shape
-        assert (Be, Te) == tuple(c.cross[0][0].shape[:2])
-        enc2 = enc.view(Be * Te, D)
-        for i, layer in enumerate(self.dec.layers):
-            a = layer.encoder_attn
-            c.cross[i][0].copy_(F_._linear_fwd(enc2, a.key_linear.weight, a.key_linear.bias).view(Be, Te, -1))
-            c.cross[i][1].copy_(F_._linear_fwd(enc2, a.value_linear.weight, a.value_linear.bias).view(Be, Te, -1))
+        assert tuple(encoder_padded_outputs.shape[:2]) == tuple(c.cross[0][0].shape[:2])
+        c.project_cross(encoder_padded_outputs, into=c.cross)
         self.state.zero_()
         self.ticket.zero_()
         self.tok.fill_(constant.SOS_TOKEN)
@@ -446,7 +418,7 @@ def greedy_search(decoder, encoder_padded_outputs, steps=300, check_every=16):
 
 class CTCPrefixScorer:
     """CTC prefix scores for joint CTC / attention beam search (csrc/ctc_prefix.hip): the scorer object of
-    Decoder._beam_search_hyps.  Holds lp = log-softmax of the encoder's CTC logits (B,T',V) and one (r_n, r_b) state (T',2) per
+    the beam search (asr_hip.search.CachedBeamStep).  Holds lp = log-softmax of the encoder's CTC logits (B,T',V) and one (r_n, r_b) state (T',2) per
     hypothesis row; row r belongs to utterance row_utt[r], whose true encoder frames are frames[row_utt[r]].  Everything stays on the
     device: step() is one launch, select() one index_select."""
 

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from asr_hip import functions as F_
-from asr_hip import ops
+from asr_hip import ops, search
 from models.common_layers import (ConvolutionModule, LowRankMultiHeadAttention, LowRankPositionwiseFeedForward, MultiHeadAttention,
                                   PositionalEncoding, PositionwiseFeedForwardWithConv, check_conv_module_kernel, check_pos_encoding)
 from utils import constant
@@ -142,7 +142,7 @@ class Transformer(nn.Module):
         """Prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): no decoder step.  lengths:
         true encoder frames per utterance (ctc_frame_lengths); beam_width W in 1..16 prefixes kept per frame, candidates C (0: min(V, 16))
         labels tried per frame.  One device-to-host copy.  The kernel's W hypotheses of an utterance, score = log-probability summed over
-        the alignments, are ranked like a decoder beam's (Decoder._rank_ended): score + sqrt(words) * c_weight, or with lm
+        the alignments, are ranked like a decoder beam's (asr_hip.search.rank_ended): score + sqrt(words) * c_weight, or with lm
         (utils.lstm_utils.LM) score + lm_weight * (lm - 2 * oov) + sqrt(words) * c_weight, all utterances' hypotheses in ONE batched LM
         call.  -> per utterance the min(nbest, found) best strings, best first (return_ids: (strings, label ids), same nesting); the ids
         are CTC labels as they stand: no SOS, no EOS.
@@ -170,12 +170,7 @@ class Transformer(nn.Module):
                 for h, a in zip(hs, scores_b):
                     h['ctc_score'], h['att_score'] = h['score'], a
                     h['score'] = (1.0 - lam) * h['ctc_score'] + lam * a
-        ranked, _ = self.decoder._rank_ended(ended, nbest, c_weight, lm, lm_weight)
-        hyp_ids, at = [], 0
-        for hs in ended:                                 # _rank_ended returns min(len, nbest) hypotheses per utterance, flat
-            n = min(len(hs), nbest)
-            hyp_ids.append(ranked[at:at + n])
-            at += n
+        hyp_ids = [[h['yseq'] for h in hs] for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight)]
         strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
         return (strs, hyp_ids) if return_ids else strs
 
@@ -577,41 +572,25 @@ class Decoder(nn.Module):
             use_cache = False
         if use_cache == "eager":                      # cached, launches issued from Python per token
             from asr_hip.decode import greedy_search as cached_greedy
-            toks = cached_greedy(self, encoder_padded_outputs, steps=300).cpu().tolist()
+            toks = cached_greedy(self, encoder_padded_outputs, steps=300)
         elif use_cache:                               # cached + one hipGraph replay per token (device-side position)
             from asr_hip.decode import greedy_search_graphed
             fused = False if use_cache == "graph" else None      # "graph": the kernel-per-op step; True: 30-launch step in bf16
-            toks = greedy_search_graphed(self, encoder_padded_outputs, steps=300, fused=fused).cpu().tolist()
+            toks = greedy_search_graphed(self, encoder_padded_outputs, steps=300, fused=fused)
         else:
-            B = encoder_padded_outputs.size(0)
-            ys = torch.full((B, 1), constant.SOS_TOKEN, dtype=torch.int64, device=encoder_padded_outputs.device)
-            steps = []
-            for _ in range(300):
-                logits = self._step_logits(ys, encoder_padded_outputs)
-                nxt = ops.argmax_rows(logits[:, -1].contiguous())
-                steps.append(nxt)
-                ys = torch.cat([ys, nxt.unsqueeze(1)], dim=1)
-            toks = torch.stack(steps, dim=1).cpu().tolist()       # one D2H copy instead of per-token .item()
-        sents, ids = [], []
-        for row in toks:
-            st, kept = '', []
-            for t in row:
-                if t == constant.EOS_TOKEN:
-                    break
-                st += self.id2label[t]
-                kept.append(t)
-            sents.append(st)
-            ids.append(kept)
+            toks = search.greedy_rerun(self, encoder_padded_outputs)
+        sents, ids = search.strings_up_to_eos(toks.cpu().tolist(), self.id2label)       # one D2H copy instead of per-token .item()
         return (sents, ids) if return_ids else sents
 
     @torch.no_grad()
     def beam_search(self, encoder_padded_outputs, beam_width=2, nbest=5, lm_rescoring=False, lm=None, lm_weight=0.1,
                     c_weight=1, prob_weight=1.0, use_cache=True, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0, ctc_candidates=0):
         """Per-utterance beam search with the reference's scoring (transformer.py:396-517).  With
-        use_cache the live hypotheses of an utterance are one batch of the KV-cached decoder (one step = one token per
-        hypothesis); the candidate bookkeeping on the host is the reference's, including its in-loop re-sort (:460).
-        With more than one utterance the cached search runs for all of them at once (_beam_search_batched);
-        use_cache="per_utterance" keeps the utterance loop.  lm_rescoring=True with lm (utils/lstm_utils.LM) re-ranks the finished
+        use_cache the live hypotheses are one batch of the KV-cached decoder (one step = one token per
+        hypothesis); the candidate bookkeeping on the host is the reference's, including its in-loop re-sort (:460)
+        (asr_hip.search.beam_search).  The cached search runs for all utterances at once, one or many;
+        use_cache="per_utterance" runs it on one utterance at a time; False re-runs the full decoder over every prefix like the
+        reference.  lm_rescoring=True with lm (utils/lstm_utils.LM) re-ranks the finished
         hypotheses with the LM score (_rank_ended); the search itself prunes on the acoustic score alone, as in the reference.
         ctc_weight = mu > 0 with ctc_logits (B,T',V) fp32 (the encoder CTC head's) and ctc_lengths (true encoder frames): joint CTC /
         attention scoring -- every step ranks the ctc_candidates (0: min(V, 16, 2 * beam_width)) best attention candidates of a
@@ -620,9 +599,9 @@ class Decoder(nn.Module):
         if lm_rescoring and lm is None:
             raise ValueError("lm_rescoring=True needs lm (utils.lstm_utils.LM)")
         lm = lm if lm_rescoring else None
-        from asr_hip.decode import DecoderKVCache
         if not self._kv_cache_supported():
             use_cache = False
+        ctc = None
         if ctc_weight > 0:
             if not 0.0 < ctc_weight <= 1.0:
                 raise ValueError("ctc_weight must lie in [0, 1], got %g" % ctc_weight)
@@ -638,173 +617,41 @@ class Decoder(nn.Module):
                 raise ValueError("ctc_candidates %d must lie in [beam_width %d, min(V, 16) = %d]" % (K, beam_width, min(V, 16)))
             if ctc_lengths is None:
                 ctc_lengths = [Te] * B
-            scorer = CTCPrefixScorer(ctc_logits, ctc_lengths, [b for b in range(B) for _ in range(beam_width)])
-            ended = self._beam_search_hyps(encoder_padded_outputs, beam_width, ctc=(scorer, float(ctc_weight), K))
-            return self._rank_ended(ended, nbest, c_weight, lm, lm_weight)
-        if use_cache and use_cache != "per_utterance" and encoder_padded_outputs.size(0) > 1:
-            return self._beam_search_batched(encoder_padded_outputs, beam_width, nbest, c_weight, lm, lm_weight)
-        all_ended = []
-        max_len = encoder_padded_outputs.size(1)
-        dev = encoder_padded_outputs.device
-        for b in range(encoder_padded_outputs.size(0)):
-            enc = encoder_padded_outputs[b:b + 1]
-            hyps = [{'score': 0.0, 'yseq': [constant.SOS_TOKEN]}]
-            ended = []
-            cache = DecoderKVCache(self, enc, max_len=300, batch=1) if use_cache else None
-            for i in range(300):
-                if use_cache:
-                    last = torch.tensor([h['yseq'][-1] for h in hyps], dtype=torch.int64, device=dev)
-                    best_all, idx_all = ops.logsoftmax_topk(cache.step(last).float().contiguous(), beam_width)
-                    best_all, idx_all = best_all.tolist(), idx_all.tolist()
-                cand = []
-                for hi, hyp in enumerate(hyps):
-                    if use_cache:
-                        best, idx = best_all[hi], idx_all[hi]
-                    else:
-                        ys = torch.tensor([hyp['yseq']], dtype=torch.int64, device=dev)
-                        logits = self._step_logits(ys, enc)[:, -1]
-                        best, idx = ops.logsoftmax_topk(logits.float().contiguous(), beam_width)
-                        best, idx = best[0].tolist(), idx[0].tolist()
-                    for j in range(beam_width):
-                        cand.append({'score': hyp['score'] + best[j], 'yseq': hyp['yseq'] + [idx[j]], 'parent': hi})
-                    # the reference re-sorts the running candidate list inside the hypothesis loop (:460)
-                    cand = sorted(cand, key=lambda h: h['score'], reverse=True)[:beam_width]
-                hyps = cand
-                if i == max_len - 1:
-                    for hyp in hyps:
-                        hyp['yseq'] = hyp['yseq'] + [constant.EOS_TOKEN]
-                alive = []
-                for hyp in hyps:
-                    if hyp['yseq'][-1] == constant.EOS_TOKEN:
-                        ended.append(hyp)
-                    else:
-                        alive.append(hyp)
-                hyps = alive
-                if not hyps:
-                    break
-                if use_cache:
-                    cache.select([h['parent'] for h in hyps])
-            all_ended.append(ended)
-        return self._rank_ended(all_ended, nbest, c_weight, lm, lm_weight)
+            ctc = (CTCPrefixScorer(ctc_logits, ctc_lengths, [b for b in range(B) for _ in range(beam_width)]), float(ctc_weight), K)
+        if use_cache == "per_utterance":
+            ended = [self._beam_search_hyps(encoder_padded_outputs[b:b + 1], beam_width)[0] for b in range(encoder_padded_outputs.size(0))]
+        else:
+            ended = self._beam_search_hyps(encoder_padded_outputs, beam_width, ctc=ctc, use_cache=use_cache)
+        return self._rank_ended(ended, nbest, c_weight, lm, lm_weight)
 
     def _rank_ended(self, ended, nbest, c_weight, lm=None, lm_weight=0.1):
         """The nbest finished hypotheses of every utterance (ended: one list per utterance) by final_score, best first
-        (reference: transformer.py:475-497, 499-514).  Without an LM final_score = score + sqrt(words) * c_weight.  With one,
-        final_score = score + lm_weight * (lm_score - 2 * oov) + sqrt(num_words) * c_weight, num_words = LM words + 1: the LM
-        score only re-ranks finished hypotheses, so those of ALL utterances are scored by ONE batched LM call here."""
-        if lm is not None:
-            from utils.lstm_utils import calculate_lm_scores
-            flat = [h for hs in ended for h in hs]
-            for hyp, (lm_score, num_words, oov) in zip(flat, calculate_lm_scores([h['yseq'] for h in flat], lm, self.id2label)):
-                hyp['lm_score'], hyp['num_words'] = lm_score - oov * 2, num_words
-                hyp['final_score'] = hyp['score'] + lm_weight * hyp['lm_score'] + math.sqrt(num_words) * c_weight
-        else:
-            for hs in ended:
-                for hyp in hs:
-                    self._finish_hyp(hyp, c_weight)
-        ids_out, strs_out = [], []
-        for hs in ended:
-            for hyp in sorted(hs, key=lambda h: h['final_score'], reverse=True)[:min(len(hs), nbest)]:
-                ids_out.append(hyp['yseq'])
-                strs_out.append(self.post_process_hyp(hyp))
-        return ids_out, strs_out
+        (asr_hip.search.rank_ended: score + sqrt(words) * c_weight, with an LM score + lm_weight * (lm_score - 2 * oov) +
+        sqrt(num_words) * c_weight from ONE batched LM call) -> (label ids, strings), flat over the utterances."""
+        ranked = [hyp for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight) for hyp in hs]
+        return [hyp['yseq'] for hyp in ranked], [self.post_process_hyp(hyp) for hyp in ranked]
 
     def _finish_hyp(self, hyp, c_weight):
-        s = "".join(self.id2label[t] for t in hyp['yseq'])
-        for ch in (constant.PAD_CHAR, constant.SOS_CHAR, constant.EOS_CHAR):
-            s = s.replace(ch, "")
-        s = s.replace("  ", " ")
-        hyp['final_score'] = hyp['score'] + math.sqrt(len(s.split())) * c_weight
-        return hyp
+        return search.finish_hyp(hyp, c_weight, self.id2label)
 
-    def _beam_search_batched(self, encoder_padded_outputs, beam_width, nbest, c_weight, lm=None, lm_weight=0.1):
-        return self._rank_ended(self._beam_search_hyps(encoder_padded_outputs, beam_width), nbest, c_weight, lm, lm_weight)
+    def _beam_search_hyps(self, encoder_padded_outputs, beam_width, ctc=None, use_cache=True):
+        """The search for ALL utterances of the batch at once (asr_hip.search.beam_search): utterance b owns decoder rows b * W ..
+        b * W + W - 1.  use_cache: ONE KV-cached decoder batch, so a step is one decoder step, one log-softmax / top-W launch and one
+        device -> host copy for the whole batch; else one full decoder pass per live hypothesis, like the reference.  The candidate
+        bookkeeping per utterance is the reference's (transformer.py:437-497: the in-loop re-sort, forced EOS at the last encoder frame),
+        so the strings are those of a loop over utterances.  -> the finished hypotheses, one list per utterance (for _rank_ended).
 
-    def _beam_search_hyps(self, encoder_padded_outputs, beam_width, ctc=None):
-        """The same search for ALL utterances of the batch at once: utterance b owns decoder rows b * W .. b * W + W - 1 of ONE
-        KV-cached decoder batch (its live hypotheses in the first rows, the others idle), so a step is one decoder step, one
-        log-softmax / top-W launch and one device -> host copy for the whole batch instead of one of each per utterance.  The
-        candidate bookkeeping per utterance is the reference's (transformer.py:437-497: the in-loop re-sort, forced EOS at the
-        last encoder frame, sqrt(words) * c_weight on finished hypotheses), so the strings are those of the per-utterance loop.
-        -> the finished hypotheses, one list per utterance (for _rank_ended).
-
-        ctc = (scorer, mu, K): joint CTC / attention scoring.  The step takes the top-K attention
-        log-probabilities per row instead of the top-W, the scorer (an object with step(last, cand) -> psi (R,K) and select(flat):
-        asr_hip.decode.CTCPrefixScorer, or a host restatement in the tests) gives the CTC prefix log-probability psi of every
-        candidate, and the W best of a hypothesis by joint = (1 - mu) * att + mu * (psi' - psi(g)) go into the unchanged bookkeeping.
-        'score' accumulates the joint increments ('att' the attention terms and 'psi' the prefix's CTC score alone); the CTC states are
-        selected with the rows of the KV cache.  psi reaches the host in the same copy as the top-K values and indices."""
-        from asr_hip.decode import DecoderKVCache
-        W = beam_width
+        ctc = (scorer, mu, K): joint CTC / attention scoring, cached only.  The step takes the top-K attention
+        log-probabilities per row instead of the top-W and the scorer (asr_hip.decode.CTCPrefixScorer, or a host restatement in the
+        tests; its interface: search.CachedBeamStep) their CTC prefix log-probabilities; search.beam_search keeps the W best of a
+        hypothesis by the joint score and names what 'score', 'att', 'psi' and 'slot' of a hypothesis hold."""
         B, max_len = encoder_padded_outputs.size(0), encoder_padded_outputs.size(1)
-        dev = encoder_padded_outputs.device
-        cache = DecoderKVCache(self, encoder_padded_outputs.repeat_interleave(W, dim=0), max_len=300)
-        hyps = [[{'score': 0.0, 'yseq': [constant.SOS_TOKEN]}] for _ in range(B)]
         if ctc is not None:
             scorer, mu, K = ctc
-            for b in range(B):
-                hyps[b][0].update(att=0.0, psi=0.0)
-        ended = [[] for _ in range(B)]
-        for i in range(300):
-            last = [constant.SOS_TOKEN] * (B * W)
-            for b in range(B):
-                for hi, h in enumerate(hyps[b]):
-                    last[b * W + hi] = h['yseq'][-1]
-            last = torch.tensor(last, dtype=torch.int64, device=dev)
-            logits = cache.step(last)
-            if ctc is None:
-                best_all, idx_all = ops.logsoftmax_topk(logits.float().contiguous(), W)
-                best_all, idx_all = best_all.tolist(), idx_all.tolist()
-            else:
-                best_all, idx_all = ops.logsoftmax_topk(logits.float().contiguous(), K)
-                psi_all = scorer.step(last, idx_all)
-                if psi_all.is_cuda:               # one device -> host copy per step (ids up to 2^24 are exact in fp32)
-                    packed = torch.cat([best_all, psi_all, idx_all.float()], dim=1).tolist()
-                    best_all, psi_all = [r[:K] for r in packed], [r[K:2 * K] for r in packed]
-                    idx_all = [[int(x) for x in r[2 * K:]] for r in packed]
-                else:
-                    best_all, idx_all, psi_all = best_all.tolist(), idx_all.tolist(), psi_all.tolist()
-            rows = list(range(B * W))
-            slots = [0] * (B * W)                  # (ctc) the candidate slot k a surviving row continues: its state is (parent row, k)
-            moved = False
-            for b in range(B):
-                if not hyps[b]:
-                    continue
-                cand = []
-                for hi, hyp in enumerate(hyps[b]):
-                    best, idx = best_all[b * W + hi], idx_all[b * W + hi]
-                    if ctc is None:
-                        for j in range(W):
-                            cand.append({'score': hyp['score'] + best[j], 'yseq': hyp['yseq'] + [idx[j]], 'parent': hi})
-                    else:
-                        psi = psi_all[b * W + hi]
-                        # a candidate CTC rules out (blank, SOS, more labels than frames) scores -inf, never inf - inf
-                        joint = [((1.0 - mu) * best[j] + mu * (psi[j] - hyp['psi'])) if psi[j] > -math.inf else -math.inf for j in range(K)]
-                        for j in sorted(range(K), key=lambda j: joint[j], reverse=True)[:W]:      # stable: ties keep the attention order
-                            cand.append({'score': hyp['score'] + joint[j], 'yseq': hyp['yseq'] + [idx[j]], 'parent': hi, 'slot': j,
-                                         'att': hyp['att'] + best[j], 'psi': psi[j]})
-                    cand = sorted(cand, key=lambda h: h['score'], reverse=True)[:W]      # the reference's in-loop re-sort (:460)
-                if i == max_len - 1:
-                    for hyp in cand:
-                        hyp['yseq'] = hyp['yseq'] + [constant.EOS_TOKEN]
-                alive = []
-                for hyp in cand:
-                    if hyp['yseq'][-1] == constant.EOS_TOKEN:
-                        ended[b].append(hyp)
-                    else:
-                        alive.append(hyp)
-                hyps[b] = alive
-                for j, hyp in enumerate(alive):
-                    moved |= hyp['parent'] != j
-                    rows[b * W + j] = b * W + hyp['parent']
-                    slots[b * W + j] = hyp.get('slot', 0)
-            if not any(hyps):
-                break
-            if moved:
-                cache.select(rows, cross=False)           # parents stay inside their utterance: the cross keys / values do not move
-            if ctc is not None:
-                scorer.select([r * K + k for r, k in zip(rows, slots)])
-        return ended
+            step, ctc = search.CachedBeamStep(self, encoder_padded_outputs, beam_width, K, scorer), (mu, K)
+        else:
+            step = (search.CachedBeamStep if use_cache else search.RerunBeamStep)(self, encoder_padded_outputs, beam_width)
+        return search.beam_search(step, B, beam_width, max_len, ctc)
 
 
 class DecoderLayer(nn.Module):

@@ -61,6 +61,8 @@ def test_greedy_and_beam_cached_match_uncached(precision):
     ib, sb = dec.beam_search(enc, beam_width=3, nbest=2, use_cache=False)
     ic, sc = dec.beam_search(enc, beam_width=3, nbest=2, use_cache="per_utterance")
     assert sa == sb == sc and ia == ib == ic
+    one = [dec.beam_search(enc[:1], beam_width=3, nbest=2, use_cache=mode) for mode in (True, False, "per_utterance")]
+    assert one[0] == one[1] == one[2] and 1 <= len(one[0][1]) <= 2          # one utterance goes through the same batched loop
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])

@@ -174,11 +174,12 @@ def decode():
                                       (time.time() - t0) * 1e3))
     if os.environ.get("MICRO_DECODE_BEAM", "1") == "1":
         print("== beam search (width 4), the same 32 utterances (random weights: every hypothesis runs to the 200-frame limit)")
-        for mode, label in ((True, "all utterances in one decoder batch"), ("per_utterance", "loop over utterances")):
+        for mode, label, n in ((True, "all utterances in one decoder batch", 32), ("per_utterance", "loop over utterances", 32),
+                               (True, "one utterance", 1)):
             with torch.no_grad():
                 torch.cuda.synchronize()
                 t0 = time.time()
-                model.decoder.beam_search(enc, beam_width=4, nbest=1, c_weight=0.1, use_cache=mode)
+                model.decoder.beam_search(enc[:n], beam_width=4, nbest=1, c_weight=0.1, use_cache=mode)
                 torch.cuda.synchronize()
             print("  %-36s %8.1f ms" % (label, (time.time() - t0) * 1e3))
 
