@@ -675,11 +675,26 @@ def ctc_align(logits, targets, input_lengths, target_lengths, blank=0):
     return out
 
 
-def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0):
+def ngram_logp(table, ctx, sym):
+    """q(ctx[i], sym[i]) of a label n-gram LM (csrc/ngram.hip): table = NgramLM.device_table(device), ctx (n, order-1) int32 with the
+    oldest symbol first and -1 for no symbol, sym (n) int32, both on the device -> (n) fp32, the bits of NgramLM.logp."""
+    n, order = sym.numel(), int(table["order"])
+    assert sym.dtype == torch.int32 and sym.is_contiguous() and ctx.dtype == torch.int32 and ctx.is_contiguous()
+    assert ctx.numel() == n * (order - 1)
+    out = torch.empty((n,), device=sym.device, dtype=torch.float32)
+    L.call("asr_ngram_logp", L.ptr(table["keys"]), L.ptr(table["vals"]), int(table["capacity"]), int(table["max_probe"]), order,
+           L.ptr(ctx) if ctx.numel() else None, L.ptr(sym), n, L.ptr(out), L.stream())
+    return out
+
+
+def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0, ngram=None, alpha=0.0, beta=0.0, bos=1, eos=2):
     """CTC prefix beam search (csrc/ctc_beam.hip): logits (B,T,V) fp32 (rows contiguous, any row stride), lengths (B) int32 on the device
     = true frames; beam_width W <= 16 prefixes kept per frame, candidates C <= 16 labels tried per frame (0: min(V, 16)), nbest <= W ->
     dict(ids (B,nbest,T) int32, lengths (B,nbest) int32 (-1: no such hypothesis), scores (B,nbest) fp32) on the device, best first.
-    blank defaults to PAD (0).  The logits of the true frames must be finite."""
+    blank defaults to PAD (0).  The logits of the true frames must be finite.
+    ngram (utils.ngram.NgramLM over these V labels): the fused arm.  The beam is pruned by score + alpha * lm + beta * labels, the result
+    ordered by that with alpha * q(context, eos) added (eos -1: no end term; bos opens the context; both default to SOS / EOS), and the
+    dict also holds lm (B,nbest) fp32, the LM's log-probability of the hypothesis; scores stays the CTC log-probability."""
     B, T, V = logits.shape
     W, nbest = int(beam_width), int(nbest)
     C = int(candidates) if candidates else min(V, 16)
@@ -691,8 +706,17 @@ def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0)
     rows = max(nbest, 1)
     out = dict(ids=torch.empty((B, rows, T), device=dev, dtype=torch.int32), lengths=torch.empty((B, rows), device=dev, dtype=torch.int32),
                scores=torch.empty((B, rows), device=dev, dtype=torch.float32))
-    L.call("asr_ctc_beam_search", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
-           L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.stream())
+    if ngram is None:
+        L.call("asr_ctc_beam_search", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
+               L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.stream())
+        return out
+    if ngram.V != V:
+        raise ValueError("the n-gram LM has %d labels, the logits %d" % (ngram.V, V))
+    t = ngram.device_table(dev)
+    out["lm"] = torch.empty((B, rows), device=dev, dtype=torch.float32)
+    L.call("asr_ctc_beam_search_lm", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
+           L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"],
+           t["max_probe"], t["order"], int(bos), int(eos), float(alpha), float(beta), L.ptr(out["lm"]), L.stream())
     return out
 
 

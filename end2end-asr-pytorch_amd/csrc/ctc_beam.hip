@@ -30,7 +30,24 @@
 // 16 frames ahead in registers and handed to LDS at the chunk boundary, so the walk's global reads are off its critical path -- except
 // lp(t, last(g)) of a prefix whose last label is NOT among the frame's candidates, the one dependent read (in a peaked posterior the
 // label of a live prefix usually is a candidate and the staged value -- the same fp32 subtraction -- is used).
+//
+// The fused arm (asr_ctc_beam_search_lm, template <true>): a label n-gram LM has its say while the beam is pruned.  q(h, c) is the query
+// of csrc/ngram.h; tests/ctc_beam_lm_reference.py restates the arm.  Added to the definition above:
+//   state                   every list entry also carries lm = the fp32 sum of q over its labels, len = their number, and ctx = the key of
+//                           the last N - 1 symbols of [bos] + prefix.  Before frame 0: lm 0, len 0, ctx [bos]
+//   step                    a stay slot keeps the three; the extension of h by c gets lm(h) + q(ctx(h), c), len(h) + 1 and the shifted
+//                           context.  They depend on the label sequence alone: a prefix pruned and created again gets the same bits
+//   prune                   slots ranked by f = tot + (alpha lm + beta (float)len) in fp32, tot = lae2(p_b', p_nb'); greater first, lower
+//                           slot index first among equals; a slot is live iff tot is finite
+//   result                  the W entries ordered by f + alpha q(ctx, eos) (f alone for eos = -1), the list place first among equals; the
+//                           first nbest are written: scores = tot (the CTC log-probability, as in the plain search), lm = the raw lm sum
+//                           with the end term; missing entries: length -1, scores and lm -inf
+// Only a live extension slot that is no merge runs a lookup, a dependent global read inside the step; the entries' extra state lives in
+// LDS and the workspace is the plain search's.  The plain arm instantiates none of it.
+#include <type_traits>
+
 #include "ctc_common.h"      // NEG_INF, lae2, ctc_lse_kernel
+#include "ngram.h"           // NgramTable, ngram_query, ngram_shift
 
 namespace {
 
@@ -63,11 +80,22 @@ __device__ __forceinline__ uint2 beam_key(uint2 parent, int label) {
 }
 constexpr uint32_t BEAM_ROOT_KEY_LO = 0x2545F491u | 1u, BEAM_ROOT_KEY_HI = 0x4F6CDD1Du;      // the empty prefix
 
-// blockDim.x = 256, or 320 when W + W C > 256: one slot per thread; the first 256 threads stage the chunks
+// What the fused arm adds to the plain search's arguments; the plain arm takes the empty BeamNoLm
+struct BeamLm {
+  NgramTable tab;
+  int bos, eos;             // eos -1: no end term
+  float alpha, beta;
+  float* lm;                // (B,nbest)
+};
+struct BeamNoLm {};
+
+// blockDim.x = 256, or 320 when W + W C > 256: one slot per thread; the first 256 threads stage the chunks.  LM: the fused arm
+template <bool LM>
 __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__ logits, int64_t ld, const float* __restrict__ lse,
                                                        const int64_t* __restrict__ cand, const int32_t* __restrict__ in_len, int T, int W,
                                                        int C, int nbest, int blank, int2* trie, int32_t* __restrict__ ids,
-                                                       int32_t* __restrict__ out_len, float* __restrict__ scores) {
+                                                       int32_t* __restrict__ out_len, float* __restrict__ scores,
+                                                       std::conditional_t<LM, BeamLm, BeamNoLm> fuse) {
   // the list, double buffered; node -1: no entry (then keys 0, last -1, all three values -inf).  (klo, khi): the prefix' key, (plo, phi):
   // its parent's (0 for the empty prefix).  tot = lae2(p_b, p_nb), kept from the prune step that computed it as the slot's score
   __shared__ __attribute__((aligned(16))) int l_node[2][BEAM_MAX], l_last[2][BEAM_MAX];
@@ -78,6 +106,11 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
   __shared__ float f_lpb[BEAM_CHUNK], f_lse[BEAM_CHUNK];
   __shared__ __attribute__((aligned(16))) float sc[BEAM_SLOTS];
   __shared__ int o_len[BEAM_MAX];
+  // the fused arm: the float32 sum of q over the prefix' labels, their number, and the key of the last order - 1 symbols of [bos] + prefix
+  // (functions of the label sequence alone: a stay slot keeps them, a merge needs no rule); o_src: the list place of final rank r
+  __shared__ float l_lm[2][BEAM_MAX], o_lm[BEAM_MAX];
+  __shared__ uint64_t l_ctx[2][BEAM_MAX];
+  __shared__ int l_len[2][BEAM_MAX], o_src[BEAM_MAX];
   const int tid = threadIdx.x, b = blockIdx.x, nthr = blockDim.x;
   int Tb = in_len[b];
   Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
@@ -100,6 +133,11 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     l_pb[0][tid] = tid == 0 ? 0.f : NEG_INF;
     l_pnb[0][tid] = NEG_INF;
     l_tot[0][tid] = tid == 0 ? 0.f : NEG_INF;          // lae2(0, -inf) = 0
+    if constexpr (LM) {
+      l_lm[0][tid] = 0.f;
+      l_len[0][tid] = 0;
+      l_ctx[0][tid] = ngram_shift(0, fuse.bos, fuse.tab.order);
+    }
   }
   for (int y = tid; y < BEAM_SLOTS; y += nthr) sc[y] = NEG_INF;         // (slots >= NS are never written: they never count)
 
@@ -133,6 +171,10 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
       const int t = t0 + f, nxt = cur ^ 1;
       float npb = NEG_INF, npnb = NEG_INF, sx = NEG_INF;
       int ext_c = -1;
+      // fused arm: the slot's rank key f = tot + (alpha lm + beta len) (the plain arm ranks by sx = tot itself) and what its entry carries
+      float fx = NEG_INF, elm = 0.f;
+      int elen = 0;
+      uint64_t ectx = 0;
       if (x < W) {
         int cid[BEAM_MAX], klo[BEAM_MAX], khi[BEAM_MAX];
         beam_row16(c_id[f], cid);
@@ -156,7 +198,13 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
           }
         }
         sx = lae2(npb, npnb);
-        sc[x] = sx;
+        if constexpr (LM) {
+          elm = l_lm[cur][x];
+          elen = l_len[cur][x];
+          ectx = l_ctx[cur][x];
+          if (sx > NEG_INF) fx = sx + (fuse.alpha * elm + fuse.beta * (float)elen);
+        }
+        sc[x] = LM ? fx : sx;
       } else if (x < NS) {
         int plos[BEAM_MAX], phis[BEAM_MAX], lasts[BEAM_MAX];
         beam_row16(l_plo[cur], plos);
@@ -172,9 +220,18 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
             npnb = (hl == c ? hb : ht) + lpc;
             sx = npnb;
             ext_c = c;
+            if constexpr (LM) {
+              if (sx > NEG_INF) {                          // a live extension that is no merge: the one lookup of the step
+                const uint64_t hctx = l_ctx[cur][sj];
+                elm = l_lm[cur][sj] + ngram_query(fuse.tab, hctx, c);
+                elen = l_len[cur][sj] + 1;
+                ectx = ngram_shift(hctx, c, fuse.tab.order);
+                fx = sx + (fuse.alpha * elm + fuse.beta * (float)elen);
+              }
+            }
           }
         }
-        sc[x] = sx;
+        sc[x] = LM ? fx : sx;
       }
       if (tid < BEAM_MAX) {                                   // places no survivor takes stay empty
         l_node[nxt][tid] = -1;
@@ -189,13 +246,14 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
       }
       __syncthreads();
       if (x < NS && sx > NEG_INF) {
+        const float rx = LM ? fx : sx;
         int rank = 0;
         for (int y = 0; y < NS16; y += 16) {
 #pragma unroll
           for (int q = 0; q < 16; q += 4) {
             const float4 v = *reinterpret_cast<const float4*>(&sc[y + q]);
-            rank += (v.x > sx || (v.x == sx && y + q < x)) + (v.y > sx || (v.y == sx && y + q + 1 < x)) +
-                    (v.z > sx || (v.z == sx && y + q + 2 < x)) + (v.w > sx || (v.w == sx && y + q + 3 < x));
+            rank += (v.x > rx || (v.x == rx && y + q < x)) + (v.y > rx || (v.y == rx && y + q + 1 < x)) +
+                    (v.z > rx || (v.z == rx && y + q + 2 < x)) + (v.w > rx || (v.w == rx && y + q + 3 < x));
           }
         }
         if (rank < W) {
@@ -222,6 +280,11 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
           l_pb[nxt][rank] = npb;
           l_pnb[nxt][rank] = npnb;
           l_tot[nxt][rank] = sx;
+          if constexpr (LM) {
+            l_lm[nxt][rank] = elm;
+            l_len[nxt][rank] = elen;
+            l_ctx[nxt][rank] = ectx;
+          }
         }
       }
       __syncthreads();
@@ -229,10 +292,36 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     }
   }
   __syncthreads();
+  if constexpr (LM) {       // the final order: f + alpha q(ctx, eos) (f alone without an end term), the list place first among equals
+    const bool live = tid < W && l_node[cur][tid] >= 0;
+    float fk = NEG_INF, lmv = NEG_INF;
+    if (live) {
+      lmv = l_lm[cur][tid];
+      fk = l_tot[cur][tid] + (fuse.alpha * lmv + fuse.beta * (float)l_len[cur][tid]);
+      if (fuse.eos >= 0) {
+        const float qe = ngram_query(fuse.tab, l_ctx[cur][tid], fuse.eos);
+        fk = fk + fuse.alpha * qe;
+        lmv = lmv + qe;
+      }
+    }
+    if (tid < BEAM_MAX) { sc[tid] = fk; o_src[tid] = -1; }
+    __syncthreads();
+    if (live) {
+      int rank = 0;
+      for (int i = 0; i < W; ++i) {
+        const float v = sc[i];
+        rank += v > fk || (v == fk && i < tid);
+      }
+      o_src[rank] = tid;
+      o_lm[rank] = lmv;
+    }
+    __syncthreads();
+  }
   // the n-best: one lane per hypothesis walks its parent chain (a parent is an older node: the chain ends at node 0)
   int32_t* ids_b = ids + (int64_t)b * nbest * T;
   if (tid < nbest) {
-    const int node = l_node[cur][tid];
+    const int src = LM ? o_src[tid] : tid;               // the list place of hypothesis tid (fused arm: -1 where there is none)
+    const int node = src >= 0 ? l_node[cur][src] : -1;
     int len = -1;
     if (node >= 0) {
       len = 0;
@@ -246,7 +335,8 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     }
     o_len[tid] = len < 0 ? 0 : len;
     out_len[(int64_t)b * nbest + tid] = len;
-    scores[(int64_t)b * nbest + tid] = l_tot[cur][tid];
+    scores[(int64_t)b * nbest + tid] = src >= 0 ? l_tot[cur][src] : NEG_INF;
+    if constexpr (LM) fuse.lm[(int64_t)b * nbest + tid] = src >= 0 ? o_lm[tid] : NEG_INF;
   }
   __syncthreads();
   for (int y = tid; y < nbest * T; y += nthr) {
@@ -265,9 +355,13 @@ extern "C" int64_t asr_ctc_beam_workspace(int B, int T, int W, int C) {
   return beam_idx_offset(B, T, C) + 2 * (int64_t)B * T * C + 2 * (int64_t)B * (1 + (int64_t)T * W);
 }
 
-extern "C" int asr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C,
-                                   int nbest, int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
-                                   float* scores, hipStream_t s) {
+namespace {
+
+// both entries: the row log-sum-exp, the candidates, then the search with or without the fused LM
+template <bool LM>
+int beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C, int nbest, int blank,
+                float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+                std::conditional_t<LM, BeamLm, BeamNoLm> fuse, hipStream_t s) {
   ASR_CHECK_ARG(logits && input_lengths && workspace && ids && lengths && scores);
   ASR_CHECK_ARG(B > 0 && T > 0 && V > 0 && ld >= V && W >= 1 && C >= 1 && nbest >= 1 && blank >= 0 && blank < V);
   if (W > BEAM_MAX || C > BEAM_MAX || nbest > W) return ASR_EUNSUPPORTED;
@@ -285,8 +379,32 @@ extern "C" int asr_ctc_beam_search(const float* logits, int64_t ld, const int32_
   const int rc = asr_logsoftmax_topk(logits, ld, (int)rows, V, C, vals, idx, s);
   if (rc != ASR_OK) return rc;
   const int threads = W + W * C > 256 ? 320 : 256;                 // one per slot
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(threads), 0, s, logits, ld, lse, idx, input_lengths, T, W, C, nbest, blank, trie, ids,
-                     lengths, scores);
+  hipLaunchKernelGGL(ctc_beam_kernel<LM>, dim3(B), dim3(threads), 0, s, logits, ld, lse, idx, input_lengths, T, W, C, nbest, blank, trie,
+                     ids, lengths, scores, fuse);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
+}
+
+}  // namespace
+
+extern "C" int asr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C,
+                                   int nbest, int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
+                                   float* scores, hipStream_t s) {
+  return beam_search<false>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths, scores,
+                            BeamNoLm{}, s);
+}
+
+// The fused arm: the table must hold a unigram for every label 0..V-1 (utils/ngram.py's estimator does), so that every q is finite.
+extern "C" int asr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C,
+                                      int nbest, int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
+                                      float* scores, const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order,
+                                      int bos, int eos, float alpha, float beta, float* lm, hipStream_t s) {
+  const int rc = ngram_check_table(keys, vals, capacity, max_probe, order);
+  if (rc != ASR_OK) return rc;
+  ASR_CHECK_ARG(lm && bos >= 0 && bos < V && eos >= -1 && eos < V);
+  if (V > NGRAM_MAX_ID + 1) return ASR_EUNSUPPORTED;          // ids + 1 in 16-bit key fields
+  const BeamLm fuse{NgramTable{keys, reinterpret_cast<const float2*>(vals), (uint32_t)(capacity - 1), max_probe, order}, bos, eos, alpha,
+                    beta, lm};
+  return beam_search<true>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths, scores,
+                           fuse, s);
 }

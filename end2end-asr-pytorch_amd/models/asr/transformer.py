@@ -138,7 +138,7 @@ class Transformer(nn.Module):
 
     @torch.no_grad()
     def ctc_beam_search(self, enc_out, lengths, beam_width, nbest=1, candidates=0, lm=None, lm_weight=0.1, c_weight=1, return_ids=False,
-                        rescoring_weight=0.0):
+                        rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0):
         """Prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): no decoder step.  lengths:
         true encoder frames per utterance (ctc_frame_lengths); beam_width W in 1..16 prefixes kept per frame, candidates C (0: min(V, 16))
         labels tried per frame.  One device-to-host copy.  The kernel's W hypotheses of an utterance, score = log-probability summed over
@@ -148,9 +148,17 @@ class Transformer(nn.Module):
         are CTC labels as they stand: no SOS, no EOS.
         rescoring_weight = lambda in (0, 1]: attention rescoring.  ALL W hypotheses of every utterance get 'ctc_score' (the kernel's),
         'att_score' (Decoder.score_hypotheses: one teacher-forced decoder pass, one more small device-to-host copy) and score =
-        (1 - lambda) * ctc_score + lambda * att_score before the ranking above; 0 makes no decoder launch."""
+        (1 - lambda) * ctc_score + lambda * att_score before the ranking above; 0 makes no decoder launch.
+        ngram (utils.ngram.NgramLM over this model's labels): first-pass fusion.  The kernel prunes its beam by the CTC score +
+        ngram_weight * the n-gram's log-probability of the labels + length_bonus * their number (contexts open with SOS, the final
+        order counts EOS), so the LM decides which prefixes survive; its table goes to the device once per LM.  Every hypothesis gets
+        'ctc_score', 'ngram_score' (with the EOS term) and score = ctc_score + ngram_weight * ngram_score + length_bonus * labels, with
+        rescoring (1 - lambda) * ctc_score + lambda * att_score + the same two terms, before the ranking above.  None: the plain search."""
         W = int(beam_width)
         lam = float(rescoring_weight)
+        a, beta = float(ngram_weight), float(length_bonus)
+        if ngram is not None:
+            ngram.check_labels(self.id2label)
         if not 0.0 <= lam <= 1.0:
             raise ValueError("rescoring_weight must lie in [0, 1], got %g" % lam)
         if not 1 <= W <= 16:
@@ -159,17 +167,32 @@ class Transformer(nn.Module):
             raise ValueError("nbest must be at least 1, got %d" % nbest)
         logits = self.ctc_logits(enc_out)
         B, T, V = logits.shape
-        out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN)
-        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1), out["scores"].view(torch.int32).reshape(-1)]).cpu()
-        ids, lens, scores = torch.split(flat, [B * W * T, B * W, B * W])
-        ids, lens, scores = ids.view(B, W, T).tolist(), lens.view(B, W).tolist(), scores.view(torch.float32).view(B, W).tolist()
+        if ngram is None:
+            out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN)
+            parts = [out["scores"]]
+        else:
+            out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN,
+                                      ngram=ngram, alpha=a, beta=beta, bos=constant.SOS_TOKEN, eos=constant.EOS_TOKEN)
+            parts = [out["scores"], out["lm"]]
+        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1)] + [p.view(torch.int32).reshape(-1) for p in parts]).cpu()
+        ids, lens, *parts = torch.split(flat, [B * W * T, B * W] + [B * W] * len(parts))
+        ids, lens = ids.view(B, W, T).tolist(), lens.view(B, W).tolist()
+        scores, *lm_scores = [p.view(torch.float32).view(B, W).tolist() for p in parts]
         ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n]} for n in range(W) if lens[b][n] >= 0] for b in range(B)]
+        if ngram is not None:
+            for b, hs in enumerate(ended):
+                for h, g in zip(hs, [lm_scores[0][b][n] for n in range(W) if lens[b][n] >= 0]):
+                    h['ctc_score'], h['ngram_score'] = h['score'], g
+                    h['score'] = h['ctc_score'] + a * g + beta * len(h['yseq'])
         if lam > 0.0:
             att = self.decoder.score_hypotheses(enc_out, [[h['yseq'] for h in hs] for hs in ended])
             for hs, scores_b in zip(ended, att):
-                for h, a in zip(hs, scores_b):
-                    h['ctc_score'], h['att_score'] = h['score'], a
-                    h['score'] = (1.0 - lam) * h['ctc_score'] + lam * a
+                for h, att_score in zip(hs, scores_b):
+                    h.setdefault('ctc_score', h['score'])
+                    h['att_score'] = att_score
+                    h['score'] = (1.0 - lam) * h['ctc_score'] + lam * att_score
+                    if ngram is not None:
+                        h['score'] += a * h['ngram_score'] + beta * len(h['yseq'])
         hyp_ids = [[h['yseq'] for h in hs] for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight)]
         strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
         return (strs, hyp_ids) if return_ids else strs
@@ -225,14 +248,15 @@ class Transformer(nn.Module):
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
                  ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,
-                 attention_rescoring_weight=0.0):
+                 attention_rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
         ctc_greedy: best-path decoding from the head alone; ctc_beam: prefix beam search over the head's posteriors alone
         (ctc_beam_search: beam_width prefixes, ctc_candidates labels per frame, the beam_nbest best re-ranked with lm when lm_rescoring),
         not together with beam_search, ctc_greedy or ctc_weight; attention_rescoring_weight = lambda in (0, 1] (ctc_beam only): all
         beam_width hypotheses are rescored by the decoder in one teacher-forced pass and ranked by (1 - lambda) * CTC + lambda * attention
-        log-probability (ctc_beam_search's rescoring_weight).  align_source "gold" / "hyp": a fourth value, the forced alignment
+        log-probability (ctc_beam_search's rescoring_weight); ngram / ngram_weight / length_bonus (ctc_beam only): a label n-gram LM fused
+        into that search's pruning (ctc_beam_search's arguments of the same names).  align_source "gold" / "hyp": a fourth value, the forced alignment
         (ctc_align) of padded_target with target_lengths, or of the label ids the decoder produced (SOS and EOS dropped; never a
         re-tokenised string)."""
         if ctc_weight > 0 and not beam_search:
@@ -244,6 +268,8 @@ class Transformer(nn.Module):
         if attention_rescoring_weight > 0 and not ctc_beam:
             raise ValueError("--attention-rescoring-weight %g needs --ctc-beam-search: the decoder rescores the CTC search's n-best"
                              % attention_rescoring_weight)
+        if ngram is not None and not ctc_beam:
+            raise ValueError("--ngram-path needs --ctc-beam-search: the n-gram LM is fused into the CTC prefix beam search")
         if ctc_beam and not hasattr(self, "ctc_linear"):
             self.ctc_logits(None)                      # the "no encoder CTC head" ValueError, before any device work
         if lm_rescoring and ctc_beam and lm is None:
@@ -271,7 +297,8 @@ class Transformer(nn.Module):
             nbest_strs, nbest_ids = self.ctc_beam_search(enc_out, ctc_lengths, beam_width, nbest=max(1, int(beam_nbest)),
                                                          candidates=ctc_candidates, lm=lm if lm_rescoring else None,
                                                          lm_weight=lm_weight, c_weight=c_weight, return_ids=True,
-                                                         rescoring_weight=attention_rescoring_weight)
+                                                         rescoring_weight=attention_rescoring_weight, ngram=ngram,
+                                                         ngram_weight=ngram_weight, length_bonus=length_bonus)
             strs_hyps, hyp_ids = [rows[0] if rows else "" for rows in nbest_strs], [rows[0] if rows else [] for rows in nbest_ids]
         elif beam_search:
             hyp_ids, strs_hyps = self.decoder.beam_search(enc_out, beam_width=beam_width, nbest=1, lm=lm, lm_rescoring=lm_rescoring,

@@ -1,6 +1,7 @@
 """Evaluation entry point -- same command line as the reference (reference: test.py): loads --continue-from, decodes
 every test utterance (greedy, beam search with --beam-search, or from the encoder CTC head alone with --ctc-greedy / --ctc-beam-search,
-the latter's n-best rescored by the decoder with --attention-rescoring-weight) and reports CER / WER.  --align-out PATH also writes label and word
+the latter's n-best rescored by the decoder with --attention-rescoring-weight, its pruning guided by a label n-gram LM with --ngram-path)
+and reports CER / WER.  --align-out PATH also writes label and word
 timestamps from the encoder CTC head (forced alignment of the transcript, or of the hypothesis with --align-source hyp)."""
 import torch
 from tqdm import tqdm
@@ -9,9 +10,12 @@ from utils import constant
 from utils.metrics import calculate_cer, calculate_cer_en_zh, calculate_wer
 
 
-def evaluate(model, test_loader, lm=None, noise_dir=None):
-    """reference: test.py:19-62.  noise_dir: the checkpoint's --noise-dir (the reference injects noise into the test set too)."""
+def evaluate(model, test_loader, lm=None, noise_dir=None, ngram=None):
+    """reference: test.py:19-62.  noise_dir: the checkpoint's --noise-dir (the reference injects noise into the test set too); ngram: the
+    NgramLM of --ngram-path (None: the plain search, no table and no further launch)."""
     args = constant.args
+    fusion = {} if ngram is None else dict(ngram=ngram, ngram_weight=getattr(args, "ngram_weight", 0.3),
+                                           length_bonus=getattr(args, "ngram_length_bonus", 0.0))
     model.eval()
     total_word = total_char = total_cer = total_wer = 0
     total_en_cer = total_zh_cer = total_en_char = total_zh_char = 0
@@ -45,7 +49,7 @@ def evaluate(model, test_loader, lm=None, noise_dir=None):
                                                                  ctc_greedy=getattr(args, "ctc_greedy", False),
                                                                  ctc_beam=getattr(args, "ctc_beam_search", False),
                                                                  attention_rescoring_weight=getattr(args, "attention_rescoring_weight", 0.0),
-                                                                 **align)
+                                                                 **align, **fusion)
             for i, (hyp, gold) in enumerate(zip(strs_hyps, strs_gold)):
                 for ch in (constant.EOS_CHAR, constant.SOS_CHAR, constant.PAD_CHAR):
                     hyp, gold = hyp.replace(ch, ""), gold.replace(ch, "")
@@ -70,7 +74,7 @@ def check_ctc_decoding(args, model):
     """--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need the encoder CTC head of a model trained with
     --ctc-weight > 0; the weight lies in [0, 1] and applies to --beam-search.  --ctc-beam-search decodes from the head alone: it excludes
     --beam-search, --ctc-greedy and a --ctc-decode-weight, and its --beam-width lies in 1..16.  --attention-rescoring-weight lies in
-    [0, 1] and applies to --ctc-beam-search."""
+    [0, 1] and applies to --ctc-beam-search, as does --ngram-path."""
     w = float(getattr(args, "ctc_decode_weight", 0.0) or 0.0)
     if not 0.0 <= w <= 1.0:
         raise ValueError("--ctc-decode-weight must lie in [0, 1], got %g" % w)
@@ -80,6 +84,8 @@ def check_ctc_decoding(args, model):
         raise ValueError("--attention-rescoring-weight must lie in [0, 1], got %g" % lam)
     if lam > 0 and not ctc_beam:
         raise ValueError("--attention-rescoring-weight %g needs --ctc-beam-search: the decoder rescores the CTC search's n-best" % lam)
+    if getattr(args, "ngram_path", None) and not ctc_beam:
+        raise ValueError("--ngram-path needs --ctc-beam-search: the n-gram LM is fused into the CTC prefix beam search")
     if ((w > 0 or getattr(args, "ctc_greedy", False) or ctc_beam or getattr(args, "align_out", None))
             and not hasattr(model, "ctc_linear")):
         raise ValueError("--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need a model with an encoder CTC head: "
@@ -131,5 +137,9 @@ if __name__ == '__main__':
     test_sampler = BucketingSampler(test_data, batch_size=args.batch_size)
     test_loader = AudioDataLoader(test_data, num_workers=args.num_workers, batch_sampler=test_sampler)
     lm = LM(args.lm_path) if args.lm_rescoring else None      # reference: test.py:91-93
+    ngram = None
+    if getattr(args, "ngram_path", None):     # --ctc-beam-search only (check_ctc_decoding); a file for other labels is refused here
+        from utils.ngram import NgramLM
+        ngram = NgramLM.load(args.ngram_path, id2label)
     print(model)
-    evaluate(model, test_loader, lm=lm, noise_dir=getattr(loaded_args, "noise_dir", None))
+    evaluate(model, test_loader, lm=lm, noise_dir=getattr(loaded_args, "noise_dir", None), ngram=ngram)

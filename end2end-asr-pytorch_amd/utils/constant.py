@@ -17,7 +17,9 @@ Differences that do not change old command lines:
     filterbank features of the same STFT (DESIGN.md section 7), on the host path and on the GPU front end alike;
   * `--conv-module-kernel K` (odd, 3..31; 0 = off): a Conformer-style convolution module in every encoder layer (DESIGN.md section 7);
   * `--pos-encoding {abs,rope}`: the reference's absolute sinusoid (default) or rotary position embedding of Q and K in every encoder
-    self-attention; the decoder keeps its sinusoid.
+    self-attention (DESIGN.md section 7); the decoder keeps its sinusoid;
+  * `--ngram-path FILE` (+ `--ngram-weight`, `--ngram-length-bonus`; test.py --ctc-beam-search): a label n-gram LM of train_ngram.py
+    fused into the CTC prefix beam search's pruning.
 """
 import argparse
 import os
@@ -84,6 +86,10 @@ _FLAGS = [
     # --attention-rescoring-weight l (test.py --ctc-beam-search): the decoder scores all --beam-width hypotheses of the
     # CTC search in one teacher-forced pass and they are ranked by (1 - l) CTC + l attention log-probability; 0 = off, no decoder pass
     (("--attention-rescoring-weight",), dict(default=0.0, type=_F)),
+    # --ngram-path FILE (test.py --ctc-beam-search): a label n-gram LM of train_ngram.py, fused into the search's
+    # pruning with --ngram-weight and a bonus of --ngram-length-bonus per label; without the path nothing changes
+    (("--ngram-path",), dict(type=_S, default=None)), (("--ngram-weight",), dict(default=0.3, type=_F)),
+    (("--ngram-length-bonus",), dict(default=0.0, type=_F)),
     # CTC forced alignment (test.py): --align-out PATH writes one JSON line per test utterance with label and word
     # timestamps from the CTC head; --align-source gold aligns the transcript, hyp the label ids the decoder produced
     (("--align-out",), dict(default=None, type=_S)), (("--align-source",), dict(default="gold", choices=["gold", "hyp"])),

@@ -292,6 +292,31 @@ int asr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* input_le
                         int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
                         asr_stream_t stream);
 
+/* ---- Label n-gram LM, fused into the CTC prefix beam search (csrc/ngram.h has the query, utils/ngram.py the estimator and the table).
+ * The table: open addressing with linear probing over `capacity` slots (a power of two <= 2^31, at least twice the entries).
+ *   key    64 bits, the n-gram's ids + 1 in 16-bit fields, the last symbol lowest (ids < 65535); its order is its highest non-zero
+ *          field; 0 = an empty slot
+ *   value  float2 (logp, bo), natural logs; vals is (capacity, 2) fp32
+ *   hash   home slot = (((key ^ (key >> 31)) * 0x9E3779B97F4A7C15 mod 2^64) >> 32) & (capacity - 1)     [the one hash: utils/ngram.py
+ *          hash_slot and csrc/ngram.h ngram_home write exactly this]
+ * A stored key lies within max_probe slots of its home; an empty slot ends a search.  order N in 1..4.  The query, fp32 adds in this order:
+ *   q(h, c): acc = 0;  for m = len(h) .. 1: g = last m of h, then c;  g stored: return acc + logp[g];  (last m of h) stored: acc += bo
+ *            return acc + logp[(c)]        (-inf when c is outside 0..65534 or has no unigram)
+ * asr_ngram_logp: out[i] = q(ctx[i], sym[i]) for n queries, one thread each; ctx (n, order-1) int32, oldest symbol first, -1 = no symbol
+ * (what stands before a -1 is dropped); ctx may be NULL for order 1.  A capacity that is no power of two or an order outside 1..4:
+ * ASR_EINVAL.                                                                                                                       */
+int asr_ngram_logp(const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order, const int32_t* ctx,
+                   const int32_t* sym, int64_t n, float* out, asr_stream_t stream);
+/* asr_ctc_beam_search with the LM in the pruning (csrc/ctc_beam.hip has the definition): slots are ranked by
+ * tot + (alpha lm + beta len), the final list by that + alpha q(ctx, eos) (eos = -1: no end term); bos opens every context.  The table
+ * must hold a unigram for every label 0..V-1.  Same arguments, workspace, launches and refusals as asr_ctc_beam_search, and
+ * V > 65535: ASR_EUNSUPPORTED; a bad table or order: ASR_EINVAL.  scores stays the CTC log-probability; lm (B,nbest) fp32 = the sum of q
+ * over the hypothesis' labels and the end term (-inf where lengths is -1).                                                            */
+int asr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C, int nbest,
+                           int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+                           const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order, int bos, int eos,
+                           float alpha, float beta, float* lm, asr_stream_t stream);
+
 /* ---- Conformer-style convolution module (csrc/convmod.hip has the definition): GLU -> depthwise convolution over time -> Swish between
  * the module's two pointwise GEMMs, channel last.  u (B,T,2D) = [a | gate], s / v / dv (B,T,D), du (B,T,2D), all in `dtype` and
  * contiguous; wd (D,K) and bd (D) fp32 (the layout of nn.Conv1d(D, D, K, padding=(K-1)/2, groups=D)); len (B) int32 on the device, clamped
