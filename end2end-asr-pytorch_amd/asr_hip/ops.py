@@ -1628,6 +1628,95 @@ def augment_wave(wav, lens, params, bank, sample_rate=16000, offsets=False):
     return (out, lens_out, offs) if offsets else (out, lens_out)
 
 
+RESAMPLE_TILE = 1024                         # outputs per workgroup of asr_resample (ASR_RESAMPLE_TILE, include/asr_hip.h)
+RESAMPLE_MAX_DEN = 1000
+
+
+def resample_launch(wav, lens, plan, table, out):
+    """asr_resample with an explicit plan: wav (B, L) fp32 and out (B, out_cols) fp32 on the device (rows evenly strided, unit column
+    stride; the kernel writes every column of out and nothing else), lens (B) input samples, plan (B, 8) integers on the host = {num,
+    den, R, table offset in floats, n_out, 0, 0, 0}, table: flat fp32 on the device or None.  The plan is checked here, before the
+    upload -- the kernel clamps what it reads; a plan it would have to clamp is a caller's mistake."""
+    import numpy as np
+    assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1
+    assert out.dim() == 2 and out.dtype == torch.float32 and (out.shape[1] <= 1 or out.stride(1) == 1) and out.device == wav.device
+    B, Lmax = wav.shape
+    out_cols = out.shape[1]
+    plan = np.ascontiguousarray(torch.as_tensor(plan).cpu().numpy().astype(np.int64).reshape(B, 8))
+    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
+    if out.shape[0] != B or (B > 1 and out.stride(0) < out_cols):
+        raise ValueError("resample: out must be (%d, out_cols) with rows that do not overlap" % B)
+    if (n_in < 0).any() or (n_in > Lmax).any():
+        raise ValueError("resample: lengths outside [0, %d]" % Lmax)
+    floats = 0 if table is None else table.numel()
+    if table is not None:
+        assert table.dim() == 1 and table.dtype == torch.float32 and table.is_contiguous() and table.device == wav.device
+    for b in range(B):
+        num, den, R, off, n_out = (int(v) for v in plan[b, :5])
+        if num < 1 or den < 1 or den > RESAMPLE_MAX_DEN or R < 1 or num > 0x7fffffff or R > 0x3fffffff:
+            raise ValueError("resample: row %d: need 1 <= num, 1 <= den <= %d and R >= 1, got %d / %d, R = %d" % (b, RESAMPLE_MAX_DEN, num, den, R))
+        if num != den and (off < 0 or off + den * 2 * R > floats):
+            raise ValueError("resample: row %d: the %d x %d taps at offset %d reach outside the table of %d floats" % (b, den, 2 * R, off, floats))
+        if n_out < 0 or n_out > out_cols:
+            raise ValueError("resample: row %d: n_out = %d outside the %d output columns" % (b, n_out, out_cols))
+    if B == 0 or out_cols == 0:
+        return out
+    dev = wav.device
+    lens_dev, plan_dev = torch.from_numpy(n_in.astype(np.int32)).to(dev), torch.from_numpy(plan.astype(np.int32)).to(dev)
+    ld_out = out.stride(0) if B > 1 else max(out.stride(0), out_cols)           # a single row's stride is arbitrary
+    L.call("asr_resample", L.ptr(wav), wav.stride(0), L.ptr(lens_dev), L.ptr(plan_dev), L.ptr(table), floats, L.ptr(out), ld_out,
+           out_cols, B, L.stream())
+    return out
+
+
+def resample(wav, lens, p, tables=None, out=None):
+    """Speed perturbation by band-limited resampling (asr_resample) of padded waveforms wav (B, L) fp32 on the
+    device.  lens (B): input samples; p (B): the speed factors in thousandths, 500 .. 2000, 0 or 1000 = none (the row is copied).
+    Returns (out (B, max n_out) fp32 zero padded, lens_out (B) int32 on the device); with every factor an identity the inputs come
+    back (wav itself, lens as int32 on the device) and nothing is launched.  tables: {p: (R, H (den, 2R) float32)} instead of
+    utils.audio.resample_table's (tests inject exact ones); out: a caller's (B, >= max n_out) buffer, every column of which is written."""
+    import numpy as np
+    from utils.audio import SPEED_RANGE, device_resample_tables, speed_length, speed_ratio
+    assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1
+    B, Lmax = wav.shape
+    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
+    ps = [int(v) for v in torch.as_tensor(p).cpu().reshape(B).tolist()]
+    if any(v != 0 and not SPEED_RANGE[0] <= v <= SPEED_RANGE[1] for v in ps):
+        raise ValueError("resample: speed factors are 0 (none) or %d .. %d thousandths, got %s" % (SPEED_RANGE + (ps,)))
+    if (n_in < 0).any() or (n_in > Lmax).any():
+        raise ValueError("resample: lengths outside [0, %d]" % Lmax)
+    dev = wav.device
+    live = sorted(set(v for v in ps if v not in (0, 1000)))
+    if not live and out is None:
+        if torch.is_tensor(lens) and lens.device == dev and lens.dtype == torch.int32:
+            return wav, lens
+        return wav, torch.from_numpy(n_in.astype(np.int32)).to(dev)
+    if tables is None:
+        table, index = device_resample_tables(live, dev) if live else (None, {})
+    else:
+        index, parts, off = {}, [], 0
+        for v in live:
+            R, H = tables[v]
+            H = np.ascontiguousarray(H, dtype=np.float32)
+            if H.shape != (speed_ratio(v)[1], 2 * int(R)):
+                raise ValueError("resample: the table of factor %d is %s, not (den, 2R) = (%d, %d)" % (v, H.shape, speed_ratio(v)[1], 2 * int(R)))
+            index[v] = (int(R), off)
+            parts.append(H.reshape(-1))
+            off += H.size
+        table = torch.from_numpy(np.concatenate(parts)).to(dev) if parts else None
+    plan = np.zeros((B, 8), dtype=np.int64)
+    for b, v in enumerate(ps):
+        n = int(n_in[b])
+        if v in (0, 1000):
+            plan[b, :5] = (1, 1, 1, 0, n)
+        else:
+            plan[b, :5] = speed_ratio(v) + index[v] + (speed_length(n, v),)
+    if out is None:
+        out = torch.empty((B, max(int(plan[:, 4].max()) if B else 0, 1)), device=dev, dtype=torch.float32)
+    resample_launch(wav, n_in, plan, table, out)
+    return out, torch.from_numpy(plan[:, 4].astype(np.int32)).to(dev)
+
+
 # ------------------------------------------------------------------------------------------------ LSTM language model (fp32)
 def lm_proj(x, w, bias, K, ids=None):
     """(M, N) fp32 = X w^T + bias, X row m = x[ids[m]] (int32 ids) or x[m]; x / w zero-padded to 16 * ceil(K / 16) columns."""

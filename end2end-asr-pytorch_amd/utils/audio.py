@@ -3,6 +3,8 @@ utils/data_loader.py:60-91).  Own implementation on numpy only: the reference's 
 are not part of this build.  The reference's sox-based tempo/gain augmentation and noise injection (audio.py:17-61,
 data_loader.py:145-179) run on the GPU instead (asr_augment_wave, csrc/augment.hip; definition in DESIGN.md section 7): the host
 keeps the random draws (utils/data_loader.py), gpu_front_end applies them to the batch before the STFT.
+--speed-perturb (no counterpart in the reference): band-limited resampling by a factor drawn per utterance (speed_ratio, speed_length,
+resample_table; asr_resample, csrc/resample.hip), ahead of tempo / gain / noise.
 --features fbank (no counterpart in the reference): log-mel filterbank features of the same STFT (mel_filterbank, log_mel_fbank;
 definition in DESIGN.md section 7).
 """
@@ -210,6 +212,80 @@ def gain_multiplier(gain_db):
     return np.float32(10.0 ** (float(gain_db) / 20.0))
 
 
+# ------------------------------------------------------------------------------------------------ speed perturbation
+SPEED_RANGE = (500, 2000)                     # speed factors in thousandths: 0.5 .. 2.0
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF = 6, (99, 100)      # Z zero crossings of the sinc, roll-off rho = 0.99 as a fraction
+
+
+def speed_thousandths(factors):
+    """--speed-perturb's factors as integers in thousandths (each rounded to the nearest); refuses an empty list and a factor outside
+    [0.5, 2.0]."""
+    out = [int(np.floor(float(f) * 1000.0 + .5)) for f in factors]
+    if not out or min(out) < SPEED_RANGE[0] or max(out) > SPEED_RANGE[1]:
+        raise ValueError("--speed-perturb %s: one or more factors, each in [0.5, 2.0]" % list(factors))
+    return out
+
+
+def speed_ratio(p):
+    """p / 1000 in lowest terms (num, den): den divides 1000."""
+    p = int(p)
+    if not SPEED_RANGE[0] <= p <= SPEED_RANGE[1]:
+        raise ValueError("speed factor %d / 1000 outside [0.5, 2.0]" % p)
+    g = int(np.gcd(p, 1000))
+    return p // g, 1000 // g
+
+
+def speed_length(n, p):
+    """Samples of an utterance of n after the speed change by p / 1000: n den / num rounded half up (n itself at 1000)."""
+    num, den = speed_ratio(p)
+    return (2 * int(n) * den + num) // (2 * num)
+
+
+_resample_tables = {}
+
+
+def resample_table(p):
+    """(R, H (den, 2R) float32) of the speed factor p / 1000 = num / den: the Hann-windowed sinc
+    h(t) = c sinc(c t) cos^2(pi c t / (2 Z)) for |c t| < Z, else 0, with Z = 6, c = 0.99 min(1, den / num), R = ceil(Z / c), sampled as
+    H[phi][q] = h(phi / den - (q - R + 1)).  Computed in float64, not normalised per phase, cached per factor."""
+    p = int(p)
+    hit = _resample_tables.get(p)
+    if hit is None:
+        num, den = speed_ratio(p)
+        rn, rd = RESAMPLE_ROLLOFF
+        Z, wide = RESAMPLE_ZEROS, max(num, den)
+        R = -((-Z * rd * wide) // (rn * den))                                     # ceil(Z / c) in integers
+        c = (rn / rd) * min(1.0, den / num)
+        # t = (phi - (q - R + 1) den) / den: an integer numerator, so that mirrored taps are the same float64
+        t = (np.arange(den, dtype=np.int64)[:, None] - (np.arange(2 * R, dtype=np.int64)[None, :] - R + 1) * den) / float(den)
+        h = c * np.sinc(c * t) * np.cos(np.pi * c * t / (2.0 * Z)) ** 2
+        h[np.abs(c * t) >= Z] = 0.0
+        H = h.astype(np.float32)
+        H.setflags(write=False)
+        hit = _resample_tables[p] = (int(R), H)
+    return hit
+
+
+_device_resample_tables = {}
+
+
+def device_resample_tables(factors, device):
+    """The tap tables of the distinct non-identity factors (thousandths) concatenated on the device, uploaded once per (factor set,
+    device) like the mel bank: (table fp32, {p: (R, offset in floats)})."""
+    import torch
+    key = (tuple(sorted(set(int(p) for p in factors))), str(device))
+    hit = _device_resample_tables.get(key)
+    if hit is None:
+        index, parts, off = {}, [], 0
+        for p in key[0]:
+            R, H = resample_table(p)
+            index[p] = (R, off)
+            parts.append(H.reshape(-1))
+            off += H.size
+        hit = _device_resample_tables[key] = (torch.from_numpy(np.concatenate(parts)).to(device), index)
+    return hit
+
+
 def noise_files(noise_dir, sample_rate):
     """Every *.wav under noise_dir (recursive, sorted: the population the noise draw picks from) and their lengths in samples.
     Refuses, at start-up: a missing or empty directory, audio of another format (the reference would pick it up too, so skipping it
@@ -300,7 +376,9 @@ def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, wind
     normalisation (data_loader.py:49-53), and the frame counts.
     aug: the loader's (B, 6) float64 draws {input samples, tempo (0: none), gain dB, noise clip (-1: none), noise start s, level}
     (utils/data_loader.py); they are applied on the device first (ops.augment_wave) and `input_sizes` are then the samples after
-    the tempo change.  noise_dir: the directory the clip indices refer to.
+    the tempo change.  noise_dir: the directory the clip indices refer to.  With --speed-perturb the draws are (B, 7), the seventh
+    column the speed factor in thousandths (0 or 1000: none): the batch is resampled first (ops.resample), tempo / gain / noise then
+    work on the resampled waveforms, and `input_sizes` count the samples after both.
     spec: the loader's (B, 40) int32 SpecAugment rows; their n must be the kept frame counts of this batch.
     Normalisation, cut and SpecAugment are then one launch (asr_spect_finish_aug).
     features="fbank": (B,1,num_mel_bins,T) log-mel filterbank features instead (log_mel_fbank's; asr_fbank_finish[_aug])."""
@@ -315,6 +393,12 @@ def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, wind
     wav = inputs.reshape(inputs.shape[0], inputs.shape[-1]).float().contiguous()
     if aug is not None:
         aug = torch.as_tensor(aug, dtype=torch.float64)
+        if aug.shape[1] == 7:
+            # speed perturbation first: the resampled batch and its lengths then take the place of the loader's
+            speed = aug[:, 6].long()
+            wav, _ = ops.resample(wav, aug[:, 0].long(), speed)
+            aug = aug[:, :6].clone()
+            aug[:, 0] = aug.new_tensor([speed_length(n, p) if p else n for n, p in zip(aug[:, 0].long().tolist(), speed.tolist())])
         bank = noise_bank(noise_dir, sample_rate, wav.device) if (aug[:, 3] >= 0).any() else None
         wav, lens = ops.augment_wave(wav, aug[:, 0].long(), aug[:, 1:], bank, sample_rate=sample_rate)
         if not torch.equal(torch.as_tensor(input_sizes).long(), aug[:, 0].new_tensor(

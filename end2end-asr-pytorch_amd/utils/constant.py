@@ -13,6 +13,9 @@ Differences that do not change old command lines:
     fp32 MFMA DFT + asr_spect_finish) instead of on the host in the DataLoader workers;
   * `--spec-augment` (+ `--spec-time-warp/-freq-mask/-freq-masks/-time-mask/-time-masks/-time-mask-ratio`): SpecAugment of the
     training batches on the GPU front end;
+  * `--speed-perturb F [F ...]`: speed perturbation of the training utterances on the GPU front end -- each is resampled (band-limited,
+    csrc/resample.hip) by a factor drawn from the list, e.g. 0.9 1.0 1.1, before tempo / gain / noise; factors in [0.5, 2.0], rounded to
+    thousandths (DESIGN.md section 7);
   * `--features {spect,fbank}` (+ `--num-mel-bins`, `--mel-fmin`): the reference's 161 linear log1p(|STFT|) bins (default) or log-mel
     filterbank features of the same STFT (DESIGN.md section 7), on the host path and on the GPU front end alike;
   * `--conv-module-kernel K` (odd, 3..31; 0 = off): a Conformer-style convolution module in every encoder layer (DESIGN.md section 7);
@@ -29,6 +32,16 @@ import torch
 
 # (flags, kwargs) -- one row per option of the reference CLI, grouped as in its --help
 _S, _I, _F = str, int, float
+
+
+def _speed_factor(text):
+    """One --speed-perturb factor, rounded to thousandths; outside [0.5, 2.0] the command line is refused."""
+    f = round(float(text) * 1000.0) / 1000.0
+    if not 0.5 <= f <= 2.0:
+        raise argparse.ArgumentTypeError("--speed-perturb %s: a speed factor lies in [0.5, 2.0]" % text)
+    return f
+
+
 _FLAGS = [
     # experiment
     (("--model",), dict(default="TRFS", type=_S)), (("--name",), dict(default="model")),
@@ -50,6 +63,9 @@ _FLAGS = [
     (("--augment",), dict(dest="augment", action="store_true")), (("--noise-dir",), dict(default=None)),
     (("--noise-prob",), dict(default=0.4)), (("--noise-min",), dict(default=0.0, type=_F)),
     (("--noise-max",), dict(default=0.5, type=_F)),
+    # speed perturbation on the GPU front end: every training utterance is resampled by one of these factors, drawn
+    # uniformly, e.g. 0.9 1.0 1.1; each is rounded to thousandths and must lie in [0.5, 2.0]; default: off
+    (("--speed-perturb",), dict(default=None, nargs="+", type=_speed_factor, metavar="F")),
     # SpecAugment on the GPU front end; defaults: the LibriSpeech "LD" policy of arXiv:1904.08779 (W 80, F 27,
     # mF 2, T 100, p 1.0, mT 2) -- on the 161 linear bins of --features spect; --features fbank gives the paper's 80 mel bins
     (("--spec-augment",), dict(action="store_true")), (("--spec-time-warp",), dict(default=80, type=_I)),

@@ -7,7 +7,9 @@
     {input samples, tempo (0: none), gain dB, noise clip (-1: none), noise start s, noise level}, and the batch is sorted by, and
     input_sizes / input_percentages count, the samples AFTER the tempo change (utils.audio.gpu_front_end applies the draws);
   * with SpecAugment (training dataset, GPU front end only) a 7th element: the (B, 40) int32 rows {n, c, w, nF, nT, 0, 0, 0,
-    8 x (f0, fw), 8 x (t0, tw)} of DESIGN.md section 7; the 6th element is then the wave draws or None.
+    8 x (f0, fw), 8 x (t0, tw)} of DESIGN.md section 7; the 6th element is then the wave draws or None;
+  * with speed perturbation (audio_conf['speed_perturb'], training dataset, GPU front end only) the draws are (B, 7): the seventh
+    column is the speed factor in thousandths, and the sizes count the samples after the speed AND the tempo change.
 BucketingSampler keeps the reference's consecutive bins and additionally shards them over data-parallel ranks.
 """
 import random
@@ -20,7 +22,7 @@ from torch.utils.data.sampler import Sampler
 from asr_hip.ddp import rank_shard
 from utils import constant
 from utils.audio import (FEATURES, load_audio, log_mel_fbank, log_spectrogram, mel_filterbank, noise_files, resolve_window, spec_frames,
-                         tempo_length)
+                         speed_length, speed_thousandths, tempo_length)
 
 TEMPO_RANGE, GAIN_RANGE = (0.85, 1.15), (-6, 8)          # reference: utils/audio.py:54
 SPEC_PARAMS, SPEC_MAX_MASKS = 40, 8                      # one SpecAugment row (include/asr_hip.h, ASR_SPEC_AUGMENT_PARAMS)
@@ -54,9 +56,14 @@ class SpectrogramParser(object):
             mel_filterbank(self.num_mel_bins, n_fft, self.sample_rate, self.mel_fmin)
         self.feature_bins = self.num_mel_bins if self.features == "fbank" else n_fft // 2 + 1
         self.noise_dir = audio_conf.get('noise_dir')
+        # speed perturbation: the factors in thousandths one is drawn from per utterance, or None
+        self.speed = speed_thousandths(audio_conf['speed_perturb']) if audio_conf.get('speed_perturb') else None
         if (augment or self.noise_dir is not None) and not getattr(constant.args, "gpu_frontend", False):
             raise NotImplementedError("tempo/gain augmentation (--augment) and noise injection (--noise-dir) run on the GPU front end "
                                       "only: use --cuda (it turns on --gpu-frontend)")
+        if self.speed is not None and not getattr(constant.args, "gpu_frontend", False):
+            raise NotImplementedError("speed perturbation (--speed-perturb) runs on the GPU front end only: use --cuda (it turns on "
+                                      "--gpu-frontend)")
         self.spec = None
         if spec_augment is not None:
             if not getattr(constant.args, "gpu_frontend", False):
@@ -78,19 +85,26 @@ class SpectrogramParser(object):
     def draw(self, n):
         """The random draws for an utterance of n samples, on the global np.random in the reference's call order
         (utils/audio.py:49-61, data_loader.py:62-70,160-170): (n, tempo, gain dB, noise clip, noise start s, level, n_out) with
-        tempo 0 = no tempo / gain, clip -1 = no noise; tempo and gain rounded through "%.3f" as sox's command line."""
+        tempo 0 = no tempo / gain, clip -1 = no noise; tempo and gain rounded through "%.3f" as sox's command line.
+        With speed perturbation ONE more draw comes first, the index of the factor, and the tuple gains an 8th element, the factor p
+        in thousandths; n_out then counts the samples after the speed and the tempo change."""
         tempo = gain = 0.0
         n_out = n
+        if self.speed is not None:
+            p = self.speed[np.random.randint(len(self.speed))]
+            n_out = speed_length(n, p)
         if self.augment:
             tempo = float("%.3f" % np.random.uniform(low=TEMPO_RANGE[0], high=TEMPO_RANGE[1]))
             gain = float("%.3f" % np.random.uniform(low=GAIN_RANGE[0], high=GAIN_RANGE[1]))
-            n_out = tempo_length(n, tempo)
+            n_out = tempo_length(n_out, tempo)
         clip, start_s, level = -1, 0.0, 0.0
         if self.noise_paths is not None and np.random.binomial(1, self.noise_prob):
             clip = self.noise_index[np.random.choice(self.noise_paths)]
             level = float(np.random.uniform(*self.noise_levels))
             data_len = n_out / self.sample_rate
             start_s = float(np.random.rand() * (self.noise_lens[clip] / self.sample_rate - data_len))
+        if self.speed is not None:
+            return (n, tempo, gain, clip, start_s, level, n_out, p)
         return (n, tempo, gain, clip, start_s, level, n_out)
 
     def draw_spec(self, samples):
@@ -115,7 +129,7 @@ class SpectrogramParser(object):
 
     @property
     def augmenting(self):
-        return self.augment or self.noise_paths is not None
+        return self.augment or self.noise_paths is not None or self.speed is not None
 
     def parse_audio(self, audio_path):
         y = load_audio(audio_path)
@@ -169,7 +183,7 @@ class SpectrogramDataset(Dataset, SpectrogramParser):
 def _collate_fn(batch):
     aug = len(batch[0]) > 2 and batch[0][2] is not None
     spec_rows = len(batch[0]) > 3
-    size = (lambda s: s[2][6]) if aug else (lambda s: s[0].size(1))      # augmented: samples after the tempo change
+    size = (lambda s: s[2][6]) if aug else (lambda s: s[0].size(1))      # augmented: samples after the speed / tempo change
     batch = sorted(batch, key=size, reverse=True)
     B = len(batch)
     t_max = max(s[0].size(1) for s in batch)
@@ -189,7 +203,8 @@ def _collate_fn(batch):
         input_percentages[i] = size(s) / float(n_max)
         target_sizes[i] = len(tgt)
         targets[i, :len(tgt)] = torch.tensor(tgt, dtype=torch.int64)
-    draws = torch.tensor([s[2][:6] for s in batch], dtype=torch.float64) if aug else None
+    # speed perturbation: a seventh column, the factor in thousandths
+    draws = torch.tensor([s[2][:6] + s[2][7:8] for s in batch], dtype=torch.float64) if aug else None
     if spec_rows:
         return inputs, targets, input_percentages, input_sizes, target_sizes, draws, torch.tensor([s[3] for s in batch], dtype=torch.int32)
     if aug:

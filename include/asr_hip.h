@@ -660,6 +660,21 @@ int asr_augment_wave(const float* wav, int64_t wav_stride, const int32_t* lens, 
                      const int64_t* bank_off, const int64_t* bank_len, int nclips, float* out, int64_t out_stride, int32_t* offsets,
                      int64_t off_stride, int B, int S, int search, int O, asr_stream_t stream);
 
+/* ---- speed perturbation: band-limited resampling of the training waveforms by a rational factor num / den per utterance (no
+ * counterpart in the reference; Ko et al., Interspeech 2015; definition in DESIGN.md section 7).  wav (B, wav_stride) fp32, lens (B)
+ * samples; plan (B, 8) int32 on the device = {num, den, R, table offset in floats, n_out, 0, 0, 0}; table: the concatenated tap
+ * tables H (den, 2R) fp32 of the distinct factors of the batch, table_floats in all.  Output m of utterance b sits at input position
+ * m num / den = i + phi / den (64-bit integers) and is the fmaf chain, in ascending q from +0.0,
+ *   y[m] = sum_{q < 2R} H[phi][q] x[i + q - R + 1],  x = 0 outside [0, lens[b]).
+ * Columns [0, out_cols) of row b of out (B, out_stride >= out_cols) are written: y[m] for m < n_out, +0.0 from n_out on; nothing at or
+ * beyond out_cols.  A row with num == den is copied.  ASR_EINVAL for bad geometry (B, strides, out_cols); the plan is device data and
+ * is the caller's to validate (1 <= num, 1 <= den <= 1000, R >= 1, offset + den 2R <= table_floats, n_out <= out_cols) -- the kernel
+ * clamps what it reads: n_out to [0, out_cols], and a row whose plan breaks the rest is written as zeros.  One workgroup computes
+ * ASR_RESAMPLE_TILE consecutive outputs.  No atomics: the same inputs give the same bits.                                        */
+#define ASR_RESAMPLE_TILE 1024
+int asr_resample(const float* wav, int64_t wav_stride, const int32_t* lens, const int32_t* plan, const float* table,
+                 int64_t table_floats, float* out, int64_t out_stride, int out_cols, int B, asr_stream_t stream);
+
 /* ---- SpecAugment of the normalised log-spectrogram (no counterpart in the reference; Park et al. 2019, arXiv:1904.08779: time warp,
  * frequency masks, time masks; definition in DESIGN.md section 7).  params (B, ASR_SPEC_AUGMENT_PARAMS) int32 on the device, one row
  * per utterance: {n, c, w, nF, nT, 0, 0, 0, 8 x (f0, fw), 8 x (t0, tw)}.  n: kept frames (clamped to [0, T_out]); the warp moves frame c
