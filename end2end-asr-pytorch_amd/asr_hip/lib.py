@@ -137,6 +137,7 @@ _SIGS = {
     "asr_spect_finish": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "asr_augment_wave": (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
     "asr_resample": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _P]),
+    "asr_reverb": (_I, [_P, _L, _P, _P, _P, _L, _P, _P, _I, _P, _L, _I, _I, _P]),
     "asr_spec_augment": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _P]),
     "asr_spect_finish_aug": (_I, [_P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "asr_fbank_finish": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P]),

@@ -1717,6 +1717,52 @@ def resample(wav, lens, p, tables=None, out=None):
     return out, torch.from_numpy(plan[:, 4].astype(np.int32)).to(dev)
 
 
+REVERB_TILE, REVERB_CHUNK = 2048, 512        # outputs per workgroup and taps per staged span of asr_reverb (include/asr_hip.h)
+
+
+def reverb(wav, lens, rir, bank, out=None):
+    """Reverberation with room impulse responses (asr_reverb) of padded waveforms wav (B, L) fp32 on the device:
+    row b is convolved with the prepared taps of response rir[b] of `bank` (utils.audio.RirBank), -1 = none (the row is copied);
+    y[m] = sum_{k <= m} h[k] x[m - k] for m < lens[b], one fp32 fmaf chain in ascending k; the length does not change and the tail
+    behind it is cut.  Returns (B, L) fp32, zero from lens[b] on; with every index -1 and no `out` the input itself comes back and
+    nothing is launched.  out: a caller's (B, >= L) buffer that does not overlap wav, every column of which is written.  Lengths
+    and indices are checked here, before any launch -- the kernel clamps what it reads; what it would have to clamp is a caller's
+    mistake."""
+    import numpy as np
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
+        raise ValueError("reverb: the waveforms must be a contiguous (B, L) fp32 tensor, got %s %s with strides %s"
+                         % (tuple(wav.shape), wav.dtype, wav.stride()))
+    B, Lmax = wav.shape
+    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
+    idx = torch.as_tensor(rir).cpu().numpy().astype(np.int64).reshape(B)
+    if (n_in < 0).any() or (n_in > Lmax).any():
+        raise ValueError("reverb: lengths outside [0, %d]" % Lmax)
+    count = 0 if bank is None else len(bank)
+    if (idx < -1).any() or (idx >= count).any():
+        raise ValueError("reverb: RIR indices are -1 (none) or 0 .. %d, got %s" % (count - 1, idx.tolist()))
+    dev = wav.device
+    if bank is not None and bank.data.device != dev:
+        raise ValueError("reverb: the RIR bank lives on %s, the waveforms on %s" % (bank.data.device, dev))
+    if not (idx >= 0).any() and out is None:
+        return wav
+    if out is None:
+        out = torch.empty((B, max(Lmax, 1)), device=dev, dtype=torch.float32)[:, :Lmax]
+    if out.dim() != 2 or out.dtype != torch.float32 or out.device != dev or out.shape[0] != B or out.shape[1] < Lmax or \
+            (out.shape[1] > 1 and out.stride(1) != 1) or (B > 1 and out.stride(0) < out.shape[1]):
+        raise ValueError("reverb: out must be (%d, >= %d) fp32 on %s with unit column stride and rows that do not overlap" % (B, Lmax, dev))
+    if out.untyped_storage().data_ptr() == wav.untyped_storage().data_ptr():
+        raise ValueError("reverb: out must be another buffer than the waveforms (an output depends on thousands of earlier samples)")
+    if B == 0 or out.shape[1] == 0:
+        return out
+    lens_dev, idx_dev = torch.from_numpy(n_in.astype(np.int32)).to(dev), torch.from_numpy(idx.astype(np.int32)).to(dev)
+    ld_out = out.stride(0) if B > 1 else max(out.stride(0), out.shape[1])       # a single row's stride is arbitrary
+    ld_in = wav.stride(0) if B > 1 else max(wav.stride(0), Lmax)
+    taps, offs, counts = (None, None, None) if bank is None else (bank.data, bank.offsets, bank.lens)     # no bank: every row is copied
+    L.call("asr_reverb", L.ptr(wav), ld_in, L.ptr(lens_dev), L.ptr(idx_dev), L.ptr(taps), 0 if taps is None else taps.numel(),
+           L.ptr(offs), L.ptr(counts), count, L.ptr(out), ld_out, out.shape[1], B, L.stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ LSTM language model (fp32)
 def lm_proj(x, w, bias, K, ids=None):
     """(M, N) fp32 = X w^T + bias, X row m = x[ids[m]] (int32 ids) or x[m]; x / w zero-padded to 16 * ceil(K / 16) columns."""

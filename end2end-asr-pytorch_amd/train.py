@@ -32,11 +32,13 @@ def build_labels(path):
 
 
 def build_datasets(args, audio_conf, label2id):
-    """(training dataset, [validation datasets]): tempo / gain draws, speed perturbation and SpecAugment belong to the training dataset
-    alone."""
+    """(training dataset, [validation datasets]): tempo / gain draws, speed perturbation, reverberation and SpecAugment belong to the
+    training dataset alone."""
     from utils.data_loader import SpectrogramDataset, spec_policy
     speed = getattr(args, "speed_perturb", None)
     train_conf = dict(audio_conf, speed_perturb=list(speed)) if speed else audio_conf
+    if getattr(args, "rir_dir", None) is not None:
+        train_conf = dict(train_conf, rir_dir=args.rir_dir, rir_prob=args.rir_prob, rir_max_ms=args.rir_max_ms)
     train_data = SpectrogramDataset(train_conf, manifest_filepath_list=args.train_manifest_list, label2id=label2id,
                                     normalize=True, augment=args.augment, spec_augment=spec_policy(args))
     valid = [SpectrogramDataset(audio_conf, manifest_filepath_list=[m], label2id=label2id, normalize=True, augment=False)
@@ -46,7 +48,8 @@ def build_datasets(args, audio_conf, label2id):
 
 def augments_on_the_front_end(args):
     """A run whose augmentations exist on the GPU front end only: with --cuda, main() turns --gpu-frontend on for it."""
-    return bool(args.augment or args.noise_dir is not None or args.spec_augment or getattr(args, "speed_perturb", None))
+    return bool(args.augment or args.noise_dir is not None or args.spec_augment or getattr(args, "speed_perturb", None)
+                or getattr(args, "rir_dir", None) is not None)
 
 
 DEFAULT_GRAPH_BUCKET = 64
@@ -117,13 +120,14 @@ def main():
                       mel_fmin=args.mel_fmin)
     logging.info(audio_conf)
     if augments_on_the_front_end(args) and args.cuda and not args.gpu_frontend:
-        # speed perturbation (csrc/resample.hip), tempo / gain augmentation and noise injection (csrc/augment.hip) run between the
-        # host-to-device copy and the STFT, SpecAugment in the front end's last pass (csrc/spec_augment.hip)
+        # speed perturbation (csrc/resample.hip), reverberation (csrc/reverb.hip), tempo / gain augmentation and noise injection
+        # (csrc/augment.hip) run between the host-to-device copy and the STFT, SpecAugment in the front end's last pass
+        # (csrc/spec_augment.hip)
         args.gpu_frontend = True
-        logging.info("--augment / --noise-dir / --spec-augment / --speed-perturb: --gpu-frontend turned on")
+        logging.info("--augment / --noise-dir / --spec-augment / --speed-perturb / --rir-dir: --gpu-frontend turned on")
         if rank0:
-            print("--augment / --noise-dir / --spec-augment / --speed-perturb: speed, tempo, gain, noise and SpecAugment run on the GPU "
-                  "front end (--gpu-frontend turned on)")
+            print("--augment / --noise-dir / --spec-augment / --speed-perturb / --rir-dir: speed, reverberation, tempo, gain, noise and "
+                  "SpecAugment run on the GPU front end (--gpu-frontend turned on)")
     label2id, id2label = build_labels(args.labels_path)
 
     train_data, valid_datas = build_datasets(args, audio_conf, label2id)

@@ -207,7 +207,8 @@ class Trainer():
             src, src_lengths = gpu_front_end(src, src_lengths, a.sample_rate, a.window_size, a.window_stride, a.src_max_len,
                                              window=a.window, aug=aug, noise_dir=a.noise_dir, spec=spec,
                                              features=getattr(a, "features", "spect"), num_mel_bins=getattr(a, "num_mel_bins", 80),
-                                             mel_fmin=getattr(a, "mel_fmin", 20.0))
+                                             mel_fmin=getattr(a, "mel_fmin", 20.0), rir_dir=getattr(a, "rir_dir", None),
+                                             rir_max_ms=getattr(a, "rir_max_ms", 500))
         # --ctc-weight > 0 (joint CTC / attention training): L = (1 - w) CE + w CTC on the encoder's CTC head.
         # The hybrid step runs on the eager path; capturing it is a follow-up.
         ctc_weight = float(getattr(constant.args, "ctc_weight", 0.0) or 0.0)

@@ -5,6 +5,8 @@ data_loader.py:145-179) run on the GPU instead (asr_augment_wave, csrc/augment.h
 keeps the random draws (utils/data_loader.py), gpu_front_end applies them to the batch before the STFT.
 --speed-perturb (no counterpart in the reference): band-limited resampling by a factor drawn per utterance (speed_ratio, speed_length,
 resample_table; asr_resample, csrc/resample.hip), ahead of tempo / gain / noise.
+--rir-dir (no counterpart in the reference): reverberation with recorded room impulse responses (rir_files, prepare_rir, RirBank;
+asr_reverb, csrc/reverb.hip), after the speed change and ahead of tempo / gain / noise.
 --features fbank (no counterpart in the reference): log-mel filterbank features of the same STFT (mel_filterbank, log_mel_fbank;
 definition in DESIGN.md section 7).
 """
@@ -286,30 +288,36 @@ def device_resample_tables(factors, device):
     return hit
 
 
-def noise_files(noise_dir, sample_rate):
-    """Every *.wav under noise_dir (recursive, sorted: the population the noise draw picks from) and their lengths in samples.
-    Refuses, at start-up: a missing or empty directory, audio of another format (the reference would pick it up too, so skipping it
-    would change the draws) and a sample rate other than --sample-rate (noise clips are not resampled)."""
-    if not os.path.isdir(noise_dir):
-        raise ValueError("--noise-dir %s is not a directory" % noise_dir)
+def _wav_files(directory, sample_rate, flag, what):
+    """Every *.wav under `directory` (recursive, sorted) and their lengths in samples, under the rules --noise-dir and --rir-dir share:
+    refuses a missing or empty directory, audio of another format, and a sample rate other than --sample-rate."""
+    if not os.path.isdir(directory):
+        raise ValueError("%s %s is not a directory" % (flag, directory))
     paths, other = [], []
-    for p in glob.glob(os.path.join(noise_dir, "**", "*"), recursive=True):
+    for p in glob.glob(os.path.join(directory, "**", "*"), recursive=True):
         ext = os.path.splitext(p)[1].lower()
         if os.path.isfile(p) and ext in AUDIO_EXTENSIONS:
             (paths if ext == ".wav" else other).append(p)
     if other:
-        raise ValueError("--noise-dir %s holds non-wav audio (%s): only .wav noise clips are supported" % (noise_dir, sorted(other)[0]))
+        raise ValueError("%s %s holds non-wav audio (%s): only .wav %ss are supported" % (flag, directory, sorted(other)[0], what))
     if not paths:
-        raise ValueError("--noise-dir %s holds no .wav files" % noise_dir)
+        raise ValueError("%s %s holds no .wav files" % (flag, directory))
     paths.sort()
     lens = []
     for p in paths:
         with wave.open(p, "rb") as f:
             if f.getframerate() != sample_rate:
-                raise ValueError("noise clip %s has sample rate %d, not --sample-rate %d (noise clips are not resampled)"
-                                 % (p, f.getframerate(), sample_rate))
+                raise ValueError("%s %s has sample rate %d, not --sample-rate %d (%ss are not resampled)"
+                                 % (what, p, f.getframerate(), sample_rate, what))
             lens.append(f.getnframes())
     return paths, lens
+
+
+def noise_files(noise_dir, sample_rate):
+    """Every *.wav under noise_dir (recursive, sorted: the population the noise draw picks from) and their lengths in samples.
+    Refuses, at start-up: a missing or empty directory, audio of another format (the reference would pick it up too, so skipping it
+    would change the draws) and a sample rate other than --sample-rate (noise clips are not resampled)."""
+    return _wav_files(noise_dir, sample_rate, "--noise-dir", "noise clip")
 
 
 def load_pcm16(path):
@@ -349,6 +357,96 @@ def noise_bank(noise_dir, sample_rate, device):
     return bank
 
 
+# ------------------------------------------------------------------------------------------------ reverberation
+RIR_TAIL = 1e-3                               # taps behind the last one at or above -60 dB of the direct path are dropped
+
+
+def rir_files(rir_dir, sample_rate):
+    """Every *.wav under rir_dir (recursive, sorted: the population the RIR draw indexes) and their lengths in samples, under
+    noise_files' rules: refuses a missing or empty directory, non-wav audio and a sample rate other than --sample-rate."""
+    return _wav_files(rir_dir, sample_rate, "--rir-dir", "room impulse response")
+
+
+def prepare_rir(h, sample_rate, max_ms):
+    """The taps of one recorded room impulse response h, in float64 until the last step: the samples before
+    the direct path (the FIRST index of max |h|) are dropped, so that it sits at lag 0 and the transcript stays aligned; at most
+    floor(max_ms sample_rate / 1000) >= 1 taps are kept; the tail behind the last tap with |h[k]| >= 1e-3 |h[k0]| is dropped; the
+    rest is divided by sqrt(sum h^2) and cast to float32.  Refuses an empty or all-zero response."""
+    h = np.asarray(h, dtype=np.float64).reshape(-1)
+    cap = int(np.floor(float(max_ms) * int(sample_rate) / 1000.0))
+    if cap < 1:
+        raise ValueError("--rir-max-ms %s keeps no tap at %d Hz" % (max_ms, sample_rate))
+    if h.size == 0 or not np.any(h):
+        raise ValueError("an empty or all-zero room impulse response")
+    mag = np.abs(h)
+    k0 = int(np.argmax(mag))
+    h, mag = h[k0:k0 + cap], mag[k0:k0 + cap]
+    h = h[:int(np.nonzero(mag >= RIR_TAIL * mag[0])[0][-1]) + 1]
+    return (h / np.sqrt(np.sum(h * h))).astype(np.float32)
+
+
+_prepared_rirs = {}
+
+
+def prepared_rirs(rir_dir, sample_rate, max_ms):
+    """(paths, [taps]) of every response under rir_dir, prepared once per (directory, sample rate, max_ms) on the host.  The training
+    dataset calls it at start-up, so that a directory or a file that is refused is refused before the first batch."""
+    key = (os.path.abspath(rir_dir), int(sample_rate), float(max_ms))
+    hit = _prepared_rirs.get(key)
+    if hit is None:
+        paths, _ = rir_files(rir_dir, sample_rate)
+        taps = []
+        for p in paths:
+            try:
+                taps.append(prepare_rir(load_audio(p), sample_rate, max_ms))
+            except ValueError as e:
+                raise ValueError("--rir-dir: %s: %s" % (p, e))
+        hit = _prepared_rirs[key] = (paths, taps)
+    return hit
+
+
+class RirBank:
+    """The prepared taps of all room impulse responses concatenated as fp32 on the device, with per-response offsets and lengths
+    (int64), as asr_reverb reads them; len() = the number of responses."""
+
+    def __init__(self, rir_dir, sample_rate, max_ms, device):
+        self.paths, taps = prepared_rirs(rir_dir, sample_rate, max_ms)
+        self._upload(taps, device)
+
+    @classmethod
+    def from_arrays(cls, taps, device):
+        """A bank of the given float32 tap arrays as they are, without prepare_rir (tests inject exact taps)."""
+        self = cls.__new__(cls)
+        self.paths = None
+        self._upload([np.ascontiguousarray(t, dtype=np.float32).reshape(-1) for t in taps], device)
+        return self
+
+    def _upload(self, taps, device):
+        import torch
+        if not taps or any(t.size < 1 for t in taps):
+            raise ValueError("a RIR bank needs at least one response and every response at least one tap")
+        self.lengths = np.array([t.size for t in taps], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.data = torch.from_numpy(np.concatenate(taps)).to(device)
+        self.offsets = torch.from_numpy(offs).to(device)
+        self.lens = torch.from_numpy(self.lengths).to(device)
+
+    def __len__(self):
+        return int(self.lengths.size)
+
+
+_rir_banks = {}
+
+
+def rir_bank(rir_dir, sample_rate, max_ms, device):
+    """The RirBank of (rir_dir, sample_rate, max_ms, device), built once per process like noise_bank."""
+    key = (os.path.abspath(rir_dir), int(sample_rate), float(max_ms), str(device))
+    bank = _rir_banks.get(key)
+    if bank is None:
+        bank = _rir_banks[key] = RirBank(rir_dir, sample_rate, max_ms, device)
+    return bank
+
+
 def spec_frames(samples, hop, src_max_len=None):
     """Frames the front end keeps of an utterance of `samples` samples: min(1 + max(samples, 2) // hop, --src-max-len)."""
     n = 1 + max(int(samples), 2) // int(hop)
@@ -369,7 +467,7 @@ def _device_mel_bank(M, n_fft, sample_rate, f_min, device):
 
 
 def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, window_stride=0.01, src_max_len=None, window="hamming",
-                  aug=None, noise_dir=None, spec=None, features="spect", num_mel_bins=80, mel_fmin=20.0):
+                  aug=None, noise_dir=None, spec=None, features="spect", num_mel_bins=80, mel_fmin=20.0, rir_dir=None, rir_max_ms=500):
     """--gpu-frontend: `inputs` (B,1,1,Lmax) are the loader's zero padded WAVEFORMS and `input_sizes` (B) their sample
     counts (the collate function is unchanged: a waveform is a 1-bin "spectrogram").  Returns what the host path would have
     put in the batch: log-spectrograms (B,1,F,T) normalised per utterance, cut to --src-max-len frames AFTER the
@@ -378,7 +476,10 @@ def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, wind
     (utils/data_loader.py); they are applied on the device first (ops.augment_wave) and `input_sizes` are then the samples after
     the tempo change.  noise_dir: the directory the clip indices refer to.  With --speed-perturb the draws are (B, 7), the seventh
     column the speed factor in thousandths (0 or 1000: none): the batch is resampled first (ops.resample), tempo / gain / noise then
-    work on the resampled waveforms, and `input_sizes` count the samples after both.
+    work on the resampled waveforms, and `input_sizes` count the samples after both.  With --rir-dir the draws are (B, 8): column 6
+    is the speed factor (0 without --speed-perturb), column 7 the index of the room impulse response among rir_files(rir_dir) (-1:
+    none).  The order is speed, then reverberation (ops.reverb: the length does not change), then tempo / gain / noise -- noise is
+    added to the reverberant speech and is not itself reverberated.
     spec: the loader's (B, 40) int32 SpecAugment rows; their n must be the kept frame counts of this batch.
     Normalisation, cut and SpecAugment are then one launch (asr_spect_finish_aug).
     features="fbank": (B,1,num_mel_bins,T) log-mel filterbank features instead (log_mel_fbank's; asr_fbank_finish[_aug])."""
@@ -393,12 +494,18 @@ def gpu_front_end(inputs, input_sizes, sample_rate=16000, window_size=0.02, wind
     wav = inputs.reshape(inputs.shape[0], inputs.shape[-1]).float().contiguous()
     if aug is not None:
         aug = torch.as_tensor(aug, dtype=torch.float64)
-        if aug.shape[1] == 7:
+        rir = aug[:, 7].long() if aug.shape[1] == 8 else None
+        if aug.shape[1] >= 7:
             # speed perturbation first: the resampled batch and its lengths then take the place of the loader's
             speed = aug[:, 6].long()
             wav, _ = ops.resample(wav, aug[:, 0].long(), speed)
             aug = aug[:, :6].clone()
             aug[:, 0] = aug.new_tensor([speed_length(n, p) if p else n for n, p in zip(aug[:, 0].long().tolist(), speed.tolist())])
+        if rir is not None and (rir >= 0).any():
+            # then the room: the taps' direct path sits at lag 0 and the length stays, so the sizes and the transcript's alignment do too
+            if rir_dir is None:
+                raise ValueError("the draws name room impulse responses but no rir_dir is given")
+            wav = ops.reverb(wav, aug[:, 0].long(), rir, rir_bank(rir_dir, sample_rate, rir_max_ms, wav.device))
         bank = noise_bank(noise_dir, sample_rate, wav.device) if (aug[:, 3] >= 0).any() else None
         wav, lens = ops.augment_wave(wav, aug[:, 0].long(), aug[:, 1:], bank, sample_rate=sample_rate)
         if not torch.equal(torch.as_tensor(input_sizes).long(), aug[:, 0].new_tensor(

@@ -16,6 +16,9 @@ Differences that do not change old command lines:
   * `--speed-perturb F [F ...]`: speed perturbation of the training utterances on the GPU front end -- each is resampled (band-limited,
     csrc/resample.hip) by a factor drawn from the list, e.g. 0.9 1.0 1.1, before tempo / gain / noise; factors in [0.5, 2.0], rounded to
     thousandths (DESIGN.md section 7);
+  * `--rir-dir DIR` (+ `--rir-prob P`, `--rir-max-ms MS`): reverberation of the training utterances on the GPU front end -- with
+    probability P (default 0.5) an utterance is convolved (csrc/reverb.hip) with one of the recorded room impulse responses under DIR,
+    cut to MS milliseconds (default 500), after the speed change and before tempo / gain / noise (DESIGN.md section 7);
   * `--features {spect,fbank}` (+ `--num-mel-bins`, `--mel-fmin`): the reference's 161 linear log1p(|STFT|) bins (default) or log-mel
     filterbank features of the same STFT (DESIGN.md section 7), on the host path and on the GPU front end alike;
   * `--conv-module-kernel K` (odd, 3..31; 0 = off): a Conformer-style convolution module in every encoder layer (DESIGN.md section 7);
@@ -42,6 +45,22 @@ def _speed_factor(text):
     return f
 
 
+def _probability(text):
+    """--rir-prob: a probability in [0, 1]."""
+    p = float(text)
+    if not 0.0 <= p <= 1.0:
+        raise argparse.ArgumentTypeError("%s: a probability lies in [0, 1]" % text)
+    return p
+
+
+def _positive(text):
+    """--rir-max-ms: a number above 0."""
+    v = float(text)
+    if not v > 0.0:
+        raise argparse.ArgumentTypeError("%s: must be above 0" % text)
+    return v
+
+
 _FLAGS = [
     # experiment
     (("--model",), dict(default="TRFS", type=_S)), (("--name",), dict(default="model")),
@@ -66,6 +85,10 @@ _FLAGS = [
     # speed perturbation on the GPU front end: every training utterance is resampled by one of these factors, drawn
     # uniformly, e.g. 0.9 1.0 1.1; each is rounded to thousandths and must lie in [0.5, 2.0]; default: off
     (("--speed-perturb",), dict(default=None, nargs="+", type=_speed_factor, metavar="F")),
+    # reverberation on the GPU front end: with probability --rir-prob a training utterance is convolved with one of
+    # the room impulse responses (*.wav at --sample-rate) under --rir-dir, each cut to --rir-max-ms behind its direct path; default: off
+    (("--rir-dir",), dict(default=None)), (("--rir-prob",), dict(default=0.5, type=_probability)),
+    (("--rir-max-ms",), dict(default=500.0, type=_positive)),
     # SpecAugment on the GPU front end; defaults: the LibriSpeech "LD" policy of arXiv:1904.08779 (W 80, F 27,
     # mF 2, T 100, p 1.0, mT 2) -- on the 161 linear bins of --features spect; --features fbank gives the paper's 80 mel bins
     (("--spec-augment",), dict(action="store_true")), (("--spec-time-warp",), dict(default=80, type=_I)),

@@ -9,7 +9,9 @@
   * with SpecAugment (training dataset, GPU front end only) a 7th element: the (B, 40) int32 rows {n, c, w, nF, nT, 0, 0, 0,
     8 x (f0, fw), 8 x (t0, tw)} of DESIGN.md section 7; the 6th element is then the wave draws or None;
   * with speed perturbation (audio_conf['speed_perturb'], training dataset, GPU front end only) the draws are (B, 7): the seventh
-    column is the speed factor in thousandths, and the sizes count the samples after the speed AND the tempo change.
+    column is the speed factor in thousandths, and the sizes count the samples after the speed AND the tempo change;
+  * with reverberation (audio_conf['rir_dir'], training dataset, GPU front end only) the draws are (B, 8): column 6 is the speed factor
+    (0 without speed perturbation), column 7 the index of the utterance's room impulse response (-1: none).
 BucketingSampler keeps the reference's consecutive bins and additionally shards them over data-parallel ranks.
 """
 import random
@@ -22,7 +24,7 @@ from torch.utils.data.sampler import Sampler
 from asr_hip.ddp import rank_shard
 from utils import constant
 from utils.audio import (FEATURES, load_audio, log_mel_fbank, log_spectrogram, mel_filterbank, noise_files, resolve_window, spec_frames,
-                         speed_length, speed_thousandths, tempo_length)
+                         prepared_rirs, speed_length, speed_thousandths, tempo_length)
 
 TEMPO_RANGE, GAIN_RANGE = (0.85, 1.15), (-6, 8)          # reference: utils/audio.py:54
 SPEC_PARAMS, SPEC_MAX_MASKS = 40, 8                      # one SpecAugment row (include/asr_hip.h, ASR_SPEC_AUGMENT_PARAMS)
@@ -64,6 +66,16 @@ class SpectrogramParser(object):
         if self.speed is not None and not getattr(constant.args, "gpu_frontend", False):
             raise NotImplementedError("speed perturbation (--speed-perturb) runs on the GPU front end only: use --cuda (it turns on "
                                       "--gpu-frontend)")
+        # reverberation: the number of room impulse responses an index is drawn from with probability rir_prob, or None
+        self.rir_dir, self.rir_count = audio_conf.get('rir_dir'), None
+        if self.rir_dir is not None:
+            if not getattr(constant.args, "gpu_frontend", False):
+                raise NotImplementedError("reverberation (--rir-dir) runs on the GPU front end only: use --cuda (it turns on "
+                                          "--gpu-frontend)")
+            self.rir_prob, self.rir_max_ms = float(audio_conf.get('rir_prob', 0.5)), float(audio_conf.get('rir_max_ms', 500))
+            if not 0.0 <= self.rir_prob <= 1.0 or not self.rir_max_ms > 0:
+                raise ValueError("--rir-prob %g must lie in [0, 1] and --rir-max-ms %g above 0" % (self.rir_prob, self.rir_max_ms))
+            self.rir_count = len(prepared_rirs(self.rir_dir, self.sample_rate, self.rir_max_ms)[0])
         self.spec = None
         if spec_augment is not None:
             if not getattr(constant.args, "gpu_frontend", False):
@@ -87,7 +99,10 @@ class SpectrogramParser(object):
         (utils/audio.py:49-61, data_loader.py:62-70,160-170): (n, tempo, gain dB, noise clip, noise start s, level, n_out) with
         tempo 0 = no tempo / gain, clip -1 = no noise; tempo and gain rounded through "%.3f" as sox's command line.
         With speed perturbation ONE more draw comes first, the index of the factor, and the tuple gains an 8th element, the factor p
-        in thousandths; n_out then counts the samples after the speed and the tempo change."""
+        in thousandths; n_out then counts the samples after the speed and the tempo change.
+        With reverberation the draws above come first and unchanged, then np.random.binomial(1, rir_prob) and, on a hit,
+        np.random.randint(number of RIRs); the tuple then has 9 elements: the first seven as above, p (0 without speed perturbation)
+        and the index of the room impulse response (-1: none).  The length does not change."""
         tempo = gain = 0.0
         n_out = n
         if self.speed is not None:
@@ -103,6 +118,9 @@ class SpectrogramParser(object):
             level = float(np.random.uniform(*self.noise_levels))
             data_len = n_out / self.sample_rate
             start_s = float(np.random.rand() * (self.noise_lens[clip] / self.sample_rate - data_len))
+        if self.rir_count is not None:
+            rir = int(np.random.randint(self.rir_count)) if np.random.binomial(1, self.rir_prob) else -1
+            return (n, tempo, gain, clip, start_s, level, n_out, p if self.speed is not None else 0, rir)
         if self.speed is not None:
             return (n, tempo, gain, clip, start_s, level, n_out, p)
         return (n, tempo, gain, clip, start_s, level, n_out)
@@ -129,7 +147,7 @@ class SpectrogramParser(object):
 
     @property
     def augmenting(self):
-        return self.augment or self.noise_paths is not None or self.speed is not None
+        return self.augment or self.noise_paths is not None or self.speed is not None or self.rir_count is not None
 
     def parse_audio(self, audio_path):
         y = load_audio(audio_path)
@@ -203,8 +221,8 @@ def _collate_fn(batch):
         input_percentages[i] = size(s) / float(n_max)
         target_sizes[i] = len(tgt)
         targets[i, :len(tgt)] = torch.tensor(tgt, dtype=torch.int64)
-    # speed perturbation: a seventh column, the factor in thousandths
-    draws = torch.tensor([s[2][:6] + s[2][7:8] for s in batch], dtype=torch.float64) if aug else None
+    # speed perturbation: a seventh column, the factor in thousandths; reverberation: an eighth, the index of the response
+    draws = torch.tensor([s[2][:6] + s[2][7:9] for s in batch], dtype=torch.float64) if aug else None
     if spec_rows:
         return inputs, targets, input_percentages, input_sizes, target_sizes, draws, torch.tensor([s[3] for s in batch], dtype=torch.int32)
     if aug:

@@ -675,6 +675,24 @@ int asr_augment_wave(const float* wav, int64_t wav_stride, const int32_t* lens, 
 int asr_resample(const float* wav, int64_t wav_stride, const int32_t* lens, const int32_t* plan, const float* table,
                  int64_t table_floats, float* out, int64_t out_stride, int out_cols, int B, asr_stream_t stream);
 
+/* ---- reverberation: the training waveforms convolved with recorded room impulse responses (no counterpart in the reference; Ko et
+ * al., ICASSP 2017; definition in DESIGN.md section 7).  wav (B, wav_stride) fp32, lens (B) samples; rir (B) int32 on the device: the
+ * row's response, -1 = none; bank: the prepared taps of all nrir responses concatenated (fp32, bank_floats in all; direct path at lag 0,
+ * unit energy: utils/audio.py prepare_rir), rir_off / rir_len (nrir) int64 on the device: where response r starts and its taps L >= 1.
+ * Output m < n = lens[b] of a row with r >= 0 is the fmaf chain, in ascending k from +0.0,
+ *   y[m] = sum_{k = 0}^{min(L - 1, m)} h[k] x[m - k]       (fp32; the length is unchanged, the tail behind n is cut; taps are finite).
+ * Columns [0, out_cols) of row b of out (B, out_stride >= out_cols) are written: y[m] below n, +0.0 from n on; nothing at or beyond
+ * out_cols.  A row with r = -1 is copied bit for bit.  out must not overlap wav.  ASR_EINVAL for bad geometry (B, strides, out_cols,
+ * counts); indices, offsets and lengths are device data and the caller's to validate -- the kernel clamps what it reads: n to
+ * [0, min(wav_stride, out_cols)], and a row whose index is outside [-1, nrir) or whose taps leave the bank is written as zeros.  One
+ * workgroup computes ASR_REVERB_TILE consecutive outputs and walks the taps in chunks of ASR_REVERB_CHUNK.  One launch, no atomics, no
+ * workspace: a row's bits depend on its samples, taps and length alone.                                                            */
+#define ASR_REVERB_TILE 2048
+#define ASR_REVERB_CHUNK 512
+int asr_reverb(const float* wav, int64_t wav_stride, const int32_t* lens, const int32_t* rir, const float* bank, int64_t bank_floats,
+               const int64_t* rir_off, const int64_t* rir_len, int nrir, float* out, int64_t out_stride, int out_cols, int B,
+               asr_stream_t stream);
+
 /* ---- SpecAugment of the normalised log-spectrogram (no counterpart in the reference; Park et al. 2019, arXiv:1904.08779: time warp,
  * frequency masks, time masks; definition in DESIGN.md section 7).  params (B, ASR_SPEC_AUGMENT_PARAMS) int32 on the device, one row
  * per utterance: {n, c, w, nF, nT, 0, 0, 0, 8 x (f0, fw), 8 x (t0, tw)}.  n: kept frames (clamped to [0, T_out]); the warp moves frame c
