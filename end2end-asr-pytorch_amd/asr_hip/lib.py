@@ -77,6 +77,9 @@ _SIGS = {
     "asr_ngram_logp": (_I, [_P, _P, _L, _I, _I, _P, _P, _L, _P, _P]),
     "asr_ctc_beam_search_lm": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _F, _F, _P,
                                     _P]),
+    "asr_ctx_step": (_I, [_P, _P, _L, _I, _P, _I, _P, _P, _L, _P, _P, _P]),
+    "asr_ctc_beam_search_ctx": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _F, _F, _P,
+                                     _P, _P, _L, _I, _P, _I, _F, _P, _P]),
     "asr_convmod_workspace": (_L, [_I, _I, _I, _I]),
     "asr_convmod_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "asr_convmod_bwd_data": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

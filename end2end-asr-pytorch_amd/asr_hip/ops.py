@@ -687,14 +687,31 @@ def ngram_logp(table, ctx, sym):
     return out
 
 
-def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0, ngram=None, alpha=0.0, beta=0.0, bos=1, eos=2):
+def context_step(table, state, sym):
+    """The phrase automaton's step (csrc/context.hip): table = ContextGraph.device_table(device), state and sym (n) int32 on the device
+    -> (next, delta), both (n) int32: ContextGraph.step(state[i], sym[i]) exactly."""
+    n = sym.numel()
+    assert sym.dtype == torch.int32 and sym.is_contiguous() and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == n
+    nxt = torch.empty((n,), device=sym.device, dtype=torch.int32)
+    delta = torch.empty((n,), device=sym.device, dtype=torch.int32)
+    L.call("asr_ctx_step", L.ptr(table["keys"]), L.ptr(table["vals"]), int(table["capacity"]), int(table["max_probe"]),
+           L.ptr(table["hold"]), int(table["states"]), L.ptr(state), L.ptr(sym), n, L.ptr(nxt), L.ptr(delta), L.stream())
+    return nxt, delta
+
+
+def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0, ngram=None, alpha=0.0, beta=0.0, bos=1, eos=2,
+                    context=None, gamma=0.0):
     """CTC prefix beam search (csrc/ctc_beam.hip): logits (B,T,V) fp32 (rows contiguous, any row stride), lengths (B) int32 on the device
     = true frames; beam_width W <= 16 prefixes kept per frame, candidates C <= 16 labels tried per frame (0: min(V, 16)), nbest <= W ->
     dict(ids (B,nbest,T) int32, lengths (B,nbest) int32 (-1: no such hypothesis), scores (B,nbest) fp32) on the device, best first.
     blank defaults to PAD (0).  The logits of the true frames must be finite.
     ngram (utils.ngram.NgramLM over these V labels): the fused arm.  The beam is pruned by score + alpha * lm + beta * labels, the result
     ordered by that with alpha * q(context, eos) added (eos -1: no end term; bos opens the context; both default to SOS / EOS), and the
-    dict also holds lm (B,nbest) fp32, the LM's log-probability of the hypothesis; scores stays the CTC log-probability."""
+    dict also holds lm (B,nbest) fp32, the LM's log-probability of the hypothesis; scores stays the CTC log-probability.
+    context (utils.context.ContextGraph over these V labels): phrase biasing, with or without ngram.  Every prefix carries the phrase
+    automaton's state and an integer credit; gamma * credit joins the pruning key (without ngram: score + beta * labels + gamma *
+    credit), the result is ordered with what is earned (an unfinished phrase gets nothing), and the dict also holds credit (B,nbest)
+    int32, the earned labels (-1: no such hypothesis), and lm (0 without ngram).  None: exactly the two paths above."""
     B, T, V = logits.shape
     W, nbest = int(beam_width), int(nbest)
     C = int(candidates) if candidates else min(V, 16)
@@ -706,6 +723,20 @@ def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0,
     rows = max(nbest, 1)
     out = dict(ids=torch.empty((B, rows, T), device=dev, dtype=torch.int32), lengths=torch.empty((B, rows), device=dev, dtype=torch.int32),
                scores=torch.empty((B, rows), device=dev, dtype=torch.float32))
+    if context is not None:
+        if context.V != V or (ngram is not None and ngram.V != V):
+            raise ValueError("the phrase list has %d labels%s, the logits %d" % (
+                context.V, "" if ngram is None else ", the n-gram LM %d" % ngram.V, V))
+        c = context.device_table(dev)
+        t = ngram.device_table(dev) if ngram is not None else dict(keys=None, vals=None, capacity=0, max_probe=0, order=0)
+        out["lm"] = torch.empty((B, rows), device=dev, dtype=torch.float32)
+        out["credit"] = torch.empty((B, rows), device=dev, dtype=torch.int32)
+        L.call("asr_ctc_beam_search_ctx", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
+               L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"],
+               t["max_probe"], t["order"], int(bos), int(eos), float(alpha), float(beta), L.ptr(out["lm"]), L.ptr(c["keys"]),
+               L.ptr(c["vals"]), c["capacity"], c["max_probe"], L.ptr(c["hold"]), c["states"], float(gamma), L.ptr(out["credit"]),
+               L.stream())
+        return out
     if ngram is None:
         L.call("asr_ctc_beam_search", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
                L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.stream())

@@ -44,10 +44,26 @@
 //                           with the end term; missing entries: length -1, scores and lm -inf
 // Only a live extension slot that is no merge runs a lookup, a dependent global read inside the step; the entries' extra state lives in
 // LDS and the workspace is the plain search's.  The plain arm instantiates none of it.
+//
+// The phrase arms (asr_ctc_beam_search_ctx, template <LM, true>): hypotheses that spell a listed phrase get a bonus while the beam is
+// pruned.  state(y), credit(y), hold(s) and earned(y) are those of utils/context.py, step(s, c) -> (next, delta) the lookup of
+// csrc/context.h; tests/ctc_beam_ctx_reference.py restates the arms.  Added to the definitions above:
+//   state                   every list entry also carries cst = state(prefix) and cnt = credit(prefix), both int32.  Before frame 0: eps, 0
+//   step                    a stay slot keeps them; the extension of h by c gets (next, cnt(h) + delta) of step(cst(h), c).  Functions of
+//                           the label sequence alone, like lm, len and ctx
+//   prune                   slots ranked by f = tot + ((alpha lm + beta (float)len) + gamma (float)cnt) in fp32, in this order; without an
+//                           n-gram table lm = 0.f and len is still counted; liveness and the tie rules as above
+//   result                  ordered by the fused arm's final key with gamma (float)earned in place of gamma (float)cnt, earned = cnt -
+//                           hold(cst): a phrase left unfinished at the end of the utterance gets nothing.  Written: scores = tot, lm as in
+//                           the fused arm (0 for found hypotheses without a table, -inf for missing ones), credit = earned (-1: missing)
+// gamma times an integer: both arms and the host form the same bits from the same count.  The lookup sits where ngram_query sits, a live
+// extension that is no merge; with both, the first probes of both tables are issued before either is consumed.  The arms without
+// phrases instantiate none of it.
 #include <type_traits>
 
 #include "ctc_common.h"      // NEG_INF, lae2, ctc_lse_kernel
 #include "ngram.h"           // NgramTable, ngram_query, ngram_shift
+#include "context.h"         // CtxTable, ctx_probe, ctx_finish
 
 namespace {
 
@@ -88,14 +104,36 @@ struct BeamLm {
   float* lm;                // (B,nbest)
 };
 struct BeamNoLm {};
+// What the phrase arms add; with them and no LM, BeamLm still brings beta and lm (its table, bos, eos and alpha are not looked at)
+struct BeamCtx {
+  CtxTable tab;
+  float gamma;
+  int32_t* credit;          // (B,nbest)
+};
+struct BeamNoCtx {};
 
-// blockDim.x = 256, or 320 when W + W C > 256: one slot per thread; the first 256 threads stage the chunks.  LM: the fused arm
-template <bool LM>
+// the fused arms' addend to tot in a slot's rank key, fp32 in this order (without an LM, lm is 0.f and alpha is not looked at)
+template <bool LM, bool CTX>
+__device__ __forceinline__ float beam_bonus(const BeamLm& fuse, float gamma, float lm, int len, int cnt) {
+  float a;
+  if constexpr (LM) a = fuse.alpha * lm + fuse.beta * (float)len;
+  else a = 0.f * lm + fuse.beta * (float)len;
+  if constexpr (CTX) a = a + gamma * (float)cnt;
+  return a;
+}
+
+// blockDim.x = 256, or 320 when W + W C > 256: one slot per thread; the first 256 threads stage the chunks.  LM: the fused arm;
+// CTX: the phrase arm, with or without it
+template <bool LM, bool CTX>
 __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__ logits, int64_t ld, const float* __restrict__ lse,
                                                        const int64_t* __restrict__ cand, const int32_t* __restrict__ in_len, int T, int W,
                                                        int C, int nbest, int blank, int2* trie, int32_t* __restrict__ ids,
                                                        int32_t* __restrict__ out_len, float* __restrict__ scores,
-                                                       std::conditional_t<LM, BeamLm, BeamNoLm> fuse) {
+                                                       std::conditional_t<LM || CTX, BeamLm, BeamNoLm> fuse,
+                                                       std::conditional_t<CTX, BeamCtx, BeamNoCtx> bias) {
+  constexpr bool FUSED = LM || CTX;                  // the slots are ranked by a fused key and the final list is ordered again
+  float gamma = 0.f;
+  if constexpr (CTX) gamma = bias.gamma;
   // the list, double buffered; node -1: no entry (then keys 0, last -1, all three values -inf).  (klo, khi): the prefix' key, (plo, phi):
   // its parent's (0 for the empty prefix).  tot = lae2(p_b, p_nb), kept from the prune step that computed it as the slot's score
   __shared__ __attribute__((aligned(16))) int l_node[2][BEAM_MAX], l_last[2][BEAM_MAX];
@@ -111,6 +149,8 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
   __shared__ float l_lm[2][BEAM_MAX], o_lm[BEAM_MAX];
   __shared__ uint64_t l_ctx[2][BEAM_MAX];
   __shared__ int l_len[2][BEAM_MAX], o_src[BEAM_MAX];
+  // the phrase arms: the automaton's state and the credit of the prefix (functions of the label sequence alone, as above)
+  __shared__ int l_cst[2][BEAM_MAX], l_cnt[2][BEAM_MAX], o_cr[BEAM_MAX];
   const int tid = threadIdx.x, b = blockIdx.x, nthr = blockDim.x;
   int Tb = in_len[b];
   Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
@@ -133,10 +173,12 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     l_pb[0][tid] = tid == 0 ? 0.f : NEG_INF;
     l_pnb[0][tid] = NEG_INF;
     l_tot[0][tid] = tid == 0 ? 0.f : NEG_INF;          // lae2(0, -inf) = 0
-    if constexpr (LM) {
-      l_lm[0][tid] = 0.f;
-      l_len[0][tid] = 0;
-      l_ctx[0][tid] = ngram_shift(0, fuse.bos, fuse.tab.order);
+    if constexpr (LM) l_lm[0][tid] = 0.f;
+    if constexpr (FUSED) l_len[0][tid] = 0;
+    if constexpr (LM) l_ctx[0][tid] = ngram_shift(0, fuse.bos, fuse.tab.order);
+    if constexpr (CTX) {
+      l_cst[0][tid] = 0;
+      l_cnt[0][tid] = 0;
     }
   }
   for (int y = tid; y < BEAM_SLOTS; y += nthr) sc[y] = NEG_INF;         // (slots >= NS are never written: they never count)
@@ -173,7 +215,7 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
       int ext_c = -1;
       // fused arm: the slot's rank key f = tot + (alpha lm + beta len) (the plain arm ranks by sx = tot itself) and what its entry carries
       float fx = NEG_INF, elm = 0.f;
-      int elen = 0;
+      int elen = 0, ecst = 0, ecnt = 0;
       uint64_t ectx = 0;
       if (x < W) {
         int cid[BEAM_MAX], klo[BEAM_MAX], khi[BEAM_MAX];
@@ -198,13 +240,17 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
           }
         }
         sx = lae2(npb, npnb);
-        if constexpr (LM) {
-          elm = l_lm[cur][x];
+        if constexpr (FUSED) {
+          if constexpr (LM) elm = l_lm[cur][x];
           elen = l_len[cur][x];
-          ectx = l_ctx[cur][x];
-          if (sx > NEG_INF) fx = sx + (fuse.alpha * elm + fuse.beta * (float)elen);
+          if constexpr (LM) ectx = l_ctx[cur][x];
+          if constexpr (CTX) {
+            ecst = l_cst[cur][x];
+            ecnt = l_cnt[cur][x];
+          }
+          if (sx > NEG_INF) fx = sx + beam_bonus<LM, CTX>(fuse, gamma, elm, elen, ecnt);
         }
-        sc[x] = LM ? fx : sx;
+        sc[x] = FUSED ? fx : sx;
       } else if (x < NS) {
         int plos[BEAM_MAX], phis[BEAM_MAX], lasts[BEAM_MAX];
         beam_row16(l_plo[cur], plos);
@@ -220,18 +266,28 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
             npnb = (hl == c ? hb : ht) + lpc;
             sx = npnb;
             ext_c = c;
-            if constexpr (LM) {
+            if constexpr (FUSED) {
               if (sx > NEG_INF) {                          // a live extension that is no merge: the one lookup of the step
-                const uint64_t hctx = l_ctx[cur][sj];
-                elm = l_lm[cur][sj] + ngram_query(fuse.tab, hctx, c);
+                CtxProbe probe;                            // (both structures' first probes are in flight before either is consumed)
+                if constexpr (CTX) probe = ctx_probe(bias.tab, l_cst[cur][sj], c);
+                uint64_t hctx = 0;
+                if constexpr (LM) {
+                  hctx = l_ctx[cur][sj];
+                  elm = l_lm[cur][sj] + ngram_query(fuse.tab, hctx, c);
+                }
                 elen = l_len[cur][sj] + 1;
-                ectx = ngram_shift(hctx, c, fuse.tab.order);
-                fx = sx + (fuse.alpha * elm + fuse.beta * (float)elen);
+                if constexpr (LM) ectx = ngram_shift(hctx, c, fuse.tab.order);
+                if constexpr (CTX) {
+                  const int2 tr = ctx_finish(bias.tab, probe);
+                  ecst = tr.x;
+                  ecnt = l_cnt[cur][sj] + tr.y;
+                }
+                fx = sx + beam_bonus<LM, CTX>(fuse, gamma, elm, elen, ecnt);
               }
             }
           }
         }
-        sc[x] = LM ? fx : sx;
+        sc[x] = FUSED ? fx : sx;
       }
       if (tid < BEAM_MAX) {                                   // places no survivor takes stay empty
         l_node[nxt][tid] = -1;
@@ -246,7 +302,7 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
       }
       __syncthreads();
       if (x < NS && sx > NEG_INF) {
-        const float rx = LM ? fx : sx;
+        const float rx = FUSED ? fx : sx;
         int rank = 0;
         for (int y = 0; y < NS16; y += 16) {
 #pragma unroll
@@ -280,10 +336,12 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
           l_pb[nxt][rank] = npb;
           l_pnb[nxt][rank] = npnb;
           l_tot[nxt][rank] = sx;
-          if constexpr (LM) {
-            l_lm[nxt][rank] = elm;
-            l_len[nxt][rank] = elen;
-            l_ctx[nxt][rank] = ectx;
+          if constexpr (LM) l_lm[nxt][rank] = elm;
+          if constexpr (FUSED) l_len[nxt][rank] = elen;
+          if constexpr (LM) l_ctx[nxt][rank] = ectx;
+          if constexpr (CTX) {
+            l_cst[nxt][rank] = ecst;
+            l_cnt[nxt][rank] = ecnt;
           }
         }
       }
@@ -292,16 +350,24 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     }
   }
   __syncthreads();
-  if constexpr (LM) {       // the final order: f + alpha q(ctx, eos) (f alone without an end term), the list place first among equals
-    const bool live = tid < W && l_node[cur][tid] >= 0;
+  if constexpr (FUSED) {    // the final order: f + alpha q(ctx, eos) (f alone without an end term), the list place first among equals;
+    const bool live = tid < W && l_node[cur][tid] >= 0;       // the phrase arms count what is earned: an unfinished phrase gets nothing
     float fk = NEG_INF, lmv = NEG_INF;
+    int cr = -1;
     if (live) {
-      lmv = l_lm[cur][tid];
-      fk = l_tot[cur][tid] + (fuse.alpha * lmv + fuse.beta * (float)l_len[cur][tid]);
-      if (fuse.eos >= 0) {
-        const float qe = ngram_query(fuse.tab, l_ctx[cur][tid], fuse.eos);
-        fk = fk + fuse.alpha * qe;
-        lmv = lmv + qe;
+      lmv = 0.f;
+      if constexpr (LM) lmv = l_lm[cur][tid];
+      if constexpr (CTX) {
+        const int st = l_cst[cur][tid];
+        cr = l_cnt[cur][tid] - bias.tab.hold[st >= 0 && st < bias.tab.states ? st : 0];
+      }
+      fk = l_tot[cur][tid] + beam_bonus<LM, CTX>(fuse, gamma, lmv, l_len[cur][tid], cr);
+      if constexpr (LM) {
+        if (fuse.eos >= 0) {
+          const float qe = ngram_query(fuse.tab, l_ctx[cur][tid], fuse.eos);
+          fk = fk + fuse.alpha * qe;
+          lmv = lmv + qe;
+        }
       }
     }
     if (tid < BEAM_MAX) { sc[tid] = fk; o_src[tid] = -1; }
@@ -314,13 +380,14 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
       }
       o_src[rank] = tid;
       o_lm[rank] = lmv;
+      if constexpr (CTX) o_cr[rank] = cr;
     }
     __syncthreads();
   }
   // the n-best: one lane per hypothesis walks its parent chain (a parent is an older node: the chain ends at node 0)
   int32_t* ids_b = ids + (int64_t)b * nbest * T;
   if (tid < nbest) {
-    const int src = LM ? o_src[tid] : tid;               // the list place of hypothesis tid (fused arm: -1 where there is none)
+    const int src = FUSED ? o_src[tid] : tid;               // the list place of hypothesis tid (fused arm: -1 where there is none)
     const int node = src >= 0 ? l_node[cur][src] : -1;
     int len = -1;
     if (node >= 0) {
@@ -336,7 +403,8 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     o_len[tid] = len < 0 ? 0 : len;
     out_len[(int64_t)b * nbest + tid] = len;
     scores[(int64_t)b * nbest + tid] = src >= 0 ? l_tot[cur][src] : NEG_INF;
-    if constexpr (LM) fuse.lm[(int64_t)b * nbest + tid] = src >= 0 ? o_lm[tid] : NEG_INF;
+    if constexpr (FUSED) fuse.lm[(int64_t)b * nbest + tid] = src >= 0 ? o_lm[tid] : NEG_INF;
+    if constexpr (CTX) bias.credit[(int64_t)b * nbest + tid] = src >= 0 ? o_cr[tid] : -1;
   }
   __syncthreads();
   for (int y = tid; y < nbest * T; y += nthr) {
@@ -357,11 +425,11 @@ extern "C" int64_t asr_ctc_beam_workspace(int B, int T, int W, int C) {
 
 namespace {
 
-// both entries: the row log-sum-exp, the candidates, then the search with or without the fused LM
-template <bool LM>
+// every entry: the row log-sum-exp, the candidates, then the search with or without the fused LM and the phrase automaton
+template <bool LM, bool CTX>
 int beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C, int nbest, int blank,
                 float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
-                std::conditional_t<LM, BeamLm, BeamNoLm> fuse, hipStream_t s) {
+                std::conditional_t<LM || CTX, BeamLm, BeamNoLm> fuse, std::conditional_t<CTX, BeamCtx, BeamNoCtx> bias, hipStream_t s) {
   ASR_CHECK_ARG(logits && input_lengths && workspace && ids && lengths && scores);
   ASR_CHECK_ARG(B > 0 && T > 0 && V > 0 && ld >= V && W >= 1 && C >= 1 && nbest >= 1 && blank >= 0 && blank < V);
   if (W > BEAM_MAX || C > BEAM_MAX || nbest > W) return ASR_EUNSUPPORTED;
@@ -379,8 +447,8 @@ int beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, i
   const int rc = asr_logsoftmax_topk(logits, ld, (int)rows, V, C, vals, idx, s);
   if (rc != ASR_OK) return rc;
   const int threads = W + W * C > 256 ? 320 : 256;                 // one per slot
-  hipLaunchKernelGGL(ctc_beam_kernel<LM>, dim3(B), dim3(threads), 0, s, logits, ld, lse, idx, input_lengths, T, W, C, nbest, blank, trie,
-                     ids, lengths, scores, fuse);
+  hipLaunchKernelGGL((ctc_beam_kernel<LM, CTX>), dim3(B), dim3(threads), 0, s, logits, ld, lse, idx, input_lengths, T, W, C, nbest, blank,
+                     trie, ids, lengths, scores, fuse, bias);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
 }
@@ -390,8 +458,8 @@ int beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, i
 extern "C" int asr_ctc_beam_search(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C,
                                    int nbest, int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
                                    float* scores, hipStream_t s) {
-  return beam_search<false>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths, scores,
-                            BeamNoLm{}, s);
+  return beam_search<false, false>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
+                                   scores, BeamNoLm{}, BeamNoCtx{}, s);
 }
 
 // The fused arm: the table must hold a unigram for every label 0..V-1 (utils/ngram.py's estimator does), so that every q is finite.
@@ -405,6 +473,34 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, int64_t ld, const int
   if (V > NGRAM_MAX_ID + 1) return ASR_EUNSUPPORTED;          // ids + 1 in 16-bit key fields
   const BeamLm fuse{NgramTable{keys, reinterpret_cast<const float2*>(vals), (uint32_t)(capacity - 1), max_probe, order}, bos, eos, alpha,
                     beta, lm};
-  return beam_search<true>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths, scores,
-                           fuse, s);
+  return beam_search<true, false>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
+                                  scores, fuse, BeamNoCtx{}, s);
+}
+
+// The phrase arms: the table of utils/context.py (ContextGraph.device_table).  ng_keys == NULL: no LM -- alpha, bos and eos are not looked
+// at, lm is 0 for every found hypothesis and the length bonus beta still counts.
+extern "C" int asr_ctc_beam_search_ctx(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C,
+                                       int nbest, int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
+                                       float* scores, const uint64_t* ng_keys, const float* ng_vals, int64_t ng_capacity,
+                                       int ng_max_probe, int ng_order, int bos, int eos, float alpha, float beta, float* lm,
+                                       const uint64_t* cx_keys, const int32_t* cx_vals, int64_t cx_capacity, int cx_max_probe,
+                                       const int32_t* cx_hold, int cx_states, float gamma, int32_t* credit, hipStream_t s) {
+  int rc = ctx_check_table(cx_keys, cx_vals, cx_capacity, cx_max_probe, cx_hold, cx_states);
+  if (rc != ASR_OK) return rc;
+  ASR_CHECK_ARG(lm && credit);
+  if (V > CTX_MAX_ID + 1) return ASR_EUNSUPPORTED;            // labels + 1 in a 16-bit key field
+  const BeamCtx bias{CtxTable{cx_keys, reinterpret_cast<const int2*>(cx_vals), cx_hold, (uint32_t)(cx_capacity - 1), cx_max_probe,
+                              cx_states}, gamma, credit};
+  if (!ng_keys) {
+    const BeamLm fuse{NgramTable{nullptr, nullptr, 0, 1, 1}, 0, -1, 0.f, beta, lm};
+    return beam_search<false, true>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
+                                    scores, fuse, bias, s);
+  }
+  rc = ngram_check_table(ng_keys, ng_vals, ng_capacity, ng_max_probe, ng_order);
+  if (rc != ASR_OK) return rc;
+  ASR_CHECK_ARG(bos >= 0 && bos < V && eos >= -1 && eos < V);
+  const BeamLm fuse{NgramTable{ng_keys, reinterpret_cast<const float2*>(ng_vals), (uint32_t)(ng_capacity - 1), ng_max_probe, ng_order},
+                    bos, eos, alpha, beta, lm};
+  return beam_search<true, true>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
+                                 scores, fuse, bias, s);
 }

@@ -138,7 +138,7 @@ class Transformer(nn.Module):
 
     @torch.no_grad()
     def ctc_beam_search(self, enc_out, lengths, beam_width, nbest=1, candidates=0, lm=None, lm_weight=0.1, c_weight=1, return_ids=False,
-                        rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0):
+                        rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0, context=None, context_score=0.0):
         """Prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): no decoder step.  lengths:
         true encoder frames per utterance (ctc_frame_lengths); beam_width W in 1..16 prefixes kept per frame, candidates C (0: min(V, 16))
         labels tried per frame.  One device-to-host copy.  The kernel's W hypotheses of an utterance, score = log-probability summed over
@@ -153,12 +153,19 @@ class Transformer(nn.Module):
         ngram_weight * the n-gram's log-probability of the labels + length_bonus * their number (contexts open with SOS, the final
         order counts EOS), so the LM decides which prefixes survive; its table goes to the device once per LM.  Every hypothesis gets
         'ctc_score', 'ngram_score' (with the EOS term) and score = ctc_score + ngram_weight * ngram_score + length_bonus * labels, with
-        rescoring (1 - lambda) * ctc_score + lambda * att_score + the same two terms, before the ranking above.  None: the plain search."""
+        rescoring (1 - lambda) * ctc_score + lambda * att_score + the same two terms, before the ranking above.  None: the plain search.
+        context (utils.context.ContextGraph over this model's labels): phrase biasing, with or without ngram.  The kernel adds
+        context_score * the phrase credit of every prefix to its pruning key, so hypotheses that spell a listed phrase survive the
+        beam; its table goes to the device once per list.  Every hypothesis gets 'context_credit' (int: the labels earned, an unfinished
+        phrase earns nothing), 'ctc_score' and 'ngram_score' (0 without ngram; length_bonus still counts), and context_score *
+        context_credit joins score beside the n-gram terms on both branches.  None: the two paths above, unchanged."""
         W = int(beam_width)
         lam = float(rescoring_weight)
-        a, beta = float(ngram_weight), float(length_bonus)
+        a, beta, gamma = float(ngram_weight), float(length_bonus), float(context_score)
         if ngram is not None:
             ngram.check_labels(self.id2label)
+        if context is not None:
+            context.check_labels(self.id2label)
         if not 0.0 <= lam <= 1.0:
             raise ValueError("rescoring_weight must lie in [0, 1], got %g" % lam)
         if not 1 <= W <= 16:
@@ -167,7 +174,12 @@ class Transformer(nn.Module):
             raise ValueError("nbest must be at least 1, got %d" % nbest)
         logits = self.ctc_logits(enc_out)
         B, T, V = logits.shape
-        if ngram is None:
+        if context is not None:
+            out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN,
+                                      ngram=ngram, alpha=a, beta=beta, bos=constant.SOS_TOKEN, eos=constant.EOS_TOKEN, context=context,
+                                      gamma=gamma)
+            parts = [out["scores"], out["lm"], out["credit"].view(torch.float32)]
+        elif ngram is None:
             out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN)
             parts = [out["scores"]]
         else:
@@ -177,13 +189,19 @@ class Transformer(nn.Module):
         flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1)] + [p.view(torch.int32).reshape(-1) for p in parts]).cpu()
         ids, lens, *parts = torch.split(flat, [B * W * T, B * W] + [B * W] * len(parts))
         ids, lens = ids.view(B, W, T).tolist(), lens.view(B, W).tolist()
+        credits = parts.pop().view(B, W).tolist() if context is not None else None
         scores, *lm_scores = [p.view(torch.float32).view(B, W).tolist() for p in parts]
         ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n]} for n in range(W) if lens[b][n] >= 0] for b in range(B)]
-        if ngram is not None:
+        if ngram is not None or context is not None:
             for b, hs in enumerate(ended):
-                for h, g in zip(hs, [lm_scores[0][b][n] for n in range(W) if lens[b][n] >= 0]):
+                found = [n for n in range(W) if lens[b][n] >= 0]
+                for h, n in zip(hs, found):
+                    g = lm_scores[0][b][n]
                     h['ctc_score'], h['ngram_score'] = h['score'], g
                     h['score'] = h['ctc_score'] + a * g + beta * len(h['yseq'])
+                    if context is not None:
+                        h['context_credit'] = credits[b][n]
+                        h['score'] += gamma * h['context_credit']
         if lam > 0.0:
             att = self.decoder.score_hypotheses(enc_out, [[h['yseq'] for h in hs] for hs in ended])
             for hs, scores_b in zip(ended, att):
@@ -191,8 +209,10 @@ class Transformer(nn.Module):
                     h.setdefault('ctc_score', h['score'])
                     h['att_score'] = att_score
                     h['score'] = (1.0 - lam) * h['ctc_score'] + lam * att_score
-                    if ngram is not None:
+                    if ngram is not None or context is not None:
                         h['score'] += a * h['ngram_score'] + beta * len(h['yseq'])
+                    if context is not None:
+                        h['score'] += gamma * h['context_credit']
         hyp_ids = [[h['yseq'] for h in hs] for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight)]
         strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
         return (strs, hyp_ids) if return_ids else strs
@@ -248,7 +268,7 @@ class Transformer(nn.Module):
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
                  ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,
-                 attention_rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0):
+                 attention_rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0, context=None, context_score=0.0):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
         ctc_greedy: best-path decoding from the head alone; ctc_beam: prefix beam search over the head's posteriors alone
@@ -256,7 +276,8 @@ class Transformer(nn.Module):
         not together with beam_search, ctc_greedy or ctc_weight; attention_rescoring_weight = lambda in (0, 1] (ctc_beam only): all
         beam_width hypotheses are rescored by the decoder in one teacher-forced pass and ranked by (1 - lambda) * CTC + lambda * attention
         log-probability (ctc_beam_search's rescoring_weight); ngram / ngram_weight / length_bonus (ctc_beam only): a label n-gram LM fused
-        into that search's pruning (ctc_beam_search's arguments of the same names).  align_source "gold" / "hyp": a fourth value, the forced alignment
+        into that search's pruning, context / context_score (ctc_beam only): a phrase list biasing it (ctc_beam_search's arguments of the
+        same names).  align_source "gold" / "hyp": a fourth value, the forced alignment
         (ctc_align) of padded_target with target_lengths, or of the label ids the decoder produced (SOS and EOS dropped; never a
         re-tokenised string)."""
         if ctc_weight > 0 and not beam_search:
@@ -270,6 +291,8 @@ class Transformer(nn.Module):
                              % attention_rescoring_weight)
         if ngram is not None and not ctc_beam:
             raise ValueError("--ngram-path needs --ctc-beam-search: the n-gram LM is fused into the CTC prefix beam search")
+        if context is not None and not ctc_beam:
+            raise ValueError("--context-path needs --ctc-beam-search: the phrase list biases the CTC prefix beam search's pruning")
         if ctc_beam and not hasattr(self, "ctc_linear"):
             self.ctc_logits(None)                      # the "no encoder CTC head" ValueError, before any device work
         if lm_rescoring and ctc_beam and lm is None:
@@ -298,7 +321,8 @@ class Transformer(nn.Module):
                                                          candidates=ctc_candidates, lm=lm if lm_rescoring else None,
                                                          lm_weight=lm_weight, c_weight=c_weight, return_ids=True,
                                                          rescoring_weight=attention_rescoring_weight, ngram=ngram,
-                                                         ngram_weight=ngram_weight, length_bonus=length_bonus)
+                                                         ngram_weight=ngram_weight, length_bonus=length_bonus, context=context,
+                                                         context_score=context_score)
             strs_hyps, hyp_ids = [rows[0] if rows else "" for rows in nbest_strs], [rows[0] if rows else [] for rows in nbest_ids]
         elif beam_search:
             hyp_ids, strs_hyps = self.decoder.beam_search(enc_out, beam_width=beam_width, nbest=1, lm=lm, lm_rescoring=lm_rescoring,

@@ -1,6 +1,6 @@
 """Evaluation entry point -- same command line as the reference (reference: test.py): loads --continue-from, decodes
 every test utterance (greedy, beam search with --beam-search, or from the encoder CTC head alone with --ctc-greedy / --ctc-beam-search,
-the latter's n-best rescored by the decoder with --attention-rescoring-weight, its pruning guided by a label n-gram LM with --ngram-path)
+the latter's n-best rescored by the decoder with --attention-rescoring-weight, its pruning guided by a label n-gram LM with --ngram-path and biased towards the phrases of --context-path)
 and reports CER / WER.  --align-out PATH also writes label and word
 timestamps from the encoder CTC head (forced alignment of the transcript, or of the hypothesis with --align-source hyp)."""
 import torch
@@ -10,12 +10,14 @@ from utils import constant
 from utils.metrics import calculate_cer, calculate_cer_en_zh, calculate_wer
 
 
-def evaluate(model, test_loader, lm=None, noise_dir=None, ngram=None):
+def evaluate(model, test_loader, lm=None, noise_dir=None, ngram=None, context=None):
     """reference: test.py:19-62.  noise_dir: the checkpoint's --noise-dir (the reference injects noise into the test set too); ngram: the
-    NgramLM of --ngram-path (None: the plain search, no table and no further launch)."""
+    NgramLM of --ngram-path, context: the ContextGraph of --context-path (None: the plain search, no table and no further launch)."""
     args = constant.args
     fusion = {} if ngram is None else dict(ngram=ngram, ngram_weight=getattr(args, "ngram_weight", 0.3),
                                            length_bonus=getattr(args, "ngram_length_bonus", 0.0))
+    if context is not None:
+        fusion.update(context=context, context_score=getattr(args, "context_score", 3.0))
     model.eval()
     total_word = total_char = total_cer = total_wer = 0
     total_en_cer = total_zh_cer = total_en_char = total_zh_char = 0
@@ -74,7 +76,7 @@ def check_ctc_decoding(args, model):
     """--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need the encoder CTC head of a model trained with
     --ctc-weight > 0; the weight lies in [0, 1] and applies to --beam-search.  --ctc-beam-search decodes from the head alone: it excludes
     --beam-search, --ctc-greedy and a --ctc-decode-weight, and its --beam-width lies in 1..16.  --attention-rescoring-weight lies in
-    [0, 1] and applies to --ctc-beam-search, as does --ngram-path."""
+    [0, 1] and applies to --ctc-beam-search, as do --ngram-path and --context-path."""
     w = float(getattr(args, "ctc_decode_weight", 0.0) or 0.0)
     if not 0.0 <= w <= 1.0:
         raise ValueError("--ctc-decode-weight must lie in [0, 1], got %g" % w)
@@ -86,6 +88,8 @@ def check_ctc_decoding(args, model):
         raise ValueError("--attention-rescoring-weight %g needs --ctc-beam-search: the decoder rescores the CTC search's n-best" % lam)
     if getattr(args, "ngram_path", None) and not ctc_beam:
         raise ValueError("--ngram-path needs --ctc-beam-search: the n-gram LM is fused into the CTC prefix beam search")
+    if getattr(args, "context_path", None) and not ctc_beam:
+        raise ValueError("--context-path needs --ctc-beam-search: the phrase list biases the CTC prefix beam search's pruning")
     if ((w > 0 or getattr(args, "ctc_greedy", False) or ctc_beam or getattr(args, "align_out", None))
             and not hasattr(model, "ctc_linear")):
         raise ValueError("--ctc-decode-weight / --ctc-greedy / --ctc-beam-search / --align-out need a model with an encoder CTC head: "
@@ -141,5 +145,9 @@ if __name__ == '__main__':
     if getattr(args, "ngram_path", None):     # --ctc-beam-search only (check_ctc_decoding); a file for other labels is refused here
         from utils.ngram import NgramLM
         ngram = NgramLM.load(args.ngram_path, id2label)
+    context = None
+    if getattr(args, "context_path", None):   # --ctc-beam-search only (check_ctc_decoding); a character that is no label is refused here
+        from utils.context import ContextGraph
+        context = ContextGraph.from_file(args.context_path, label2id)
     print(model)
-    evaluate(model, test_loader, lm=lm, noise_dir=getattr(loaded_args, "noise_dir", None), ngram=ngram)
+    evaluate(model, test_loader, lm=lm, noise_dir=getattr(loaded_args, "noise_dir", None), ngram=ngram, context=context)

@@ -25,7 +25,9 @@ Differences that do not change old command lines:
   * `--pos-encoding {abs,rope}`: the reference's absolute sinusoid (default) or rotary position embedding of Q and K in every encoder
     self-attention (DESIGN.md section 7); the decoder keeps its sinusoid;
   * `--ngram-path FILE` (+ `--ngram-weight`, `--ngram-length-bonus`; test.py --ctc-beam-search): a label n-gram LM of train_ngram.py
-    fused into the CTC prefix beam search's pruning.
+    fused into the CTC prefix beam search's pruning (DESIGN.md section 7);
+  * `--context-path FILE` (+ `--context-score`; test.py --ctc-beam-search): a list of phrases, one per line, that the CTC prefix beam
+    search's pruning is biased towards (utils/context.py).
 """
 import argparse
 import os
@@ -129,6 +131,10 @@ _FLAGS = [
     # pruning with --ngram-weight and a bonus of --ngram-length-bonus per label; without the path nothing changes
     (("--ngram-path",), dict(type=_S, default=None)), (("--ngram-weight",), dict(default=0.3, type=_F)),
     (("--ngram-length-bonus",), dict(default=0.0, type=_F)),
+    # --context-path FILE (test.py --ctc-beam-search): phrase (hotword) biasing -- one phrase per line in the model's
+    # labels; every label that advances a listed phrase adds --context-score to a prefix' pruning key, a phrase that breaks off gives it
+    # back; combines with --ngram-path, --attention-rescoring-weight and --lm-rescoring; without the path nothing changes
+    (("--context-path",), dict(type=_S, default=None)), (("--context-score",), dict(default=3.0, type=_F)),
     # CTC forced alignment (test.py): --align-out PATH writes one JSON line per test utterance with label and word
     # timestamps from the CTC head; --align-source gold aligns the transcript, hyp the label ids the decoder produced
     (("--align-out",), dict(default=None, type=_S)), (("--align-source",), dict(default="gold", choices=["gold", "hyp"])),

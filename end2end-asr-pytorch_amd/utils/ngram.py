@@ -42,6 +42,32 @@ def hash_slot(keys, capacity):
     return ((h >> np.uint64(32)) & np.uint64(capacity - 1)).astype(np.int64)
 
 
+def place_keys(keys):
+    """Places distinct non-zero keys, ascending, in an open-addressing table with linear probing: -> (slot of every key, capacity,
+    max_probe).  The capacity is a power of two >= 16 and twice the entries; max_probe = the most slots a stored key's search reads.
+    Entries are placed in rounds: of the pending keys that meet at a free slot the smallest takes it, the others move one slot on."""
+    keys = np.asarray(keys, dtype=np.uint64)
+    n = len(keys)
+    cap = 16
+    while cap < 2 * n:
+        cap *= 2
+    taken = np.zeros(cap, dtype=bool)
+    home = hash_slot(keys, cap)
+    pos, pending = home.copy(), np.arange(n)
+    while pending.size:
+        p = pos[pending]
+        free = ~taken[p]
+        slots, first = np.unique(p[free], return_index=True)           # pending is ascending in key order: the first is the smallest
+        won = pending[free][first]
+        taken[slots] = True
+        placed = np.zeros(n, dtype=bool)
+        placed[won] = True
+        pending = pending[~placed[pending]]
+        pos[pending] = (pos[pending] + 1) & (cap - 1)
+    max_probe = int((((pos - home) & (cap - 1)) + 1).max()) if n else 1
+    return pos, cap, max_probe
+
+
 class NgramLM:
     def __init__(self, order, V, labels, keys, logp, bo):
         self.order, self.V, self.labels = int(order), int(V), list(labels)
@@ -164,25 +190,10 @@ class NgramLM:
         """-> (keys (capacity) uint64, vals (capacity, 2) float32 = (logp, bo), max_probe): open addressing, linear probing, capacity a
         power of two >= twice the entries, key 0 = empty; max_probe = the most slots a stored key's search reads.  Entries are placed in
         rounds: of the pending keys that meet at a free slot the smallest takes it, the others move one slot on.  Same arrays, same bytes."""
-        n = len(self.keys)
-        cap = 16
-        while cap < 2 * n:
-            cap *= 2
+        slots, cap, max_probe = place_keys(self.keys)
         keys, vals = np.zeros(cap, dtype=np.uint64), np.zeros((cap, 2), dtype=np.float32)
-        home = hash_slot(self.keys, cap)
-        pos, pending = home.copy(), np.arange(n)
-        while pending.size:
-            p = pos[pending]
-            free = keys[p] == 0
-            slots, first = np.unique(p[free], return_index=True)       # pending is ascending in key order: the first is the smallest
-            won = pending[free][first]
-            keys[slots] = self.keys[won]
-            vals[slots, 0], vals[slots, 1] = self.lp[won], self.bo[won]
-            placed = np.zeros(n, dtype=bool)
-            placed[won] = True
-            pending = pending[~placed[pending]]
-            pos[pending] = (pos[pending] + 1) & (cap - 1)
-        max_probe = int((((pos - home) & (cap - 1)) + 1).max()) if n else 1
+        keys[slots] = self.keys
+        vals[slots, 0], vals[slots, 1] = self.lp, self.bo
         return keys, vals, max_probe
 
     def find(self, table, key):

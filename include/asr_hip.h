@@ -317,6 +317,34 @@ int asr_ctc_beam_search_lm(const float* logits, int64_t ld, const int32_t* input
                            const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order, int bos, int eos,
                            float alpha, float beta, float* lm, asr_stream_t stream);
 
+/* ---- Phrase (hotword) biasing of the CTC prefix beam search (csrc/context.h has the step, utils/context.py the automaton, its credit
+ * and the table).  A phrase list's prefixes are the states of an Aho-Corasick automaton, eps = state 0; a prefix' credit is an integer,
+ * the labels of completed phrases plus the `hold` labels of the partial match it ends in.  The table has the n-gram table's form: open
+ * addressing with linear probing over `capacity` slots (a power of two <= 2^31), uint64 keys, 0 = an empty slot, a stored key within
+ * max_probe slots of its home, the same hash.
+ *   key    (state + 1) << 16 | (label + 1)      (labels < 65535)
+ *   value  int32 pair (next state, delta of the credit); vals is (capacity, 2) int32
+ *   hold   (states) int32: the labels of a state's partial match that are not yet earned (0 for eps and for a whole phrase)
+ * Stored is a transition (s, c) only if s = eps or it leads neither to eps nor where (eps, c) leads.  The step:
+ *   (s, c) stored: its value;  else (eps, c) stored: (next, delta_eps - hold[s]);  else (eps, -hold[s])
+ * A label outside 0..65534 steps to eps; a state outside 0..states-1 is taken for eps.
+ * asr_ctx_step: (next[i], delta[i]) = step(state[i], sym[i]) for n transitions, one thread each.  A capacity that is no power of two,
+ * max_probe < 1, states < 1 or a null pointer: ASR_EINVAL.                                                                           */
+int asr_ctx_step(const uint64_t* keys, const int32_t* vals, int64_t capacity, int max_probe, const int32_t* hold, int states,
+                 const int32_t* state, const int32_t* sym, int64_t n, int32_t* next, int32_t* delta, asr_stream_t stream);
+/* asr_ctc_beam_search with the phrase automaton, and optionally the LM, in the pruning (csrc/ctc_beam.hip has the definition): every
+ * prefix carries its state and credit cnt, slots are ranked by tot + ((alpha lm + beta len) + gamma cnt), the final list by the same
+ * with earned = cnt - hold[state] for cnt (a phrase left unfinished earns nothing) + alpha q(ctx, eos).  ng_keys == NULL: no LM -- lm
+ * counts as 0, alpha, bos and eos are not looked at, beta still counts.  Same arguments, workspace, launches and refusals as
+ * asr_ctc_beam_search(_lm); V > 65535: ASR_EUNSUPPORTED; a bad table: ASR_EINVAL.  scores stays the CTC log-probability; lm as in
+ * asr_ctc_beam_search_lm (0 without an LM, -inf where lengths is -1); credit (B,nbest) int32 = earned (-1 where lengths is -1).      */
+int asr_ctc_beam_search_ctx(const float* logits, int64_t ld, const int32_t* input_lengths, int B, int T, int V, int W, int C, int nbest,
+                            int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+                            const uint64_t* ng_keys, const float* ng_vals, int64_t ng_capacity, int ng_max_probe, int ng_order, int bos,
+                            int eos, float alpha, float beta, float* lm, const uint64_t* cx_keys, const int32_t* cx_vals,
+                            int64_t cx_capacity, int cx_max_probe, const int32_t* cx_hold, int cx_states, float gamma, int32_t* credit,
+                            asr_stream_t stream);
+
 /* ---- Conformer-style convolution module (csrc/convmod.hip has the definition): GLU -> depthwise convolution over time -> Swish between
  * the module's two pointwise GEMMs, channel last.  u (B,T,2D) = [a | gate], s / v / dv (B,T,D), du (B,T,2D), all in `dtype` and
  * contiguous; wd (D,K) and bd (D) fp32 (the layout of nn.Conv1d(D, D, K, padding=(K-1)/2, groups=D)); len (B) int32 on the device, clamped
