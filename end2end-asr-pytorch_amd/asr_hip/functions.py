@@ -1113,6 +1113,55 @@ class CTCFn(Function):
         return dl, None, None, None, None
 
 
+# ================================================================================================ MWER over the n-best
+class SeqLogProbFn(Function):
+    """score[r] = sum over the rows of segment r of log_softmax(logits)[m, tgt[m]] (ops.seq_logprob), differentiable in the logits
+    (MWER training).  -> (score (R,) fp32, tok (M,) fp32, not differentiable).
+    backward: ONE launch of asr_seq_logprob_bwd with the incoming gradient of `score` as the per-segment coefficients.  When the logits
+    come straight from the vocabulary projection of a bf16 model, its part of the gradient goes through the logit hand-over slot exactly
+    as CEFn's does (bf16, zero padded to 64 columns, a stride-0 zero as the formal gradient); otherwise the formal fp32 gradient is
+    returned."""
+
+    @staticmethod
+    def forward(ctx, logits, tgt, seg_off):
+        assert logits.dim() == 2 and logits.dtype == torch.float32
+        out = ops.seq_logprob(logits, tgt, seg_off)
+        ctx.t = (logits, tgt, seg_off)
+        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        ctx.mark_non_differentiable(out["tok"])
+        return out["score"], out["tok"]
+
+    @staticmethod
+    def backward(ctx, dscore, *unused):
+        logits, tgt, seg_off = ctx.t
+        coef = dscore.float().contiguous()
+        if ctx.handover is not None:
+            ctx.handover["dy"] = ops.seq_logprob_bwd(logits, tgt, seg_off, coef, out_dtype=torch.bfloat16, pad=64)
+            return ops.zero_scalar(logits.device).expand(logits.shape), None, None
+        return ops.seq_logprob_bwd(logits, tgt, seg_off, coef), None, None
+
+
+class MwerLossFn(Function):
+    """m * mean risk + (1 - m)(1 - w) * NLL of a step from its R segment scores (ops.mwer_loss): risk_scale = m / B,
+    gold_scale = (1 - m)(1 - w) / sum_b (len(gold_b) + 1); the first segment of an utterance is its gold.
+    -> (loss, prob (R,), risk (B,), sums (2,)), the last three not differentiable.  backward hands asr_mwer_loss's coefficients, times
+    the incoming gradient, to the scores (SeqLogProbFn.backward multiplies them into the rows)."""
+
+    @staticmethod
+    def forward(ctx, score, err, utt_off, risk_scale, gold_scale):
+        out = ops.mwer_loss(score.contiguous(), err, utt_off, risk_scale, gold_scale)
+        loss = out["sums"][0] * float(risk_scale)
+        if gold_scale != 0.0:                    # (with m = 1 an infinite gold score must not turn the risk into a NaN)
+            loss = loss - out["sums"][1] * float(gold_scale)
+        ctx.coef = out["coef"]
+        ctx.mark_non_differentiable(out["prob"], out["risk"], out["sums"])
+        return loss, out["prob"], out["risk"], out["sums"]
+
+    @staticmethod
+    def backward(ctx, dloss, *unused):
+        return ctx.coef * dloss.reshape(()).float(), None, None, None, None
+
+
 # ================================================================================================ composable pieces
 # The fused sub-layer Functions above cover the reference's layers.  The low-rank variant (BASELINE configs[4]) factorises
 # every projection W (out, in) into V (out, r) . U (r, in); its sub-layers are assembled from LinearFn plus these two.

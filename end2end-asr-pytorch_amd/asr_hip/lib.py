@@ -97,6 +97,8 @@ _SIGS = {
     "asr_edit_distance_batch": (_I, [_P, _P, _P, _P, _I, _P]),
     "asr_logsoftmax_topk": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
     "asr_seq_logprob": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "asr_seq_logprob_bwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _P, _L, _I, _P]),
+    "asr_mwer_loss": (_I, [_P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P]),
     "asr_dec_gemm": (_I, [_P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _F, _P, _P, _P, _P, _F, _P, _P]),
     "asr_dec_attn": (_I, [_P, _L, _P, _P, _L, _P, _P, _L, _L, _I, _P, _L, _I, _I, _I, _F, _I, _P, _P]),
     "asr_dec_attn_fused": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _L, _L, _I, _P, _L, _I, _I, _I, _F, _I,

@@ -1021,6 +1021,44 @@ def seq_logprob(logits, tgt, seg_off):
     return out
 
 
+def seq_logprob_bwd(logits, tgt, seg_off, coef, grad_out=None, out_dtype=torch.float32, pad=8):
+    """The backward of seq_logprob (csrc/mwer.hip): row m of segment r gets c * ([v == tgt[m]] - softmax(logits[m])[v]) with c = grad_out
+    * coef[r]; coef (R,) fp32 on the device, grad_out a device scalar or None (= 1).  Returned like ce_bwd's: an (M,V) view of an (M, V
+    rounded up to `pad`) buffer whose pad columns are zero, the WHOLE buffer with pad=64 (what the data-gradient GEMM contracts).  Rows
+    with c == 0, a tgt outside [0,V) or no segment are zero and their logits are not read."""
+    M, V = logits.shape
+    R = seg_off.numel() - 1
+    assert logits.dtype == torch.float32 and (logits.stride(1) == 1 or V == 1 or M == 0)
+    assert tgt.dtype == torch.int64 and tgt.numel() == M and tgt.is_contiguous()
+    assert seg_off.dtype == torch.int32 and R >= 0 and seg_off.is_contiguous()
+    assert coef.dtype == torch.float32 and coef.numel() == R and coef.is_contiguous()
+    assert grad_out is None or (grad_out.dtype == torch.float32 and grad_out.numel() == 1)
+    ld = (V + pad - 1) // pad * pad
+    dl = torch.empty((M, ld), device=logits.device, dtype=out_dtype)
+    L.call("asr_seq_logprob_bwd", L.ptr(logits), logits.stride(0) if M else V, L.ptr(tgt), L.ptr(seg_off), L.ptr(coef), L.ptr(grad_out),
+           R, M, V, L.ptr(dl), ld, L.dt(dl), L.stream())
+    return dl if pad == 64 else dl[:, :V]
+
+
+MWER_NBEST_MAX = 16          # hypotheses per utterance asr_mwer_loss is specified for (= the CTC prefix beam search's widest beam)
+
+
+def mwer_loss(score, err, utt_off, risk_scale, gold_scale):
+    """MWER statistics of a step (csrc/mwer.hip): score, err (R,) fp32 and utt_off (B+1,) int32 on the device; the
+    FIRST segment of an utterance is its gold (err ignored), the others its at most 16 hypotheses.  -> dict(prob (R,), coef (R,) =
+    risk_scale * P_i (e_i - sum_j P_j e_j) on hypotheses and -gold_scale on gold, risk (B,), sums (2,) = [sum of risks, sum of gold
+    scores]); one launch, the same bits for the same input."""
+    R, B = score.numel(), utt_off.numel() - 1
+    assert score.dtype == torch.float32 and score.is_contiguous() and err.dtype == torch.float32 and err.is_contiguous() and err.numel() == R
+    assert utt_off.dtype == torch.int32 and utt_off.is_contiguous() and B >= 0
+    dev = score.device
+    out = dict(prob=torch.empty((R,), device=dev, dtype=torch.float32), coef=torch.empty((R,), device=dev, dtype=torch.float32),
+               risk=torch.empty((B,), device=dev, dtype=torch.float32), sums=torch.empty((2,), device=dev, dtype=torch.float32))
+    L.call("asr_mwer_loss", L.ptr(score), L.ptr(err), L.ptr(utt_off), B, R, float(risk_scale), float(gold_scale), L.ptr(out["prob"]),
+           L.ptr(out["coef"]), L.ptr(out["risk"]), L.ptr(out["sums"]), L.stream())
+    return out
+
+
 def ce_bwd(logits, gold, lse, smoothing, pad_id, grad_out, count, out_dtype=torch.float32, pad=8):
     """Returns dlogits as an (M,V) view of an (M, V rounded up to `pad`) buffer whose pad columns are zero; with a 64-column pad
     the WHOLE padded buffer is returned (the data-gradient GEMM contracts the padded width)."""

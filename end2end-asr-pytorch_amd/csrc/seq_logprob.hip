@@ -7,40 +7,11 @@
 // the bits are a function of the input alone.  HBM-bound: M * V * 4 bytes in, M + R floats out.
 // Requirement: every row has at least one finite logit among its V and none is +inf.
 #include "common.h"
+#include "lse.h"        // Lse, lse_row: shared with the backward (csrc/mwer.hip); no multiply-add contraction from here on
 
 namespace {
 
-// No multiply-add contraction in this file: the compiler chooses where to fuse loop by loop, and the two load arms of the row pass
-// must round the same sums at the same places.
-#pragma clang fp contract(off)
-
 constexpr int SEQ_ROWS = 8;                    // == CE_ROWS of csrc/ce.hip
-
-// Online log-sum-exp state of a set of logits: m = their maximum and s1 = sum exp(x - m) over all of them EXCEPT one copy of the maximum
-// (whose term is exactly 1), so that logsumexp - m = log1p(s1).  A row whose target is its arg max has a log-probability near 0, and
-// log(1 + s1) from a rounded 1 + s1 would lose it; log1p(s1) keeps s1's own relative precision.  m = -inf: the empty set (or all -inf).
-struct Lse { float m, s1; };
-
-// a, then b: the pair of a butterfly step in (lower lane, higher lane) order, so both lanes compute the same bits
-__device__ __forceinline__ Lse lse_merge(Lse a, Lse b) {
-  const bool first = a.m >= b.m;
-  const Lse hi = first ? a : b, lo = first ? b : a;
-  if (lo.m == -INFINITY) return hi;
-  return Lse{hi.m, hi.s1 + (lo.s1 + 1.f) * expf(lo.m - hi.m)};
-}
-
-// one logit into a lane's state: one expf whichever of the two is larger, and no branch.  Both load arms of the row pass feed the same
-// values in the same order through this, which is what makes their results the same bits.
-__device__ __forceinline__ void lse_add(Lse& st, float x) {
-  const bool up = x > st.m;
-  float e = expf(fminf(x, st.m) - fmaxf(x, st.m));          // exp(-inf) = 0: the first finite value of a lane, or a -inf logit
-  if (x == -INFINITY) e = 0.f;                              // (-inf) - (-inf) is not a number
-  st.s1 = up ? (st.s1 + 1.f) * e : st.s1 + e;               // a new maximum: the old one becomes an ordinary term
-  st.m = up ? x : st.m;
-}
-__device__ __forceinline__ void lse_add4(Lse& st, float x0, float x1, float x2, float x3) {
-  lse_add(st, x0); lse_add(st, x1); lse_add(st, x2); lse_add(st, x3);
-}
 
 __global__ __launch_bounds__(64 * SEQ_ROWS) void seq_row_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ tgt,
                                                                 int M, int V, float* __restrict__ tok_lp) {
@@ -48,25 +19,7 @@ __global__ __launch_bounds__(64 * SEQ_ROWS) void seq_row_kernel(const float* __r
   const int row = blockIdx.x * SEQ_ROWS + wave;
   if (row >= M) return;
   const float* l = logits + (int64_t)row * ld;
-  const int V4 = V & ~3;
-  Lse st{-INFINITY, 0.f};
-  // Lane `lane` owns columns 4 lane + 256 k .. + 3 in BOTH arms, then column V4 + lane of the tail: the arms differ in how the four
-  // values are loaded and in nothing else, so a row gives the same bits through either (tests/test_gpu_attn_rescore.py pins it).
-  if ((((uintptr_t)l) & 15) == 0) {            // 16-byte loads, four in flight per lane
-#pragma unroll 4
-    for (int v = lane * 4; v < V4; v += 256) {
-      const float4 x = *reinterpret_cast<const float4*>(l + v);
-      lse_add4(st, x.x, x.y, x.z, x.w);
-    }
-  } else {                                     // a row base that is no multiple of 16 bytes (ld = V = 3): the same columns, one by one
-    for (int v = lane * 4; v < V4; v += 256) lse_add4(st, l[v], l[v + 1], l[v + 2], l[v + 3]);
-  }
-  if (V4 + lane < V) lse_add(st, l[V4 + lane]);          // columns >= V are never read
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {           // wave64 butterfly (the idiom of ce.hip): every lane merges (lower lane, higher lane) in that order
-    const Lse t{__shfl_xor(st.m, o, 64), __shfl_xor(st.s1, o, 64)};
-    st = (lane & o) ? lse_merge(t, st) : lse_merge(st, t);
-  }
+  const Lse st = lse_row(l, V, lane);           // the row read ONCE; both load arms give the same bits (csrc/lse.h)
   if (lane == 0) {
     const int64_t t = tgt[row];
     float lp = -INFINITY;                      // a target outside [0, V): -inf, nothing read

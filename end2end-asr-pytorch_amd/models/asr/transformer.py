@@ -265,6 +265,130 @@ class Transformer(nn.Module):
             return pred, gold, hyp_seq, gold, ctc
         return pred, gold, hyp_seq, gold
 
+    # -------------------------------------------------------------------------------------------- MWER training
+    def space_id(self):
+        """The id of the space label (--mwer-unit word splits label sequences there); ValueError when the label file has none."""
+        ids = [i for i, c in self.id2label.items() if c == " "]
+        if not ids:
+            raise ValueError("--mwer-unit word needs a space label to split words at, and the label file has none (use --mwer-unit label)")
+        return int(ids[0])
+
+    def mwer_errors(self, hyps, golds, unit="label"):
+        """Levenshtein distances (raw counts) of every hypothesis to its utterance's gold label sequence, on the host
+        (asr_hip.text.edit_distance_batch): unit 'label' over label ids, 'word' over the runs of ids between space labels.
+        hyps: one list of id lists per utterance, golds: one id list per utterance -> the same nesting of ints."""
+        if unit not in ("label", "word"):
+            raise ValueError("--mwer-unit must be 'label' or 'word', got %r" % (unit,))
+        if unit == "word":
+            sp = self.space_id()
+
+            def words(y):
+                out, cur = [], []
+                for t in y:
+                    if t == sp:
+                        if cur:
+                            out.append(tuple(cur))
+                        cur = []
+                    else:
+                        cur.append(t)
+                return out + ([tuple(cur)] if cur else [])
+        else:
+            def words(y):
+                return list(y)
+        from asr_hip.text import edit_distance_batch
+        dist = edit_distance_batch([(words(y), words(g)) for hs, g in zip(hyps, golds) for y in hs])
+        out, at = [], 0
+        for hs in hyps:
+            out.append(dist[at:at + len(hs)])
+            at += len(hs)
+        return out
+
+    def mwer_step(self, padded_input, input_lengths, padded_target, target_lengths, mwer_weight, ctc_weight, nbest=4, unit="label",
+                  candidates=0, hyps=None):
+        """One training step's loss with minimum word error rate training over the CTC n-best (train.py --mwer-weight, DESIGN.md
+        section 7) -> (L, gold_seq (B, Lg), hyp_seq (B, Lg), stats).  With m = mwer_weight and w = ctc_weight,
+            L = m * (1/B) sum_b risk_b + (1 - m) * [(1 - w) * NLL + w * CTC],      risk_b = sum_i P_i (e_i - mean_j e_j),
+        P = softmax over the attention decoder's log p(y, EOS | x) of the utterance's n_b <= nbest distinct hypotheses, e_i their
+        Levenshtein distance to the gold labels (mwer_errors), NLL = - sum_b log p(gold_b, EOS | x) / sum_b (len(gold_b) + 1) (no label
+        smoothing), CTC the joint step's term (F_.CTCFn, true encoder frames).  The stages: features, encoder, CTC logits, the n-best =
+        the nbest survivors of ops.ctc_beam_search on the detached CTC logits of this very pass (under no_grad, in the kernel's own order:
+        no word bonus, no LM), their errors on the host, ONE decoder pass over gold and hypotheses together (Decoder._score_rows: every
+        parameter is used once per backward), ops.mwer_loss.  padded_target (B, L) / target_lengths: the collated raw label ids (host
+        or device).  hyps: the hypotheses to use instead of the search's (tests).  gold_seq / hyp_seq: the gold targets (EOS included)
+        and the arg-max of the gold rows' logits, PAD behind them, for the trainer's metrics.  stats: 'risk' (B,), 'prob' (R,), 'sums'
+        (2,) device tensors of ops.mwer_loss, 'nll' / 'ctc' device scalars, and on the host 'hyps', 'errors', 'expected_base' (the mean
+        over utterances of mean_j e_j: the mean expected error is sum(risk) / B + expected_base) and 'top_error' (mean e of the first
+        hypothesis)."""
+        m, w, N = float(mwer_weight), float(ctc_weight), int(nbest)
+        if not 0.0 < m <= 1.0:
+            raise ValueError("--mwer-weight must lie in (0, 1] for an MWER step, got %g" % m)
+        if not 2 <= N <= ops.MWER_NBEST_MAX:
+            raise ValueError("--mwer-nbest %d: the n-best of an MWER step holds 2..%d hypotheses (the CTC prefix beam search's beam)"
+                             % (N, ops.MWER_NBEST_MAX))
+        if not 0.0 < w <= 1.0 or not hasattr(self, "ctc_linear"):
+            raise ValueError("--mwer-weight %g needs --ctc-weight > 0 and a model with an encoder CTC head: the n-best comes from the "
+                             "CTC prefix beam search" % m)
+        if unit == "word":
+            self.space_id()                            # refuse before any device work
+        feats = self._features(padded_input)
+        enc_out, _ = self.encoder(feats, input_lengths)
+        ctc = self.ctc_logits(enc_out)                 # (before the decoder: the logit hand-over slot belongs to the projection that runs last)
+        B, T, V = ctc.shape
+        dev = ctc.device
+        frames = self.ctc_frame_lengths(input_lengths, T)
+        tl = [int(x) for x in torch.as_tensor(target_lengths).tolist()]
+        tgt_host = torch.as_tensor(padded_target).cpu().tolist()
+        golds = [[int(t) for t in row[:n]] for row, n in zip(tgt_host, tl)]
+        if hyps is None:
+            with torch.no_grad():
+                out = ops.ctc_beam_search(ctc.detach(), _lengths_to_device(frames, dev), N, candidates, N, constant.PAD_TOKEN)
+                flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1)]).cpu()       # one device-to-host copy
+            ids, lens = torch.split(flat, [B * N * T, B * N])
+            ids, lens = ids.view(B, N, T).tolist(), lens.view(B, N).tolist()
+            hyps = [[ids[b][n][:lens[b][n]] for n in range(N) if lens[b][n] >= 0] for b in range(B)]
+        else:
+            hyps = [[[int(t) for t in y] for y in hs] for hs in hyps]
+            if len(hyps) != B or any(len(hs) > ops.MWER_NBEST_MAX for hs in hyps):
+                raise ValueError("mwer_step: hyps needs one list of at most %d hypotheses per utterance" % ops.MWER_NBEST_MAX)
+        errors = self.mwer_errors(hyps, golds, unit)
+        dec = self.decoder
+        rows = sum(len(y) + 1 for g, hs in zip(golds, hyps) for y in [g] + hs)
+        if rows * 4 * dec.num_trg_vocab > dec.RESCORE_LOGIT_BYTES:
+            raise ValueError("the MWER step scores %d decoder rows (%d utterances, gold + up to %d hypotheses each): %d bytes of fp32 logits "
+                             "over %d labels, above the %d-byte cap of one pass (Decoder.RESCORE_LOGIT_BYTES); a training step is not "
+                             "run in chunks -- lower --batch-size or --mwer-nbest"
+                             % (rows, B, N, rows * 4 * dec.num_trg_vocab, dec.num_trg_vocab, dec.RESCORE_LOGIT_BYTES))
+        limit = dec.positional_encoding.pe.shape[1] - 1
+        longest = max(len(y) for g, hs in zip(golds, hyps) for y in [g] + hs)
+        if longest > limit:
+            raise ValueError("the MWER step: a sequence has %d labels, the decoder's positional encoding reaches %d" % (longest, limit))
+        scored, seg_off, logits, _ = dec._score_rows(enc_out, [[g] + hs for g, hs in zip(golds, hyps)], differentiable=True)
+        utt_off, err = [0], []
+        for hs, es in zip(hyps, errors):
+            utt_off.append(utt_off[-1] + 1 + len(hs))
+            err += [0.0] + [float(e) for e in es]
+        ntok = sum(len(g) + 1 for g in golds)
+        Lg = max(len(g) for g in golds) + 1
+        M = seg_off[-1]
+        pos = [[seg_off[utt_off[b]] + j if j <= len(golds[b]) else M for j in range(Lg)] for b in range(B)]      # M: the PAD behind the rows
+        gold_rows = [g + [constant.EOS_TOKEN] + [constant.PAD_TOKEN] * (Lg - 1 - len(g)) for g in golds]
+        packed = torch.tensor([t for row in pos for t in row] + [t for row in gold_rows for t in row], dtype=torch.int64).to(dev, non_blocking=True)
+        pos_d, gold_seq = packed[:B * Lg].view(B, Lg), packed[B * Lg:].view(B, Lg)
+        err_d = torch.tensor(err, dtype=torch.float32).to(dev, non_blocking=True)
+        utt_d = torch.tensor(utt_off, dtype=torch.int32).to(dev, non_blocking=True)
+        part, prob, risk, sums = F_.MwerLossFn.apply(scored["score"], err_d, utt_d, m / B, (1.0 - m) * (1.0 - w) / ntok)
+        ctc_loss = F_.CTCFn.apply(ctc, torch.as_tensor(padded_target), torch.tensor(frames, dtype=torch.int32), torch.as_tensor(target_lengths),
+                                  constant.PAD_TOKEN)
+        loss = part + ((1.0 - m) * w) * ctc_loss
+        with torch.no_grad():
+            am = ops.argmax_rows(logits.detach())
+            hyp_seq = torch.cat([am, am.new_full((1,), constant.PAD_TOKEN)])[pos_d]
+        ranked = [es for es in errors if es]
+        stats = dict(risk=risk, prob=prob, sums=sums, nll=sums[1].detach() * (-1.0 / ntok), ctc=ctc_loss.detach(), hyps=hyps, errors=errors,
+                     expected_base=sum(sum(es) / len(es) for es in ranked) / B,
+                     top_error=sum(es[0] for es in ranked) / max(1, len(ranked)))
+        return loss, gold_seq, hyp_seq, stats
+
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
                  ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,
@@ -553,10 +677,26 @@ class Decoder(nn.Module):
 
     def _score_chunk(self, enc, hyps, return_tokens):
         """score_hypotheses for utterances whose logits fit one pass -> (scores, per-token terms or empty lists), nested per utterance."""
-        Bc = len(hyps)
         flat = [y for hs in hyps for y in hs]
         if not flat:
             return [[] for _ in hyps], [[] for _ in hyps]
+        out, seg_off = self._score_rows(enc, hyps)[:2]
+        back = torch.cat([out["score"], out["tok"]] if return_tokens else [out["score"]]).cpu().tolist()
+        scores, tokens, at = [], [], 0
+        for hs in hyps:
+            scores.append(back[at:at + len(hs)])
+            tokens.append([back[len(flat) + seg_off[at + w]:len(flat) + seg_off[at + w + 1]] for w in range(len(hs))] if return_tokens else [])
+            at += len(hs)
+        return scores, tokens
+
+    def _score_rows(self, enc, hyps, differentiable=False):
+        """The one teacher-forced pass of score_hypotheses over `hyps` (label-id lists per utterance, at least one in all) ->
+        (dict(score (R,), tok (M,)) on the device, seg_off (the R + 1 row offsets, a list), logits (M, V) fp32, targets (M,) on the
+        device), the R hypotheses in order.  differentiable: the same launches with the scores through F_.SeqLogProbFn, so that they carry
+        a gradient back to the parameters and the encoder output (MWER training, Transformer.mwer_step); the vocabulary projection then
+        reports its weight ready as Decoder.forward's does."""
+        Bc = len(hyps)
+        flat = [y for hs in hyps for y in hs]
         W = max(len(hs) for hs in hyps)
         L = max(len(y) for y in flat) + 1
         dev = enc.device
@@ -588,15 +728,14 @@ class Decoder(nn.Module):
                 x, _ = layer.encoder_attn(q, enc, enc, need_attn=False)
             x = layer.pos_ffn(x)
         scored = x.reshape(Bc * W * L, D).index_select(0, index_d)
-        logits = F_.linear(scored, self.output_linear.weight, None, True, False)
-        out = ops.seq_logprob(logits, tgt_d.contiguous(), seg_d)
-        back = torch.cat([out["score"], out["tok"]] if return_tokens else [out["score"]]).cpu().tolist()
-        scores, tokens, at = [], [], 0
-        for hs in hyps:
-            scores.append(back[at:at + len(hs)])
-            tokens.append([back[len(flat) + seg_off[at + w]:len(flat) + seg_off[at + w + 1]] for w in range(len(hs))] if return_tokens else [])
-            at += len(hs)
-        return scores, tokens
+        logits = F_.linear(scored, self.output_linear.weight, None, True, differentiable and not self.emb_trg_sharing)
+        tgt_d = tgt_d.contiguous()
+        if differentiable:
+            score, tok = F_.SeqLogProbFn.apply(logits, tgt_d, seg_d)
+            out = {"score": score, "tok": tok}
+        else:
+            out = ops.seq_logprob(logits, tgt_d, seg_d)
+        return out, seg_off, logits, tgt_d
 
     def _kv_cache_supported(self):
         """The incremental decoders (asr_hip/decode.py) read the full-rank projection weights of every layer; the Low-Rank

@@ -87,6 +87,9 @@ def main():
     args = constant.args
     from utils.functions import check_ctc_weight
     check_ctc_weight(args.ctc_weight, args)          # at start-up, before any process group or dataset exists
+    from utils.functions import check_mwer
+    if args.continue_from == "":                     # (a checkpoint brings its own --ctc-weight: checked again below, once it is known)
+        check_mwer(args)
     if "OMP_NUM_THREADS" not in os.environ:
         # the training process only issues kernel launches and small host tensor ops (collation runs in the loader's worker
         # processes): with torch's default of one intra-op thread per core, every host-side tensor op wakes a pool whose workers
@@ -143,6 +146,9 @@ def main():
         opt = init_optimizer(args, model, "noam")
     else:
         raise SystemExit("The model is not supported, check args --h")
+    if check_mwer(args, label2id) > 0:                # with the checkpoint's --ctc-weight and the labels the model trains on
+        logging.info("--mwer-weight %g: MWER training over the %d-best of the CTC prefix beam search, errors per %s; the step runs as "
+                     "eager launches", args.mwer_weight, args.mwer_nbest, args.mwer_unit)
     if constant.USE_CUDA:
         model = model.cuda()
     resolve_graph_buckets(args, constant.explicit, model)          # after the model exists: its front end decides, not the command line's default

@@ -224,23 +224,40 @@ class Trainer():
             if r is not None:
                 loss, gold_seq, hyp_seq = r
                 return _Pending(gold_seq, hyp_seq, loss, id2label, graph_opt=opt)         # asynchronous D2H; no sync in this step
+        # --mwer-weight m > 0 (MWER training over the CTC n-best): training steps only, on the eager path like the
+        # joint step; validation keeps the joint loss below.  With m = 0 nothing here runs.
+        mwer_step = opt is not None and float(getattr(constant.args, "mwer_weight", 0.0) or 0.0) > 0
+        self._log_mwer()                                # the previous MWER step's figures have reached the host by now
         if opt is not None:
             opt.zero_grad()
-        if ctc_weight > 0:
+        if mwer_step:
+            a = constant.args
+            mwer_weight = float(a.mwer_weight)
+            if ctc_weight <= 0 or loss_type != "ce":
+                raise ValueError("--mwer-weight %g needs --ctc-weight > 0 and --loss ce" % mwer_weight)
+            if smoothing > 0 and not self.__dict__.get("_logged_mwer_smoothing"):
+                self._logged_mwer_smoothing = True
+                logging.info("--mwer-weight %g: --label-smoothing %g does not apply to the MWER step's gold term (unsmoothed NLL of the "
+                             "gold transcript, EOS included)", mwer_weight, smoothing)
+            core = model.module if hasattr(model, "module") else model
+            loss, gold_seq, hyp_seq, stats = core.mwer_step(src, src_lengths, tgt, tgt_lengths, mwer_weight, ctc_weight,
+                                                            nbest=int(getattr(a, "mwer_nbest", 4)), unit=getattr(a, "mwer_unit", "label"),
+                                                            candidates=int(getattr(a, "ctc_candidates", 0) or 0))
+            self._queue_mwer_log(stats, int(src.shape[0]))
+        elif ctc_weight > 0:
             pred, gold, hyp_seq, gold_seq, ctc_logits = model(src, src_lengths, tgt, verbose=False, return_ctc=True)
-        else:
-            pred, gold, hyp_seq, gold_seq = model(src, src_lengths, tgt, verbose=False)
-        if ctc_weight > 0:
             core = model.module if hasattr(model, "module") else model
             loss, _, _ = calculate_joint_loss(core, pred, gold, ctc_logits, tgt, src_lengths, tgt_lengths, smoothing, ctc_weight)
-        elif loss_type == "ctc":
-            # reference trainer.py:81-85: input lengths = source percentages x decoder positions, targets' true lengths
-            sizes = (src_percentages.float() * int(pred.size(1))).int()
-            loss, sums = calculate_metrics(pred, gold, input_lengths=sizes, target_lengths=tgt_lengths, loss_type="ctc")
-            if opt is not None:
-                self.publish_mean_loss(opt, loss)
         else:
-            loss, sums = calculate_metrics(pred, gold, smoothing=smoothing, loss_type=loss_type, sync=False)
+            pred, gold, hyp_seq, gold_seq = model(src, src_lengths, tgt, verbose=False)
+            if loss_type == "ctc":
+                # reference trainer.py:81-85: input lengths = source percentages x decoder positions, targets' true lengths
+                sizes = (src_percentages.float() * int(pred.size(1))).int()
+                loss, sums = calculate_metrics(pred, gold, input_lengths=sizes, target_lengths=tgt_lengths, loss_type="ctc")
+                if opt is not None:
+                    self.publish_mean_loss(opt, loss)
+            else:
+                loss, sums = calculate_metrics(pred, gold, smoothing=smoothing, loss_type=loss_type, sync=False)
         finite = torch.isfinite(loss.detach()).float()
         if dist.is_initialized() and dist.get_world_size() > 1:
             dist.all_reduce(finite, op=dist.ReduceOp.MIN)        # skip on every rank or on none
@@ -262,6 +279,31 @@ class Trainer():
             return _Pending(gold_seq, hyp_seq, loss, id2label)  # training: the ids / loss reach the host under the next step
         ids = torch.stack([gold_seq, hyp_seq]).cpu().tolist()   # one D2H copy
         return ((loss.item() if loss_value is None else loss_value),) + self._text_metrics(ids, id2label)
+
+    def _queue_mwer_log(self, stats, B):
+        """The sum of the batch's risks starts its way to the host (pinned memory, no synchronisation); _log_mwer reports it later."""
+        buf = self.__dict__.get("_mwer_buf")
+        if buf is None:
+            buf = self._mwer_buf = torch.empty(2, dtype=torch.float32).pin_memory() if stats["sums"].is_cuda else torch.empty(2)
+        buf.copy_(stats["sums"].detach(), non_blocking=True)
+        ev = None
+        if stats["sums"].is_cuda:
+            ev = torch.cuda.Event()
+            ev.record()
+        self._mwer_pending = (ev, B, stats["expected_base"], stats["top_error"], sum(len(hs) for hs in stats["hyps"]))
+
+    def _log_mwer(self):
+        """logging.info of the last MWER step: the mean expected error of the batch under the decoder's renormalised n-best
+        probabilities (sum of risks / B + the mean of the lists' mean errors) and the mean error of the top hypothesis."""
+        pend = self.__dict__.get("_mwer_pending")
+        if pend is None:
+            return
+        self._mwer_pending = None
+        ev, B, base, top, nhyp = pend
+        if ev is not None:
+            ev.synchronize()
+        logging.info("MWER step: mean expected error %.4f, mean error of the top hypothesis %.4f (%d utterances, %d hypotheses)",
+                     float(self._mwer_buf[0]) / max(1, B) + base, top, B, nhyp)
 
     @staticmethod
     def _text_metrics(ids, id2label):
@@ -318,6 +360,7 @@ class Trainer():
                     account(r, i)
             if pending is not None:
                 account(pending[0].result(), pending[1])
+            self._log_mwer()
             logging.info("(Epoch {}) TRAIN LOSS:{:.4f} CER:{:.2f}% LR:{:.7f}".format(
                 epoch + 1, total_loss / max(1, len(train_loader)), total_cer * 100 / max(1, total_char), opt._rate))
 

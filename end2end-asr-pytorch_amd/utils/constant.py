@@ -27,7 +27,9 @@ Differences that do not change old command lines:
   * `--ngram-path FILE` (+ `--ngram-weight`, `--ngram-length-bonus`; test.py --ctc-beam-search): a label n-gram LM of train_ngram.py
     fused into the CTC prefix beam search's pruning (DESIGN.md section 7);
   * `--context-path FILE` (+ `--context-score`; test.py --ctc-beam-search): a list of phrases, one per line, that the CTC prefix beam
-    search's pruning is biased towards (utils/context.py).
+    search's pruning is biased towards (utils/context.py, DESIGN.md section 7);
+  * `--mwer-weight m` (+ `--mwer-nbest`, `--mwer-unit`; train.py with --ctc-weight > 0): minimum word error rate training over the CTC
+    prefix beam search's n-best, rescored by the attention decoder with grad (csrc/mwer.hip).
 """
 import argparse
 import os
@@ -121,6 +123,12 @@ _FLAGS = [
     # decoding from the CTC head alone
     (("--ctc-weight",), dict(default=0.0, type=_F)), (("--ctc-decode-weight",), dict(default=0.0, type=_F)),
     (("--ctc-candidates",), dict(default=0, type=_I)), (("--ctc-greedy",), dict(action="store_true")),
+    # minimum word error rate training over the CTC n-best (train.py, after --continue-from).  --mwer-weight m in
+    # (0, 1]: L = m * expected errors above the list's mean + (1 - m) * [(1 - w) NLL + w CTC] with w = --ctc-weight > 0; the n-best = the
+    # --mwer-nbest (2..16) survivors of the CTC prefix beam search (--ctc-candidates labels per frame), rescored by the decoder WITH grad;
+    # --mwer-unit: errors counted over label ids or over the words between space labels.  0 = off: nothing new is built or launched
+    (("--mwer-weight",), dict(default=0.0, type=_F)), (("--mwer-nbest",), dict(default=4, type=_I)),
+    (("--mwer-unit",), dict(default="label", choices=["label", "word"])),
     # --ctc-beam-search (test.py): prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): --beam-width (1..16)
     # prefixes kept per frame, --ctc-candidates (0: min(V, 16)) labels tried per frame, the n-best ranked like --beam-search's
     (("--ctc-beam-search",), dict(action="store_true")),

@@ -162,6 +162,34 @@ def check_ctc_weight(w, args=None):
     return w
 
 
+def check_mwer(args, label2id=None):
+    """--mwer-weight m (minimum word error rate training over the CTC n-best) -> m.  m must lie in [0, 1]; m > 0
+    needs --ctc-weight > 0 (the n-best comes from the encoder CTC head's prefix beam search), --loss ce, no --parallel, --mwer-nbest in
+    2..16 and, with --mwer-unit word, a space among the labels (label2id, when given).  m = 0: nothing is checked beyond the range."""
+    m = float(getattr(args, "mwer_weight", 0.0) or 0.0)
+    if not 0.0 <= m <= 1.0:
+        raise ValueError("--mwer-weight must lie in [0, 1], got %g" % m)
+    if m == 0.0:
+        return m
+    if not float(getattr(args, "ctc_weight", 0.0) or 0.0) > 0.0:
+        raise ValueError("--mwer-weight %g needs --ctc-weight > 0: the n-best comes from the prefix beam search over the encoder CTC "
+                         "head, and without the weight the model has no such head" % m)
+    if getattr(args, "parallel", False):
+        raise ValueError("--mwer-weight %g with --parallel is not supported: the MWER step runs on the single-process eager path" % m)
+    if getattr(args, "loss", "ce") != "ce":
+        raise ValueError("--mwer-weight %g with --loss %s is not supported: the risk is interpolated with the joint cross-entropy / CTC "
+                         "loss (--loss ce)" % (m, args.loss))
+    n = int(getattr(args, "mwer_nbest", 4))
+    if not 2 <= n <= 16:
+        raise ValueError("--mwer-nbest %d: the n-best holds 2..16 hypotheses (the CTC prefix beam search keeps at most 16 prefixes)" % n)
+    unit = getattr(args, "mwer_unit", "label")
+    if unit not in ("label", "word"):
+        raise ValueError("--mwer-unit must be 'label' or 'word', got %r" % (unit,))
+    if unit == "word" and label2id is not None and " " not in label2id:
+        raise ValueError("--mwer-unit word needs a space label to split words at, and the label file has none (use --mwer-unit label)")
+    return m
+
+
 def init_transformer_model(args, label2id, id2label):
     """Builds Encoder / Decoder / Transformer from the flags; mutates args.dim_input exactly like the reference
     (functions.py:116-162): 5120 for vgg_cnn, 672 for emb_cnn, unchanged (161) without a CNN.  With --features fbank the bins are

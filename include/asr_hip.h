@@ -457,6 +457,24 @@ int asr_logsoftmax_topk(const float* logits, int64_t ld, int M, int V, int k, fl
  * V < 1, ld < V, R < 0 or M < 0: ASR_EINVAL.                                                                                            */
 int asr_seq_logprob(const float* logits, int64_t ld, const int64_t* tgt, const int32_t* seg_off, int R, int M, int V, float* tok_lp,
                     float* score, asr_stream_t stream);
+/* MWER training over the CTC n-best (csrc/mwer.hip).
+ * asr_seq_logprob_bwd: the backward of asr_seq_logprob.  Row m of segment r (seg_off as above), c = grad_out * coef[r] (coef (R) fp32 on
+ * the device; grad_out a device scalar, NULL = 1): dlogits[m,v] = c * ([v == tgt[m]] - softmax(logits[m,:V])[v]), in the form asr_ce_bwd
+ * writes: dtype `out_dtype` (ASR_F32 / ASR_BF16), leading dimension ldd >= V, columns V..ldd-1 zero.  A row with c == 0, with a tgt
+ * outside [0,V) or in no segment is all zeros and its logits are not read.  The log-sum-exp is recomputed with asr_seq_logprob's code
+ * (the same bits through an aligned and a misaligned row base); one owner per element, no atomics.  M == 0: nothing is launched.
+ * V < 1, ld < V, ldd < V, R < 0, M < 0 or another out_dtype: ASR_EINVAL.                                                                */
+int asr_seq_logprob_bwd(const float* logits, int64_t ld, const int64_t* tgt, const int32_t* seg_off, const float* coef,
+                        const float* grad_out, int R, int M, int V, void* dlogits, int64_t ldd, int out_dtype, asr_stream_t stream);
+/* asr_mwer_loss: one launch per step over the R segment scores.  utt_off (B+1) int32 on the device, non-decreasing, utt_off[B] = R
+ * (clamped to [0,R] when read): utterance b owns segments utt_off[b] .. utt_off[b+1]-1, the FIRST is its gold (err is ignored there),
+ * the other n_b are its hypotheses.  P_i = softmax over the hypotheses' scores, risk[b] = sum_i P_i (err_i - mean_j err_j),
+ * prob[R] (0 on gold), coef[R] = risk_scale * P_i (err_i - sum_j P_j err_j) on hypotheses and -gold_scale on gold,
+ * sums[2] = [sum_b risk[b], sum_b score[gold_b]].  n_b <= 1: risk 0, coef 0 (prob 1 for a single finite hypothesis); a score of -inf:
+ * prob 0, coef 0.  One lane per utterance, everything in index order in fp32, sums added in utterance order by one lane: the bits are
+ * a function of the input alone.                                                                                                        */
+int asr_mwer_loss(const float* score, const float* err, const int32_t* utt_off, int B, int R, float risk_scale, float gold_scale,
+                  float* prob, float* coef, float* risk, float* sums, asr_stream_t stream);
 /* dlogits[m,v] = coef * (softmax*sum_q - q), coef = *grad_out / *count (device scalars), 0 for PAD rows.
  * dlogits has leading dimension ldd >= V and dtype `out_dtype`; columns V..ldd-1 are zero-filled.              */
 int asr_ce_bwd(const float* logits, int64_t ld, const int64_t* gold, const float* row_lse, int M, int V,
