@@ -1089,6 +1089,57 @@ class CEFn(Function):
         return dl.view(ctx.shape), None, None, None, None
 
 
+class DistillFn(Function):
+    """loss = (ce_scale * sum of CEFn's row losses + kd_scale * sum_m kd_m) / count over the live rows (gold != pad_id), with
+    kd_m = tau^2 KL(softmax(teacher / tau) || softmax(student / tau)) of row m (ops.distill_fwd).  count is the
+    live-row count.  with_ce=False: the KD term alone -- gold only marks the live rows
+    and ce_scale is taken as 0.  -> (loss, sums (4,) = [sum ce, #live, #correct, sum kd], argmax (M,) or an empty tensor without with_ce),
+    the last two not differentiable; the teacher logits never get a gradient.
+    backward: ONE asr_distill_bwd launch writes the combined CE + KD gradient.  The vocabulary projection's hand-over slot takes one
+    gradient per logits tensor, which is why the two terms share a Function: when the student logits come straight from the projection
+    of a bf16 model the gradient goes through the slot exactly as CEFn's does (bf16, zero padded to 64 columns, a stride-0 zero as the
+    formal gradient); otherwise the fp32 gradient is returned.  The claim empties the slot whoever makes it: of two DistillFn calls
+    in one step, the one on the projection's logits comes first."""
+
+    @staticmethod
+    def forward(ctx, student_logits, teacher_logits, gold, smoothing, pad_id, temperature, ce_scale, kd_scale, with_ce):
+        ctx.set_materialize_grads(False)
+        V = student_logits.shape[-1]
+        if teacher_logits.shape != student_logits.shape:
+            raise ValueError("DistillFn: student logits %s and teacher logits %s differ in shape"
+                             % (tuple(student_logits.shape), tuple(teacher_logits.shape)))
+        logits = student_logits.reshape(-1, V)
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        logits = logits.contiguous()
+        teach = teacher_logits.detach().reshape(-1, V)
+        if teach.dtype != torch.float32:
+            teach = teach.float()
+        teach = teach.contiguous()
+        g = gold.reshape(-1).contiguous()
+        if not with_ce:
+            ce_scale = 0.0
+        stats, am, sums, loss = ops.distill_fwd(logits, teach, g, smoothing, pad_id, temperature, ce_scale, kd_scale, with_ce=with_ce)
+        if am is None:
+            am = g.new_empty(0)
+        ctx.t = (logits, teach, g, stats, sums[1:2])
+        ctx.cfg = (float(smoothing), int(pad_id), float(temperature), float(ce_scale), float(kd_scale))
+        ctx.shape = student_logits.shape
+        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        ctx.mark_non_differentiable(sums, am)
+        return loss.reshape(()), sums, am
+
+    @staticmethod
+    def backward(ctx, dloss, *unused):
+        logits, teach, g, stats, count = ctx.t
+        go = dloss.reshape(1).float().contiguous()
+        if ctx.handover is not None:
+            ctx.handover["dy"] = ops.distill_bwd(logits, teach, g, stats, *ctx.cfg, go, count, out_dtype=torch.bfloat16, pad=64)
+            return (ops.zero_scalar(logits.device).expand(ctx.shape),) + (None,) * 8
+        dl = ops.distill_bwd(logits, teach, g, stats, *ctx.cfg, go, count)
+        return (dl.view(ctx.shape),) + (None,) * 8
+
+
 class CTCFn(Function):
     """loss = F.ctc_loss(F.log_softmax(pred, 2).transpose(0, 1), gold, input_lengths, target_lengths, reduction="mean")
     (reference: utils/metrics.py:133-154; blank = PAD = 0)."""

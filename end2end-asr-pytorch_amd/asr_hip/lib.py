@@ -105,6 +105,10 @@ _SIGS = {
                                 _P, _P]),
     "asr_dec_finish": (_I, [_P, _L, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "asr_ce_bwd": (_I, [_P, _L, _P, _P, _I, _I, _F, _I, _P, _P, _P, _L, _I, _P]),
+    "asr_distill_partial_blocks": (_I, [_I]),
+    "asr_distill_fwd": (_I, [_P, _L, _P, _L, _P, _I, _I, _F, _I, _F, _I, _P, _P, _P, _P]),
+    "asr_distill_finish": (_I, [_P, _I, _P, _F, _F, _P, _P, _P]),
+    "asr_distill_bwd": (_I, [_P, _L, _P, _L, _P, _P, _I, _I, _F, _I, _F, _F, _F, _P, _P, _P, _L, _I, _P]),
     "asr_adam_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _P]),
     "asr_step_advance": (_I, [_P, _P]),
     "asr_adam_noam_step": (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P]),

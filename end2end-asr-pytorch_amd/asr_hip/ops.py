@@ -1070,6 +1070,49 @@ def ce_bwd(logits, gold, lse, smoothing, pad_id, grad_out, count, out_dtype=torc
     return dl if pad == 64 else dl[:, :V]
 
 
+def _distill_args(student, teacher, gold):
+    M, V = student.shape
+    assert student.dtype == torch.float32 and teacher.dtype == torch.float32 and teacher.shape == student.shape
+    assert (student.stride(1) == 1 or V == 1) and (teacher.stride(1) == 1 or V == 1)
+    assert gold.dtype == torch.int64 and gold.numel() == M and gold.is_contiguous()
+    return M, V
+
+
+def distill_fwd(student, teacher, gold, smoothing, pad_id, temperature, ce_scale, kd_scale, with_ce=True, den=None):
+    """Knowledge distillation from a teacher's logits (csrc/distill.hip): student, teacher (M,V) fp32 with unit
+    column stride and any row stride, gold (M) int64; row m is live iff gold[m] != pad_id.  One row pass and one finish launch ->
+    (row_stats (M,4) = [lse(s), lse(s/tau), lse(t/tau), kd_m], argmax (M) int64 or None without with_ce, sums (4) = [sum ce, #live,
+    #correct, sum kd], loss (1) = (ce_scale sums[0] + kd_scale sums[3]) / den), den = the live count unless a device scalar is given.
+    Per-block partial sums added in a fixed order: the same bits for the same input."""
+    M, V = _distill_args(student, teacher, gold)
+    dev = student.device
+    stats = torch.empty((M, 4), device=dev, dtype=torch.float32)
+    am = torch.empty(M, device=dev, dtype=torch.int64) if with_ce else None
+    nb = int(L.load().asr_distill_partial_blocks(M))
+    part = torch.empty(max(nb, 1) * 4, device=dev, dtype=torch.float32)
+    sums = torch.empty(4, device=dev, dtype=torch.float32)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    L.call("asr_distill_fwd", L.ptr(student), student.stride(0), L.ptr(teacher), teacher.stride(0), L.ptr(gold), M, V, float(smoothing),
+           int(pad_id), float(temperature), 1 if with_ce else 0, L.ptr(stats), L.ptr(am), L.ptr(part), L.stream())
+    L.call("asr_distill_finish", L.ptr(part), nb, L.ptr(den), float(ce_scale), float(kd_scale), L.ptr(sums), L.ptr(loss), L.stream())
+    return stats, am, sums, loss
+
+
+def distill_bwd(student, teacher, gold, row_stats, smoothing, pad_id, temperature, ce_scale, kd_scale, grad_out, count,
+                out_dtype=torch.float32, pad=8):
+    """The combined CE + KD logit gradient of distill_fwd, one launch: c (ce_scale (softmax(s) sum_q - q) + kd_scale tau (pS - pT)) with
+    c = grad_out / count (device scalars) on live rows, zero on dead ones.  Returned like ce_bwd's: an (M,V) view of an (M, V rounded up
+    to `pad`) buffer whose pad columns are zero, the WHOLE buffer with pad=64."""
+    M, V = _distill_args(student, teacher, gold)
+    assert row_stats.dtype == torch.float32 and row_stats.shape == (M, 4) and row_stats.is_contiguous()
+    ld = (V + pad - 1) // pad * pad
+    dl = torch.empty((M, ld), device=student.device, dtype=out_dtype)
+    L.call("asr_distill_bwd", L.ptr(student), student.stride(0), L.ptr(teacher), teacher.stride(0), L.ptr(gold), L.ptr(row_stats), M, V,
+           float(smoothing), int(pad_id), float(temperature), float(ce_scale), float(kd_scale), L.ptr(grad_out), L.ptr(count), L.ptr(dl),
+           ld, L.dt(dl), L.stream())
+    return dl if pad == 64 else dl[:, :V]
+
+
 # ------------------------------------------------------------------------------------------------ optimiser
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=None):
     bc1 = 1.0 - beta1 ** step

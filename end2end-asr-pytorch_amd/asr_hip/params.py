@@ -58,8 +58,11 @@ def linear_shadow(p, dtype=None):
     w2 = p.data.view(p.shape[0], -1)
     N, K = w2.shape
     if sh is None or sh["w"].dtype != dtype or sh["w"].device != p.device:
-        sh = {"w": torch.zeros((N, ops._pad8(K)), device=p.device, dtype=dtype),
-              "wt": torch.zeros((K, ops._pad8(N)), device=p.device, dtype=dtype)}
+        # (rows allocated up to a multiple of 8, and zero: the GEMM kernels read an operand in 8-row chunks, and what lies behind the 4
+        # rows of a --rank 4 projection's W or W^T must be finite for the zero columns it meets to cancel it -- the backward of a
+        # --rank 4 bf16 model without a flat parameter buffer returned NaN whenever that memory happened to hold one)
+        sh = {"w": torch.zeros((ops._pad8(N), ops._pad8(K)), device=p.device, dtype=dtype)[:N],
+              "wt": torch.zeros((ops._pad8(K), ops._pad8(N)), device=p.device, dtype=dtype)[:K]}
         p.__dict__["_asr_shadow"] = sh
     ops.cast_into(w2, sh["w"], sh["wt"])
     sh["key"] = key

@@ -389,6 +389,63 @@ class Transformer(nn.Module):
                      top_error=sum(es[0] for es in ranked) / max(1, len(ranked)))
         return loss, gold_seq, hyp_seq, stats
 
+    # -------------------------------------------------------------------------------------------- knowledge distillation
+    def distill_step(self, padded_input, input_lengths, padded_target, target_lengths, teacher, distill_weight, temperature, smoothing,
+                     ctc_weight=0.0, distill_ctc_weight=0.0):
+        """One training step's loss with knowledge distillation from `teacher` (train.py --distill-from)
+        -> (L, gold, hyp_seq, stats).  With a = distill_weight, c = distill_ctc_weight, w = ctc_weight, tau = temperature, n live decoder
+        rows and F = sum_b T'_b live CTC frames (ctc_frame_lengths):
+            L_att = (1 - a) CE + a KD,     KD = (1/n) sum_m tau^2 KL(softmax(teacher_m / tau) || softmax(student_m / tau)),
+            w = 0:  L = L_att;     w > 0:  L = (1 - w) L_att + w [(1 - c) CTC + c KDF],     KDF = (1/F) sum_{t < T'_b} kd over the CTC heads.
+        The teacher runs forward(..., return_ctc = c > 0) under no_grad in eval mode on the very batch the student sees (already
+        augmented), and it runs FIRST: every vocabulary projection empties the logit hand-over slot, and the slot must hold the student's
+        when F_.DistillFn claims it.  L_att is one DistillFn call on the decoder logits (CE and KD gradients leave in one launch); KDF is a
+        second one without the CE term, on a gold tensor that is PAD on dead frames, and autograd adds its fp32 gradient to F_.CTCFn's.
+        stats: the device scalars 'ce', 'kd', 'ctc', 'kdf' (zeros where a term does not exist); no host synchronisation."""
+        a, c, w, tau = float(distill_weight), float(distill_ctc_weight), float(ctc_weight), float(temperature)
+        if not (0.0 <= a <= 1.0 and 0.0 <= c <= 1.0) or (a == 0.0 and c == 0.0):
+            raise ValueError("a distillation step needs --distill-weight or --distill-ctc-weight in (0, 1], got %g and %g" % (a, c))
+        if not 0.5 <= tau <= 16.0:
+            raise ValueError("--distill-temperature must lie in [0.5, 16], got %g" % tau)
+        if c > 0.0:
+            if not 0.0 < w <= 1.0 or not hasattr(self, "ctc_linear"):
+                raise ValueError("--distill-ctc-weight %g needs --ctc-weight > 0 and a student with an encoder CTC head" % c)
+            if not hasattr(teacher, "ctc_linear"):
+                raise ValueError("--distill-ctc-weight %g: the teacher has no encoder CTC head (ctc_linear), the student has one" % c)
+            if teacher.feat_extractor != self.feat_extractor:
+                raise ValueError("--distill-ctc-weight %g: the teacher's feat_extractor %s and the student's %s give different frame "
+                                 "counts" % (c, teacher.feat_extractor, self.feat_extractor))
+        if teacher.training:
+            teacher.eval()
+        with torch.no_grad():
+            t_out = teacher(padded_input, input_lengths, padded_target, return_ctc=c > 0.0)
+        s_out = self.forward(padded_input, input_lengths, padded_target, return_ctc=w > 0.0)
+        pred, gold, hyp_seq = s_out[0], s_out[1], s_out[2]
+        if t_out[0].shape != pred.shape:
+            raise ValueError("the teacher's decoder logits %s and the student's %s differ in shape: distillation needs the same labels "
+                             "and target positions" % (tuple(t_out[0].shape), tuple(pred.shape)))
+        PAD = constant.PAD_TOKEN
+        l_att, sums, _ = F_.DistillFn.apply(pred, t_out[0], gold, float(smoothing), PAD, tau, 1.0 - a, a, True)
+        zero = ops.zero_scalar(pred.device).reshape(())
+        stats = dict(ce=sums[0] / sums[1], kd=sums[3] / sums[1], ctc=zero, kdf=zero)
+        if not w > 0.0:
+            return l_att, gold, hyp_seq, stats
+        ctc = s_out[4]
+        frames = self.ctc_frame_lengths(input_lengths, ctc.shape[1])
+        ctc_loss = F_.CTCFn.apply(ctc, torch.as_tensor(padded_target), torch.tensor(frames, dtype=torch.int32), torch.as_tensor(target_lengths),
+                                  PAD)
+        stats["ctc"] = ctc_loss.detach()
+        ctc_term = ctc_loss
+        if c > 0.0:
+            if t_out[4].shape != ctc.shape:
+                raise ValueError("the teacher's CTC logits %s and the student's %s differ in shape" % (tuple(t_out[4].shape), tuple(ctc.shape)))
+            live = torch.arange(ctc.shape[1], device=ctc.device)[None, :] < _lengths_to_device(frames, ctc.device)[:, None]
+            gold_f = live.to(torch.int64) * (PAD + 1) + (~live).to(torch.int64) * PAD        # any non-PAD value marks a live frame
+            kdf, _, _ = F_.DistillFn.apply(ctc, t_out[4], gold_f, 0.0, PAD, tau, 0.0, 1.0, False)
+            stats["kdf"] = kdf.detach()
+            ctc_term = (1.0 - c) * ctc_loss + c * kdf
+        return (1.0 - w) * l_att + w * ctc_term, gold, hyp_seq, stats
+
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
                  ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,

@@ -90,6 +90,8 @@ def main():
     from utils.functions import check_mwer
     if args.continue_from == "":                     # (a checkpoint brings its own --ctc-weight: checked again below, once it is known)
         check_mwer(args)
+        from utils.functions import check_distill
+        check_distill(args)
     if "OMP_NUM_THREADS" not in os.environ:
         # the training process only issues kernel launches and small host tensor ops (collation runs in the loader's worker
         # processes): with torch's default of one intra-op thread per core, every host-side tensor op wakes a pool whose workers
@@ -149,14 +151,22 @@ def main():
     if check_mwer(args, label2id) > 0:                # with the checkpoint's --ctc-weight and the labels the model trains on
         logging.info("--mwer-weight %g: MWER training over the %d-best of the CTC prefix beam search, errors per %s; the step runs as "
                      "eager launches", args.mwer_weight, args.mwer_nbest, args.mwer_unit)
+    from utils.functions import check_distill, load_teacher
+    trainer = Trainer()
+    distill_a, distill_c = check_distill(args)         # with the checkpoint's --ctc-weight
+    if distill_a > 0 or distill_c > 0:
+        # the teacher is frozen and lives beside the run: it is never handed to init_optimizer and never saved with the student
+        trainer.teacher = load_teacher(args.distill_from, args, label2id)
+        logging.info("--distill-from %s: knowledge distillation, weight %g on the decoder logits and %g on the CTC head, temperature %g; "
+                     "the step runs as eager launches", args.distill_from, distill_a, distill_c, args.distill_temperature)
     if constant.USE_CUDA:
         model = model.cuda()
     resolve_graph_buckets(args, constant.explicit, model)          # after the model exists: its front end decides, not the command line's default
     logging.info("training step: %s", ("hipGraph replay per (batch, frames padded to a multiple of %d) shape (--graph-buckets 0: eager launches)"
                                        % args.graph_buckets) if args.graph_buckets > 0 else "eager launches (--graph-buckets N: captured hipGraphs)")
     logging.info(model)
-    Trainer().train(model, train_loader, train_sampler, valid_loader_list, opt, args.loss, start_epoch, args.epochs, label2id,
-                    id2label, metrics)
+    trainer.train(model, train_loader, train_sampler, valid_loader_list, opt, args.loss, start_epoch, args.epochs, label2id,
+                  id2label, metrics)
     if dist.is_initialized():
         dist.destroy_process_group()
 

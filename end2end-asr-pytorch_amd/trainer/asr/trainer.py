@@ -218,8 +218,17 @@ class Trainer():
         if ctc_weight > 0 and opt is not None and not self.__dict__.get("_logged_ctc_eager"):
             self._logged_ctc_eager = True
             logging.info("--ctc-weight %g: the hybrid CTC / attention step runs as eager launches (no hipGraph replay)", ctc_weight)
+        # --distill-from (knowledge distillation from a frozen teacher): training steps only, on the eager path like the
+        # joint step; validation keeps the losses below.  With both weights 0 nothing here runs and the step is unchanged.
+        distill_a = float(getattr(constant.args, "distill_weight", 0.0) or 0.0)
+        distill_c = float(getattr(constant.args, "distill_ctc_weight", 0.0) or 0.0)
+        distill_step = opt is not None and (distill_a > 0 or distill_c > 0)
+        if distill_step and not self.__dict__.get("_logged_distill_eager"):
+            self._logged_distill_eager = True
+            logging.info("--distill-weight %g --distill-ctc-weight %g: the distillation step runs as eager launches (no hipGraph replay)",
+                         distill_a, distill_c)
         if (opt is not None and loss_type == "ce" and getattr(constant.args, "graph_buckets", 0) > 0 and src.is_cuda
-                and ctc_weight == 0):
+                and ctc_weight == 0 and not distill_step):
             r = self._graph_step(model, opt, src, src_lengths, tgt, smoothing)
             if r is not None:
                 loss, gold_seq, hyp_seq = r
@@ -244,6 +253,17 @@ class Trainer():
                                                             nbest=int(getattr(a, "mwer_nbest", 4)), unit=getattr(a, "mwer_unit", "label"),
                                                             candidates=int(getattr(a, "ctc_candidates", 0) or 0))
             self._queue_mwer_log(stats, int(src.shape[0]))
+        elif distill_step:
+            teacher = self.__dict__.get("teacher")
+            if teacher is None:
+                raise ValueError("--distill-weight %g / --distill-ctc-weight %g: no teacher was loaded (Trainer.teacher = "
+                                 "utils.functions.load_teacher(--distill-from, ...))" % (distill_a, distill_c))
+            if loss_type != "ce":
+                raise ValueError("--distill-from needs --loss ce, got --loss %s" % loss_type)
+            core = model.module if hasattr(model, "module") else model
+            loss, gold_seq, hyp_seq, _ = core.distill_step(src, src_lengths, tgt, tgt_lengths, teacher, distill_a,
+                                                           float(getattr(constant.args, "distill_temperature", 2.0)), smoothing,
+                                                           ctc_weight=ctc_weight, distill_ctc_weight=distill_c)
         elif ctc_weight > 0:
             pred, gold, hyp_seq, gold_seq, ctc_logits = model(src, src_lengths, tgt, verbose=False, return_ctc=True)
             core = model.module if hasattr(model, "module") else model

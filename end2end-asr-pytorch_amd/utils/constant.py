@@ -29,7 +29,9 @@ Differences that do not change old command lines:
   * `--context-path FILE` (+ `--context-score`; test.py --ctc-beam-search): a list of phrases, one per line, that the CTC prefix beam
     search's pruning is biased towards (utils/context.py, DESIGN.md section 7);
   * `--mwer-weight m` (+ `--mwer-nbest`, `--mwer-unit`; train.py with --ctc-weight > 0): minimum word error rate training over the CTC
-    prefix beam search's n-best, rescored by the attention decoder with grad (csrc/mwer.hip).
+    prefix beam search's n-best, rescored by the attention decoder with grad (csrc/mwer.hip, DESIGN.md section 7);
+  * `--distill-from PATH` (+ `--distill-weight`, `--distill-ctc-weight`, `--distill-temperature`; train.py): knowledge distillation from
+    a frozen teacher checkpoint, word-level on the decoder logits and frame-level on the CTC head (csrc/distill.hip).
 """
 import argparse
 import os
@@ -129,6 +131,12 @@ _FLAGS = [
     # --mwer-unit: errors counted over label ids or over the words between space labels.  0 = off: nothing new is built or launched
     (("--mwer-weight",), dict(default=0.0, type=_F)), (("--mwer-nbest",), dict(default=4, type=_I)),
     (("--mwer-unit",), dict(default="label", choices=["label", "word"])),
+    # knowledge distillation from a teacher checkpoint (train.py; csrc/distill.hip).  --distill-from PATH: the
+    # teacher, frozen, run on every training batch; --distill-weight a in [0, 1]: L_att = (1 - a) CE + a KD on the decoder logits, KD =
+    # tau^2 KL(teacher || student) at --distill-temperature tau in [0.5, 16]; --distill-ctc-weight c in [0, 1] (with --ctc-weight w > 0):
+    # the CTC term becomes (1 - c) CTC + c KD over the CTC heads' frames.  Everything off: no teacher is built, nothing new is launched
+    (("--distill-from",), dict(default=None, type=_S)), (("--distill-weight",), dict(default=0.0, type=_F)),
+    (("--distill-ctc-weight",), dict(default=0.0, type=_F)), (("--distill-temperature",), dict(default=2.0, type=_F)),
     # --ctc-beam-search (test.py): prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): --beam-width (1..16)
     # prefixes kept per frame, --ctc-candidates (0: min(V, 16)) labels tried per frame, the n-best ranked like --beam-search's
     (("--ctc-beam-search",), dict(action="store_true")),

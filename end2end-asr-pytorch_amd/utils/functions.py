@@ -190,6 +190,95 @@ def check_mwer(args, label2id=None):
     return m
 
 
+def check_distill(args):
+    """--distill-from / --distill-weight a / --distill-ctc-weight c / --distill-temperature tau (knowledge distillation from a teacher
+    checkpoint) -> (a, c).  a and c lie in [0, 1], tau in [0.5, 16]; a positive weight needs --distill-from and a
+    path needs a positive weight; distillation excludes --parallel, --loss ctc and --mwer-weight > 0, and c > 0 needs --ctc-weight > 0
+    (the student's CTC head).  Everything off: (0, 0), nothing else is checked."""
+    a = float(getattr(args, "distill_weight", 0.0) or 0.0)
+    c = float(getattr(args, "distill_ctc_weight", 0.0) or 0.0)
+    path = getattr(args, "distill_from", None) or None
+    if not 0.0 <= a <= 1.0:
+        raise ValueError("--distill-weight must lie in [0, 1], got %g" % a)
+    if not 0.0 <= c <= 1.0:
+        raise ValueError("--distill-ctc-weight must lie in [0, 1], got %g" % c)
+    if a == 0.0 and c == 0.0:
+        if path is not None:
+            raise ValueError("--distill-from %s with --distill-weight 0 and --distill-ctc-weight 0: the teacher would be loaded and never "
+                             "used; give one of the weights" % path)
+        return a, c
+    if path is None:
+        raise ValueError("--distill-weight %g / --distill-ctc-weight %g need --distill-from PATH: the teacher checkpoint" % (a, c))
+    tau = float(getattr(args, "distill_temperature", 2.0))
+    if not 0.5 <= tau <= 16.0:
+        raise ValueError("--distill-temperature must lie in [0.5, 16], got %g" % tau)
+    if getattr(args, "parallel", False):
+        raise ValueError("--distill-from with --parallel is not supported: the distillation step runs on the single-process eager path")
+    if getattr(args, "loss", "ce") != "ce":
+        raise ValueError("--distill-from with --loss %s is not supported: the distillation term is interpolated with the cross-entropy "
+                         "loss (--loss ce)" % args.loss)
+    if float(getattr(args, "mwer_weight", 0.0) or 0.0) > 0.0:
+        raise ValueError("--distill-from with --mwer-weight %g is not supported: a training step is either the MWER step or the "
+                         "distillation step" % args.mwer_weight)
+    if c > 0.0 and not float(getattr(args, "ctc_weight", 0.0) or 0.0) > 0.0:
+        raise ValueError("--distill-ctc-weight %g needs --ctc-weight > 0: the frame-level term is taken on the student's encoder CTC "
+                         "head, and without the weight the model has no such head" % c)
+    return a, c
+
+
+_TEACHER_FRONT_END = ("sample_rate", "window_size", "window_stride", "window")
+
+
+def load_teacher(path, args, label2id):
+    """The frozen teacher of a distillation run (train.py --distill-from): built from the checkpoint's OWN
+    Namespace, on a copy, with parallel=False and the student's --precision (ops.set_compute_dtype is process-wide); constant.args and
+    constant.explicit are not touched.  -> the model in eval mode, no parameter requiring grad, on the GPU with --cuda.  It is never
+    handed to init_optimizer.  ValueError for a missing file, for labels or feature settings that differ from the student's (args,
+    label2id), and -- with --distill-ctc-weight > 0 -- for a teacher without a CTC head or with another feat_extractor."""
+    import copy
+    if not os.path.isfile(path):
+        raise ValueError("--distill-from %s: no such teacher checkpoint (the student is %s)" % (path, getattr(args, "name", "this run")))
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    if "args" not in ckpt:
+        raise ValueError("--distill-from %s: the checkpoint carries no args to rebuild the teacher from" % path)
+    t_l2i = ckpt["label2id"]
+    if dict(t_l2i) != dict(label2id):
+        raise ValueError("--distill-from %s: the teacher's labels (%d) differ from the student's (%d): distillation compares the two "
+                         "models' distributions label by label" % (path, len(t_l2i), len(label2id)))
+    t_args = copy.deepcopy(ckpt["args"])
+    names = ("features", "num_mel_bins", "mel_fmin")
+    for k, tv, sv in zip(names, feature_settings(t_args), feature_settings(args)):
+        if tv != sv:
+            raise ValueError("--distill-from %s: the teacher was trained with --%s %s, the student runs with --%s %s: both models read "
+                             "the same batch" % (path, k.replace("_", "-"), tv, k.replace("_", "-"), sv))
+    for k in _TEACHER_FRONT_END:
+        tv, sv = getattr(t_args, k, None), getattr(args, k, None)
+        if tv != sv:
+            raise ValueError("--distill-from %s: the teacher was trained with --%s %s, the student runs with --%s %s: both models read "
+                             "the same batch" % (path, k.replace("_", "-"), tv, k.replace("_", "-"), sv))
+    t_args.parallel = False
+    t_args.precision = getattr(args, "precision", "bf16")
+    for k, v in zip(names, feature_settings(t_args)):
+        setattr(t_args, k, v)
+    teacher = init_transformer_model(t_args, t_l2i, ckpt["id2label"])
+    sd = ckpt["model_state_dict"]
+    if any(k.startswith("module.") for k in sd):
+        sd = {k[len("module."):]: v for k, v in sd.items()}
+    teacher.load_state_dict(sd)
+    if float(getattr(args, "distill_ctc_weight", 0.0) or 0.0) > 0.0:
+        if not hasattr(teacher, "ctc_linear"):
+            raise ValueError("--distill-ctc-weight %g: the teacher %s has no encoder CTC head (it was trained with --ctc-weight 0), the "
+                             "student has one" % (args.distill_ctc_weight, path))
+        if teacher.feat_extractor != getattr(args, "feat_extractor", None):
+            raise ValueError("--distill-ctc-weight %g: the teacher %s has --feat_extractor %s, the student %s: their CTC heads see "
+                             "different frame counts" % (args.distill_ctc_weight, path, teacher.feat_extractor, args.feat_extractor))
+    teacher.eval()
+    teacher.requires_grad_(False)
+    if getattr(args, "cuda", False):
+        teacher = teacher.cuda()
+    return teacher
+
+
 def init_transformer_model(args, label2id, id2label):
     """Builds Encoder / Decoder / Transformer from the flags; mutates args.dim_input exactly like the reference
     (functions.py:116-162): 5120 for vgg_cnn, 672 for emb_cnn, unchanged (161) without a CNN.  With --features fbank the bins are

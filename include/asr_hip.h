@@ -480,6 +480,33 @@ int asr_mwer_loss(const float* score, const float* err, const int32_t* utt_off, 
 int asr_ce_bwd(const float* logits, int64_t ld, const int64_t* gold, const float* row_lse, int M, int V,
                float smoothing, int pad_id, const float* grad_out, const float* count, void* dlogits, int64_t ldd,
                int out_dtype, asr_stream_t stream);
+/* Knowledge distillation from a teacher's logits (csrc/distill.hip).  student (M, ld_s) and teacher (M, ld_t) fp32;
+ * row m is LIVE iff gold[m] != pad_id; with tau = temperature, pS = softmax(student / tau), pT = softmax(teacher / tau) over the first V
+ * columns.  One wave per row, no atomics: every output is a function of the inputs alone.  Logits are assumed finite.
+ * asr_distill_fwd: kd_m = tau^2 sum_v pT_v (log pT_v - log pS_v) for every live row; with_ce != 0 also asr_ce_fwd's label-smoothed row
+ * loss and correct flag of the student row, and argmax (M) for EVERY row: the lowest index of the row maximum on live rows, 0 on dead
+ * ones.  row_stats (M,4) = [lse(student), lse(student / tau), lse(teacher / tau), kd_m], zeros on dead rows.  partials
+ * (asr_distill_partial_blocks(M), 4) = per block [sum ce, #live, #correct, sum kd], every slot written.  with_ce == 0: gold is only
+ * compared with pad_id, argmax may be NULL, slots 0 and 2 and row_stats[:,0] are 0.  The logits of dead rows and columns >= V are never
+ * read; rows are read with 16-byte loads where the row base allows, and give the same bits where it does not.
+ * asr_distill_finish: sums[0..3] = the partials added in a fixed order (overwritten), loss[0] = (ce_scale sums[0] + kd_scale sums[3]) /
+ * (den ? den[0] : sums[1]).
+ * asr_distill_bwd: c = grad_out[0] / count[0]; a live row gets dlogits[m,v] = c (ce_scale (softmax(student)_v sum_q - q_v) + kd_scale tau
+ * (pS_v - pT_v)) -- the first bracket is asr_ce_bwd's and is skipped (row_stats[:,0] unread) when ce_scale == 0; pS and pT come from one
+ * instruction sequence, so equal student and teacher bits give the gradient of kd_scale = 0.  Dead rows and columns V..ldd-1 are zero;
+ * out_dtype ASR_F32 or ASR_BF16.
+ * ASR_EINVAL: M < 1, V < 1, ld_s < V, ld_t < V, ldd < V, temperature outside [0.5, 16], smoothing outside [0, 1), another out_dtype, a
+ * NULL required pointer.                                                                                                              */
+int asr_distill_partial_blocks(int M);
+int asr_distill_fwd(const float* student, int64_t ld_s, const float* teacher, int64_t ld_t, const int64_t* gold, int M, int V,
+                    float smoothing, int pad_id, float temperature, int with_ce, float* row_stats, int64_t* argmax,
+                    float* partials, asr_stream_t stream);
+int asr_distill_finish(const float* partials, int nblocks, const float* den, float ce_scale, float kd_scale, float* sums,
+                       float* loss, asr_stream_t stream);
+int asr_distill_bwd(const float* student, int64_t ld_s, const float* teacher, int64_t ld_t, const int64_t* gold,
+                    const float* row_stats, int M, int V, float smoothing, int pad_id, float temperature, float ce_scale,
+                    float kd_scale, const float* grad_out, const float* count, void* dlogits, int64_t ldd, int out_dtype,
+                    asr_stream_t stream);
 
 /* ---- optimiser: Adam(beta 0.9/0.98, eps 1e-9) under the Noam schedule (utils/optimizer.py:15-32,
  * utils/functions.py:107).  One launch over the flat fp32 parameter/gradient/moment buffers.
