@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Which GEMM (or, with --family attention / --family conv, attention / convolution and pooling) kernels does a test run launch?  (tests/test_gpu_gemm_exact.py pins every arm of the
+"""Which GEMM (or, with --family attention / --family conv / --family embcnn, attention / convolution and pooling / emb_cnn data-path) kernels does a test run launch?  (tests/test_gpu_gemm_exact.py pins every arm of the
 GEMM dispatch, tests/test_gpu_attention_arms.py every arm of the attention dispatch; this is the evidence.)
 
   tools/kernel_coverage.py asm OUT_DIR                 compile the device side of the GEMM translation units (csrc/gemm_nt.hip, gemm_nn.hip,
@@ -21,7 +21,11 @@ of ASR_ATTN_DQ / ASR_ATTN_DKV reaches).  With `--family conv` they cover the nin
 and the trace is that of tests/test_gpu_conv_arms.py; --auto is the trace of the same command with `-k "not hooked"` (the cases that set no
 tuning hook carry no "hooked" in their ids), CONV_HOOK_ONLY explains the symbols only a hook reaches and CONV_HOOK_FORMS lists the launch
 forms of a shared symbol that only a hook reaches.  Instantiations that exist only in -DASR_TUNE_ABLATE or C64_TIMING builds are not in a
-default build's assembly and so not in the report.  The counter run is a run of its own: no --pmc next to the tracing."""
+default build's assembly and so not in the report.  With `--family embcnn` they cover csrc/embcnn.hip (im2col, col2im, window sum and
+the BatchNorm kernels of the emb_cnn front end) and the trace is that of tests/test_gpu_embcnn_arms.py; no tuning hook selects a kernel of
+that file.  `--group NAME=CSV` (any family, repeatable) adds a column with the launches in the trace of a part of the file -- the same
+command with `-k NAME` -- so that the report says which cases reach which symbol.  The counter run is a run of its own: no --pmc next to
+the tracing."""
 import argparse
 import collections
 import csv
@@ -37,8 +41,9 @@ GEMM_FILES = ("gemm_nt.hip", "gemm_nn.hip", "gemm_tn.hip", "gemm_big.hip")
 ATTENTION_FILES = ("attention_generic.hip", "attention_d64_fwd.hip", "attention_d64_bwd.hip", "attention_d64_bwd_fused.hip", "attention_pp.hip")
 CONV_FILES = ("conv1.hip", "conv1_wgrad_mfma.hip", "conv_igemm.hip", "conv_c64.hip", "conv_ws.hip", "conv_wgrad.hip", "conv_wgrad_dma.hip",
               "conv_level0.hip", "pool.hip")
-FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES, "conv": CONV_FILES}
-LABEL = {"gemm": "GEMM", "attention": "attention", "conv": "convolution / pooling"}
+EMBCNN_FILES = ("embcnn.hip",)
+FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES, "conv": CONV_FILES, "embcnn": EMBCNN_FILES}
+LABEL = {"gemm": "GEMM", "attention": "attention", "conv": "convolution / pooling", "embcnn": "emb_cnn data-path"}
 
 # kernels the automatic dispatch cannot choose: (substring of the demangled name, the line that decides)
 HOOK_ONLY = (
@@ -73,7 +78,7 @@ CONV_HOOK_FORMS = (
     ("vgg_level0_fwd / _dgrad / _wgrad_kernel with wsplit = 0",
      "conv_level0.hip: conv.0 on split weights unless L0_WSPLIT = 0 (an argument of the same kernels)"),
 )
-HOOK_ONLY_OF = {"gemm": HOOK_ONLY, "attention": (), "conv": CONV_HOOK_ONLY}
+HOOK_ONLY_OF = {"gemm": HOOK_ONLY, "attention": (), "conv": CONV_HOOK_ONLY, "embcnn": ()}
 
 # attention kernels that ops.attn_bwd never chooses (it asks for dQ and dK / dV in one launch): reached by a direct asr_attn_bwd call with one part
 PARTS_ONLY = (
@@ -143,7 +148,7 @@ def coverage(symbols, names, counts):
     return out
 
 
-def report(asm_dir, all_csv, auto_csv, walls, family="gemm"):
+def report(asm_dir, all_csv, auto_csv, walls, family="gemm", groups=()):
     ks = family_kernels(asm_dir, FAMILIES[family])
     syms = [s for _, s in ks]
     names = demangle(syms)
@@ -153,11 +158,17 @@ def report(asm_dir, all_csv, auto_csv, walls, family="gemm"):
     if auto_csv:
         with open(auto_csv, newline="") as fh:
             cauto = coverage(syms, names, launch_counts(fh))
+    cgroup = []
+    for g in groups:
+        gname, gcsv = g.split("=", 1)
+        with open(gcsv, newline="") as fh:
+            cgroup.append((gname, coverage(syms, names, launch_counts(fh))))
     for w in walls:
         print("wall time  %s s" % w.replace("=", "  "))
-    print("%-18s %9s %9s  kernel" % ("file", "launches", "no hook" if cauto is not None else ""))
+    gcols = "".join(" %11s" % n[:11] for n, _ in cgroup)
+    print("%-18s %9s %9s%s  kernel" % ("file", "launches", "no hook" if cauto is not None else "", gcols))
     for f, s in ks:
-        print("%-18s %9d %9s  %s" % (f, call[s], cauto[s] if cauto is not None else "", names[s]))
+        print("%-18s %9d %9s%s  %s" % (f, call[s], cauto[s] if cauto is not None else "", "".join(" %11d" % c[s] for _, c in cgroup), names[s]))
     never = [s for s in syms if call[s] == 0]
     print("\n%s kernel symbols: %d, launched: %d, never launched: %d" % (LABEL[family], len(syms), len(syms) - len(never), len(never)))
     for s in never:
@@ -192,8 +203,9 @@ if __name__ == "__main__":
     r_.add_argument("--auto")
     r_.add_argument("--wall", action="append", default=[])
     r_.add_argument("--family", choices=sorted(FAMILIES), default="gemm")
+    r_.add_argument("--group", action="append", default=[], metavar="NAME=CSV")
     a = ap.parse_args()
     if a.cmd == "asm":
         dump_asm(a.out, FAMILIES[a.family])
     else:
-        sys.exit(report(a.asm_dir, a.all_csv, a.auto, a.wall, a.family))
+        sys.exit(report(a.asm_dir, a.all_csv, a.auto, a.wall, a.family, a.group))
