@@ -12,6 +12,12 @@ GEMM dispatch, tests/test_gpu_attention_arms.py every arm of the attention dispa
                                                        no tuning hook); then the symbols never launched, and those launched only under a hook
                                                        with the dispatch line that keeps them from the automatic choice.  Exit status 1 if a
                                                        symbol was never launched.
+  tools/kernel_coverage.py diff A.csv B.csv [--only REGEX]
+                                                       the kernel names dispatched in kernel-trace A and never in B (names matched as `report`
+                                                       matches them): A = a `bench.py --workload lowrank --steps 2 --warmup 1` run (bf16, and
+                                                       again with --precision fp8), B = `pytest tests/test_gpu_lowrank_widths.py -m gpu` -- what the
+                                                       benchmark step launches that the test file never does.  --only 'gemm|fp8' keeps the GEMM family.
+                                                       Exit status 1 if the list is not empty.
 
 The trace is matched by mangled name (rocprofv3 -M; a trailing .kd is dropped) or, for a demangled trace, by the c++filt form with white
 space removed.  With `--family attention` both commands cover the five attention translation units that hold kernels (ATTENTION_FILES; csrc/attention.hip
@@ -191,6 +197,29 @@ def report(asm_dir, all_csv, auto_csv, walls, family="gemm", groups=()):
     return 1 if never else 0
 
 
+def diff(a_csv, b_csv, only=None):
+    """Kernel names (matched as `report` matches them: launch_counts' keys) dispatched in kernel-trace A and never in B, with their
+    dispatches in A; `only`: a regular expression the c++filt form of the name must contain.  Exit status 1 if there is one."""
+    with open(a_csv, newline="") as fh:
+        ca = launch_counts(fh)
+    with open(b_csv, newline="") as fh:
+        cb = launch_counts(fh)
+    na, nb = demangle(sorted(ca)), demangle(sorted(cb))                    # key -> c++filt form (a demangled key stays itself)
+    have = set(cb) | {_key(v) for v in nb.values()}                        # a mangled name in one trace may be demangled in the other
+    missing = []
+    for k in sorted(ca):
+        if k in have or _key(na[k]) in have:
+            continue
+        if only and not re.search(only, na[k]):
+            continue
+        missing.append((na[k], ca[k]))
+    print("kernel names dispatched in %s: %d, in %s: %d%s" % (a_csv, len(ca), b_csv, len(cb), ", filter %r" % only if only else ""))
+    print("dispatched in the first trace and never in the second: %d" % len(missing))
+    for shown, n in missing:
+        print("  ONLY-A %9d  %s" % (n, shown))
+    return 1 if missing else 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -204,8 +233,14 @@ if __name__ == "__main__":
     r_.add_argument("--wall", action="append", default=[])
     r_.add_argument("--family", choices=sorted(FAMILIES), default="gemm")
     r_.add_argument("--group", action="append", default=[], metavar="NAME=CSV")
+    d_ = sub.add_parser("diff")
+    d_.add_argument("a_csv")
+    d_.add_argument("b_csv")
+    d_.add_argument("--only", metavar="REGEX")
     a = ap.parse_args()
     if a.cmd == "asm":
         dump_asm(a.out, FAMILIES[a.family])
+    elif a.cmd == "diff":
+        sys.exit(diff(a.a_csv, a.b_csv, a.only))
     else:
         sys.exit(report(a.asm_dir, a.all_csv, a.auto, a.wall, a.family, a.group))
