@@ -13,6 +13,7 @@ Sub-layer -> reference code
   VGGFn      models/asr/transformer.py:42-53, :70-76
   EmbCNNFn   models/asr/transformer.py:33-40, :70-76
   CEFn       utils/metrics.py:102-132
+  RnntJointFn, RnntFn  (no reference code: the transducer head of --transducer-weight)
 """
 import collections
 import os
@@ -1162,6 +1163,90 @@ class CTCFn(Function):
         logits, tg, il, tl, ws = ctx.t
         dl = ops.ctc_bwd(logits, tg, il, tl, ws, dloss.reshape(1).float().contiguous(), ctx.blank)
         return dl, None, None, None, None
+
+
+# ================================================================================================ transducer head
+RNNT_MAX_LOGIT_BYTES = 1 << 31
+
+
+class RnntJointFn(Function):
+    """z (B,T,U+1,J) = tanh(e (B,T,J) + p (B,U+1,J)) in the compute dtype (ops.rnnt_joint).
+    backward: ONE launch (ops.rnnt_joint_bwd) reads dz and z once and leaves de = sum_u dz (1 - z^2) and dp = sum_t dz (1 - z^2)."""
+
+    @staticmethod
+    def forward(ctx, e, p):
+        cd = ops.compute_dtype()
+        z = ops.rnnt_joint(e if e.dtype == cd else e.to(cd), p if p.dtype == cd else p.to(cd))
+        ctx.z = z
+        ctx.dtypes = (e.dtype, p.dtype)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        z = ctx.z
+        de, dp = ops.rnnt_joint_bwd(dz if dz.dtype == z.dtype else dz.to(z.dtype), z)
+        return de.to(ctx.dtypes[0]), dp.to(ctx.dtypes[1])
+
+
+class RnntFn(Function):
+    """loss = mean_b nll_b / max(U_b, 1) of the transducer lattice (ops.rnnt_fwd): pred (B,T,U+1,V) fp32 joint
+    logits, gold (B,>=U) label ids without SOS / EOS, frame_lengths = true encoder frames T_b, target_lengths = U_b, blank = PAD.  The
+    reduction is CTCFn's, so --ctc-weight and --transducer-weight compare.  An utterance without an alignment (T_b = 0, a label that
+    is the blank or outside [0,V)) makes the loss +inf and gets zero gradient rows.
+    backward: ONE launch (ops.rnnt_bwd).  The logit hand-over slot: this Function CLAIMS it, as SeqLogProbFn does.  The model applies it
+    right behind the joint's vocabulary projection and before the decoder runs (Transformer.transducer_loss), so the slot it claims is
+    that projection's and the decoder's projection leaves a fresh one for CEFn afterwards.  In a bf16 model the gradient therefore
+    travels as bf16, zero padded to 64 columns, with a stride-0 zero as the formal gradient.  Memory at B 32, T' 75, V 4364: the fp32
+    logits are B T' (U+1) V 4 bytes = 0.88 GB at U 20 and 1.72 GB at U 40 (kept for the backward), the handed-over gradient half of a
+    4416-wide copy of that, 0.45 / 0.87 GB; returning the formal fp32 gradient instead would cost another 0.88 / 1.72 GB plus the cast
+    and pad launch.  Outside the slot (an fp32 model) the fp32 gradient is returned.
+    A shape whose fp32 logits (rows 64-column padded) reach 2^31 bytes is refused with a ValueError before any launch.  The new
+    kernels index in 64 bits; the vocabulary projection then runs B T' (U+1) rows through the GEMM arms of _linear_fwd / _lin_bwd, whose
+    row bases are 64 bit but whose M, tile counts and per-thread chunk offsets (csrc/gemm_tn.hip, csrc/gemm_nn.hip: offA / offB,
+    stage relative) are 32 bit, and not every arm has been read for products of them: the bound keeps every byte offset below 2^31
+    whatever an arm computes."""
+
+    @staticmethod
+    def forward(ctx, pred, gold, frame_lengths, target_lengths, blank):
+        if pred.dim() != 4:
+            raise ValueError("RnntFn: joint logits (B,T,U+1,V) expected, got %s" % (tuple(pred.shape),))
+        B, T, U1, V = pred.shape
+        check_rnnt_shape(B, T, U1, V)
+        logits = pred if pred.dtype == torch.float32 else pred.float()
+        logits = logits.contiguous()
+        dev = logits.device
+        tg = torch.as_tensor(gold).to(device=dev, dtype=torch.int64)
+        if U1 == 1 and tg.shape[1] == 0:
+            tg = tg.new_zeros((B, 1))
+        if tg.shape[1] < max(U1 - 1, 1):
+            raise ValueError("RnntFn: %d label columns for logits with U + 1 = %d" % (tg.shape[1], U1))
+        tg = tg[:, :max(U1 - 1, 1)].contiguous()
+        fl = torch.as_tensor(frame_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        loss, ws = ops.rnnt_fwd(logits, tg, fl, tl, blank)
+        ctx.t = (logits, tg, fl, tl, ws)
+        ctx.blank, ctx.shape = blank, pred.shape
+        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, tg, fl, tl, ws = ctx.t
+        go = dloss.reshape(1).float().contiguous()
+        if ctx.handover is not None:
+            ctx.handover["dy"] = ops.rnnt_bwd(logits, tg, fl, tl, ws, go, ctx.blank, out_dtype=torch.bfloat16, pad=64)
+            return ops.zero_scalar(logits.device).expand(ctx.shape), None, None, None, None
+        dl = ops.rnnt_bwd(logits, tg, fl, tl, ws, go, ctx.blank)
+        return dl.reshape(ctx.shape), None, None, None, None
+
+
+def check_rnnt_shape(B, T, U1, V):
+    """ValueError for joint logits (B,T,U1,V) whose fp32 bytes (rows 64-column padded, as their gradient is) reach 2^31."""
+    n = int(B) * int(T) * int(U1) * ((int(V) + 63) // 64 * 64) * 4
+    if n >= RNNT_MAX_LOGIT_BYTES:
+        raise ValueError("transducer joint logits (B %d, T %d, U+1 %d, V %d) take %d bytes in fp32: 2^31 or more is refused (the "
+                         "vocabulary projection's GEMMs keep 32-bit sizes and chunk offsets); use a smaller batch or shorter targets"
+                         % (B, T, U1, V, n))
 
 
 # ================================================================================================ MWER over the n-best

@@ -70,6 +70,12 @@ _SIGS = {
     "asr_ctc_workspace": (_L, [_I, _I, _I]),
     "asr_ctc_fwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     "asr_ctc_bwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "asr_rnnt_joint_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "asr_rnnt_joint_bwd_workspace": (_L, [_I, _I, _I, _I]),
+    "asr_rnnt_joint_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "asr_rnnt_workspace": (_L, [_I, _I, _I]),
+    "asr_rnnt_fwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "asr_rnnt_bwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P]),
     "asr_ctc_align_workspace": (_L, [_I, _I, _I]),
     "asr_ctc_align": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
     "asr_ctc_beam_workspace": (_L, [_I, _I, _I, _I]),

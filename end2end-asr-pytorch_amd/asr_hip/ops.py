@@ -653,6 +653,73 @@ def ctc_bwd(logits, targets, input_lengths, target_lengths, ws, grad_out, blank=
     return dl
 
 
+# ------------------------------------------------------------------------------------------------ transducer head (csrc/rnnt.hip)
+def rnnt_joint(e, p):
+    """z (B,T,U1,J) = tanh(e (B,T,J) + p (B,U1,J)): one launch, in the dtype of e (fp32 / bf16).  J must be a multiple of 8."""
+    B, T, J = e.shape
+    U1 = p.shape[1]
+    if p.shape[0] != B or p.shape[2] != J or p.dtype != e.dtype:
+        raise ValueError("rnnt_joint: e %s %s and p %s %s do not match" % (tuple(e.shape), e.dtype, tuple(p.shape), p.dtype))
+    if J % 8 != 0:
+        raise ValueError("rnnt_joint: the joint width must be a multiple of 8, got %d" % J)
+    e, p = e.contiguous(), p.contiguous()
+    z = torch.empty((B, T, U1, J), device=e.device, dtype=e.dtype)
+    if z.numel():
+        L.call("asr_rnnt_joint_fwd", L.ptr(e), L.ptr(p), L.ptr(z), B, T, U1, J, L.dt(e), L.stream())
+    return z
+
+
+def rnnt_joint_bwd(dz, z):
+    """(de (B,T,J), dp (B,U1,J)) = (sum_u, sum_t) of dz (1 - z^2) for dz, z (B,T,U1,J): one launch that reads both once and adds in a
+    fixed order (the same bits for the same input); outputs in the dtype of z."""
+    B, T, U1, J = z.shape
+    if dz.shape != z.shape or dz.dtype != z.dtype:
+        raise ValueError("rnnt_joint_bwd: dz %s %s and z %s %s do not match" % (tuple(dz.shape), dz.dtype, tuple(z.shape), z.dtype))
+    dz, z = dz.contiguous(), z.contiguous()
+    de = torch.empty((B, T, J), device=z.device, dtype=z.dtype)
+    dp = torch.empty((B, U1, J), device=z.device, dtype=z.dtype)
+    if z.numel():
+        n = L.load().asr_rnnt_joint_bwd_workspace(B, T, U1, J)
+        ws = torch.empty(n, device=z.device, dtype=torch.float32) if n else None
+        L.call("asr_rnnt_joint_bwd", L.ptr(dz), L.ptr(z), L.ptr(de), L.ptr(dp), L.ptr(ws), n, B, T, U1, J, L.dt(z), L.stream())
+    return de, dp
+
+
+def _rnnt_args(logits, targets, frame_lengths, target_lengths):
+    B, T, U1, V = logits.shape
+    assert logits.dtype == torch.float32 and (logits.stride(3) == 1 or V == 1)
+    ld = logits.stride(2)
+    assert logits.stride(1) == U1 * ld and logits.stride(0) == T * U1 * ld, "rnnt: logits rows at one stride"
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (B, max(U1 - 1, 1))
+    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
+    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    return B, T, U1 - 1, V, ld
+
+
+def rnnt_fwd(logits, targets, frame_lengths, target_lengths, blank=0):
+    """Transducer loss (csrc/rnnt.hip): logits (B,T,U+1,V) fp32 (rows at any one stride ld >= V), targets (B,max(U,1)) int64, lengths (B)
+    int32 on the device -> (loss (1,) = mean_b nll_b / max(U_b,1), workspace); workspace[-B:] holds nll_b."""
+    B, T, U, V, ld = _rnnt_args(logits, targets, frame_lengths, target_lengths)
+    n = L.load().asr_rnnt_workspace(B, T, U)
+    ws = torch.empty(n, device=logits.device, dtype=torch.float32)
+    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+    L.call("asr_rnnt_fwd", L.ptr(logits), ld, L.ptr(targets), L.ptr(frame_lengths), L.ptr(target_lengths), B, T, U, V, int(blank),
+           L.ptr(ws), n, L.ptr(loss), L.stream())
+    return loss, ws
+
+
+def rnnt_bwd(logits, targets, frame_lengths, target_lengths, ws, grad_out=None, blank=0, out_dtype=torch.float32, pad=8):
+    """grad_out * d loss / d logits of rnnt_fwd, ONE launch.  Returned like ce_bwd's: a (B T (U+1), V) view of a buffer V rounded up to
+    `pad` wide whose pad columns are zero, the WHOLE buffer with pad=64 (what the data-gradient GEMM contracts)."""
+    B, T, U, V, ld = _rnnt_args(logits, targets, frame_lengths, target_lengths)
+    assert grad_out is None or (grad_out.dtype == torch.float32 and grad_out.numel() == 1)
+    ldd = (V + pad - 1) // pad * pad
+    dl = torch.empty((B * T * (U + 1), ldd), device=logits.device, dtype=out_dtype)
+    L.call("asr_rnnt_bwd", L.ptr(logits), ld, L.ptr(targets), L.ptr(frame_lengths), L.ptr(target_lengths), B, T, U, V, int(blank),
+           L.ptr(ws), L.ptr(grad_out), L.ptr(dl), ldd, L.dt(dl), L.stream())
+    return dl if pad == 64 else dl[:, :V]
+
+
 def ctc_align(logits, targets, input_lengths, target_lengths, blank=0):
     """Forced alignment (csrc/ctc_align.hip): logits (B,T,V) fp32 (rows contiguous, any row stride), targets (B,Lmax) int64, lengths (B)
     int32 on the device -> dict(path (B,T) int32, start / end (B,Lmax) int32, lab_score (B,Lmax) fp32, score (B) fp32) on the device;

@@ -52,6 +52,21 @@ def ctc_collapse(ids, length=None, blank=constant.PAD_TOKEN):
     return out
 
 
+def check_transducer(dim_joint, context, dim_model=None):
+    """(J, C) of a transducer head, or ValueError: the joint width J = --transducer-dim-joint is the K of rnnt_out's GEMM and the N of
+    rnnt_enc's, and the joint kernel moves whole 16-byte chunks: a positive multiple of 8 (so must dim_model be, the K of rnnt_enc);
+    the stateless predictor's context C = --transducer-context is 1 or 2."""
+    J, C = int(dim_joint), int(context)
+    if J < 8 or J % 8 != 0:
+        raise ValueError("--transducer-dim-joint %d: the joint width must be a positive multiple of 8 (whole 16-byte chunks in the joint "
+                         "kernel and in the vocabulary projection's GEMM)" % J)
+    if C not in (1, 2):
+        raise ValueError("--transducer-context %d: the stateless predictor looks back 1 or 2 labels" % C)
+    if dim_model is not None and int(dim_model) % 8 != 0:
+        raise ValueError("a transducer head needs --dim-model to be a multiple of 8, got %d" % int(dim_model))
+    return J, C
+
+
 def hypothesis_labels(ids):
     """The label ids of a decoded hypothesis as a CTC target: SOS and EOS dropped, PAD dropped from the end.  A PAD (= the CTC blank)
     left inside has no alignment, and the aligner reports it so."""
@@ -70,9 +85,13 @@ class Transformer(nn.Module):
     """Transformer(encoder, decoder, feat_extractor='vgg_cnn')   (reference: transformer.py:16-57)
 
     ctc_head=True (train.py --ctc-weight > 0) adds `ctc_linear`, a CTC output layer on the ENCODER output for joint
-    CTC / attention training and decoding (blank = PAD).  Without it the module, its parameters and its state_dict keys do not exist."""
+    CTC / attention training and decoding (blank = PAD).  Without it the module, its parameters and its state_dict keys do not exist.
 
-    def __init__(self, encoder, decoder, feat_extractor='vgg_cnn', ctc_head=False):
+    transducer=dict(dim_joint=J, context=C) (train.py --transducer-weight > 0) adds a transducer head on the ENCODER
+    output: `rnnt_enc` (D -> J), the stateless predictor's tables `rnnt_embed.{0..C-1}` ((V, J) each, one per context position) and
+    `rnnt_out` (J -> V); blank = PAD.  None: none of them exists, nor their state_dict keys."""
+
+    def __init__(self, encoder, decoder, feat_extractor='vgg_cnn', ctc_head=False, transducer=None):
         super().__init__()
         self.encoder = encoder
         self.decoder = decoder
@@ -80,6 +99,11 @@ class Transformer(nn.Module):
         self.feat_extractor = feat_extractor
         if ctc_head:
             self.ctc_linear = nn.Linear(decoder.dim_model, decoder.num_trg_vocab)
+        if transducer is not None:
+            J, C = check_transducer(transducer.get("dim_joint", 256), transducer.get("context", 2), decoder.dim_model)
+            self.rnnt_enc = nn.Linear(decoder.dim_model, J)
+            self.rnnt_embed = nn.ModuleList([nn.Embedding(decoder.num_trg_vocab, J) for _ in range(C)])
+            self.rnnt_out = nn.Linear(J, decoder.num_trg_vocab)
         if feat_extractor == 'emb_cnn':
             self.conv = nn.Sequential(
                 nn.Conv2d(1, 32, kernel_size=(41, 11), stride=(2, 2), padding=(0, 10)), nn.BatchNorm2d(32),
@@ -252,6 +276,127 @@ class Transformer(nn.Module):
                        "logp": lab[b][l]} for l in range(Lmax) if start[b][l] >= 0]
             result.append({"score": score[b], "frames": n, "path": path[b][:n] if score[b] > -math.inf else [], "labels": labels})
         return result
+
+    # -------------------------------------------------------------------------------------------- transducer head
+    def _need_transducer(self):
+        if not hasattr(self, "rnnt_out"):
+            raise ValueError("this model has no transducer head (rnnt_enc / rnnt_embed / rnnt_out): it was trained with "
+                             "--transducer-weight 0")
+
+    def _rnnt_zero_pe(self, n, device):
+        """(n, J) fp32 zeros: the position term F_.EmbedFn adds (the predictor has none), kept per device and grown on demand."""
+        buf = self.__dict__.get("_rnnt_pe")
+        if buf is None or buf.shape[0] < n or buf.device != device:
+            buf = self.__dict__["_rnnt_pe"] = torch.zeros((max(int(n), 64), self.rnnt_out.in_features), device=device)
+        return buf
+
+    def _rnnt_predict(self, tokens):
+        """p (B,n,J) = sum_k E_k[tokens[k]] in the compute dtype; tokens: C tensors (B,n) int64, tokens[k] = the label k places back."""
+        p = None
+        for emb, tok in zip(self.rnnt_embed, tokens):
+            tok = tok.contiguous()
+            q = F_.EmbedFn.apply(tok, emb.weight, self._rnnt_zero_pe(tok.shape[1], tok.device), 1.0, 0.0, -1, True)
+            p = q if p is None else p + q
+        return p
+
+    def transducer_logits(self, enc_out, targets, target_lengths):
+        """(B,T',U+1,V) fp32 joint logits of the transducer head, U = the longest transcript of the batch
+        (target_lengths are host values): e = rnnt_enc(enc_out); p[b,u] = sum_k rnnt_embed.k[y_{u-k}] with SOS wherever u - k < 1; z =
+        tanh(e + p) (F_.RnntJointFn); logits = rnnt_out(z).  targets: (B,L) raw label ids without SOS / EOS, as the CTC term takes them."""
+        self._need_transducer()
+        tl = [int(x) for x in torch.as_tensor(target_lengths).tolist()]
+        B, T = enc_out.shape[0], enc_out.shape[1]
+        V, C = self.rnnt_out.out_features, len(self.rnnt_embed)
+        tg = torch.as_tensor(targets).to(enc_out.device, dtype=torch.int64)
+        U = max(0, min(int(tg.shape[1]), max(tl) if tl else 0))
+        F_.check_rnnt_shape(B, T, U + 1, V)                     # before the first launch
+        sos = torch.full((B, C), constant.SOS_TOKEN, dtype=torch.int64, device=tg.device)
+        hist = torch.cat([sos, tg[:, :U].clamp(0, V - 1)], 1)    # (a label outside [0,V) has no table row; the loss refuses it by itself)
+        tokens = [hist[:, C - 1 - k:C + U - k] for k in range(C)]
+        e = F_.linear(enc_out, self.rnnt_enc.weight, self.rnnt_enc.bias, False, True)
+        z = F_.RnntJointFn.apply(e, self._rnnt_predict(tokens))
+        return F_.linear(z, self.rnnt_out.weight, self.rnnt_out.bias, True, True)
+
+    def transducer_loss(self, enc_out, input_lengths, padded_target, target_lengths):
+        """The transducer loss of a batch, mean_b nll_b / max(U_b, 1) (F_.RnntFn), with T_b = ctc_frame_lengths.  Call it BEFORE the
+        decoder runs: RnntFn claims the logit hand-over slot its own projection has just left, and the decoder's projection then
+        leaves a fresh one for the cross-entropy."""
+        logits = self.transducer_logits(enc_out, padded_target, target_lengths)
+        frames = torch.tensor(self.ctc_frame_lengths(input_lengths, enc_out.shape[1]), dtype=torch.int32)
+        return F_.RnntFn.apply(logits, torch.as_tensor(padded_target), frames, torch.as_tensor(target_lengths), constant.PAD_TOKEN)
+
+    def transducer_step(self, padded_input, input_lengths, padded_target, target_lengths, transducer_weight, smoothing, ctc_weight=0.0):
+        """One training step's loss with the transducer term (train.py --transducer-weight r)
+        -> (L, gold, hyp_seq, stats): L = (1 - r) L_existing + r L_rnnt, L_existing = CE, or (1 - w) CE + w CTC with ctc_weight w > 0.
+        stats: the device scalars 'ce', 'ctc' (zero without the head) and 'rnnt'; no host synchronisation."""
+        from utils.metrics import calculate_metrics
+        r, w = float(transducer_weight), float(ctc_weight)
+        if not 0.0 < r <= 1.0:
+            raise ValueError("a transducer step needs --transducer-weight in (0, 1], got %g" % r)
+        if not 0.0 <= w <= 1.0 or (w > 0.0 and not hasattr(self, "ctc_linear")):
+            raise ValueError("--ctc-weight %g needs a value in [0, 1] and a model with an encoder CTC head" % w)
+        self._need_transducer()
+        feats = self._features(padded_input)
+        enc_out, _ = self.encoder(feats, input_lengths)
+        ctc = self.ctc_logits(enc_out) if w > 0.0 else None
+        rnnt = self.transducer_loss(enc_out, input_lengths, padded_target, target_lengths)
+        pred, gold, *_ = self.decoder(padded_target, enc_out, input_lengths)
+        hyp_seq = ops.argmax_rows(pred.detach().reshape(-1, pred.shape[-1])).view(pred.shape[0], pred.shape[1])
+        ce, _ = calculate_metrics(pred, gold, smoothing=smoothing, loss_type="ce", sync=False)
+        stats = dict(ce=ce.detach(), ctc=ops.zero_scalar(pred.device).reshape(()), rnnt=rnnt.detach())
+        existing = ce
+        if w > 0.0:
+            frames = torch.tensor(self.ctc_frame_lengths(input_lengths, ctc.shape[1]), dtype=torch.int32)
+            ctc_loss = F_.CTCFn.apply(ctc, torch.as_tensor(padded_target), frames, torch.as_tensor(target_lengths), constant.PAD_TOKEN)
+            stats["ctc"] = ctc_loss.detach()
+            existing = (1.0 - w) * ce + w * ctc_loss
+        return (1.0 - r) * existing + r * rnnt, gold, hyp_seq, stats
+
+    @torch.no_grad()
+    def transducer_greedy(self, enc_out, lengths, max_symbols=5, return_ids=False):
+        """Time-synchronous greedy search of the transducer head: at frame t of an utterance emit the joint's arg-max while it is not
+        blank, at most max_symbols times, then go to frame t + 1; frames >= lengths[b] (true encoder frames, ctc_frame_lengths) are never
+        visited.  All utterances advance together, each with its own frame pointer: T' * max_symbols steps of F_.linear / ops.rnnt_joint /
+        ops.argmax_rows with torch.where on the device, no host synchronisation inside the loop and one device-to-host copy at the end.
+        -> strings (return_ids: (strings, label ids)); the ids are labels as they stand: no SOS, no EOS."""
+        self._need_transducer()
+        S = int(max_symbols)
+        if S < 1:
+            raise ValueError("--transducer-max-symbols must be at least 1, got %d" % S)
+        B, T = enc_out.shape[0], enc_out.shape[1]
+        C, blank = len(self.rnnt_embed), constant.PAD_TOKEN
+        dev = enc_out.device
+        e = F_.linear(enc_out, self.rnnt_enc.weight, self.rnnt_enc.bias, False, True)
+        J = e.shape[-1]
+        frames = _lengths_to_device(lengths, dev).to(torch.int64).clamp(0, T)
+        cap = T * S
+        t_idx = torch.zeros(B, dtype=torch.int64, device=dev)
+        syms = torch.zeros(B, dtype=torch.int64, device=dev)
+        n_out = torch.zeros(B, dtype=torch.int64, device=dev)
+        hist = torch.full((B, C), constant.SOS_TOKEN, dtype=torch.int64, device=dev)        # hist[:, k] = the label k places back
+        out = torch.zeros((B, cap + 1), dtype=torch.int64, device=dev)                      # column `cap` takes the writes of idle rows
+        trash = torch.full((B,), cap, dtype=torch.int64, device=dev)
+        zero = torch.zeros(B, dtype=torch.int64, device=dev)
+        for _ in range(cap):
+            active = t_idx < frames
+            e_t = e.gather(1, t_idx.clamp(max=T - 1).view(B, 1, 1).expand(B, 1, J))
+            p = self._rnnt_predict([hist[:, k:k + 1] for k in range(C)])
+            z = ops.rnnt_joint(e_t.contiguous(), p)
+            logits = F_.linear(z.view(B, J), self.rnnt_out.weight, self.rnnt_out.bias, True, True)
+            k = ops.argmax_rows(logits)
+            emit = active & (k != blank)
+            out.scatter_(1, torch.where(emit, n_out, trash).view(B, 1), k.view(B, 1))
+            n_out = n_out + emit.to(torch.int64)
+            hist = torch.where(emit.view(B, 1), torch.cat([k.view(B, 1), hist[:, :C - 1]], 1), hist)
+            syms = torch.where(emit, syms + 1, zero)
+            adv = active & (~emit | (syms >= S))
+            t_idx = t_idx + adv.to(torch.int64)
+            syms = torch.where(adv, zero, syms)
+        flat = torch.cat([out[:, :cap].reshape(-1), n_out]).cpu()
+        ids, n = flat[:B * cap].view(B, cap).tolist(), flat[B * cap:].tolist()
+        hyp_ids = [row[:m] for row, m in zip(ids, n)]
+        strs = ["".join(self.id2label[x] for x in row) for row in hyp_ids]
+        return (strs, hyp_ids) if return_ids else strs
 
     def forward(self, padded_input, input_lengths, padded_target, verbose=False, return_ctc=False):
         """-> (pred (B,Td,V) fp32, gold (B,Td), hyp_seq (B,Td), gold_seq)   (reference: transformer.py:59-85); with return_ctc also
@@ -449,7 +594,8 @@ class Transformer(nn.Module):
     def evaluate(self, padded_input, input_lengths, padded_target, beam_search=False, beam_width=0, beam_nbest=0, lm=None,
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
                  ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,
-                 attention_rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0, context=None, context_score=0.0):
+                 attention_rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0, context=None, context_score=0.0,
+                 transducer_greedy=False, transducer_max_symbols=5):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
         ctc_greedy: best-path decoding from the head alone; ctc_beam: prefix beam search over the head's posteriors alone
@@ -460,7 +606,17 @@ class Transformer(nn.Module):
         into that search's pruning, context / context_score (ctc_beam only): a phrase list biasing it (ctc_beam_search's arguments of the
         same names).  align_source "gold" / "hyp": a fourth value, the forced alignment
         (ctc_align) of padded_target with target_lengths, or of the label ids the decoder produced (SOS and EOS dropped; never a
-        re-tokenised string)."""
+        re-tokenised string).  transducer_greedy: time-synchronous greedy search of the transducer head (transducer_greedy, at most
+        transducer_max_symbols labels per frame), not together with any other decoding mode or with align_source."""
+        if transducer_greedy:
+            if beam_search or ctc_greedy or ctc_beam or ctc_weight > 0 or attention_rescoring_weight > 0 or align_source is not None \
+                    or ngram is not None or context is not None:
+                raise ValueError("--transducer-greedy decodes from the transducer head alone: not together with --beam-search, "
+                                 "--ctc-greedy, --ctc-beam-search, --ctc-decode-weight, --attention-rescoring-weight, --ngram-path, "
+                                 "--context-path or --align")
+            self._need_transducer()                    # the "no transducer head" ValueError, before any device work
+            if int(transducer_max_symbols) < 1:
+                raise ValueError("--transducer-max-symbols must be at least 1, got %d" % int(transducer_max_symbols))
         if ctc_weight > 0 and not beam_search:
             raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % ctc_weight)
         if ctc_beam and (beam_search or ctc_greedy or ctc_weight > 0):
@@ -495,7 +651,10 @@ class Transformer(nn.Module):
             if ctc_logits is None and ctc_weight > 0 and not ctc_greedy:
                 with torch.no_grad():
                     ctc_logits = self.ctc_logits(enc_out)
-        if ctc_greedy:
+        if transducer_greedy:
+            strs_hyps = self.transducer_greedy(enc_out, self.ctc_frame_lengths(input_lengths, enc_out.shape[1]),
+                                               max_symbols=int(transducer_max_symbols))
+        elif ctc_greedy:
             strs_hyps, hyp_ids = self.ctc_greedy(enc_out, ctc_lengths, return_ids=True)
         elif ctc_beam:
             nbest_strs, nbest_ids = self.ctc_beam_search(enc_out, ctc_lengths, beam_width, nbest=max(1, int(beam_nbest)),

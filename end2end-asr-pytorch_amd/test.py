@@ -1,5 +1,6 @@
 """Evaluation entry point -- same command line as the reference (reference: test.py): loads --continue-from, decodes
-every test utterance (greedy, beam search with --beam-search, or from the encoder CTC head alone with --ctc-greedy / --ctc-beam-search,
+every test utterance (greedy, beam search with --beam-search, from the transducer head alone with --transducer-greedy, or from the encoder
+CTC head alone with --ctc-greedy / --ctc-beam-search,
 the latter's n-best rescored by the decoder with --attention-rescoring-weight, its pruning guided by a label n-gram LM with --ngram-path and biased towards the phrases of --context-path)
 and reports CER / WER.  --align-out PATH also writes label and word
 timestamps from the encoder CTC head (forced alignment of the transcript, or of the hypothesis with --align-source hyp)."""
@@ -51,7 +52,7 @@ def evaluate(model, test_loader, lm=None, noise_dir=None, ngram=None, context=No
                                                                  ctc_greedy=getattr(args, "ctc_greedy", False),
                                                                  ctc_beam=getattr(args, "ctc_beam_search", False),
                                                                  attention_rescoring_weight=getattr(args, "attention_rescoring_weight", 0.0),
-                                                                 **align, **fusion)
+                                                                 **align, **fusion, **transducer_decoding(args))
             for i, (hyp, gold) in enumerate(zip(strs_hyps, strs_gold)):
                 for ch in (constant.EOS_CHAR, constant.SOS_CHAR, constant.PAD_CHAR):
                     hyp, gold = hyp.replace(ch, ""), gold.replace(ch, "")
@@ -109,6 +110,34 @@ def check_ctc_decoding(args, model):
         raise ValueError("--ctc-decode-weight %g needs --beam-search: CTC prefix scores re-rank beam candidates" % w)
 
 
+def transducer_decoding(args):
+    """The evaluate() arguments of --transducer-greedy (empty without the flag: the call is the one it was)."""
+    if not getattr(args, "transducer_greedy", False):
+        return {}
+    return dict(transducer_greedy=True, transducer_max_symbols=int(getattr(args, "transducer_max_symbols", 5)))
+
+
+def check_transducer_decoding(args, model):
+    """--transducer-greedy needs the transducer head of a model trained with --transducer-weight > 0, decodes from that head alone (no
+    --beam-search, --ctc-greedy, --ctc-beam-search, --ctc-decode-weight, --attention-rescoring-weight, --ngram-path, --context-path or
+    --align-out) and emits 1 <= --transducer-max-symbols labels per frame at the most.  Without the flag nothing is checked."""
+    if not getattr(args, "transducer_greedy", False):
+        return
+    if not hasattr(model, "rnnt_out"):
+        raise ValueError("--transducer-greedy needs a model with a transducer head: this checkpoint was trained with "
+                         "--transducer-weight 0")
+    for flag, on in (("--beam-search", getattr(args, "beam_search", False)), ("--ctc-greedy", getattr(args, "ctc_greedy", False)),
+                     ("--ctc-beam-search", getattr(args, "ctc_beam_search", False)),
+                     ("--ctc-decode-weight", float(getattr(args, "ctc_decode_weight", 0.0) or 0.0) > 0),
+                     ("--attention-rescoring-weight", float(getattr(args, "attention_rescoring_weight", 0.0) or 0.0) > 0),
+                     ("--ngram-path", bool(getattr(args, "ngram_path", None))), ("--context-path", bool(getattr(args, "context_path", None))),
+                     ("--align-out", bool(getattr(args, "align_out", None)))):
+        if on:
+            raise ValueError("--transducer-greedy decodes from the transducer head alone: it cannot be combined with %s" % flag)
+    if int(getattr(args, "transducer_max_symbols", 5)) < 1:
+        raise ValueError("--transducer-max-symbols must be at least 1, got %d" % int(args.transducer_max_symbols))
+
+
 def feature_conf(loaded_args):
     """The audio_conf of a checkpoint's run: the features the model was trained on (its window and --features settings; load_model has
     filled in `spect` for a checkpoint from before --features and copied the three settings into constant.args for evaluate())."""
@@ -129,6 +158,7 @@ if __name__ == '__main__':
     if getattr(loaded_args, "parallel", False):
         print("unwrap data parallel")
         model = model.module
+    check_transducer_decoding(args, model)
     check_ctc_decoding(args, model)
     constant.args.tgt_max_len = max(constant.args.tgt_max_len, 301)      # greedy/beam search always run 300 steps
     if getattr(loaded_args, "noise_dir", None) is not None and args.cuda and not args.gpu_frontend:

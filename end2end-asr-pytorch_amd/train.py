@@ -74,6 +74,8 @@ def resolve_graph_buckets(args, explicit, model=None):
         feat = getattr(args, "feat_extractor", "")
     if getattr(args, "ctc_weight", 0.0) > 0:
         return args.graph_buckets       # the hybrid CTC / attention step runs as eager launches (trainer/asr/trainer.py)
+    if float(getattr(args, "transducer_weight", 0.0) or 0.0) > 0:
+        return args.graph_buckets       # so does the transducer step
     if getattr(args, "cuda", False) and feat in ("vgg_cnn", "emb_cnn") and getattr(args, "loss", "ce") == "ce":
         args.graph_buckets = DEFAULT_GRAPH_BUCKET
     return args.graph_buckets
@@ -87,7 +89,8 @@ def main():
     args = constant.args
     from utils.functions import check_ctc_weight
     check_ctc_weight(args.ctc_weight, args)          # at start-up, before any process group or dataset exists
-    from utils.functions import check_mwer
+    from utils.functions import check_mwer, check_transducer_weight
+    check_transducer_weight(args)                    # --transducer-weight: range and exclusions, before any process group or dataset exists
     if args.continue_from == "":                     # (a checkpoint brings its own --ctc-weight: checked again below, once it is known)
         check_mwer(args)
         from utils.functions import check_distill
@@ -151,6 +154,9 @@ def main():
     if check_mwer(args, label2id) > 0:                # with the checkpoint's --ctc-weight and the labels the model trains on
         logging.info("--mwer-weight %g: MWER training over the %d-best of the CTC prefix beam search, errors per %s; the step runs as "
                      "eager launches", args.mwer_weight, args.mwer_nbest, args.mwer_unit)
+    if check_transducer_weight(args) > 0:             # with the checkpoint's settings
+        logging.info("--transducer-weight %g: a transducer head (joint width %d, predictor context %d) trains beside the decoder; the "
+                     "step runs as eager launches", args.transducer_weight, args.transducer_dim_joint, args.transducer_context)
     from utils.functions import check_distill, load_teacher
     trainer = Trainer()
     distill_a, distill_c = check_distill(args)         # with the checkpoint's --ctc-weight

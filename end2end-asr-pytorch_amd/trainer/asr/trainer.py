@@ -227,8 +227,21 @@ class Trainer():
             self._logged_distill_eager = True
             logging.info("--distill-weight %g --distill-ctc-weight %g: the distillation step runs as eager launches (no hipGraph replay)",
                          distill_a, distill_c)
+        # --transducer-weight r > 0 (a transducer head beside the decoder): L = (1 - r) L_existing + r L_rnnt, training
+        # and validation alike, on the eager path like the joint step.  With r = 0 nothing here runs and the step is unchanged.
+        rnnt_weight = float(getattr(constant.args, "transducer_weight", 0.0) or 0.0)
+        if rnnt_weight > 0:
+            if loss_type != "ce":
+                raise ValueError("--transducer-weight %g combines the transducer loss with the cross-entropy loss: --loss %s is not "
+                                 "supported with it" % (rnnt_weight, loss_type))
+            if distill_step or float(getattr(constant.args, "mwer_weight", 0.0) or 0.0) > 0:
+                raise ValueError("--transducer-weight %g: a training step is either the MWER step, the distillation step or the "
+                                 "transducer step" % rnnt_weight)
+            if opt is not None and not self.__dict__.get("_logged_rnnt_eager"):
+                self._logged_rnnt_eager = True
+                logging.info("--transducer-weight %g: the transducer step runs as eager launches (no hipGraph replay)", rnnt_weight)
         if (opt is not None and loss_type == "ce" and getattr(constant.args, "graph_buckets", 0) > 0 and src.is_cuda
-                and ctc_weight == 0 and not distill_step):
+                and ctc_weight == 0 and not distill_step and rnnt_weight == 0):
             r = self._graph_step(model, opt, src, src_lengths, tgt, smoothing)
             if r is not None:
                 loss, gold_seq, hyp_seq = r
@@ -264,6 +277,10 @@ class Trainer():
             loss, gold_seq, hyp_seq, _ = core.distill_step(src, src_lengths, tgt, tgt_lengths, teacher, distill_a,
                                                            float(getattr(constant.args, "distill_temperature", 2.0)), smoothing,
                                                            ctc_weight=ctc_weight, distill_ctc_weight=distill_c)
+        elif rnnt_weight > 0:
+            core = model.module if hasattr(model, "module") else model
+            loss, gold_seq, hyp_seq, _ = core.transducer_step(src, src_lengths, tgt, tgt_lengths, rnnt_weight, smoothing,
+                                                              ctc_weight=ctc_weight)
         elif ctc_weight > 0:
             pred, gold, hyp_seq, gold_seq, ctc_logits = model(src, src_lengths, tgt, verbose=False, return_ctc=True)
             core = model.module if hasattr(model, "module") else model

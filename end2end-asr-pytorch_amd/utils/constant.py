@@ -31,7 +31,10 @@ Differences that do not change old command lines:
   * `--mwer-weight m` (+ `--mwer-nbest`, `--mwer-unit`; train.py with --ctc-weight > 0): minimum word error rate training over the CTC
     prefix beam search's n-best, rescored by the attention decoder with grad (csrc/mwer.hip, DESIGN.md section 7);
   * `--distill-from PATH` (+ `--distill-weight`, `--distill-ctc-weight`, `--distill-temperature`; train.py): knowledge distillation from
-    a frozen teacher checkpoint, word-level on the decoder logits and frame-level on the CTC head (csrc/distill.hip).
+    a frozen teacher checkpoint, word-level on the decoder logits and frame-level on the CTC head (csrc/distill.hip, DESIGN.md section 7);
+  * `--transducer-weight r` (+ `--transducer-dim-joint`, `--transducer-context`; train.py): a transducer (RNN-T) head on the encoder
+    output, L = (1 - r) L_existing + r L_rnnt (csrc/rnnt.hip, DESIGN.md section 7); `--transducer-greedy` (+ `--transducer-max-symbols`;
+    test.py): time-synchronous greedy decoding from that head alone.
 """
 import argparse
 import os
@@ -137,6 +140,14 @@ _FLAGS = [
     # the CTC term becomes (1 - c) CTC + c KD over the CTC heads' frames.  Everything off: no teacher is built, nothing new is launched
     (("--distill-from",), dict(default=None, type=_S)), (("--distill-weight",), dict(default=0.0, type=_F)),
     (("--distill-ctc-weight",), dict(default=0.0, type=_F)), (("--distill-temperature",), dict(default=2.0, type=_F)),
+    # transducer (RNN-T) head (csrc/rnnt.hip).  --transducer-weight r in [0, 1] (train.py): L = (1 - r) L_existing + r
+    # L_rnnt, L_existing = CE or the --ctc-weight joint loss, L_rnnt = mean_b nll_b / max(U_b, 1) over the T'_b x (U_b + 1) lattice, blank =
+    # PAD; 0 = no head: nothing new is built or launched.  --transducer-dim-joint J (a multiple of 8): the joint's width;
+    # --transducer-context C in {1, 2}: the labels the stateless predictor looks back.  --transducer-greedy (test.py): time-synchronous
+    # greedy search from the head alone, at most --transducer-max-symbols labels per frame
+    (("--transducer-weight",), dict(default=0.0, type=_F)), (("--transducer-dim-joint",), dict(default=256, type=_I)),
+    (("--transducer-context",), dict(default=2, type=_I)), (("--transducer-greedy",), dict(action="store_true")),
+    (("--transducer-max-symbols",), dict(default=5, type=_I)),
     # --ctc-beam-search (test.py): prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): --beam-width (1..16)
     # prefixes kept per frame, --ctc-candidates (0: min(V, 16)) labels tried per frame, the n-best ranked like --beam-search's
     (("--ctc-beam-search",), dict(action="store_true")),

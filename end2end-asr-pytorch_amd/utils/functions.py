@@ -88,6 +88,30 @@ def load_model(load_path):
             kept = float(cur.ctc_weight)
         args.ctc_weight = kept
         cur.ctc_weight = kept           # the trainer of this run reads the process-global Namespace
+        # the transducer head (--transducer-weight, with its --transducer-dim-joint and --transducer-context) follows the same rule: the
+        # checkpoint's settings rebuild it (one written before the flags existed: 0, no head); another positive weight may replace a
+        # positive one, the head can be neither added nor dropped, and its two sizes cannot be changed
+        given = getattr(constant, "explicit", ())
+        kept = float(getattr(args, "transducer_weight", 0.0) or 0.0)
+        if "transducer_weight" in given and hasattr(cur, "transducer_weight") and float(cur.transducer_weight) != kept:
+            if not 0.0 <= float(cur.transducer_weight) <= 1.0:
+                raise ValueError("--transducer-weight must lie in [0, 1], got %g" % float(cur.transducer_weight))
+            if (float(cur.transducer_weight) > 0) != (kept > 0):
+                raise ValueError("--transducer-weight %g on the command line, but %s was trained with --transducer-weight %g: the "
+                                 "transducer head cannot be added to or dropped from a checkpoint"
+                                 % (cur.transducer_weight, load_path, kept))
+            logging.info("load_model: --transducer-weight %g from the command line replaces the checkpoint's %g",
+                         cur.transducer_weight, kept)
+            kept = float(cur.transducer_weight)
+        args.transducer_weight = kept
+        cur.transducer_weight = kept
+        for k, dflt in (("transducer_dim_joint", 256), ("transducer_context", 2)):
+            v = int(getattr(args, k, dflt) or dflt)
+            if kept > 0 and k in given and int(getattr(cur, k, dflt)) != v:
+                raise ValueError("--%s %d on the command line, but %s was trained with --%s %d: a trained transducer head cannot be "
+                                 "resized" % (k.replace("_", "-"), getattr(cur, k), load_path, k.replace("_", "-"), v))
+            setattr(args, k, v)
+            setattr(cur, k, v)
         # the encoder's convolution modules (--conv-module-kernel) are part of the model too: the checkpoint's kernel size rebuilds them
         # (one written before the flag existed: 0, none); typing a different size is an error, never an override
         kept = int(getattr(args, "conv_module_kernel", 0) or 0)
@@ -160,6 +184,35 @@ def check_ctc_weight(w, args=None):
             raise ValueError("--ctc-weight %g with --loss %s is not supported: the weight combines the encoder CTC loss with the "
                              "cross-entropy loss (--loss ce)" % (w, args.loss))
     return w
+
+
+def check_transducer_weight(args):
+    """--transducer-weight r (a transducer head beside the decoder) -> r.  r must lie in [0, 1]; r > 0 checks
+    --transducer-dim-joint (a positive multiple of 8) and --transducer-context (1 or 2) and excludes --parallel, --loss ctc,
+    --mwer-weight > 0, --distill-from and --rank > 0.  r = 0: nothing is checked beyond the range."""
+    r = float(getattr(args, "transducer_weight", 0.0) or 0.0)
+    if not 0.0 <= r <= 1.0:
+        raise ValueError("--transducer-weight must lie in [0, 1], got %g" % r)
+    if r == 0.0:
+        return r
+    from models.asr.transformer import check_transducer
+    check_transducer(getattr(args, "transducer_dim_joint", 256), getattr(args, "transducer_context", 2), getattr(args, "dim_model", None))
+    if getattr(args, "parallel", False):
+        raise ValueError("--transducer-weight %g with --parallel is not supported: the cross-entropy loss is a mean over tokens and the "
+                         "transducer loss a mean over utterances, and the data-parallel gradient reducer normalises by one of them" % r)
+    if getattr(args, "loss", "ce") != "ce":
+        raise ValueError("--transducer-weight %g with --loss %s is not supported: the weight combines the transducer loss with the "
+                         "cross-entropy loss (--loss ce)" % (r, args.loss))
+    if float(getattr(args, "mwer_weight", 0.0) or 0.0) > 0.0:
+        raise ValueError("--transducer-weight %g with --mwer-weight %g is not supported: a training step is either the MWER step or the "
+                         "transducer step" % (r, args.mwer_weight))
+    if getattr(args, "distill_from", None) or float(getattr(args, "distill_weight", 0.0) or 0.0) > 0.0 \
+            or float(getattr(args, "distill_ctc_weight", 0.0) or 0.0) > 0.0:
+        raise ValueError("--transducer-weight %g with --distill-from is not supported: a training step is either the distillation step "
+                         "or the transducer step" % r)
+    if int(getattr(args, "rank", 0) or 0) > 0:
+        raise ValueError("--transducer-weight %g with --rank %d is not supported: the transducer head is not factorised" % (r, args.rank))
+    return r
 
 
 def check_mwer(args, label2id=None):
@@ -313,7 +366,10 @@ def init_transformer_model(args, label2id, id2label):
                       dim_key=args.dim_key, dim_value=args.dim_value, trg_max_length=args.tgt_max_len, dropout=args.dropout,
                       emb_trg_sharing=args.emb_trg_sharing, rank=getattr(args, "rank", 0))
     ctc_weight = check_ctc_weight(getattr(args, "ctc_weight", 0.0), args)
-    model = Transformer(encoder, decoder, feat_extractor=args.feat_extractor, ctc_head=ctc_weight > 0)
+    transducer = None
+    if check_transducer_weight(args) > 0:
+        transducer = dict(dim_joint=int(getattr(args, "transducer_dim_joint", 256)), context=int(getattr(args, "transducer_context", 2)))
+    model = Transformer(encoder, decoder, feat_extractor=args.feat_extractor, ctc_head=ctc_weight > 0, transducer=transducer)
     if args.parallel:
         model = HipDataParallel(model, device_ids=args.device_ids)
     return model

@@ -241,6 +241,35 @@ int asr_ctc_bwd(const float* logits, int64_t ld, const int64_t* targets, const i
                 const int32_t* target_lengths, int B, int T, int V, int Lmax, int blank, const float* workspace,
                 const float* grad_out, float* dlogits, int64_t ldo, asr_stream_t stream);
 
+/* ---- transducer (RNN-T) head (csrc/rnnt.hip has the definition; blank = `blank`).  No atomics: every output is a
+ * function of the inputs alone.
+ * asr_rnnt_joint_fwd: z (B,T,U1,J) = tanh(e (B,T,J) + p (B,U1,J)) in `dtype` (ASR_F32 / ASR_BF16), everything contiguous.  J must be a
+ *   multiple of 8 and the pointers 16-byte aligned, else ASR_EUNSUPPORTED.
+ * asr_rnnt_joint_bwd: de (B,T,J) = sum_u dz (1 - z^2), dp (B,U1,J) = sum_t dz (1 - z^2) from dz, z (B,T,U1,J), all in `dtype`, sums in
+ *   fp32 in a fixed order (u order; t order within four interleaved frame sets, then the four in order).  Any J >= 1.  workspace:
+ *   asr_rnnt_joint_bwd_workspace floats (0 for U1 <= 32: may then be NULL).
+ * asr_rnnt_fwd: logits (B,T,Umax+1,ld) fp32 with row stride ld >= V (columns >= V never read), targets (B,Umax) int64 (row b holds
+ *   target_lengths[b] labels; may be NULL when Umax == 0), frame_lengths / target_lengths (B) int32 on the device, clamped to [0,T] /
+ *   [0,Umax].  loss[0] = mean_b(nll_b / max(U_b,1)), asr_ctc_fwd's reduction.  Rows with t >= T_b or u > U_b are never read.  T_b == 0, or a
+ *   label among the U_b that is `blank` or outside [0,V): nll_b = +inf (and so the loss); the other utterances are unaffected.  U_b == 0 is
+ *   legal (the blank path).  The workspace (asr_rnnt_workspace floats, 8-byte aligned) carries the lattice (fp64), row statistics and,
+ *   in its last B floats, nll_b to asr_rnnt_bwd.  Rows are fp32; the lattice, log Z and the loss sum are fp64 (csrc/rnnt.hip says why).
+ *   ASR_EUNSUPPORTED when two diagonals (2 (Umax + 1) doubles) exceed 64 KB of LDS or B T (Umax+1) / 8 does not fit a grid.
+ * asr_rnnt_bwd: ONE launch.  dlogits (B,T,Umax+1,ldd) in `out_dtype` (ASR_F32 / ASR_BF16), ldd >= V, columns V..ldd-1 zero (the form
+ *   asr_ce_bwd / asr_seq_logprob_bwd write) = grad_out[0] / (B max(U_b,1)) * d nll_b / d logits (grad_out: device scalar, NULL = 1).  Dead
+ *   rows and the rows of an utterance with nll_b = +inf are zero and their logits are not read.                                       */
+int asr_rnnt_joint_fwd(const void* e, const void* p, void* z, int B, int T, int U1, int J, int dtype, asr_stream_t stream);
+int64_t asr_rnnt_joint_bwd_workspace(int B, int T, int U1, int J);
+int asr_rnnt_joint_bwd(const void* dz, const void* z, void* de, void* dp, float* workspace, int64_t workspace_floats, int B, int T,
+                       int U1, int J, int dtype, asr_stream_t stream);
+int64_t asr_rnnt_workspace(int B, int T, int Umax);
+int asr_rnnt_fwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* frame_lengths,
+                 const int32_t* target_lengths, int B, int T, int Umax, int V, int blank, float* workspace,
+                 int64_t workspace_floats, float* loss, asr_stream_t stream);
+int asr_rnnt_bwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* frame_lengths,
+                 const int32_t* target_lengths, int B, int T, int Umax, int V, int blank, const float* workspace,
+                 const float* grad_out, void* dlogits, int64_t ldd, int out_dtype, asr_stream_t stream);
+
 /* ---- CTC prefix scorer for joint CTC / attention beam search (csrc/ctc_prefix.hip has the recursion; blank = `blank`).
  * asr_ctc_prefix_init: logits (B,T,ld) fp32 = the encoder's CTC logits, frames (B) int32 = true frames T_b per utterance, row_utt (R)
  *   int32 = utterance of every hypothesis row.  Writes lse (B*T) scratch, lp (B,T,V) = log-softmax, and state (R,T,2) fp32 = the
