@@ -12,6 +12,10 @@
 // goes to a caller-owned workspace for the backward pass); everything else is row parallel.  Path probabilities through (t, s)
 // never exceed the total p(l|x), so exp(alpha + beta - lp + nll) lies in [0, 1]: the per-label sums of the gradient are
 // accumulated in linear space with LDS atomics, no second max pass.
+//
+// T_b and len_b are the given lengths clamped to [0, T] and [0, Lmax], in every kernel.  T_b = 0: nll_b = 0 for len_b = 0, else +inf.
+// A label among the len_b used ones outside [0, V): nll_b = +inf and no address is formed from it.  An utterance with nll_b = +inf
+// has NaN rows for t < T_b.  Target slots l >= len_b are loaded and never used (include/asr_hip.h has the contract).
 #include "ctc_common.h"      // NEG_INF, lae2, ctc_lse_kernel (shared with ctc_prefix.hip)
 
 namespace {
@@ -26,12 +30,15 @@ __device__ __forceinline__ float lae3(float a, float b, float c) {
 __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restrict__ logits, int64_t ld, const float* __restrict__ lse,
                                                           const int64_t* __restrict__ targets, int Lmax,
                                                           const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
-                                                          int T, int S, int blank, float* __restrict__ alpha,
+                                                          int T, int V, int S, int blank, float* __restrict__ alpha,
                                                           float* __restrict__ beta, float* __restrict__ nll) {
   extern __shared__ float sh[];       // [2][S] previous / current row, then [S] labels as int
   float* row0 = sh;
   float* row1 = sh + S;
   int* lab = reinterpret_cast<int*>(sh + 2 * S);
+  // block-wide flag: a label among the Lb used ones lies outside [0, V).  It borrows row0[0], which the time loop first writes at
+  // step 1, behind the barrier of step 0: no LDS beyond the 3 S words (S = 5461 fills the 64 KB to the last word)
+  int* bad_flag = reinterpret_cast<int*>(row0);
   const int b = blockIdx.x;
   const bool backward = blockIdx.y == 1;
   int Tb = in_len[b];
@@ -39,9 +46,24 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
   int Lb = tg_len[b];
   Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
   const int Sb = 2 * Lb + 1;
-  for (int s = threadIdx.x; s < S; s += 256) lab[s] = (s & 1) ? (int)targets[(int64_t)b * Lmax + (s >> 1 < Lmax ? s >> 1 : Lmax - 1)] : blank;
+  if (threadIdx.x == 0) *bad_flag = 0;
+  __syncthreads();
+  for (int s = threadIdx.x; s < S; s += 256) {
+    int v = blank;
+    if (s & 1) {
+      const int64_t id = targets[(int64_t)b * Lmax + (s >> 1 < Lmax ? s >> 1 : Lmax - 1)];      // the int64 is tested: 2^40 must not wrap
+      const bool ok = id >= 0 && id < V;
+      if (!ok && s < Sb) *bad_flag = 1;
+      v = ok ? (int)id : blank;       // slots l >= Lb may hold anything: loaded, never used (s >= Sb below)
+    }
+    lab[s] = v;
+  }
   __syncthreads();
   float* lat = (backward ? beta : alpha) + (int64_t)b * T * S;
+  if (*bad_flag) {                    // both halves leave before the time loop: no address is formed from that label
+    if (!backward && threadIdx.x == 0) nll[b] = INFINITY;
+    return;
+  }
   if (Tb == 0) {
     if (!backward && threadIdx.x == 0) nll[b] = Lb == 0 ? 0.f : INFINITY;      // empty input: only the empty target is reachable
     return;
@@ -82,11 +104,14 @@ __global__ __launch_bounds__(256) void ctc_lattice_kernel(const float* __restric
   }
 }
 
-// loss = mean_b nll_b / max(len_b, 1)
-__global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ nll, const int32_t* __restrict__ tg_len, int B,
+// loss = mean_b nll_b / max(len_b, 1), len_b clamped to [0, Lmax] as in the lattice and the gradient
+__global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ nll, const int32_t* __restrict__ tg_len, int B, int Lmax,
                                                       float* __restrict__ loss) {
   float s = 0.f;
-  for (int b = threadIdx.x; b < B; b += 64) s += nll[b] / (float)(tg_len[b] > 1 ? tg_len[b] : 1);
+  for (int b = threadIdx.x; b < B; b += 64) {
+    const int Lb = tg_len[b] > Lmax ? Lmax : tg_len[b];
+    s += nll[b] / (float)(Lb > 1 ? Lb : 1);
+  }
   s = wave_sum(s);
   if (threadIdx.x == 0) *loss = s / (float)B;
 }
@@ -118,14 +143,18 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   const float l_t = lse[row];
   const float* a = alpha + row * S;
   const float* be = beta + row * S;
-  for (int s = threadIdx.x; s < Sb; s += 256) {
-    const int v = (s & 1) ? (int)targets[(int64_t)b * Lmax + (s >> 1)] : blank;
-    const float e = a[s] + be[s] - (lg[v] - l_t) + nl;
-    if (e > NEG_INF) atomicAdd(&acc[v], expf(e));
+  // an unreachable target has loss = inf; its gradient is NaN in torch (zero_infinity=False).  Tested BEFORE the state loop: the
+  // lattice of such an utterance may be unwritten (a label outside [0, V)), and that label must not index lg[] or acc[]
+  const bool finite = nl < INFINITY;
+  if (finite) {
+    for (int s = threadIdx.x; s < Sb; s += 256) {
+      const int v = (s & 1) ? (int)targets[(int64_t)b * Lmax + (s >> 1)] : blank;
+      const float e = a[s] + be[s] - (lg[v] - l_t) + nl;
+      if (e > NEG_INF) atomicAdd(&acc[v], expf(e));
+    }
   }
   __syncthreads();
   const float scale = grad_out[0] / ((float)(Lb > 1 ? Lb : 1) * (float)B);
-  const bool finite = nl < INFINITY;   // an unreachable target has loss = inf; its gradient is NaN in torch (zero_infinity=False)
   for (int v = threadIdx.x; v < ldo; v += 256) {
     float g = 0.f;
     if (v < V) g = finite ? (expf(lg[v] - l_t) - acc[v]) * scale : NAN;
@@ -160,9 +189,9 @@ extern "C" int asr_ctc_fwd(const float* logits, int64_t ld, const int64_t* targe
   if (lds > 48 * 1024) (void)asr_grant_lds<ctc_lattice_kernel>(64 * 1024);
   // both recursions in one launch (alpha and beta are independent): the backward pass only runs the gradient kernel
   hipLaunchKernelGGL(ctc_lattice_kernel, dim3(B, 2), dim3(256), lds, s, logits, ld, lse, targets, Lmax, input_lengths, target_lengths,
-                     T, S, blank, alpha, beta, nll);
+                     T, V, S, blank, alpha, beta, nll);
   ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_loss_kernel, dim3(1), dim3(64), 0, s, nll, target_lengths, B, loss);
+  hipLaunchKernelGGL(ctc_loss_kernel, dim3(1), dim3(64), 0, s, nll, target_lengths, B, Lmax, loss);
   ASR_LAUNCH_CHECK();
   return ASR_OK;
 }

@@ -231,8 +231,18 @@ int asr_gemm_nt_fp8(const uint8_t* A, int64_t lda, const float* scale_a, const u
  * zero_infinity=False) and its gradient w.r.t. the LOGITS (log-softmax included).  logits (B,T,ld) fp32, targets
  * (B,Lmax) int64 (row b holds target_lengths[b] labels), lengths int32 on the device.  loss[0] = mean_b(nll_b /
  * max(len_b,1)); an unreachable target gives +inf (the reference skips such a batch, trainer.py:87-90).  The workspace
- * (asr_ctc_workspace floats) carries the lattice from asr_ctc_fwd to asr_ctc_bwd.  dlogits (B,T,ldo) fp32, columns
- * >= V zeroed; grad_out: device scalar d(loss).                                                                  */
+ * (asr_ctc_workspace floats) carries the lattice from asr_ctc_fwd to asr_ctc_bwd and, in its last B floats, nll_b.
+ * dlogits (B,T,ldo) fp32, columns >= V zeroed; grad_out: device scalar d(loss).  Any row strides ld >= V (columns >= V
+ * never read) and ldo >= V.
+ * Lengths are clamped to [0,T] and [0,Lmax]: loss, lattice and gradient are one function of the clamped T_b and L_b.
+ * T_b = 0: feasible for L_b = 0 only (nll_b = 0), else nll_b = +inf.  An utterance without a feasible alignment (too few
+ * frames, or a label among the L_b used ones outside [0,V): no address is formed from it) has nll_b = +inf, and so the
+ * loss; its rows of dlogits are NaN for t < T_b (torch, zero_infinity=False) and 0 for t >= T_b; the other rows of the
+ * batch are unaffected.  A used label equal to `blank` is not refused: it is scored as the blank column, and the rule
+ * that lets a label skip the blank before it sees it as a blank.  Frames >= T_b and targets >= L_b influence nothing:
+ * those target slots are loaded and may hold any int64, those frames any float.
+ * ASR_EUNSUPPORTED: Lmax > 2730 (asr_ctc_fwd: three rows of 2 Lmax + 1 words exceed 64 KB of LDS), V > 16384
+ * (asr_ctc_bwd: one row of V floats does).                                                                        */
 int64_t asr_ctc_workspace(int B, int T, int Lmax);
 int asr_ctc_fwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* input_lengths,
                 const int32_t* target_lengths, int B, int T, int V, int Lmax, int blank, float* workspace,
