@@ -1,6 +1,6 @@
 """LM rescoring on the host (no GPU): the reference's word segmentation, the checkpoint loader / weight packing of asr_hip/lm.py
 and the scoring algebra, against tests/golden/lm_tiny.npz (tools/gen_lm_golden.py: the reference executed on CPU); plus the ISA
-of csrc/lm.hip (f32-input MFMAs, no scratch)."""
+of the MFMA kernels of csrc/lm.hip and csrc/lm_train.hip (f32-input MFMAs, no scratch)."""
 import os
 import re
 import shutil
@@ -108,23 +108,42 @@ def test_greedy_refuses_lm_rescoring():
         Decoder.greedy_search.__wrapped__(None, None, lm_rescoring=True)
 
 
-# ------------------------------------------------------------------------------------------------ ISA of csrc/lm.hip
-@pytest.fixture(scope="module")
-def lm_asm(tmp_path_factory):
+# ------------------------------------------------------------------------------------------------ ISA of csrc/lm.hip, lm_train.hip
+def _asm(tmp_path_factory, name):
     from asr_hip import build
     hipcc = build._hipcc()
     if os.path.isabs(hipcc) and not os.path.exists(hipcc) or not os.path.isabs(hipcc) and shutil.which(hipcc) is None:
         pytest.skip("hipcc not available")
-    out = os.path.join(str(tmp_path_factory.mktemp("isa")), "lm.s")
-    flags = [f for f in build.FLAGS if f != "-fPIC"] + build.PER_FILE_FLAGS.get("lm.hip", [])
-    r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", os.path.join(build.CSRC, "lm.hip"), "-o", out],
+    out = os.path.join(str(tmp_path_factory.mktemp("isa")), name + ".s")
+    flags = [f for f in build.FLAGS if f != "-fPIC"] + build.PER_FILE_FLAGS.get(name + ".hip", [])
+    r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", os.path.join(build.CSRC, name + ".hip"), "-o", out],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     return open(out).read().split("\n")
 
 
+@pytest.fixture(scope="module")
+def lm_asm(tmp_path_factory):
+    return _asm(tmp_path_factory, "lm")
+
+
+@pytest.fixture(scope="module")
+def lm_train_asm(tmp_path_factory):
+    return _asm(tmp_path_factory, "lm_train")
+
+
 @pytest.mark.parametrize("kernel", ["lstm_step_kernelILi1E", "lstm_step_kernelILi4E", "lm_nll_partials_kernel", "lm_proj_kernel"])
 def test_lm_kernels_use_f32_mfma_and_no_scratch(lm_asm, kernel):
+    _f32_mfma_and_no_scratch(lm_asm, kernel)
+
+
+@pytest.mark.parametrize("kernel", ["lstm_step_train_kernelILi1E", "lstm_step_train_kernelILi4E", "lstm_bptt_step_kernelILi1E",
+                                    "lstm_bptt_step_kernelILi4E", "lm_dlogits_kernel"])
+def test_lm_train_kernels_use_f32_mfma_and_no_scratch(lm_train_asm, kernel):
+    _f32_mfma_and_no_scratch(lm_train_asm, kernel)
+
+
+def _f32_mfma_and_no_scratch(lm_asm, kernel):
     starts = [i for i, l in enumerate(lm_asm) if re.match(r"^_Z\w+:", l)]
     a = next(i for i in starts if kernel in lm_asm[i])
     body = lm_asm[a:min([i for i in starts if i > a] + [len(lm_asm)])]
