@@ -24,7 +24,7 @@ GEMM_RELU, GEMM_ACCUMULATE = 1, 2
 EUNSUPPORTED = -3
 ATTN_DELTA, ATTN_DQ, ATTN_DKV, ATTN_ALL = 1, 2, 4, 7
 OP_GEMM, OP_CONV_IGEMM, OP_CONV_WGRAD, OP_ATTN_FWD, OP_ATTN_BWD, OP_ADD_LN, OP_CE, OP_ADAM, OP_CONV1, OP_POOL, \
-    OP_LAYOUT = range(11)
+    OP_LAYOUT, OP_SEARCH = range(12)
 
 _lib = None
 
@@ -76,6 +76,8 @@ _SIGS = {
     "asr_rnnt_workspace": (_L, [_I, _I, _I]),
     "asr_rnnt_fwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     "asr_rnnt_bwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P]),
+    "asr_rnnt_beam_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
+    "asr_rnnt_beam_search": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
     "asr_ctc_align_workspace": (_L, [_I, _I, _I]),
     "asr_ctc_align": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
     "asr_ctc_beam_workspace": (_L, [_I, _I, _I, _I]),

@@ -720,6 +720,44 @@ def rnnt_bwd(logits, targets, frame_lengths, target_lengths, ws, grad_out=None, 
     return dl if pad == 64 else dl[:, :V]
 
 
+def rnnt_beam_search(e, tables, w_out, b_out, lengths, beam_width, candidates=0, max_symbols=5, nbest=1, blank=0, sos=1):
+    """Transducer beam search (csrc/rnnt_beam.hip), ONE launch: e (B,T,J) = rnnt_enc's output, tables = the predictor's one or two (V,J)
+    tables (tables[k]: the label k places back), w_out (V,J), all contiguous in one dtype (fp32 / bf16: what the model's forward reads),
+    b_out (V) fp32, lengths (B) int32 on the device = true frames.  beam_width W <= 16, candidates K <= 16 labels tried per hypothesis
+    row (0: min(V - 1, 16)), max_symbols S >= 1 labels per frame, nbest <= W -> dict(ids (B,nbest,T*S) int32 with blank behind the
+    length, lengths (B,nbest) int32 (-1: no such hypothesis), scores (B,nbest) fp32 = log-probability summed over the alignments
+    found) on the device, best first.  blank defaults to PAD (0), sos to SOS (1)."""
+    B, T, J = e.shape
+    V = w_out.shape[0]
+    W, S, nbest = int(beam_width), int(max_symbols), int(nbest)
+    K = int(candidates) if candidates else min(V - 1, 16)
+    tables = list(tables)
+    if len(tables) not in (1, 2):
+        raise ValueError("rnnt_beam_search: one or two predictor tables, got %d" % len(tables))
+    for name, t, shape in [("w_out", w_out, (V, J))] + [("tables[%d]" % k, t, (V, J)) for k, t in enumerate(tables)]:
+        if tuple(t.shape) != shape or t.dtype != e.dtype or not t.is_contiguous():
+            raise ValueError("rnnt_beam_search: %s must be a contiguous %s %s tensor, got %s %s" % (name, shape, e.dtype, tuple(t.shape),
+                                                                                                 t.dtype))
+    if e.dtype not in (torch.float32, torch.bfloat16) or not e.is_contiguous():
+        raise ValueError("rnnt_beam_search: e must be a contiguous fp32 or bf16 tensor, got %s" % e.dtype)
+    if b_out.dtype != torch.float32 or b_out.numel() != V or not b_out.is_contiguous():
+        raise ValueError("rnnt_beam_search: b_out must be a contiguous fp32 tensor of %d elements (the bias as F_.linear hands it to "
+                         "asr_gemm_nt), got %s %s" % (V, tuple(b_out.shape), b_out.dtype))
+    if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError("rnnt_beam_search: lengths must be a contiguous int32 tensor of %d elements, got %s %s"
+                         % (B, tuple(lengths.shape), lengths.dtype))
+    dev = e.device
+    n = L.load().asr_rnnt_beam_workspace(B, T, V, W, K, S)
+    ws = torch.empty(max(n, 4), device=dev, dtype=torch.float32)
+    rows, cols = max(nbest, 1), max(T * S, 1)
+    out = dict(ids=torch.empty((B, rows, cols), device=dev, dtype=torch.int32), lengths=torch.empty((B, rows), device=dev, dtype=torch.int32),
+               scores=torch.empty((B, rows), device=dev, dtype=torch.float32))
+    L.call("asr_rnnt_beam_search", L.ptr(e), L.ptr(tables[0]), L.ptr(tables[1]) if len(tables) == 2 else None, L.ptr(w_out), L.ptr(b_out),
+           L.ptr(lengths), B, T, J, V, W, K, S, nbest, int(blank), int(sos), L.dt(e), L.ptr(ws), n, L.ptr(out["ids"]),
+           L.ptr(out["lengths"]), L.ptr(out["scores"]), L.stream())
+    return out
+
+
 def ctc_align(logits, targets, input_lengths, target_lengths, blank=0):
     """Forced alignment (csrc/ctc_align.hip): logits (B,T,V) fp32 (rows contiguous, any row stride), targets (B,Lmax) int64, lengths (B)
     int32 on the device -> dict(path (B,T) int32, start / end (B,Lmax) int32, lab_score (B,Lmax) fp32, score (B) fp32) on the device;

@@ -3,14 +3,9 @@
 // HBM-bound: forward reads M*V*4 bytes once (second pass is L2-resident), backward reads M*V*4 and writes
 // M*ldd*sizeof(T).
 #include "common.h"
+#include "topk.h"            // MaxIdx, better: the arg-max order (shared with csrc/rnnt_beam.hip)
 
 namespace {
-
-struct MaxIdx { float v; int i; };
-__device__ __forceinline__ MaxIdx better(MaxIdx a, MaxIdx b) {     // greater value, lowest index on ties
-  if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
 
 // One wave per row, CE_ROWS rows per block: the three running sums (loss, #non-PAD rows, #correct) are reduced over the block's
 // rows in LDS first -- one set of same-address atomics per block instead of per row (they were most of this kernel's time).

@@ -64,6 +64,7 @@
 #include "ctc_common.h"      // NEG_INF, lae2, ctc_lse_kernel
 #include "ngram.h"           // NgramTable, ngram_query, ngram_shift
 #include "context.h"         // CtxTable, ctx_probe, ctx_finish
+#include "beam_key.h"        // beam_key, BEAM_ROOT_KEY_LO / _HI (shared with csrc/rnnt_beam.hip)
 
 namespace {
 
@@ -85,16 +86,8 @@ __device__ __forceinline__ void beam_row16(const int* p, int (&a)[BEAM_MAX]) {
   }
 }
 
-// The key of a prefix: 64 bits mixed from its parent's key and its last label, so equal label sequences have equal keys however and
-// whenever they were created (a node id does not: a prefix pruned and re-created gets a new node, and its children still in the list
-// point at the old one).  Bit 0 is set: 0 is "no key".  Two different sequences meet in a key with probability 2^-63 per comparison.
-__device__ __forceinline__ uint2 beam_key(uint2 parent, int label) {
-  uint64_t k = ((uint64_t)parent.y << 32 | parent.x) ^ (uint64_t)(uint32_t)(label + 1);
-  k *= 0x9E3779B97F4A7C15ull; k ^= k >> 29;
-  k *= 0xBF58476D1CE4E5B9ull; k ^= k >> 32;
-  return make_uint2((uint32_t)k | 1u, (uint32_t)(k >> 32));
-}
-constexpr uint32_t BEAM_ROOT_KEY_LO = 0x2545F491u | 1u, BEAM_ROOT_KEY_HI = 0x4F6CDD1Du;      // the empty prefix
+// The key of a prefix (beam_key, BEAM_ROOT_KEY_*): csrc/beam_key.h.  Its children still in the list point at the old node of a prefix
+// that was pruned and re-created, which is why entries are matched by key.
 
 // What the fused arm adds to the plain search's arguments; the plain arm takes the empty BeamNoLm
 struct BeamLm {

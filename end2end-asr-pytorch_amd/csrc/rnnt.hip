@@ -25,20 +25,13 @@
 // The lattice is latency bound (one dependent step per diagonal), so the wider arithmetic costs no time that shows.
 #include "common.h"
 #include "lse.h"        // Lse, lse_row (no multiply-add contraction from here on: a row gives the same bits through either load arm)
+#include "rnnt_common.h"      // rnnt_lae, clampi (shared with csrc/rnnt_beam.hip)
 
 namespace {
 
 constexpr int RNNT_ROWS = 8;                   // rows (waves) per workgroup of the row pass and the backward: == SEQ_ROWS of csrc/seq_logprob.hip
 constexpr int RNNT_JB_COLS = 64;               // columns of J per workgroup of the joint backward (one per lane)
 constexpr int RNNT_JB_UC = 32;                 // label positions whose dp partials a workgroup holds in LDS at once: 4 x 32 x 64 floats = 32 KB
-
-__device__ __forceinline__ double rnnt_lae(double a, double b) {      // log(exp(a) + exp(b)), -inf safe
-  const double hi = fmax(a, b), lo = fmin(a, b);
-  if (lo == -(double)INFINITY) return hi;
-  return hi + log1p(exp(lo - hi));
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ------------------------------------------------------------------------------------------------ joint
 // one thread per 16-byte chunk of z: the sum and the tanh in fp32, rounded once to the storage type

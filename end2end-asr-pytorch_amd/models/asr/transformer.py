@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from asr_hip import functions as F_
 from asr_hip import ops, search
+from asr_hip import params as P
 from models.common_layers import (ConvolutionModule, LowRankMultiHeadAttention, LowRankPositionwiseFeedForward, MultiHeadAttention,
                                   PositionalEncoding, PositionwiseFeedForwardWithConv, check_conv_module_kernel, check_pos_encoding)
 from utils import constant
@@ -398,6 +399,44 @@ class Transformer(nn.Module):
         strs = ["".join(self.id2label[x] for x in row) for row in hyp_ids]
         return (strs, hyp_ids) if return_ids else strs
 
+    @torch.no_grad()
+    def transducer_beam_search(self, enc_out, lengths, beam_width, nbest=1, candidates=0, max_symbols=5, lm=None, lm_weight=0.1,
+                               c_weight=1, return_ids=False):
+        """Beam search over the transducer head (csrc/rnnt_beam.hip): ONE rnnt_enc launch, ONE search launch (one
+        workgroup per utterance walks its frames: the joint, the vocabulary projection, the log-softmax rows, the candidates and the
+        beam bookkeeping of every step are inside it) and one device-to-host copy.  lengths: true encoder frames per utterance
+        (ctc_frame_lengths); beam_width W in 1..16 hypotheses, candidates K in 1..16 labels tried per hypothesis and step (0:
+        min(V - 1, 16)), at most max_symbols labels per frame.  The kernel's W hypotheses of an utterance, {'yseq', 'score', 'rnnt_score'}
+        with score = log-probability summed over the alignments found, are ranked like a decoder beam's and like ctc_beam_search's
+        (asr_hip.search.rank_ended): score + sqrt(words) * c_weight, or with lm (utils.lstm_utils.LM) score + lm_weight * (lm - 2 * oov) +
+        sqrt(words) * c_weight, all utterances' hypotheses in ONE batched LM call.  -> per utterance the min(nbest, found) best strings,
+        best first (return_ids: (strings, label ids), same nesting); the ids are labels as they stand: no SOS, no EOS."""
+        self._need_transducer()
+        W, S, K = int(beam_width), int(max_symbols), int(candidates)
+        if not 1 <= W <= 16:
+            raise ValueError("transducer_beam_search keeps beam_width hypotheses in the kernel's beam: 1..16, got %d" % W)
+        if nbest < 1:
+            raise ValueError("nbest must be at least 1, got %d" % nbest)
+        if S < 1:
+            raise ValueError("--transducer-max-symbols must be at least 1, got %d" % S)
+        if not 0 <= K <= 16:
+            raise ValueError("candidates must lie in 0..16 (0: min(V - 1, 16)), got %d" % K)
+        B, T = enc_out.shape[0], enc_out.shape[1]
+        e = F_.linear(enc_out, self.rnnt_enc.weight, self.rnnt_enc.bias, False, True)
+        cd = e.dtype
+        tables = [P.linear_weight(m.weight, cd) for m in self.rnnt_embed]       # what _rnnt_predict's rows round to; fp32: the masters
+        out = ops.rnnt_beam_search(e.contiguous(), tables, P.linear_weight(self.rnnt_out.weight, cd), self.rnnt_out.bias.data,
+                                   _lengths_to_device(lengths, e.device), W, K, S, W, constant.PAD_TOKEN, constant.SOS_TOKEN)
+        L = T * S
+        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1), out["scores"].view(torch.int32).reshape(-1)]).cpu()
+        ids, lens, scores = torch.split(flat, [B * W * L, B * W, B * W])
+        ids, lens, scores = ids.view(B, W, L).tolist(), lens.view(B, W).tolist(), scores.view(torch.float32).view(B, W).tolist()
+        ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n], 'rnnt_score': scores[b][n]} for n in range(W) if lens[b][n] >= 0]
+                 for b in range(B)]
+        hyp_ids = [[h['yseq'] for h in hs] for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight)]
+        strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
+        return (strs, hyp_ids) if return_ids else strs
+
     def forward(self, padded_input, input_lengths, padded_target, verbose=False, return_ctc=False):
         """-> (pred (B,Td,V) fp32, gold (B,Td), hyp_seq (B,Td), gold_seq)   (reference: transformer.py:59-85); with return_ctc also
         the CTC head's logits (B,T',V) fp32 on the encoder output."""
@@ -595,7 +634,7 @@ class Transformer(nn.Module):
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
                  ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,
                  attention_rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0, context=None, context_score=0.0,
-                 transducer_greedy=False, transducer_max_symbols=5):
+                 transducer_greedy=False, transducer_max_symbols=5, transducer_beam=False, transducer_candidates=0):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
         ctc_greedy: best-path decoding from the head alone; ctc_beam: prefix beam search over the head's posteriors alone
@@ -607,7 +646,23 @@ class Transformer(nn.Module):
         same names).  align_source "gold" / "hyp": a fourth value, the forced alignment
         (ctc_align) of padded_target with target_lengths, or of the label ids the decoder produced (SOS and EOS dropped; never a
         re-tokenised string).  transducer_greedy: time-synchronous greedy search of the transducer head (transducer_greedy, at most
-        transducer_max_symbols labels per frame), not together with any other decoding mode or with align_source."""
+        transducer_max_symbols labels per frame), not together with any other decoding mode or with align_source.  transducer_beam: beam
+        search over the transducer head (transducer_beam_search: beam_width hypotheses, transducer_candidates labels per hypothesis and
+        step, transducer_max_symbols per frame, the beam_nbest best re-ranked with lm when lm_rescoring), under the same exclusions."""
+        if transducer_beam:
+            if transducer_greedy or beam_search or ctc_greedy or ctc_beam or ctc_weight > 0 or attention_rescoring_weight > 0 \
+                    or align_source is not None or ngram is not None or context is not None:
+                raise ValueError("--transducer-beam-search decodes from the transducer head alone: not together with --transducer-greedy, "
+                                 "--beam-search, --ctc-greedy, --ctc-beam-search, --ctc-decode-weight, --attention-rescoring-weight, "
+                                 "--ngram-path, --context-path or --align")
+            self._need_transducer()                    # the "no transducer head" ValueError, before any device work
+            if int(transducer_max_symbols) < 1:
+                raise ValueError("--transducer-max-symbols must be at least 1, got %d" % int(transducer_max_symbols))
+            if not 1 <= int(beam_width) <= 16:
+                raise ValueError("--transducer-beam-search keeps --beam-width hypotheses in the kernel's beam: 1..16, got %d"
+                                 % int(beam_width))
+            if lm_rescoring and lm is None:
+                raise ValueError("lm_rescoring=True needs lm (utils.lstm_utils.LM)")
         if transducer_greedy:
             if beam_search or ctc_greedy or ctc_beam or ctc_weight > 0 or attention_rescoring_weight > 0 or align_source is not None \
                     or ngram is not None or context is not None:
@@ -651,7 +706,13 @@ class Transformer(nn.Module):
             if ctc_logits is None and ctc_weight > 0 and not ctc_greedy:
                 with torch.no_grad():
                     ctc_logits = self.ctc_logits(enc_out)
-        if transducer_greedy:
+        if transducer_beam:
+            nbest_strs = self.transducer_beam_search(enc_out, self.ctc_frame_lengths(input_lengths, enc_out.shape[1]), beam_width,
+                                                     nbest=max(1, int(beam_nbest)), candidates=transducer_candidates,
+                                                     max_symbols=int(transducer_max_symbols), lm=lm if lm_rescoring else None,
+                                                     lm_weight=lm_weight, c_weight=c_weight)
+            strs_hyps = [rows[0] if rows else "" for rows in nbest_strs]
+        elif transducer_greedy:
             strs_hyps = self.transducer_greedy(enc_out, self.ctc_frame_lengths(input_lengths, enc_out.shape[1]),
                                                max_symbols=int(transducer_max_symbols))
         elif ctc_greedy:

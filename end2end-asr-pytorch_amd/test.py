@@ -1,5 +1,6 @@
 """Evaluation entry point -- same command line as the reference (reference: test.py): loads --continue-from, decodes
-every test utterance (greedy, beam search with --beam-search, from the transducer head alone with --transducer-greedy, or from the encoder
+every test utterance (greedy, beam search with --beam-search, from the transducer head alone with --transducer-greedy /
+--transducer-beam-search, or from the encoder
 CTC head alone with --ctc-greedy / --ctc-beam-search,
 the latter's n-best rescored by the decoder with --attention-rescoring-weight, its pruning guided by a label n-gram LM with --ngram-path and biased towards the phrases of --context-path)
 and reports CER / WER.  --align-out PATH also writes label and word
@@ -111,31 +112,49 @@ def check_ctc_decoding(args, model):
 
 
 def transducer_decoding(args):
-    """The evaluate() arguments of --transducer-greedy (empty without the flag: the call is the one it was)."""
+    """The evaluate() arguments of --transducer-greedy / --transducer-beam-search (empty without either flag: the call is the one it
+    was)."""
+    if getattr(args, "transducer_beam_search", False):
+        return dict(transducer_beam=True, transducer_max_symbols=int(getattr(args, "transducer_max_symbols", 5)),
+                    transducer_candidates=int(getattr(args, "transducer_candidates", 0) or 0))
     if not getattr(args, "transducer_greedy", False):
         return {}
     return dict(transducer_greedy=True, transducer_max_symbols=int(getattr(args, "transducer_max_symbols", 5)))
 
 
 def check_transducer_decoding(args, model):
-    """--transducer-greedy needs the transducer head of a model trained with --transducer-weight > 0, decodes from that head alone (no
-    --beam-search, --ctc-greedy, --ctc-beam-search, --ctc-decode-weight, --attention-rescoring-weight, --ngram-path, --context-path or
-    --align-out) and emits 1 <= --transducer-max-symbols labels per frame at the most.  Without the flag nothing is checked."""
-    if not getattr(args, "transducer_greedy", False):
+    """--transducer-greedy / --transducer-beam-search need the transducer head of a model trained with --transducer-weight > 0, decode
+    from that head alone (no --beam-search, --ctc-greedy, --ctc-beam-search, --ctc-decode-weight, --attention-rescoring-weight,
+    --ngram-path, --context-path or --align-out, and not each other) and emit 1 <= --transducer-max-symbols labels per frame at the most.
+    --transducer-beam-search keeps --beam-width in 1..16 hypotheses and tries --transducer-candidates in 0..16 labels (0: min(V - 1, 16)).
+    Without either flag nothing is checked.  All of it before any launch."""
+    greedy, beam = getattr(args, "transducer_greedy", False), getattr(args, "transducer_beam_search", False)
+    if not greedy and not beam:
         return
+    name = "--transducer-beam-search" if beam else "--transducer-greedy"
     if not hasattr(model, "rnnt_out"):
-        raise ValueError("--transducer-greedy needs a model with a transducer head: this checkpoint was trained with "
-                         "--transducer-weight 0")
-    for flag, on in (("--beam-search", getattr(args, "beam_search", False)), ("--ctc-greedy", getattr(args, "ctc_greedy", False)),
+        raise ValueError("%s needs a model with a transducer head: this checkpoint was trained with --transducer-weight 0" % name)
+    for flag, on in (("--transducer-greedy", beam and greedy),
+                     ("--beam-search", getattr(args, "beam_search", False)), ("--ctc-greedy", getattr(args, "ctc_greedy", False)),
                      ("--ctc-beam-search", getattr(args, "ctc_beam_search", False)),
                      ("--ctc-decode-weight", float(getattr(args, "ctc_decode_weight", 0.0) or 0.0) > 0),
                      ("--attention-rescoring-weight", float(getattr(args, "attention_rescoring_weight", 0.0) or 0.0) > 0),
                      ("--ngram-path", bool(getattr(args, "ngram_path", None))), ("--context-path", bool(getattr(args, "context_path", None))),
                      ("--align-out", bool(getattr(args, "align_out", None)))):
         if on:
-            raise ValueError("--transducer-greedy decodes from the transducer head alone: it cannot be combined with %s" % flag)
+            raise ValueError("%s decodes from the transducer head alone: it cannot be combined with %s" % (name, flag))
     if int(getattr(args, "transducer_max_symbols", 5)) < 1:
         raise ValueError("--transducer-max-symbols must be at least 1, got %d" % int(args.transducer_max_symbols))
+    if beam:
+        if not 1 <= int(args.beam_width) <= 16:
+            raise ValueError("--transducer-beam-search keeps --beam-width hypotheses in the kernel's beam: 1..16, got %d"
+                             % int(args.beam_width))
+        k = int(getattr(args, "transducer_candidates", 0) or 0)
+        if not 0 <= k <= 16:
+            raise ValueError("--transducer-candidates must lie in 0..16 with --transducer-beam-search (0: min(V - 1, 16)), got %d" % k)
+        if int(args.beam_width) * (int(args.transducer_max_symbols) + 1) > 1024:
+            raise ValueError("--transducer-beam-search: --beam-width * (--transducer-max-symbols + 1) must not exceed 1024, got %d * %d"
+                             % (int(args.beam_width), int(args.transducer_max_symbols) + 1))
 
 
 def feature_conf(loaded_args):

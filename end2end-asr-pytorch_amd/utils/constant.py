@@ -34,7 +34,9 @@ Differences that do not change old command lines:
     a frozen teacher checkpoint, word-level on the decoder logits and frame-level on the CTC head (csrc/distill.hip, DESIGN.md section 7);
   * `--transducer-weight r` (+ `--transducer-dim-joint`, `--transducer-context`; train.py): a transducer (RNN-T) head on the encoder
     output, L = (1 - r) L_existing + r L_rnnt (csrc/rnnt.hip, DESIGN.md section 7); `--transducer-greedy` (+ `--transducer-max-symbols`;
-    test.py): time-synchronous greedy decoding from that head alone.
+    test.py): time-synchronous greedy decoding from that head alone; `--transducer-beam-search` (+ `--beam-width`, `--beam-nbest`,
+    `--transducer-candidates`, `--transducer-max-symbols`, `--lm-rescoring`; test.py): beam search over that head, one fused search
+    kernel per utterance (csrc/rnnt_beam.hip).
 """
 import argparse
 import os
@@ -144,10 +146,13 @@ _FLAGS = [
     # L_rnnt, L_existing = CE or the --ctc-weight joint loss, L_rnnt = mean_b nll_b / max(U_b, 1) over the T'_b x (U_b + 1) lattice, blank =
     # PAD; 0 = no head: nothing new is built or launched.  --transducer-dim-joint J (a multiple of 8): the joint's width;
     # --transducer-context C in {1, 2}: the labels the stateless predictor looks back.  --transducer-greedy (test.py): time-synchronous
-    # greedy search from the head alone, at most --transducer-max-symbols labels per frame
+    # greedy search from the head alone, at most --transducer-max-symbols labels per frame.  --transducer-beam-search (test.py): beam
+    # search from the head alone (csrc/rnnt_beam.hip): --beam-width (1..16) hypotheses, --transducer-candidates K (0: min(V - 1, 16)) labels
+    # tried per hypothesis and step, --transducer-max-symbols labels per frame, the --beam-nbest best re-ranked like a decoder beam's
     (("--transducer-weight",), dict(default=0.0, type=_F)), (("--transducer-dim-joint",), dict(default=256, type=_I)),
     (("--transducer-context",), dict(default=2, type=_I)), (("--transducer-greedy",), dict(action="store_true")),
-    (("--transducer-max-symbols",), dict(default=5, type=_I)),
+    (("--transducer-max-symbols",), dict(default=5, type=_I)), (("--transducer-beam-search",), dict(action="store_true")),
+    (("--transducer-candidates",), dict(default=0, type=_I)),
     # --ctc-beam-search (test.py): prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): --beam-width (1..16)
     # prefixes kept per frame, --ctc-candidates (0: min(V, 16)) labels tried per frame, the n-best ranked like --beam-search's
     (("--ctc-beam-search",), dict(action="store_true")),

@@ -36,6 +36,7 @@ enum { ASR_GEMM_RELU = 1, ASR_GEMM_ACCUMULATE = 2 };
 enum {
   ASR_OP_GEMM = 0, ASR_OP_CONV_IGEMM = 1, ASR_OP_CONV_WGRAD = 2, ASR_OP_ATTN_FWD = 3, ASR_OP_ATTN_BWD = 4,
   ASR_OP_ADD_LN = 5, ASR_OP_CE = 6, ASR_OP_ADAM = 7, ASR_OP_CONV1 = 8, ASR_OP_POOL = 9, ASR_OP_LAYOUT = 10,
+  ASR_OP_SEARCH = 11,      /* asr_rnnt_beam_search */
   ASR_OP_COUNT = 16
 };
 
@@ -279,6 +280,26 @@ int asr_rnnt_fwd(const float* logits, int64_t ld, const int64_t* targets, const 
 int asr_rnnt_bwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* frame_lengths,
                  const int32_t* target_lengths, int B, int T, int Umax, int V, int blank, const float* workspace,
                  const float* grad_out, void* dlogits, int64_t ldd, int out_dtype, asr_stream_t stream);
+
+/* ---- transducer beam search (csrc/rnnt_beam.hip has the definition): the n best label sequences of the head with a
+ * stateless predictor, ONE launch, one workgroup per utterance, no atomics: the outputs are a function of the inputs alone.
+ * asr_rnnt_beam_search: e (B,T,J) = the output of the rnnt_enc GEMM, table0 / table1 (V,J) = the predictor's tables for the last label
+ *   and the one before (table1 NULL: a one-label context), w_out (V,J) row-major, all contiguous in `dtype` (ASR_F32 / ASR_BF16: the
+ *   tensors the model's forward reads, in a bf16 model the bf16 shadows); b_out (V) fp32; frame_lengths (B) int32 on the device, clamped
+ *   to [0,T]: frames >= T_b of e are never read, nor a table row no hypothesis has as context.  W = beam (1..16), K = label candidates per
+ *   hypothesis row (1..16, K < V), S = max_symbols >= 1 (W (S + 1) <= 1024 entries of LDS), nbest <= W; contexts open with `sos`.
+ *   Outputs on the device in asr_ctc_beam_search's form, best first: ids (B,nbest,T*S) int32 with `blank` behind the length, lengths
+ *   (B,nbest) int32 (-1: no such hypothesis), scores (B,nbest) fp32 = log-probability summed over the alignments found (-inf: none);
+ *   T_b == 0: the empty sequence with score 0.  Rows are fp32, scores fp64 inside.  bf16 with J % 32 == 0 and J <= 256 projects with
+ *   v_mfma_f32_16x16x32_bf16 (w_out straight from global memory), everything else with an fp32 multiply-add chain in k order.
+ *   workspace: asr_rnnt_beam_workspace floats, 16-byte aligned (16 logits rows and the trie per utterance).
+ *   ASR_EUNSUPPORTED: W > 16, K > 16, nbest > W, S < 1, W (S + 1) > 1024, T S W >= 2^30, J % 8 != 0, a pointer off 16 bytes, or 16 z rows
+ *   beyond 120 KB of LDS; ASR_EINVAL: a null pointer, a size < 1, another dtype, blank or sos outside [0,V), K >= V, a short workspace. */
+int64_t asr_rnnt_beam_workspace(int B, int T, int V, int W, int K, int S);
+int asr_rnnt_beam_search(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out,
+                         const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank, int sos,
+                         int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+                         asr_stream_t stream);
 
 /* ---- CTC prefix scorer for joint CTC / attention beam search (csrc/ctc_prefix.hip has the recursion; blank = `blank`).
  * asr_ctc_prefix_init: logits (B,T,ld) fp32 = the encoder's CTC logits, frames (B) int32 = true frames T_b per utterance, row_utt (R)
