@@ -137,6 +137,13 @@ __device__ __forceinline__ void asr_lds_dma16(unsigned lds_wave_base, const void
 }
 template <int N> __device__ __forceinline__ void asr_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// a * b rounded on its own: never contracted into a fused multiply-add with a following sum.  The LayerNorm variance sums of
+// asr_add_ln_fwd and of the decode-step prologues (decode.hip) use it, so that the three agree bit for bit by construction
+__device__ __forceinline__ float mul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // ---------------------------------------------------------------------------------------------- reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -79,27 +79,35 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm_kernel(DecGemmArgs p) {
         *reinterpret_cast<float4*>(gb + c * 4) = *reinterpret_cast<const float4*>(p.gamma + c * 4);
         *reinterpret_cast<float4*>(gb + K + c * 4) = *reinterpret_cast<const float4*>(p.beta + c * 4);
       }
-      // z = y + residual rounded to the storage type first (what asr_add_ln_fwd stores and normalises), fp32 statistics
-      float s = 0.f;
+      // z = y + residual rounded to the storage type first (what asr_add_ln_fwd stores and normalises), fp32 statistics.  The sums
+      // are taken in asr_add_ln_fwd's order -- a lane of that kernel owns chunk c and reduces by xor 32, 16, .. 1 over c; here chunk
+      // c = 8 j + sub, so xor 32, 16, 8 pair the registers j and xor 4, 2, 1 the lanes -- so that x is that kernel's output bit for
+      // bit (a + b == b + a: both sides of a butterfly step hold the same bits, a tree gives the same value)
+      float sc[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool live = j * 8 + sub < nch;
+        sc[j] = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           z[j].e[e] = f32_to_bf16(bf16_to_f32(cy[j].e[e]) + bf16_to_f32(cr[j].e[e]));
-          s += live ? bf16_to_f32(z[j].e[e]) : 0.f;
+          sc[j] += live ? bf16_to_f32(z[j].e[e]) : 0.f;
         }
       }
-      s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
+      float s = ((sc[0] + sc[4]) + (sc[2] + sc[6])) + ((sc[1] + sc[5]) + (sc[3] + sc[7]));
+      s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 1, 64);
       const float mu = s / (float)K;
-      float q = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool live = j * 8 + sub < nch;
+        sc[j] = 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { const float d = live ? bf16_to_f32(z[j].e[e]) - mu : 0.f; q += d * d; }
+        // (the square rounded on its own, as in asr_add_ln_fwd: a fused multiply-add here moved rstd by an ulp and 1 in 200 000
+        // elements of x by a bf16 ulp)
+        for (int e = 0; e < 8; ++e) { const float d = live ? bf16_to_f32(z[j].e[e]) - mu : 0.f; sc[j] += mul_unfused(d, d); }
       }
-      q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64); q += __shfl_xor(q, 4, 64);
+      float q = ((sc[0] + sc[4]) + (sc[2] + sc[6])) + ((sc[1] + sc[5]) + (sc[3] + sc[7]));
+      q += __shfl_xor(q, 4, 64); q += __shfl_xor(q, 2, 64); q += __shfl_xor(q, 1, 64);
       const float rs = rsqrtf(q / (float)K + p.eps);
       __syncthreads();                                             // gamma / beta are in LDS
 #pragma unroll
@@ -429,7 +437,7 @@ __global__ __launch_bounds__(512) void dec_attn_fused_kernel(DecFusedArgs p) {
       const float mu = wave_sum(sum) / (float)D;
       float q = 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = live ? z[e] - mu : 0.f; q += d * d; }
+      for (int e = 0; e < 8; ++e) { const float d = live ? z[e] - mu : 0.f; q += mul_unfused(d, d); }    // as asr_add_ln_fwd: bit for bit
       const float rs = rsqrtf(wave_sum(q) / (float)D + p.eps);
 #pragma unroll
       for (int e = 0; e < 8; ++e) xo.e[e] = f32_to_bf16((z[e] - mu) * rs * gm[e] + bt[e]);
@@ -623,6 +631,8 @@ extern "C" int asr_dec_gemm(const void* W, int64_t ldw, const float* bias, void*
   if (B > 32 || K % 64 != 0 || ldw % 8 != 0 || !aligned16(W) || ldo % 4 != 0 || !aligned16(out)) return ASR_EUNSUPPORTED;
   if ((layout & ASR_DEC_OUT_FRAG) && N % 16 != 0) return ASR_EUNSUPPORTED;
   if (prologue != 0 && K > 512) return ASR_EUNSUPPORTED;
+  if (!(layout & ASR_DEC_W_FRAG)) ASR_CHECK_ARG(ldw >= K);       // row-major rows must not overlap (fragment-major: ldw is not read)
+  if (!(layout & ASR_DEC_OUT_FRAG)) ASR_CHECK_ARG(ldo >= N);
   if (prologue == 0) ASR_CHECK_ARG(X && ldx >= K);
   if (prologue == 0 && !(layout & ASR_DEC_X_FRAG) && ldx % 8 != 0) return ASR_EUNSUPPORTED;
   if (prologue == 0 && !aligned16(X)) return ASR_EUNSUPPORTED;

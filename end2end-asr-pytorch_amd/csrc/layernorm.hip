@@ -78,7 +78,9 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(T* __restrict__ y_z, co
     const int c0 = (ch * 64 + lane) * EPC;
     if (c0 < D) {
 #pragma unroll
-      for (int j = 0; j < EPC; ++j) { const float d = z[ch * EPC + j] - mu; q += d * d; }
+      // (the square rounded on its own -- what the compiler chose for this loop anyway; the decode-step prologues, which must give
+      // the same bits, do the same)
+      for (int j = 0; j < EPC; ++j) { const float d = z[ch * EPC + j] - mu; q += mul_unfused(d, d); }
     }
   }
   const float rs = rsqrtf(wave_sum(q) / (float)D + eps);

@@ -451,6 +451,13 @@ int asr_kv_append(const void* k_src, const void* v_src, int64_t src_ld, void* k_
  *   1: x = LN(Y + R) * gamma + beta (Y, R (B, K) bf16 contiguous, K <= 512; z = Y + R rounded to bf16 before the statistics,
  *      like asr_add_ln_fwd), x also stored to x_out (B, K) when given;  2: x = table[tok[b]] * scale + pe[state[0]] (fp32
  *      table / pe), stored to x_out.  out_dtype ASR_BF16 or ASR_F32.  ASR_EUNSUPPORTED outside these shapes.
+ *   Limits: B <= 32; K <= 1024, or <= 2048 when K % 128 == 0 (8 waves split K); K <= 512 with a prologue; ldw % 8 == 0,
+ *   ldo % 4 == 0, ldx % 8 == 0 (row-major X), W / out / X 16-byte aligned: ASR_EUNSUPPORTED otherwise.  Row-major W needs
+ *   ldw >= K and a row-major out ldo >= N, X ldx >= K, x_out 16-byte aligned: ASR_EINVAL otherwise (the kernel reads no
+ *   stride of a fragment-major operand, so these two do not apply to it; ldw % 8 and ldo % 4 are still required of the values
+ *   passed: pass K and N).  B == 0: ASR_OK, nothing launched.  Prologue 1, here and in asr_dec_attn_fused, takes its sums in
+ *   asr_add_ln_fwd's order with the squares rounded unfused: x (and x_out) is that kernel's output bit for bit.  x_out must not alias Y or R: workgroup 0
+ *   stores x while the other workgroups still read their rows.
  *   Fragment-major order (`layout` flags; every wave-wide operand load of the kernel is then 1 KB of consecutive bytes): a
  *   (rows, K) matrix is cut into blocks of 32 rows x 16 columns; block (r, s) holds, for lane = 32 * h + i (h = 0, 1; i < 32),
  *   the 8 elements [32 r + i][16 s + 8 h .. + 7] at element offset ((r * K / 16 + s) * 64 + lane) * 8.  Weights: rows padded
@@ -459,9 +466,12 @@ int asr_kv_append(const void* k_src, const void* v_src, int64_t src_ld, void* k_
  *   batch / row strides.  state != NULL: self attention at position t = state[0]: k_new / v_new (B, ld_new) are this
  *   position's rows -- stored to row t of both caches by this launch -- and the keys are rows 0..t; state == NULL: all
  *   `rows` keys (cross attention, no mask: transformer.py:336-350 passes none at decode time).  out (B, ldo) bf16, or
- *   fragment-major (out_frag != 0, B <= 32).
+ *   fragment-major (out_frag != 0, B <= 32).  state[0] >= rows: every one of the `rows` keys is attended and nothing is
+ *   appended, k_new / v_new given or not (state[0] must not be negative).  Cache rows past t are never read.
  * asr_dec_finish: tok[b] = argmax of logits row b (lowest index on ties), done[b] |= tok == eos, out[t * B + b] = tok
- *   (t = state[0] < max_len), then state[0] = t + 1 (by the last workgroup; *ticket must be 0 before the first call).      */
+ *   (t = state[0] < max_len; t >= max_len or out == NULL: no column is written, tok / done / state still move), then
+ *   state[0] = t + 1 (by the last workgroup; *ticket must be 0 before the first call and is 0 again after every call).
+ *   A NaN is never the maximum; a row with no entry greater than -inf (all -inf, all NaN) gives token 0.                    */
 #define ASR_DEC_W_FRAG 1    /* W in fragment-major order (below)                                   */
 #define ASR_DEC_X_FRAG 2    /* prologue 0: X in fragment-major order (written by a producer with ..._OUT_FRAG) */
 #define ASR_DEC_OUT_FRAG 4  /* bf16 out in fragment-major order, N % 16 == 0                        */

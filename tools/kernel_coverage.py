@@ -29,9 +29,10 @@ tuning hook carry no "hooked" in their ids), CONV_HOOK_ONLY explains the symbols
 forms of a shared symbol that only a hook reaches.  Instantiations that exist only in -DASR_TUNE_ABLATE or C64_TIMING builds are not in a
 default build's assembly and so not in the report.  With `--family embcnn` they cover csrc/embcnn.hip (im2col, col2im, window sum and
 the BatchNorm kernels of the emb_cnn front end) and the trace is that of tests/test_gpu_embcnn_arms.py; no tuning hook selects a kernel of
-that file.  `--group NAME=CSV` (any family, repeatable) adds a column with the launches in the trace of a part of the file -- the same
-command with `-k NAME` -- so that the report says which cases reach which symbol.  The counter run is a run of its own: no --pmc next to
-the tracing."""
+that file.  With `--family decode` they cover csrc/decode.hip (the bf16 greedy step: asr_dec_gemm, asr_dec_attn, asr_dec_attn_fused,
+asr_dec_finish) and the trace is that of tests/test_gpu_decode_arms.py; no tuning hook selects a kernel of that file.
+`--group NAME=CSV` (any family, repeatable) adds a column with the launches in the trace of a part of the file -- the same command with
+`-k NAME` -- so that the report says which cases reach which symbol.  The counter run is a run of its own: no --pmc next to the tracing."""
 import argparse
 import collections
 import csv
@@ -48,8 +49,9 @@ ATTENTION_FILES = ("attention_generic.hip", "attention_d64_fwd.hip", "attention_
 CONV_FILES = ("conv1.hip", "conv1_wgrad_mfma.hip", "conv_igemm.hip", "conv_c64.hip", "conv_ws.hip", "conv_wgrad.hip", "conv_wgrad_dma.hip",
               "conv_level0.hip", "pool.hip")
 EMBCNN_FILES = ("embcnn.hip",)
-FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES, "conv": CONV_FILES, "embcnn": EMBCNN_FILES}
-LABEL = {"gemm": "GEMM", "attention": "attention", "conv": "convolution / pooling", "embcnn": "emb_cnn data-path"}
+DECODE_FILES = ("decode.hip",)
+FAMILIES = {"gemm": GEMM_FILES, "attention": ATTENTION_FILES, "conv": CONV_FILES, "embcnn": EMBCNN_FILES, "decode": DECODE_FILES}
+LABEL = {"gemm": "GEMM", "attention": "attention", "conv": "convolution / pooling", "embcnn": "emb_cnn data-path", "decode": "decode-step"}
 
 # kernels the automatic dispatch cannot choose: (substring of the demangled name, the line that decides)
 HOOK_ONLY = (
@@ -84,7 +86,7 @@ CONV_HOOK_FORMS = (
     ("vgg_level0_fwd / _dgrad / _wgrad_kernel with wsplit = 0",
      "conv_level0.hip: conv.0 on split weights unless L0_WSPLIT = 0 (an argument of the same kernels)"),
 )
-HOOK_ONLY_OF = {"gemm": HOOK_ONLY, "attention": (), "conv": CONV_HOOK_ONLY, "embcnn": ()}
+HOOK_ONLY_OF = {"gemm": HOOK_ONLY, "attention": (), "conv": CONV_HOOK_ONLY, "embcnn": (), "decode": ()}
 
 # attention kernels that ops.attn_bwd never chooses (it asks for dQ and dK / dV in one launch): reached by a direct asr_attn_bwd call with one part
 PARTS_ONLY = (
