@@ -14,6 +14,7 @@ Sub-layer -> reference code
   EmbCNNFn   models/asr/transformer.py:33-40, :70-76
   CEFn       utils/metrics.py:102-132
   RnntJointFn, RnntFn  (no reference code: the transducer head of --transducer-weight)
+  RnntSimpleFn, RnntJointPrunedFn, RnntPrunedFn  (no reference code: pruned transducer training, --transducer-prune-range)
 """
 import collections
 import os
@@ -1245,8 +1246,109 @@ def check_rnnt_shape(B, T, U1, V):
     n = int(B) * int(T) * int(U1) * ((int(V) + 63) // 64 * 64) * 4
     if n >= RNNT_MAX_LOGIT_BYTES:
         raise ValueError("transducer joint logits (B %d, T %d, U+1 %d, V %d) take %d bytes in fp32: 2^31 or more is refused (the "
-                         "vocabulary projection's GEMMs keep 32-bit sizes and chunk offsets); use a smaller batch or shorter targets"
-                         % (B, T, U1, V, n))
+                         "vocabulary projection's GEMMs keep 32-bit sizes and chunk offsets); use a smaller batch or shorter targets, "
+                         "or train on a band of the lattice with --transducer-prune-range" % (B, T, U1, V, n))
+
+
+# ------------------------------------------------------------------------------------------------ pruned transducer (csrc/rnnt_pruned.hip)
+def _rnnt_labels(gold, B, U, dev):
+    tg = torch.as_tensor(gold).to(device=dev, dtype=torch.int64)
+    if U == 0 and tg.shape[1] == 0:
+        tg = tg.new_zeros((B, 1))
+    if tg.shape[1] < max(U, 1):
+        raise ValueError("%d label columns for U = %d" % (tg.shape[1], U))
+    return tg[:, :max(U, 1)].contiguous()
+
+
+class RnntSimpleFn(Function):
+    """(loss, gb, gl) of the simple joiner am (B,T,V) + lm (B,U+1,V) (ops.rnnt_simple_fwd): loss = mean_b nll_b /
+    max(U_b, 1) with RnntFn's lengths, labels and edge rules; gb, gl (B,T,U+1) fp32, not differentiable: the arc posteriors the band is
+    chosen from (ops.rnnt_prune_ranges).  No (B,T,U+1,V) tensor exists: the log-normalisers are one batched fp32 contraction over V.
+    backward: three launches (ops.rnnt_simple_bwd), formal fp32 gradients of am and lm.  This Function does NOT claim the logit hand-over
+    slot (two projections feed it, the slot holds one): the slot its second projection left stays unclaimed until the next LinearFn
+    clears it, and both projections' backwards cast the fp32 gradient themselves."""
+
+    @staticmethod
+    def forward(ctx, am, lm, gold, frame_lengths, target_lengths, blank):
+        if am.dim() != 3 or lm.dim() != 3 or am.shape[0] != lm.shape[0] or am.shape[2] != lm.shape[2]:
+            raise ValueError("RnntSimpleFn: am (B,T,V) and lm (B,U+1,V) expected, got %s and %s" % (tuple(am.shape), tuple(lm.shape)))
+        B, U = am.shape[0], lm.shape[1] - 1
+        a = (am if am.dtype == torch.float32 else am.float()).contiguous()
+        l = (lm if lm.dtype == torch.float32 else lm.float()).contiguous()
+        dev = a.device
+        tg = _rnnt_labels(gold, B, U, dev)
+        fl = torch.as_tensor(frame_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        loss, ws, gb, gl = ops.rnnt_simple_fwd(a, l, tg, fl, tl, blank)
+        ctx.t = (tg, fl, tl, ws)
+        ctx.blank, ctx.shapes = blank, (am.shape, lm.shape)
+        ctx.mark_non_differentiable(gb, gl)
+        return loss.reshape(()), gb, gl
+
+    @staticmethod
+    def backward(ctx, dloss, *unused):
+        tg, fl, tl, ws = ctx.t
+        dam, dlm = ops.rnnt_simple_bwd(ctx.shapes[0], ctx.shapes[1], tg, fl, tl, ws, dloss.reshape(1).float().contiguous(), ctx.blank)
+        return dam, dlm, None, None, None, None
+
+
+class RnntJointPrunedFn(Function):
+    """z (B,T,W,J) = tanh(e (B,T,J) + p (B,U+1,J)[s_begin[b,t] + w]) in the compute dtype (ops.rnnt_joint_pruned): RnntJointFn on a band.
+    s_begin (B,T) int32 is a constant of the step.  backward: ONE launch, de = sum_w, dp[b,u] = the sum over the frames whose window
+    holds u in ascending t, one owner per element (torch index_add's GPU backward is not reproducible)."""
+
+    @staticmethod
+    def forward(ctx, e, p, s_begin, W):
+        cd = ops.compute_dtype()
+        z = ops.rnnt_joint_pruned(e if e.dtype == cd else e.to(cd), p if p.dtype == cd else p.to(cd), s_begin, int(W))
+        ctx.z, ctx.s, ctx.U1 = z, s_begin, p.shape[1]
+        ctx.dtypes = (e.dtype, p.dtype)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        z = ctx.z
+        de, dp = ops.rnnt_joint_pruned_bwd(dz if dz.dtype == z.dtype else dz.to(z.dtype), z, ctx.s, ctx.U1)
+        return de.to(ctx.dtypes[0]), dp.to(ctx.dtypes[1]), None, None
+
+
+class RnntPrunedFn(Function):
+    """RnntFn on a band (ops.rnnt_pruned_fwd): pred (B,T,W,V) fp32 logits whose row (b,t,w) is lattice cell
+    (t, s_begin[b,t] + w) of the T x (U + 1) lattice, U = `umax`; every node outside the band has no outgoing arc.  An utterance without a
+    complete path inside its band makes the loss +inf and gets zero gradient rows, like any utterance without an alignment.
+    backward: ONE launch.  This Function CLAIMS the logit hand-over slot exactly as RnntFn does: rnnt_out on the banded z must be the
+    last fp32 projection before it, and both must run before the decoder.  check_rnnt_shape(B, T, W, V) applies."""
+
+    @staticmethod
+    def forward(ctx, pred, gold, frame_lengths, target_lengths, s_begin, umax, blank):
+        if pred.dim() != 4:
+            raise ValueError("RnntPrunedFn: band logits (B,T,W,V) expected, got %s" % (tuple(pred.shape),))
+        B, T, W, V = pred.shape
+        U = int(umax)
+        if not 1 <= W <= U + 1:
+            raise ValueError("RnntPrunedFn: a band of %d label positions for U + 1 = %d" % (W, U + 1))
+        check_rnnt_shape(B, T, W, V)
+        logits = pred if pred.dtype == torch.float32 else pred.float()
+        logits = logits.contiguous()
+        dev = logits.device
+        tg = _rnnt_labels(gold, B, U, dev)
+        fl = torch.as_tensor(frame_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        loss, ws = ops.rnnt_pruned_fwd(logits, tg, fl, tl, s_begin, U, blank)
+        ctx.t = (logits, tg, fl, tl, s_begin, ws)
+        ctx.blank, ctx.shape, ctx.U = blank, pred.shape, U
+        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, tg, fl, tl, s, ws = ctx.t
+        go = dloss.reshape(1).float().contiguous()
+        if ctx.handover is not None:
+            ctx.handover["dy"] = ops.rnnt_pruned_bwd(logits, tg, fl, tl, s, ctx.U, ws, go, ctx.blank, out_dtype=torch.bfloat16, pad=64)
+            return (ops.zero_scalar(logits.device).expand(ctx.shape),) + (None,) * 6
+        dl = ops.rnnt_pruned_bwd(logits, tg, fl, tl, s, ctx.U, ws, go, ctx.blank)
+        return (dl.reshape(ctx.shape),) + (None,) * 6
 
 
 # ================================================================================================ MWER over the n-best

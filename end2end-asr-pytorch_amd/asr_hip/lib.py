@@ -76,6 +76,15 @@ _SIGS = {
     "asr_rnnt_workspace": (_L, [_I, _I, _I]),
     "asr_rnnt_fwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     "asr_rnnt_bwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P]),
+    "asr_rnnt_simple_workspace": (_L, [_I, _I, _I, _I]),
+    "asr_rnnt_simple_fwd": (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "asr_rnnt_simple_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "asr_rnnt_prune_ranges": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "asr_rnnt_joint_pruned_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "asr_rnnt_joint_pruned_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "asr_rnnt_pruned_workspace": (_L, [_I, _I, _I, _I]),
+    "asr_rnnt_pruned_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "asr_rnnt_pruned_bwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P]),
     "asr_rnnt_beam_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
     "asr_rnnt_beam_search": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
     "asr_ctc_align_workspace": (_L, [_I, _I, _I]),

@@ -720,6 +720,133 @@ def rnnt_bwd(logits, targets, frame_lengths, target_lengths, ws, grad_out=None, 
     return dl if pad == 64 else dl[:, :V]
 
 
+# ------------------------------------------------------------------------------------------------ pruned transducer (csrc/rnnt_pruned.hip)
+def _rnnt_simple_args(am, lm, targets, frame_lengths, target_lengths):
+    B, T, V = am.shape
+    U1 = lm.shape[1]
+    assert lm.shape[0] == B and lm.shape[2] == V, "rnnt_simple: am %s and lm %s do not match" % (tuple(am.shape), tuple(lm.shape))
+    for x in (am, lm):
+        assert x.dtype == torch.float32 and (x.stride(2) == 1 or V == 1) and x.stride(0) == x.shape[1] * x.stride(1), \
+            "rnnt_simple: fp32 rows at one stride"
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (B, max(U1 - 1, 1))
+    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
+    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    return B, T, U1 - 1, V
+
+
+def rnnt_simple_fwd(am, lm, targets, frame_lengths, target_lengths, blank=0):
+    """The simple-joiner transducer loss (csrc/rnnt_pruned.hip): am (B,T,V), lm (B,U+1,V) fp32 (rows at any one stride >= V), targets /
+    lengths as rnnt_fwd -> (loss (1,), workspace, gb, gl): gb, gl (B,T,U+1) fp32 views of the workspace, the arc posteriors the band is
+    chosen from (zero in dead cells); workspace[-B:] holds nll_b."""
+    B, T, U, V = _rnnt_simple_args(am, lm, targets, frame_lengths, target_lengths)
+    n = L.load().asr_rnnt_simple_workspace(B, T, U, V)
+    ws = torch.empty(n, device=am.device, dtype=torch.float32)
+    loss = torch.empty(1, device=am.device, dtype=torch.float32)
+    L.call("asr_rnnt_simple_fwd", L.ptr(am), am.stride(1), L.ptr(lm), lm.stride(1), L.ptr(targets), L.ptr(frame_lengths),
+           L.ptr(target_lengths), B, T, U, V, int(blank), L.ptr(ws), n, L.ptr(loss), L.stream())
+    cells = B * T * (U + 1)
+    off = 4 * cells + 2 * B + 2 * cells                  # behind alpha | beta | nll (fp64) and the two log-probability arrays
+    gb = ws[off:off + cells].view(B, T, U + 1)
+    gl = ws[off + cells:off + 2 * cells].view(B, T, U + 1)
+    return loss, ws, gb, gl
+
+
+def rnnt_simple_bwd(am_shape, lm_shape, targets, frame_lengths, target_lengths, ws, grad_out=None, blank=0):
+    """(grad_out * d loss / d am (B,T,V), d lm (B,U+1,V)) of rnnt_simple_fwd from its workspace, fp32 contiguous: three launches."""
+    B, T, V = am_shape
+    U = lm_shape[1] - 1
+    assert grad_out is None or (grad_out.dtype == torch.float32 and grad_out.numel() == 1)
+    assert ws.numel() == L.load().asr_rnnt_simple_workspace(B, T, U, V)
+    dam = torch.empty((B, T, V), device=ws.device, dtype=torch.float32)
+    dlm = torch.empty((B, U + 1, V), device=ws.device, dtype=torch.float32)
+    L.call("asr_rnnt_simple_bwd", L.ptr(targets), L.ptr(frame_lengths), L.ptr(target_lengths), B, T, U, V, int(blank), L.ptr(ws),
+           L.ptr(grad_out), L.ptr(dam), L.ptr(dlm), L.stream())
+    return dam, dlm
+
+
+def rnnt_prune_ranges(gb, gl, frame_lengths, target_lengths, prune_range):
+    """s_begin (B,T) int32: the first label position of every frame's band of min(prune_range, U+1) positions, from the arc posteriors gb,
+    gl (B,T,U+1) fp32 of rnnt_simple_fwd (the rule: csrc/rnnt_pruned.hip).  One launch, nothing copied to the host."""
+    B, T, U1 = gb.shape
+    assert gl.shape == gb.shape and gb.dtype == gl.dtype == torch.float32 and gb.is_contiguous() and gl.is_contiguous()
+    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
+    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    s = torch.empty((B, T), device=gb.device, dtype=torch.int32)
+    L.call("asr_rnnt_prune_ranges", L.ptr(gb), L.ptr(gl), L.ptr(frame_lengths), L.ptr(target_lengths), B, T, U1 - 1, int(prune_range),
+           L.ptr(s), L.stream())
+    return s
+
+
+def _band_args(s_begin, B, T, U1, W):
+    assert s_begin.dtype == torch.int32 and s_begin.shape == (B, T) and s_begin.is_contiguous(), "s_begin: (B,T) int32"
+    if not 1 <= W <= U1:
+        raise ValueError("a band of %d label positions for U + 1 = %d" % (W, U1))
+
+
+def rnnt_joint_pruned(e, p, s_begin, W):
+    """z (B,T,W,J) = tanh(e (B,T,J) + p (B,U1,J)[s_begin[b,t] + w]): one launch, in the dtype of e.  J must be a multiple of 8."""
+    B, T, J = e.shape
+    U1 = p.shape[1]
+    if p.shape[0] != B or p.shape[2] != J or p.dtype != e.dtype:
+        raise ValueError("rnnt_joint_pruned: e %s %s and p %s %s do not match" % (tuple(e.shape), e.dtype, tuple(p.shape), p.dtype))
+    if J % 8 != 0:
+        raise ValueError("rnnt_joint_pruned: the joint width must be a multiple of 8, got %d" % J)
+    _band_args(s_begin, B, T, U1, W)
+    e, p = e.contiguous(), p.contiguous()
+    z = torch.empty((B, T, W, J), device=e.device, dtype=e.dtype)
+    L.call("asr_rnnt_joint_pruned_fwd", L.ptr(e), L.ptr(p), L.ptr(s_begin), L.ptr(z), B, T, U1, W, J, L.dt(e), L.stream())
+    return z
+
+
+def rnnt_joint_pruned_bwd(dz, z, s_begin, U1):
+    """(de (B,T,J), dp (B,U1,J)) of rnnt_joint_pruned for dz, z (B,T,W,J): one launch, sums in a fixed order, outputs in the dtype of z."""
+    B, T, W, J = z.shape
+    if dz.shape != z.shape or dz.dtype != z.dtype:
+        raise ValueError("rnnt_joint_pruned_bwd: dz %s %s and z %s %s do not match" % (tuple(dz.shape), dz.dtype, tuple(z.shape), z.dtype))
+    _band_args(s_begin, B, T, U1, W)
+    dz, z = dz.contiguous(), z.contiguous()
+    de = torch.empty((B, T, J), device=z.device, dtype=z.dtype)
+    dp = torch.empty((B, U1, J), device=z.device, dtype=z.dtype)
+    L.call("asr_rnnt_joint_pruned_bwd", L.ptr(dz), L.ptr(z), L.ptr(s_begin), L.ptr(de), L.ptr(dp), B, T, U1, W, J, L.dt(z), L.stream())
+    return de, dp
+
+
+def _rnnt_pruned_args(logits, targets, frame_lengths, target_lengths, s_begin, U):
+    B, T, W, V = logits.shape
+    assert logits.dtype == torch.float32 and (logits.stride(3) == 1 or V == 1)
+    ld = logits.stride(2)
+    assert logits.stride(1) == W * ld and logits.stride(0) == T * W * ld, "rnnt_pruned: logits rows at one stride"
+    assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (B, max(U, 1))
+    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
+    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    _band_args(s_begin, B, T, U + 1, W)
+    return B, T, U, W, V, ld
+
+
+def rnnt_pruned_fwd(logits, targets, frame_lengths, target_lengths, s_begin, U, blank=0):
+    """The transducer loss on a band (csrc/rnnt_pruned.hip): logits (B,T,W,V) fp32 whose row (b,t,w) is lattice cell (t, s_begin[b,t] + w),
+    targets (B,max(U,1)) int64, U the longest transcript -> (loss (1,), workspace); workspace[-B:] holds nll_b."""
+    B, T, U, W, V, ld = _rnnt_pruned_args(logits, targets, frame_lengths, target_lengths, s_begin, int(U))
+    n = L.load().asr_rnnt_pruned_workspace(B, T, U, W)
+    ws = torch.empty(n, device=logits.device, dtype=torch.float32)
+    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+    L.call("asr_rnnt_pruned_fwd", L.ptr(logits), ld, L.ptr(targets), L.ptr(frame_lengths), L.ptr(target_lengths), L.ptr(s_begin), B, T, U, W,
+           V, int(blank), L.ptr(ws), n, L.ptr(loss), L.stream())
+    return loss, ws
+
+
+def rnnt_pruned_bwd(logits, targets, frame_lengths, target_lengths, s_begin, U, ws, grad_out=None, blank=0, out_dtype=torch.float32, pad=8):
+    """grad_out * d loss / d logits of rnnt_pruned_fwd, ONE launch, returned like rnnt_bwd's: a (B T W, V) view of a buffer V rounded up to
+    `pad` wide whose pad columns are zero, the WHOLE buffer with pad=64."""
+    B, T, U, W, V, ld = _rnnt_pruned_args(logits, targets, frame_lengths, target_lengths, s_begin, int(U))
+    assert grad_out is None or (grad_out.dtype == torch.float32 and grad_out.numel() == 1)
+    ldd = (V + pad - 1) // pad * pad
+    dl = torch.empty((B * T * W, ldd), device=logits.device, dtype=out_dtype)
+    L.call("asr_rnnt_pruned_bwd", L.ptr(logits), ld, L.ptr(targets), L.ptr(frame_lengths), L.ptr(target_lengths), L.ptr(s_begin), B, T, U, W,
+           V, int(blank), L.ptr(ws), L.ptr(grad_out), L.ptr(dl), ldd, L.dt(dl), L.stream())
+    return dl if pad == 64 else dl[:, :V]
+
+
 def rnnt_beam_search(e, tables, w_out, b_out, lengths, beam_width, candidates=0, max_symbols=5, nbest=1, blank=0, sos=1):
     """Transducer beam search (csrc/rnnt_beam.hip), ONE launch: e (B,T,J) = rnnt_enc's output, tables = the predictor's one or two (V,J)
     tables (tables[k]: the label k places back), w_out (V,J), all contiguous in one dtype (fp32 / bf16: what the model's forward reads),

@@ -68,6 +68,14 @@ def check_transducer(dim_joint, context, dim_model=None):
     return J, C
 
 
+def check_prune_range(S):
+    """The band width S of pruned transducer training (--transducer-prune-range): 0 = the full lattice, otherwise 2..64."""
+    S = int(S or 0)
+    if S != 0 and not 2 <= S <= 64:
+        raise ValueError("--transducer-prune-range must be 0 (off) or lie in 2..64, got %d" % S)
+    return S
+
+
 def hypothesis_labels(ids):
     """The label ids of a decoded hypothesis as a CTC target: SOS and EOS dropped, PAD dropped from the end.  A PAD (= the CTC blank)
     left inside has no alignment, and the aligner reports it so."""
@@ -90,7 +98,9 @@ class Transformer(nn.Module):
 
     transducer=dict(dim_joint=J, context=C) (train.py --transducer-weight > 0) adds a transducer head on the ENCODER
     output: `rnnt_enc` (D -> J), the stateless predictor's tables `rnnt_embed.{0..C-1}` ((V, J) each, one per context position) and
-    `rnnt_out` (J -> V); blank = PAD.  None: none of them exists, nor their state_dict keys."""
+    `rnnt_out` (J -> V); blank = PAD.  None: none of them exists, nor their state_dict keys.  prune_range=S > 0 in that dict (train.py
+    --transducer-prune-range) adds the simple joiner of pruned transducer training, `rnnt_simple_am` (D -> V) on the encoder output and
+    `rnnt_simple_lm` (J -> V) on the predictor; S = 0 (the default): neither exists and the head is the full-lattice one."""
 
     def __init__(self, encoder, decoder, feat_extractor='vgg_cnn', ctc_head=False, transducer=None):
         super().__init__()
@@ -105,6 +115,10 @@ class Transformer(nn.Module):
             self.rnnt_enc = nn.Linear(decoder.dim_model, J)
             self.rnnt_embed = nn.ModuleList([nn.Embedding(decoder.num_trg_vocab, J) for _ in range(C)])
             self.rnnt_out = nn.Linear(J, decoder.num_trg_vocab)
+            self.rnnt_prune_range = check_prune_range(transducer.get("prune_range", 0))
+            if self.rnnt_prune_range > 0:
+                self.rnnt_simple_am = nn.Linear(decoder.dim_model, decoder.num_trg_vocab)
+                self.rnnt_simple_lm = nn.Linear(J, decoder.num_trg_vocab)
         if feat_extractor == 'emb_cnn':
             self.conv = nn.Sequential(
                 nn.Conv2d(1, 32, kernel_size=(41, 11), stride=(2, 2), padding=(0, 10)), nn.BatchNorm2d(32),
@@ -318,18 +332,74 @@ class Transformer(nn.Module):
         z = F_.RnntJointFn.apply(e, self._rnnt_predict(tokens))
         return F_.linear(z, self.rnnt_out.weight, self.rnnt_out.bias, True, True)
 
-    def transducer_loss(self, enc_out, input_lengths, padded_target, target_lengths):
+    def _rnnt_tokens(self, targets, target_lengths, device):
+        """(tg (B,L) int64 on the device, U = the longest transcript, the predictor's C token tensors (B,U+1)) as transducer_logits builds
+        them."""
+        tl = [int(x) for x in torch.as_tensor(target_lengths).tolist()]
+        V, C = self.rnnt_out.out_features, len(self.rnnt_embed)
+        tg = torch.as_tensor(targets).to(device, dtype=torch.int64)
+        U = max(0, min(int(tg.shape[1]), max(tl) if tl else 0))
+        sos = torch.full((tg.shape[0], C), constant.SOS_TOKEN, dtype=torch.int64, device=tg.device)
+        hist = torch.cat([sos, tg[:, :U].clamp(0, V - 1)], 1)
+        return tg, U, [hist[:, C - 1 - k:C + U - k] for k in range(C)]
+
+    def transducer_band(self, enc_out, input_lengths, padded_target, target_lengths):
+        """The simple joiner's loss and the band it chooses (pruned transducer training) -> (L_simple, s_begin (B,T')
+        int32 on the device, W = min(S, U+1), U, p): am = rnnt_simple_am(enc_out), lm = rnnt_simple_lm(p), both fp32; F_.RnntSimpleFn
+        gives the loss and the arc posteriors of am + lm's lattice without a (T',U+1,V) tensor, ops.rnnt_prune_ranges the first label
+        position of every frame's window.  The band is a constant: no gradient flows through it.  Nothing is copied to the host."""
+        self._need_transducer()
+        S = int(getattr(self, "rnnt_prune_range", 0))
+        if S <= 0:
+            raise ValueError("this model has no simple joiner (rnnt_simple_am / rnnt_simple_lm): it was built with "
+                             "--transducer-prune-range 0")
+        tg, U, tokens = self._rnnt_tokens(padded_target, target_lengths, enc_out.device)
+        W = min(S, U + 1)
+        F_.check_rnnt_shape(enc_out.shape[0], enc_out.shape[1], W, self.rnnt_out.out_features)       # before the first launch
+        frames = _lengths_to_device(self.ctc_frame_lengths(input_lengths, enc_out.shape[1]), enc_out.device)
+        tl = _lengths_to_device(target_lengths, enc_out.device)
+        p = self._rnnt_predict(tokens)
+        am = F_.linear(enc_out, self.rnnt_simple_am.weight, self.rnnt_simple_am.bias, True, True)
+        lm = F_.linear(p, self.rnnt_simple_lm.weight, self.rnnt_simple_lm.bias, True, True)
+        simple, gb, gl = F_.RnntSimpleFn.apply(am, lm, tg, frames, tl, constant.PAD_TOKEN)
+        s_begin = ops.rnnt_prune_ranges(gb, gl, frames, tl, S)
+        return simple, s_begin, W, U, p, (tg, frames, tl)
+
+    def transducer_pruned_loss(self, enc_out, input_lengths, padded_target, target_lengths, simple_scale=0.5):
+        """(L_pruned, L_simple) of a batch, each mean_b nll_b / max(U_b, 1) (train.py --transducer-prune-range S):
+        the simple joiner's loss and band (transducer_band), then z[b,t,w] = tanh(e[b,t] + p[b, s(t) + w]) (F_.RnntJointPrunedFn), logits
+        (B,T',W,V) = rnnt_out(z) and the lattice with every node outside the band cut off (F_.RnntPrunedFn).  The training loss is
+        L_pruned + simple_scale * L_simple; simple_scale itself is applied by the caller (transducer_loss).  Call it BEFORE the decoder
+        runs, like transducer_loss: RnntPrunedFn claims the hand-over slot rnnt_out has just left."""
+        if not float(simple_scale) >= 0.0:
+            raise ValueError("--transducer-simple-scale must be >= 0, got %g" % float(simple_scale))
+        simple, s_begin, W, U, p, (tg, frames, tl) = self.transducer_band(enc_out, input_lengths, padded_target, target_lengths)
+        e = F_.linear(enc_out, self.rnnt_enc.weight, self.rnnt_enc.bias, False, True)
+        z = F_.RnntJointPrunedFn.apply(e, p, s_begin, W)
+        logits = F_.linear(z, self.rnnt_out.weight, self.rnnt_out.bias, True, True)
+        pruned = F_.RnntPrunedFn.apply(logits, tg, frames, tl, s_begin, U, constant.PAD_TOKEN)
+        return pruned, simple
+
+    def transducer_loss(self, enc_out, input_lengths, padded_target, target_lengths, simple_scale=0.5, stats=None):
         """The transducer loss of a batch, mean_b nll_b / max(U_b, 1) (F_.RnntFn), with T_b = ctc_frame_lengths.  Call it BEFORE the
         decoder runs: RnntFn claims the logit hand-over slot its own projection has just left, and the decoder's projection then
-        leaves a fresh one for the cross-entropy."""
+        leaves a fresh one for the cross-entropy.  A model built with prune_range S > 0: L_pruned + simple_scale * L_simple
+        (transducer_pruned_loss); stats, when given, receives 'rnnt_simple' = L_simple and 'rnnt_pruned' = L_pruned."""
+        if int(getattr(self, "rnnt_prune_range", 0)) > 0:
+            pruned, simple = self.transducer_pruned_loss(enc_out, input_lengths, padded_target, target_lengths, simple_scale)
+            if stats is not None:
+                stats["rnnt_simple"], stats["rnnt_pruned"] = simple.detach(), pruned.detach()
+            return pruned + float(simple_scale) * simple
         logits = self.transducer_logits(enc_out, padded_target, target_lengths)
         frames = torch.tensor(self.ctc_frame_lengths(input_lengths, enc_out.shape[1]), dtype=torch.int32)
         return F_.RnntFn.apply(logits, torch.as_tensor(padded_target), frames, torch.as_tensor(target_lengths), constant.PAD_TOKEN)
 
-    def transducer_step(self, padded_input, input_lengths, padded_target, target_lengths, transducer_weight, smoothing, ctc_weight=0.0):
+    def transducer_step(self, padded_input, input_lengths, padded_target, target_lengths, transducer_weight, smoothing, ctc_weight=0.0,
+                        simple_scale=0.5):
         """One training step's loss with the transducer term (train.py --transducer-weight r)
         -> (L, gold, hyp_seq, stats): L = (1 - r) L_existing + r L_rnnt, L_existing = CE, or (1 - w) CE + w CTC with ctc_weight w > 0.
-        stats: the device scalars 'ce', 'ctc' (zero without the head) and 'rnnt'; no host synchronisation."""
+        stats: the device scalars 'ce', 'ctc' (zero without the head), 'rnnt' and 'rnnt_simple' (zero without --transducer-prune-range;
+        with it L_rnnt = L_pruned + simple_scale L_simple and 'rnnt_pruned' is there too); no host synchronisation."""
         from utils.metrics import calculate_metrics
         r, w = float(transducer_weight), float(ctc_weight)
         if not 0.0 < r <= 1.0:
@@ -340,11 +410,14 @@ class Transformer(nn.Module):
         feats = self._features(padded_input)
         enc_out, _ = self.encoder(feats, input_lengths)
         ctc = self.ctc_logits(enc_out) if w > 0.0 else None
-        rnnt = self.transducer_loss(enc_out, input_lengths, padded_target, target_lengths)
+        extra = {}
+        rnnt = self.transducer_loss(enc_out, input_lengths, padded_target, target_lengths, simple_scale, extra)
         pred, gold, *_ = self.decoder(padded_target, enc_out, input_lengths)
         hyp_seq = ops.argmax_rows(pred.detach().reshape(-1, pred.shape[-1])).view(pred.shape[0], pred.shape[1])
         ce, _ = calculate_metrics(pred, gold, smoothing=smoothing, loss_type="ce", sync=False)
-        stats = dict(ce=ce.detach(), ctc=ops.zero_scalar(pred.device).reshape(()), rnnt=rnnt.detach())
+        stats = dict(ce=ce.detach(), ctc=ops.zero_scalar(pred.device).reshape(()), rnnt=rnnt.detach(),
+                     rnnt_simple=ops.zero_scalar(pred.device).reshape(()))
+        stats.update(extra)
         existing = ce
         if w > 0.0:
             frames = torch.tensor(self.ctc_frame_lengths(input_lengths, ctc.shape[1]), dtype=torch.int32)

@@ -157,6 +157,10 @@ def main():
     if check_transducer_weight(args) > 0:             # with the checkpoint's settings
         logging.info("--transducer-weight %g: a transducer head (joint width %d, predictor context %d) trains beside the decoder; the "
                      "step runs as eager launches", args.transducer_weight, args.transducer_dim_joint, args.transducer_context)
+        if int(getattr(args, "transducer_prune_range", 0) or 0) > 0:
+            logging.info("--transducer-prune-range %d: pruned transducer training, the joint and the loss on a band of %d label positions "
+                         "per frame chosen by the simple joiner (rnnt_simple_am / rnnt_simple_lm), L_rnnt = L_pruned + %g L_simple",
+                         args.transducer_prune_range, args.transducer_prune_range, args.transducer_simple_scale)
     from utils.functions import check_distill, load_teacher
     trainer = Trainer()
     distill_a, distill_c = check_distill(args)         # with the checkpoint's --ctc-weight

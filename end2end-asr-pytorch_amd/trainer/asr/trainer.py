@@ -239,7 +239,9 @@ class Trainer():
                                  "transducer step" % rnnt_weight)
             if opt is not None and not self.__dict__.get("_logged_rnnt_eager"):
                 self._logged_rnnt_eager = True
-                logging.info("--transducer-weight %g: the transducer step runs as eager launches (no hipGraph replay)", rnnt_weight)
+                S = int(getattr(constant.args, "transducer_prune_range", 0) or 0)
+                mode = "the pruned transducer step (--transducer-prune-range %d)" % S if S > 0 else "the transducer step"
+                logging.info("--transducer-weight %g: %s runs as eager launches (no hipGraph replay)", rnnt_weight, mode)
         if (opt is not None and loss_type == "ce" and getattr(constant.args, "graph_buckets", 0) > 0 and src.is_cuda
                 and ctc_weight == 0 and not distill_step and rnnt_weight == 0):
             r = self._graph_step(model, opt, src, src_lengths, tgt, smoothing)
@@ -279,8 +281,9 @@ class Trainer():
                                                            ctc_weight=ctc_weight, distill_ctc_weight=distill_c)
         elif rnnt_weight > 0:
             core = model.module if hasattr(model, "module") else model
+            scale = getattr(constant.args, "transducer_simple_scale", None)
             loss, gold_seq, hyp_seq, _ = core.transducer_step(src, src_lengths, tgt, tgt_lengths, rnnt_weight, smoothing,
-                                                              ctc_weight=ctc_weight)
+                                                              ctc_weight=ctc_weight, simple_scale=0.5 if scale is None else float(scale))
         elif ctc_weight > 0:
             pred, gold, hyp_seq, gold_seq, ctc_logits = model(src, src_lengths, tgt, verbose=False, return_ctc=True)
             core = model.module if hasattr(model, "module") else model

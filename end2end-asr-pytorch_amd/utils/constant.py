@@ -36,7 +36,10 @@ Differences that do not change old command lines:
     output, L = (1 - r) L_existing + r L_rnnt (csrc/rnnt.hip, DESIGN.md section 7); `--transducer-greedy` (+ `--transducer-max-symbols`;
     test.py): time-synchronous greedy decoding from that head alone; `--transducer-beam-search` (+ `--beam-width`, `--beam-nbest`,
     `--transducer-candidates`, `--transducer-max-symbols`, `--lm-rescoring`; test.py): beam search over that head, one fused search
-    kernel per utterance (csrc/rnnt_beam.hip).
+    kernel per utterance (csrc/rnnt_beam.hip, DESIGN.md section 7);
+  * `--transducer-prune-range S` (+ `--transducer-simple-scale c`; train.py with --transducer-weight > 0): pruned transducer training, the
+    joint and the loss on a band of S label positions per frame chosen by a simple joiner am + lm, L_rnnt = L_pruned + c L_simple
+    (csrc/rnnt_pruned.hip).
 """
 import argparse
 import os
@@ -153,6 +156,15 @@ _FLAGS = [
     (("--transducer-context",), dict(default=2, type=_I)), (("--transducer-greedy",), dict(action="store_true")),
     (("--transducer-max-symbols",), dict(default=5, type=_I)), (("--transducer-beam-search",), dict(action="store_true")),
     (("--transducer-candidates",), dict(default=0, type=_I)),
+    # pruned transducer training (csrc/rnnt_pruned.hip; Kuang et al. 2022).  --transducer-prune-range S (train.py;
+    # 0 = off: the model, its state_dict keys, its launches and the bits of its loss are those of the full lattice; otherwise 2..64, and
+    # --transducer-weight must be positive): two more layers, rnnt_simple_am (D -> V, on the encoder output) and rnnt_simple_lm (J -> V,
+    # on the predictor), whose sum is a joiner without a (T', U+1, V) tensor; the posteriors of ITS lattice choose, per frame, a window of
+    # min(S, U+1) label positions, and rnnt_enc / tanh / rnnt_out and the transducer loss run on that band only: logits (B,T',S,V)
+    # instead of (B,T',U+1,V).  L_rnnt = L_pruned + c L_simple with --transducer-simple-scale c >= 0 (default 0.5), each a mean_b nll_b /
+    # max(U_b, 1).  The band is a constant of the step (no gradient through it).  No am-only / lm-only smoothing term and no warm-up
+    # schedule of c.  Decoding (test.py) ignores the two simple layers.
+    (("--transducer-prune-range",), dict(default=0, type=_I)), (("--transducer-simple-scale",), dict(default=0.5, type=_F)),
     # --ctc-beam-search (test.py): prefix beam search over the CTC head's posteriors alone (csrc/ctc_beam.hip): --beam-width (1..16)
     # prefixes kept per frame, --ctc-candidates (0: min(V, 16)) labels tried per frame, the n-best ranked like --beam-search's
     (("--ctc-beam-search",), dict(action="store_true")),

@@ -112,6 +112,31 @@ def load_model(load_path):
                                  "resized" % (k.replace("_", "-"), getattr(cur, k), load_path, k.replace("_", "-"), v))
             setattr(args, k, v)
             setattr(cur, k, v)
+        # pruned transducer training (--transducer-prune-range S, --transducer-simple-scale c) follows the head's rule: S > 0 adds the two
+        # simple layers to the model, so a positive S may replace a positive one (it only sizes the band), S can go neither from 0 to
+        # positive nor back, and c only weighs the loss (a checkpoint written before the flags existed: 0 and 0.5)
+        kept_s = int(getattr(args, "transducer_prune_range", 0) or 0)
+        if "transducer_prune_range" in given and int(getattr(cur, "transducer_prune_range", 0) or 0) != kept_s:
+            new_s = int(cur.transducer_prune_range or 0)
+            check_prune_range(new_s)
+            if new_s > 0 and kept_s == 0:
+                raise ValueError("--transducer-prune-range %d on the command line, but %s was trained with --transducer-prune-range 0: "
+                                 "the simple joiner's layers (rnnt_simple_am / rnnt_simple_lm) cannot be added to a checkpoint"
+                                 % (new_s, load_path))
+            if new_s == 0 and kept_s > 0:
+                raise ValueError("--transducer-prune-range 0 on the command line, but %s was trained with --transducer-prune-range %d: "
+                                 "the simple joiner's layers (rnnt_simple_am / rnnt_simple_lm) cannot be dropped from a checkpoint"
+                                 % (load_path, kept_s))
+            logging.info("load_model: --transducer-prune-range %d from the command line replaces the checkpoint's %d", new_s, kept_s)
+            kept_s = new_s
+        args.transducer_prune_range = kept_s
+        cur.transducer_prune_range = kept_s
+        kept_c = getattr(args, "transducer_simple_scale", None)
+        kept_c = 0.5 if kept_c is None else float(kept_c)
+        if "transducer_simple_scale" in given and hasattr(cur, "transducer_simple_scale"):
+            kept_c = check_simple_scale(cur.transducer_simple_scale)
+        args.transducer_simple_scale = kept_c
+        cur.transducer_simple_scale = kept_c
         # the encoder's convolution modules (--conv-module-kernel) are part of the model too: the checkpoint's kernel size rebuilds them
         # (one written before the flag existed: 0, none); typing a different size is an error, never an override
         kept = int(getattr(args, "conv_module_kernel", 0) or 0)
@@ -193,6 +218,11 @@ def check_transducer_weight(args):
     r = float(getattr(args, "transducer_weight", 0.0) or 0.0)
     if not 0.0 <= r <= 1.0:
         raise ValueError("--transducer-weight must lie in [0, 1], got %g" % r)
+    S = check_prune_range(getattr(args, "transducer_prune_range", 0))
+    c = getattr(args, "transducer_simple_scale", None)
+    check_simple_scale(0.5 if c is None else c)
+    if S > 0 and r == 0.0:
+        raise ValueError("--transducer-prune-range %d needs --transducer-weight > 0: it prunes the transducer head's lattice" % S)
     if r == 0.0:
         return r
     from models.asr.transformer import check_transducer
@@ -213,6 +243,23 @@ def check_transducer_weight(args):
     if int(getattr(args, "rank", 0) or 0) > 0:
         raise ValueError("--transducer-weight %g with --rank %d is not supported: the transducer head is not factorised" % (r, args.rank))
     return r
+
+
+def check_prune_range(S):
+    """--transducer-prune-range S -> S: 0 (off, the full lattice) or 2..64 label positions per frame (1 would be a band without a label
+    arc; the band's upper end keeps the banded logits small, which is its point)."""
+    S = int(S or 0)
+    if S != 0 and not 2 <= S <= 64:
+        raise ValueError("--transducer-prune-range must be 0 (off) or lie in 2..64, got %d" % S)
+    return S
+
+
+def check_simple_scale(c):
+    """--transducer-simple-scale c -> c >= 0: the weight of the simple joiner's loss in L_rnnt = L_pruned + c L_simple."""
+    c = float(c)
+    if not c >= 0.0 or c == float("inf"):
+        raise ValueError("--transducer-simple-scale must be a finite number >= 0, got %g" % c)
+    return c
 
 
 def check_mwer(args, label2id=None):
@@ -368,7 +415,8 @@ def init_transformer_model(args, label2id, id2label):
     ctc_weight = check_ctc_weight(getattr(args, "ctc_weight", 0.0), args)
     transducer = None
     if check_transducer_weight(args) > 0:
-        transducer = dict(dim_joint=int(getattr(args, "transducer_dim_joint", 256)), context=int(getattr(args, "transducer_context", 2)))
+        transducer = dict(dim_joint=int(getattr(args, "transducer_dim_joint", 256)), context=int(getattr(args, "transducer_context", 2)),
+                          prune_range=int(getattr(args, "transducer_prune_range", 0) or 0))
     model = Transformer(encoder, decoder, feat_extractor=args.feat_extractor, ctc_head=ctc_weight > 0, transducer=transducer)
     if args.parallel:
         model = HipDataParallel(model, device_ids=args.device_ids)

@@ -281,6 +281,47 @@ int asr_rnnt_bwd(const float* logits, int64_t ld, const int64_t* targets, const 
                  const int32_t* target_lengths, int B, int T, int Umax, int V, int blank, const float* workspace,
                  const float* grad_out, void* dlogits, int64_t ldd, int out_dtype, asr_stream_t stream);
 
+/* ---- pruned transducer training (csrc/rnnt_pruned.hip has the definition): a simple joiner am + lm whose lattice
+ * gives node posteriors, a band of W = min(S, Umax + 1) label positions per frame, the joint and the loss on the band.  No atomics: every
+ * output is a function of the inputs alone.  Lengths, targets, blank, the edge rules and the reduction are asr_rnnt_fwd's.
+ * asr_rnnt_simple_fwd: am (B,T,lda) and lm (B,Umax+1,ldl) fp32, lda, ldl >= V (columns >= V, rows t >= T_b of am and u > U_b of lm are never
+ *   read).  loss[0] = mean_b(nll_b / max(U_b,1)) of the lattice with log-normaliser N(t,u) = ma + ml + log(max(dot, FLT_MIN)), dot = sum_v
+ *   expf(am - ma) expf(lm - ml) on v_mfma_f32_32x32x2_f32 (exact while the two rows' spreads stay below about 87 together).  The workspace
+ *   (asr_rnnt_simple_workspace floats, 8-byte aligned) is, in floats: alpha | beta (fp64, 2 B T U1 each) | nll (fp64, 2 B) | blank | label
+ *   log-prob | gb | gl | dot | G (B T U1 each) | ma (B T) | ml (B U1) | Ea (B T V) | El (B U1 V) | nll (B).  gb, gl: the arc posteriors, zero
+ *   in dead cells and in an utterance with nll_b = +inf.  ASR_EUNSUPPORTED: 2 (Umax + 1) doubles beyond 64 KB of LDS, B > 65535.
+ * asr_rnnt_simple_bwd: dam (B,T,V), dlm (B,Umax+1,V) fp32 contiguous = grad_out[0] / (B max(U_b,1)) * d nll_b / d am, d lm (grad_out: device
+ *   scalar, NULL = 1); dead rows and the rows of an utterance with nll_b = +inf are zero.  Three launches: two contractions, the one-hot
+ *   terms by one owner per row in u (t) order.
+ * asr_rnnt_prune_ranges: s_begin (B,T) int32 from gb, gl (B,T,Umax+1) fp32 by the band rule of csrc/rnnt_pruned.hip; S >= 1.
+ * asr_rnnt_joint_pruned_fwd: z (B,T,W,J) = tanh(e (B,T,J) + p (B,U1,J)[s_begin[b,t] + w]) in `dtype`; s_begin is clamped to [0, U1 - W] by
+ *   every entry that takes it.  J % 8 and 16-byte alignment as asr_rnnt_joint_fwd.
+ * asr_rnnt_joint_pruned_bwd: de (B,T,J) = sum_w dz (1 - z^2) in w order; dp (B,U1,J) = the sum over the frames t whose window holds u, in
+ *   t order; fp32 sums, one owner per element, outputs in `dtype`.
+ * asr_rnnt_pruned_fwd / _bwd: asr_rnnt_fwd / asr_rnnt_bwd on logits (B,T,W,ld) / dlogits (B,T,W,ldd) whose row (b,t,w) is lattice cell
+ *   (t, s_begin[b,t] + w); every node outside the band has blank = label = -inf.  The row pass and the gradient kernel are those of
+ *   asr_rnnt_fwd / _bwd (csrc/rnnt_lattice.h): with W = Umax + 1 and s_begin = 0 the results are the same bits.  No complete path inside the
+ *   band: nll_b = +inf and zero rows.  Workspace: asr_rnnt_pruned_workspace floats, nll_b in its last B.                                  */
+int64_t asr_rnnt_simple_workspace(int B, int T, int Umax, int V);
+int asr_rnnt_simple_fwd(const float* am, int64_t lda, const float* lm, int64_t ldl, const int64_t* targets, const int32_t* frame_lengths,
+                        const int32_t* target_lengths, int B, int T, int Umax, int V, int blank, float* workspace,
+                        int64_t workspace_floats, float* loss, asr_stream_t stream);
+int asr_rnnt_simple_bwd(const int64_t* targets, const int32_t* frame_lengths, const int32_t* target_lengths, int B, int T, int Umax, int V,
+                        int blank, const float* workspace, const float* grad_out, float* dam, float* dlm, asr_stream_t stream);
+int asr_rnnt_prune_ranges(const float* gb, const float* gl, const int32_t* frame_lengths, const int32_t* target_lengths, int B, int T,
+                          int Umax, int S, int32_t* s_begin, asr_stream_t stream);
+int asr_rnnt_joint_pruned_fwd(const void* e, const void* p, const int32_t* s_begin, void* z, int B, int T, int U1, int W, int J, int dtype,
+                              asr_stream_t stream);
+int asr_rnnt_joint_pruned_bwd(const void* dz, const void* z, const int32_t* s_begin, void* de, void* dp, int B, int T, int U1, int W, int J,
+                              int dtype, asr_stream_t stream);
+int64_t asr_rnnt_pruned_workspace(int B, int T, int Umax, int W);
+int asr_rnnt_pruned_fwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* frame_lengths,
+                        const int32_t* target_lengths, const int32_t* s_begin, int B, int T, int Umax, int W, int V, int blank,
+                        float* workspace, int64_t workspace_floats, float* loss, asr_stream_t stream);
+int asr_rnnt_pruned_bwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* frame_lengths,
+                        const int32_t* target_lengths, const int32_t* s_begin, int B, int T, int Umax, int W, int V, int blank,
+                        const float* workspace, const float* grad_out, void* dlogits, int64_t ldd, int out_dtype, asr_stream_t stream);
+
 /* ---- transducer beam search (csrc/rnnt_beam.hip has the definition): the n best label sequences of the head with a
  * stateless predictor, ONE launch, one workgroup per utterance, no atomics: the outputs are a function of the inputs alone.
  * asr_rnnt_beam_search: e (B,T,J) = the output of the rnnt_enc GEMM, table0 / table1 (V,J) = the predictor's tables for the last label
