@@ -87,6 +87,10 @@ _SIGS = {
     "asr_rnnt_pruned_bwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P]),
     "asr_rnnt_beam_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
     "asr_rnnt_beam_search": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
+    "asr_rnnt_beam_search_lm": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P,
+                                     _P, _P, _L, _I, _I, _I, _I, _F, _F, _P, _P]),
+    "asr_rnnt_beam_search_ctx": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P,
+                                      _P, _P, _L, _I, _I, _I, _I, _F, _F, _P, _P, _L, _I, _P, _I, _F, _P, _P, _P]),
     "asr_ctc_align_workspace": (_L, [_I, _I, _I]),
     "asr_ctc_align": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
     "asr_ctc_beam_workspace": (_L, [_I, _I, _I, _I]),

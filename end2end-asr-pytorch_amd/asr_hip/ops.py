@@ -847,13 +847,20 @@ def rnnt_pruned_bwd(logits, targets, frame_lengths, target_lengths, s_begin, U, 
     return dl if pad == 64 else dl[:, :V]
 
 
-def rnnt_beam_search(e, tables, w_out, b_out, lengths, beam_width, candidates=0, max_symbols=5, nbest=1, blank=0, sos=1):
+def rnnt_beam_search(e, tables, w_out, b_out, lengths, beam_width, candidates=0, max_symbols=5, nbest=1, blank=0, sos=1, ngram=None,
+                     alpha=0.0, beta=0.0, bos=1, eos=2, context=None, gamma=0.0):
     """Transducer beam search (csrc/rnnt_beam.hip), ONE launch: e (B,T,J) = rnnt_enc's output, tables = the predictor's one or two (V,J)
     tables (tables[k]: the label k places back), w_out (V,J), all contiguous in one dtype (fp32 / bf16: what the model's forward reads),
     b_out (V) fp32, lengths (B) int32 on the device = true frames.  beam_width W <= 16, candidates K <= 16 labels tried per hypothesis
     row (0: min(V - 1, 16)), max_symbols S >= 1 labels per frame, nbest <= W -> dict(ids (B,nbest,T*S) int32 with blank behind the
     length, lengths (B,nbest) int32 (-1: no such hypothesis), scores (B,nbest) fp32 = log-probability summed over the alignments
-    found) on the device, best first.  blank defaults to PAD (0), sos to SOS (1)."""
+    found) on the device, best first.  blank defaults to PAD (0), sos to SOS (1).
+    ngram (utils.ngram.NgramLM over these V labels) and / or context (utils.context.ContextGraph over them): the fused arms, with
+    ctc_beam_search's conventions.  Candidates and the frame's beam are pruned by score + alpha * lm + beta * labels + gamma * credit, the
+    result is ordered by that with q(context, eos) added to lm (eos -1: no end term; bos opens the context; both default to SOS / EOS)
+    and with what is earned for the credit (an unfinished phrase gets nothing).  The dict then also holds lm (B,nbest) fp32 (0 without
+    ngram) and, with context, credit (B,nbest) int32; both are 0 where there is no hypothesis.  scores stays the transducer's
+    log-probability.  Both None: exactly the plain call."""
     B, T, J = e.shape
     V = w_out.shape[0]
     W, S, nbest = int(beam_width), int(max_symbols), int(nbest)
@@ -873,15 +880,32 @@ def rnnt_beam_search(e, tables, w_out, b_out, lengths, beam_width, candidates=0,
     if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous():
         raise ValueError("rnnt_beam_search: lengths must be a contiguous int32 tensor of %d elements, got %s %s"
                          % (B, tuple(lengths.shape), lengths.dtype))
+    for what, t in (("n-gram LM", ngram), ("phrase list", context)):
+        if t is not None and t.V != V:
+            raise ValueError("rnnt_beam_search: the %s has %d labels, the head %d" % (what, t.V, V))
     dev = e.device
     n = L.load().asr_rnnt_beam_workspace(B, T, V, W, K, S)
     ws = torch.empty(max(n, 4), device=dev, dtype=torch.float32)
     rows, cols = max(nbest, 1), max(T * S, 1)
     out = dict(ids=torch.empty((B, rows, cols), device=dev, dtype=torch.int32), lengths=torch.empty((B, rows), device=dev, dtype=torch.int32),
                scores=torch.empty((B, rows), device=dev, dtype=torch.float32))
-    L.call("asr_rnnt_beam_search", L.ptr(e), L.ptr(tables[0]), L.ptr(tables[1]) if len(tables) == 2 else None, L.ptr(w_out), L.ptr(b_out),
-           L.ptr(lengths), B, T, J, V, W, K, S, nbest, int(blank), int(sos), L.dt(e), L.ptr(ws), n, L.ptr(out["ids"]),
-           L.ptr(out["lengths"]), L.ptr(out["scores"]), L.stream())
+    args = (L.ptr(e), L.ptr(tables[0]), L.ptr(tables[1]) if len(tables) == 2 else None, L.ptr(w_out), L.ptr(b_out), L.ptr(lengths), B, T, J,
+            V, W, K, S, nbest, int(blank), int(sos), L.dt(e), L.ptr(ws), n, L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]))
+    if ngram is None and context is None:
+        L.call("asr_rnnt_beam_search", *args, L.stream())
+        return out
+    out["lm"] = torch.empty((B, rows), device=dev, dtype=torch.float32)
+    if context is None:
+        t = ngram.device_table(dev)
+        L.call("asr_rnnt_beam_search_lm", *args, L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"], t["max_probe"], t["order"], int(bos),
+               int(eos), float(alpha), float(beta), L.ptr(out["lm"]), L.stream())
+        return out
+    c = context.device_table(dev)
+    t = ngram.device_table(dev) if ngram is not None else dict(keys=None, vals=None, capacity=0, max_probe=0, order=0)
+    out["credit"] = torch.empty((B, rows), device=dev, dtype=torch.int32)
+    L.call("asr_rnnt_beam_search_ctx", *args, L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"], t["max_probe"], t["order"], int(bos),
+           int(eos), float(alpha), float(beta), L.ptr(c["keys"]), L.ptr(c["vals"]), c["capacity"], c["max_probe"], L.ptr(c["hold"]),
+           c["states"], float(gamma), L.ptr(out["lm"]), L.ptr(out["credit"]), L.stream())
     return out
 
 

@@ -65,6 +65,7 @@
 #include "ngram.h"           // NgramTable, ngram_query, ngram_shift
 #include "context.h"         // CtxTable, ctx_probe, ctx_finish
 #include "beam_key.h"        // beam_key, BEAM_ROOT_KEY_LO / _HI (shared with csrc/rnnt_beam.hip)
+#include "beam_bonus.h"      // beam_bonus (shared with csrc/rnnt_beam.hip)
 
 namespace {
 
@@ -105,15 +106,7 @@ struct BeamCtx {
 };
 struct BeamNoCtx {};
 
-// the fused arms' addend to tot in a slot's rank key, fp32 in this order (without an LM, lm is 0.f and alpha is not looked at)
-template <bool LM, bool CTX>
-__device__ __forceinline__ float beam_bonus(const BeamLm& fuse, float gamma, float lm, int len, int cnt) {
-  float a;
-  if constexpr (LM) a = fuse.alpha * lm + fuse.beta * (float)len;
-  else a = 0.f * lm + fuse.beta * (float)len;
-  if constexpr (CTX) a = a + gamma * (float)cnt;
-  return a;
-}
+// the fused arms' addend to tot in a slot's rank key: beam_bonus of csrc/beam_bonus.h (without an LM, lm is 0.f and alpha is not looked at)
 
 // blockDim.x = 256, or 320 when W + W C > 256: one slot per thread; the first 256 threads stage the chunks.  LM: the fused arm;
 // CTX: the phrase arm, with or without it
@@ -241,7 +234,7 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
             ecst = l_cst[cur][x];
             ecnt = l_cnt[cur][x];
           }
-          if (sx > NEG_INF) fx = sx + beam_bonus<LM, CTX>(fuse, gamma, elm, elen, ecnt);
+          if (sx > NEG_INF) fx = sx + beam_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, elm, elen, ecnt);
         }
         sc[x] = FUSED ? fx : sx;
       } else if (x < NS) {
@@ -275,7 +268,7 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
                   ecst = tr.x;
                   ecnt = l_cnt[cur][sj] + tr.y;
                 }
-                fx = sx + beam_bonus<LM, CTX>(fuse, gamma, elm, elen, ecnt);
+                fx = sx + beam_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, elm, elen, ecnt);
               }
             }
           }
@@ -354,7 +347,7 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
         const int st = l_cst[cur][tid];
         cr = l_cnt[cur][tid] - bias.tab.hold[st >= 0 && st < bias.tab.states ? st : 0];
       }
-      fk = l_tot[cur][tid] + beam_bonus<LM, CTX>(fuse, gamma, lmv, l_len[cur][tid], cr);
+      fk = l_tot[cur][tid] + beam_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, lmv, l_len[cur][tid], cr);
       if constexpr (LM) {
         if (fuse.eos >= 0) {
           const float qe = ngram_query(fuse.tab, l_ctx[cur][tid], fuse.eos);

@@ -37,11 +37,40 @@
 // workspace -- the survivor of frame t, step s with rank r owns node 1 + (t S + s) W + r -- and are matched by the 64-bit key of
 // csrc/beam_key.h.  Bookkeeping (C_s double buffered, D, the selection buffers) lives in LDS; D holds at most W (S + 1) <= 1024 entries.
 // All indices into e, the tables, w_out and the workspace are 64 bit.
+//
+// The fused arms (asr_rnnt_beam_search_lm / _ctx, template <.., LM, CTX>): a label n-gram LM and a phrase list have their say while the
+// beam is pruned.  q(h, c) is the query of csrc/ngram.h, step(s, c) -> (next, delta) and hold(s) the automaton of csrc/context.h, bonus
+// the fp32 expression of csrc/beam_bonus.h; tests/rnnt_beam_fused_reference.py restates the arms in float64.  Added to the definition:
+//   state        every entry of C_s, D and A also carries lm = the fp32 sum of q over its labels, added in label order; len; nctx = the
+//                n-gram context key (order - 1 <= 3 labels: more than the predictor's, so it is carried and not rebuilt from l1 / l2),
+//                ngram_shift(0, bos, order) for the empty sequence; cst, the automaton's state, and cnt, the credit, both 0 for it.
+//                All five are functions of the label sequence alone
+//   key          f(h) = score(h) + (double)bonus(h), bonus = alpha lm + beta (float)len, then + gamma (float)cnt; without an LM lm = 0.f
+//   label step   the K candidates of a row stay the K best non-blank entries by logit (the acoustic model proposes); candidate (r, k)
+//                gets score_r + logp, lm_r + q(nctx_r, label), len_r + 1, the shifted context and (cst, cnt_r + delta) = step(cst_r,
+//                label); C_{s+1} = the W best by f descending, then the parent's place, then the label id
+//   blank step   the entry joins D with its whole state; a sequence D already holds merges score by rnnt_lae and keeps the rest, which
+//                is equal by construction
+//   frame end    A = the W best of D by f descending, then the order of first insertion
+//   result       the entries of A ordered again by score + bonus(lm + q(nctx, eos), len, cnt - hold(cst)) (no end term for eos = -1),
+//                the place in A first among equals; scores stays the acoustic log-probability, lm is written with the end term, credit
+//                = cnt - hold(cst): an unfinished phrase earns nothing; missing entries: lm 0, credit 0.  T_b = 0: the empty sequence,
+//                score 0, lm = q(ctx(bos), eos), credit 0
+// With alpha = beta = gamma = 0 every key is the score: ids, lengths and scores are the plain arms' bits.  The lookups sit in phase 4, one
+// candidate per thread (n K <= 256), the first probes of the n-gram and of the automaton issued together; the candidate's new state
+// stays in that thread's registers until phase 5 places it.  The per-entry state (24 bytes) of D's 1024 entries, D's rank keys and C_s
+// live in dynamic LDS behind the z rows (RB_FUSE_BYTES = 33 728), so the fused arms' J limit is lower (fp32 1384, bf16 2776) and the
+// plain arms' static LDS and limit are what they were.  <.., false, false> instantiates none of this: its frame loop is the same
+// instruction stream as before.
 #include "common.h"
 #include "lse.h"             // Lse, lse_row (no multiply-add contraction from here on)
 #include "rnnt_common.h"     // rnnt_lae, clampi
 #include "topk.h"            // MaxIdx, better, wave_best
 #include "beam_key.h"        // beam_key, BEAM_ROOT_KEY_LO / _HI
+#include "beam_bonus.h"      // beam_bonus (shared with csrc/ctc_beam.hip)
+#include "ngram.h"           // NgramTable, ngram_query, ngram_shift
+#include "context.h"         // CtxTable, ctx_probe, ctx_finish
+#include <type_traits>
 
 namespace {
 
@@ -62,6 +91,22 @@ struct RbArgs {
   int32_t *ids, *lengths;
   float* scores;
 };
+
+// What the fused arms add to the plain search's arguments (the plain arms take the empty RbNoFuse).  Phrases without an LM: ng, bos, eos
+// and alpha are not looked at, lm is 0 and beta still counts.  LM without phrases: cx, gamma and credit are not looked at.
+struct RbFuse {
+  NgramTable ng;
+  CtxTable cx;
+  int bos, eos;             // eos -1: no end term
+  float alpha, beta, gamma;
+  float* lm;                // (B,nbest)
+  int32_t* credit;          // (B,nbest)
+};
+struct RbNoFuse {};
+
+// The fused arms' per-entry state (lm, len, nctx, cst, cnt: 24 bytes) lives in dynamic LDS behind the z rows: D's 1024 entries and their
+// rank keys, C_s double buffered, and the final order.  The plain arms ask for none of it.
+constexpr size_t RB_FUSE_BYTES = (size_t)RB_DMAX * (8 + 8 + 4 * 4) + 2 * RB_MAX * (8 + 4 * 4) + RB_MAX * 3 * 4;
 
 inline int rb_ldv(int V) { return (V + 3) & ~3; }                                       // rows of the logits slice start on 16 bytes
 inline int64_t rb_nodes(int T, int S, int W) { return ((int64_t)T * S * W + 2) & ~(int64_t)1; }      // 1 + T S W, rounded up to even
@@ -165,8 +210,10 @@ __device__ __forceinline__ void rb_top_scan(RbTop& t, const float* l, int V, int
   if (V4 + lane < V) take(l[V4 + lane], V4 + lane);
 }
 
-template <typename T, bool MFMA>
-__global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
+// LM: the n-gram arm, CTX: the phrase arm; <.., false, false> is the plain search and instantiates none of their code
+template <typename T, bool MFMA, bool LM, bool CTX>
+__global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::conditional_t<LM || CTX, RbFuse, RbNoFuse> fz) {
+  constexpr bool FUSED = LM || CTX;                            // entries are ranked by f = score + bonus and the result is ordered again
   constexpr int EPC = DT<T>::EPC;
   extern __shared__ __attribute__((aligned(16))) unsigned char rb_dyn[];
   T* zl = reinterpret_cast<T*>(rb_dyn);                        // z rows [16][J + EPC]
@@ -194,6 +241,30 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
   const T* w = reinterpret_cast<const T*>(a.w);
   float* lg = a.ws + (int64_t)b * a.ws_stride;
   int2* trie = reinterpret_cast<int2*>(lg + (int64_t)RB_MAX * ldv);
+  // the fused arms' state of every entry of D (x_d*), of C_s (x_c*, [2][16]) and the final order, behind the z rows.  Functions of the label
+  // sequence alone: a merge in D keeps them, and a sequence created again gets the same bits
+  uint64_t *x_dctx = nullptr, *x_cctx = nullptr;
+  double* x_df = nullptr;                                      // D's rank keys at the end of a frame
+  float *x_dlm = nullptr, *x_clm = nullptr, *x_olm = nullptr;
+  int *x_dlen = nullptr, *x_dcst = nullptr, *x_dcnt = nullptr, *x_clen = nullptr, *x_ccst = nullptr, *x_ccnt = nullptr, *x_osrc = nullptr,
+      *x_ocr = nullptr;
+  if constexpr (FUSED) {
+    unsigned char* q = rb_dyn + (size_t)RB_MAX * zld * sizeof(T);          // (a multiple of 16 bytes)
+    x_dctx = reinterpret_cast<uint64_t*>(q); q += RB_DMAX * 8;
+    x_df = reinterpret_cast<double*>(q); q += RB_DMAX * 8;
+    x_cctx = reinterpret_cast<uint64_t*>(q); q += 2 * RB_MAX * 8;
+    x_dlm = reinterpret_cast<float*>(q); q += RB_DMAX * 4;
+    x_dlen = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
+    x_dcst = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
+    x_dcnt = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
+    x_clm = reinterpret_cast<float*>(q); q += 2 * RB_MAX * 4;
+    x_clen = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
+    x_ccst = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
+    x_ccnt = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
+    x_osrc = reinterpret_cast<int*>(q); q += RB_MAX * 4;
+    x_olm = reinterpret_cast<float*>(q); q += RB_MAX * 4;
+    x_ocr = reinterpret_cast<int*>(q);
+  }
 
   if (tid < RB_MAX) {
     c_score[0][tid] = tid == 0 ? 0.0 : -(double)INFINITY;
@@ -202,6 +273,14 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
     c_node[0][tid] = tid == 0 ? 0 : -1;                        // node 0 is the empty sequence
     c_l1[0][tid] = a.sos;
     c_l2[0][tid] = a.sos;
+    if constexpr (FUSED) {                                     // the empty sequence: lm 0, len 0, context [bos], state eps, credit 0
+      x_clm[tid] = 0.f;
+      x_clen[tid] = 0;
+      x_ccst[tid] = 0;
+      x_ccnt[tid] = 0;
+      x_cctx[tid] = 0;
+      if constexpr (LM) x_cctx[tid] = ngram_shift(0, fz.bos, fz.ng.order);
+    }
   }
   if (tid == 0) d_n = 0;
   __syncthreads();
@@ -296,14 +375,46 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
             d_node[pos] = c_node[cur][lane];
             d_l1[pos] = c_l1[cur][lane];
             d_l2[pos] = c_l2[cur][lane];
+            if constexpr (FUSED) {                             // the entry joins D with its whole state
+              const int ce = cur * RB_MAX + lane;
+              x_dctx[pos] = x_cctx[ce];
+              x_dlm[pos] = x_clm[ce];
+              x_dlen[pos] = x_clen[ce];
+              x_dcst[pos] = x_ccst[ce];
+              x_dcnt[pos] = x_ccnt[ce];
+            }
           }
         }
         if (lane == 0) d_n = dn + __popcll(m);
       }
       const int nk = n * K;
+      // fused arms: what candidate tid's entry would carry, kept in registers for phase 5 (the same thread places it)
+      double e_ac = 0.0;
+      float e_lm = 0.f;
+      uint64_t e_ctx = 0;
+      int e_len = 0, e_cst = 0, e_cnt = 0;
       if (s < S && tid < nk) {
         const int r = tid / K, k = tid - r * K;
-        sc[tid] = c_score[cur][r] + (double)k_lp[r][k];
+        if constexpr (FUSED) {                                 // the step's lookups: both structures' first probes are in flight together
+          const int label = k_lab[r][k], ce = cur * RB_MAX + r;
+          CtxProbe probe;
+          if constexpr (CTX) probe = ctx_probe(fz.cx, x_ccst[ce], label);
+          if constexpr (LM) {
+            const uint64_t hctx = x_cctx[ce];
+            e_lm = x_clm[ce] + ngram_query(fz.ng, hctx, label);
+            e_ctx = ngram_shift(hctx, label, fz.ng.order);
+          }
+          e_len = x_clen[ce] + 1;
+          if constexpr (CTX) {
+            const int2 tr = ctx_finish(fz.cx, probe);
+            e_cst = tr.x;
+            e_cnt = x_ccnt[ce] + tr.y;
+          }
+          e_ac = c_score[cur][r] + (double)k_lp[r][k];
+          sc[tid] = e_ac + (double)beam_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, e_lm, e_len, e_cnt);
+        } else {
+          sc[tid] = c_score[cur][r] + (double)k_lp[r][k];
+        }
         sc_tie[tid] = (uint64_t)r << 32 | (uint32_t)k_lab[r][k];
       }
       __syncthreads();
@@ -323,12 +434,20 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
             const int node = 1 + (t * S + s) * W + rank;
             const uint2 key = beam_key(make_uint2(c_klo[cur][r], c_khi[cur][r]), label);
             trie[node] = make_int2(c_node[cur][r], label);
-            c_score[nxt][rank] = my;
+            c_score[nxt][rank] = FUSED ? e_ac : my;            // (fused: my is the rank key f, the entry keeps the acoustic score)
             c_klo[nxt][rank] = key.x;
             c_khi[nxt][rank] = key.y;
             c_node[nxt][rank] = node;
             c_l1[nxt][rank] = label;
             c_l2[nxt][rank] = c_l1[cur][r];
+            if constexpr (FUSED) {
+              const int ne = nxt * RB_MAX + rank;
+              x_cctx[ne] = e_ctx;
+              x_clm[ne] = e_lm;
+              x_clen[ne] = e_len;
+              x_ccst[ne] = e_cst;
+              x_ccnt[ne] = e_cnt;
+            }
           }
         }
         n = nk < W ? nk : W;
@@ -338,20 +457,35 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
     }
     // ---- A = the W best of D, the next frame's C_0
     const int dn = d_n, nxt = cur ^ 1;
+    const double* d_rank = d_score;                            // what D is ranked by: the score, or f in the fused arms
+    if constexpr (FUSED) {
+      for (int i = tid; i < dn; i += RB_THREADS)
+        x_df[i] = d_score[i] + (double)beam_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, x_dlm[i], x_dlen[i], x_dcnt[i]);
+      d_rank = x_df;
+      __syncthreads();
+    }
     for (int i = tid; i < dn; i += RB_THREADS) {
-      const double my = d_score[i];
+      const double my = d_rank[i];
       int rank = 0;
       for (int y = 0; y < dn; ++y) {
-        const double o = d_score[y];
+        const double o = d_rank[y];
         rank += o > my || (o == my && y < i);
       }
       if (rank < W) {
-        c_score[nxt][rank] = my;
+        c_score[nxt][rank] = d_score[i];
         c_klo[nxt][rank] = d_klo[i];
         c_khi[nxt][rank] = d_khi[i];
         c_node[nxt][rank] = d_node[i];
         c_l1[nxt][rank] = d_l1[i];
         c_l2[nxt][rank] = d_l2[i];
+        if constexpr (FUSED) {
+          const int ne = nxt * RB_MAX + rank;
+          x_cctx[ne] = x_dctx[i];
+          x_clm[ne] = x_dlm[i];
+          x_clen[ne] = x_dlen[i];
+          x_ccst[ne] = x_dcst[i];
+          x_ccnt[ne] = x_dcnt[i];
+        }
       }
     }
     n = dn < W ? dn : W;
@@ -360,12 +494,44 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
     if (tid == 0) d_n = 0;                                     // (read next behind three barriers)
   }
   // ---- the n-best: one lane per hypothesis walks its parent chain (a parent is an older node: the chain ends at node 0)
+  if constexpr (FUSED) {    // the final order: score + bonus(lm + q(nctx, eos), len, earned), the place in A first among equals; earned =
+    const bool live = tid < n;                                 // cnt - hold(cst): an unfinished phrase earns nothing
+    double fk = -(double)INFINITY;
+    float lmv = 0.f;
+    int cr = 0;
+    if (live) {
+      const int ce = cur * RB_MAX + tid;
+      if constexpr (LM) {
+        lmv = x_clm[ce];
+        if (fz.eos >= 0) lmv = lmv + ngram_query(fz.ng, x_cctx[ce], fz.eos);
+      }
+      if constexpr (CTX) {
+        const int st = x_ccst[ce];
+        cr = x_ccnt[ce] - fz.cx.hold[st >= 0 && st < fz.cx.states ? st : 0];
+      }
+      fk = c_score[cur][tid] + (double)beam_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, lmv, x_clen[ce], cr);
+    }
+    if (tid < RB_MAX) { sc[tid] = fk; x_osrc[tid] = -1; }
+    __syncthreads();
+    if (live) {
+      int rank = 0;
+      for (int i = 0; i < n; ++i) {
+        const double v = sc[i];
+        rank += v > fk || (v == fk && i < tid);
+      }
+      x_osrc[rank] = tid;
+      x_olm[rank] = lmv;
+      x_ocr[rank] = cr;
+    }
+    __syncthreads();
+  }
   const int L = T_ * S;
   int32_t* ids_b = a.ids + (int64_t)b * a.nbest * L;
   if (tid < a.nbest) {
-    int len = -1;
-    if (tid < n) {
-      const int node = c_node[cur][tid];
+    int len = -1, src = tid < n ? tid : -1;                    // the place in A of hypothesis tid (-1: none)
+    if constexpr (FUSED) src = tid < n ? x_osrc[tid] : -1;
+    if (src >= 0) {
+      const int node = c_node[cur][src];
       len = 0;
       for (int nd = node; nd > 0 && len < L; nd = trie[nd].x) ++len;
       int p = len;
@@ -377,7 +543,9 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a) {
     }
     o_len[tid] = len < 0 ? 0 : len;
     a.lengths[(int64_t)b * a.nbest + tid] = len;
-    a.scores[(int64_t)b * a.nbest + tid] = tid < n ? (float)c_score[cur][tid] : -INFINITY;
+    a.scores[(int64_t)b * a.nbest + tid] = src >= 0 ? (float)c_score[cur][src] : -INFINITY;
+    if constexpr (FUSED) fz.lm[(int64_t)b * a.nbest + tid] = src >= 0 ? x_olm[tid] : 0.f;
+    if constexpr (CTX) fz.credit[(int64_t)b * a.nbest + tid] = src >= 0 ? x_ocr[tid] : 0;
   }
   __syncthreads();
   for (int y = tid; y < a.nbest * L; y += RB_THREADS) {
@@ -393,10 +561,14 @@ extern "C" int64_t asr_rnnt_beam_workspace(int B, int T, int V, int W, int K, in
   return (int64_t)B * rb_stride(T, V, W, S);
 }
 
-extern "C" int asr_rnnt_beam_search(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out,
-                                    const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank,
-                                    int sos, int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
-                                    float* scores, hipStream_t s) {
+namespace {
+
+// every entry: the plain search's checks, then the arm for the dtype and J
+template <bool LM, bool CTX>
+int rb_search(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out, const int32_t* frame_lengths,
+              int B, int T, int J, int V, int W, int K, int S, int nbest, int blank, int sos, int dtype, float* workspace,
+              int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+              std::conditional_t<LM || CTX, RbFuse, RbNoFuse> fz, hipStream_t s) {
   ASR_CHECK_ARG(e && table0 && w_out && b_out && frame_lengths && workspace && ids && lengths && scores);
   ASR_CHECK_ARG(B > 0 && T > 0 && J > 0 && V > 0 && W >= 1 && K >= 1 && nbest >= 1);
   ASR_CHECK_ARG(dtype == ASR_F32 || dtype == ASR_BF16);
@@ -408,13 +580,68 @@ extern "C" int asr_rnnt_beam_search(const void* e, const void* table0, const voi
   if (J % 8 != 0 || !aligned16(e) || !aligned16(table0) || !aligned16(table1) || !aligned16(w_out) || !aligned16(workspace))
     return ASR_EUNSUPPORTED;                                   // whole 16-byte chunks in both dtypes
   ASR_CHECK_ARG(workspace_floats >= asr_rnnt_beam_workspace(B, T, V, W, K, S));
-  const size_t lds = (size_t)RB_MAX * (J + (dtype == ASR_BF16 ? 8 : 4)) * (dtype == ASR_BF16 ? 2 : 4);
+  // the fused arms' state sits behind the z rows: their J limit is lower by RB_FUSE_BYTES of rows (fp32 J <= 1384, bf16 J <= 2776)
+  const size_t lds = (size_t)RB_MAX * (J + (dtype == ASR_BF16 ? 8 : 4)) * (dtype == ASR_BF16 ? 2 : 4) + (LM || CTX ? RB_FUSE_BYTES : 0);
   if (lds > RB_LDS_DYN_MAX) return ASR_EUNSUPPORTED;
   const RbArgs a{e, table0, table1, w_out, b_out, frame_lengths, T, J, V, W, K, S, nbest, blank, sos, rb_ldv(V), workspace,
                  rb_stride(T, V, W, S), ids, lengths, scores};
   AsrProfScope prof(ASR_OP_SEARCH, s);
   if (dtype == ASR_BF16 && J % 32 == 0 && J <= 32 * RB_NK_MAX)
-    return asr_launch<rnnt_beam_kernel<bf16_t, true>>(dim3(B), dim3(RB_THREADS), lds, s, a);
-  if (dtype == ASR_BF16) return asr_launch<rnnt_beam_kernel<bf16_t, false>>(dim3(B), dim3(RB_THREADS), lds, s, a);
-  return asr_launch<rnnt_beam_kernel<float, false>>(dim3(B), dim3(RB_THREADS), lds, s, a);
+    return asr_launch<rnnt_beam_kernel<bf16_t, true, LM, CTX>>(dim3(B), dim3(RB_THREADS), lds, s, a, fz);
+  if (dtype == ASR_BF16) return asr_launch<rnnt_beam_kernel<bf16_t, false, LM, CTX>>(dim3(B), dim3(RB_THREADS), lds, s, a, fz);
+  return asr_launch<rnnt_beam_kernel<float, false, LM, CTX>>(dim3(B), dim3(RB_THREADS), lds, s, a, fz);
+}
+
+}  // namespace
+
+extern "C" int asr_rnnt_beam_search(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out,
+                                    const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank,
+                                    int sos, int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
+                                    float* scores, hipStream_t s) {
+  return rb_search<false, false>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
+                                 workspace_floats, ids, lengths, scores, RbNoFuse{}, s);
+}
+
+// The n-gram arm: the table must hold a unigram for every label 0..V-1 (utils/ngram.py's estimator does), so that every q is finite.
+extern "C" int asr_rnnt_beam_search_lm(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out,
+                                       const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank,
+                                       int sos, int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
+                                       float* scores, const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order,
+                                       int bos, int eos, float alpha, float beta, float* lm, hipStream_t s) {
+  const int rc = ngram_check_table(keys, vals, capacity, max_probe, order);
+  if (rc != ASR_OK) return rc;
+  ASR_CHECK_ARG(lm && bos >= 0 && bos < V && eos >= -1 && eos < V);
+  if (V > NGRAM_MAX_ID + 1) return ASR_EUNSUPPORTED;          // ids + 1 in 16-bit key fields
+  const RbFuse fz{NgramTable{keys, reinterpret_cast<const float2*>(vals), (uint32_t)(capacity - 1), max_probe, order},
+                  CtxTable{nullptr, nullptr, nullptr, 0, 1, 1}, bos, eos, alpha, beta, 0.f, lm, nullptr};
+  return rb_search<true, false>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
+                                workspace_floats, ids, lengths, scores, fz, s);
+}
+
+// The phrase arms: the table of utils/context.py (ContextGraph.device_table).  ng_keys == NULL: no LM -- alpha, bos and eos are not looked
+// at, lm is 0 for every hypothesis and the length bonus beta still counts.
+extern "C" int asr_rnnt_beam_search_ctx(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out,
+                                        const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank,
+                                        int sos, int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
+                                        float* scores, const uint64_t* ng_keys, const float* ng_vals, int64_t ng_capacity,
+                                        int ng_max_probe, int ng_order, int bos, int eos, float alpha, float beta,
+                                        const uint64_t* cx_keys, const int32_t* cx_vals, int64_t cx_capacity, int cx_max_probe,
+                                        const int32_t* cx_hold, int cx_states, float gamma, float* lm, int32_t* credit, hipStream_t s) {
+  int rc = ctx_check_table(cx_keys, cx_vals, cx_capacity, cx_max_probe, cx_hold, cx_states);
+  if (rc != ASR_OK) return rc;
+  ASR_CHECK_ARG(lm && credit);
+  if (V > CTX_MAX_ID + 1) return ASR_EUNSUPPORTED;            // labels + 1 in a 16-bit key field
+  const CtxTable cx{cx_keys, reinterpret_cast<const int2*>(cx_vals), cx_hold, (uint32_t)(cx_capacity - 1), cx_max_probe, cx_states};
+  if (!ng_keys) {
+    const RbFuse fz{NgramTable{nullptr, nullptr, 0, 1, 1}, cx, 0, -1, 0.f, beta, gamma, lm, credit};
+    return rb_search<false, true>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
+                                  workspace_floats, ids, lengths, scores, fz, s);
+  }
+  rc = ngram_check_table(ng_keys, ng_vals, ng_capacity, ng_max_probe, ng_order);
+  if (rc != ASR_OK) return rc;
+  ASR_CHECK_ARG(bos >= 0 && bos < V && eos >= -1 && eos < V);
+  const RbFuse fz{NgramTable{ng_keys, reinterpret_cast<const float2*>(ng_vals), (uint32_t)(ng_capacity - 1), ng_max_probe, ng_order}, cx,
+                  bos, eos, alpha, beta, gamma, lm, credit};
+  return rb_search<true, true>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
+                               workspace_floats, ids, lengths, scores, fz, s);
 }

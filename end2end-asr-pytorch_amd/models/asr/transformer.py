@@ -474,7 +474,8 @@ class Transformer(nn.Module):
 
     @torch.no_grad()
     def transducer_beam_search(self, enc_out, lengths, beam_width, nbest=1, candidates=0, max_symbols=5, lm=None, lm_weight=0.1,
-                               c_weight=1, return_ids=False):
+                               c_weight=1, return_ids=False, ngram=None, ngram_weight=0.0, length_bonus=0.0, context=None,
+                               context_score=0.0):
         """Beam search over the transducer head (csrc/rnnt_beam.hip): ONE rnnt_enc launch, ONE search launch (one
         workgroup per utterance walks its frames: the joint, the vocabulary projection, the log-softmax rows, the candidates and the
         beam bookkeeping of every step are inside it) and one device-to-host copy.  lengths: true encoder frames per utterance
@@ -483,8 +484,20 @@ class Transformer(nn.Module):
         with score = log-probability summed over the alignments found, are ranked like a decoder beam's and like ctc_beam_search's
         (asr_hip.search.rank_ended): score + sqrt(words) * c_weight, or with lm (utils.lstm_utils.LM) score + lm_weight * (lm - 2 * oov) +
         sqrt(words) * c_weight, all utterances' hypotheses in ONE batched LM call.  -> per utterance the min(nbest, found) best strings,
-        best first (return_ids: (strings, label ids), same nesting); the ids are labels as they stand: no SOS, no EOS."""
+        best first (return_ids: (strings, label ids), same nesting); the ids are labels as they stand: no SOS, no EOS.
+        ngram (utils.ngram.NgramLM over this model's labels) and / or context (utils.context.ContextGraph over them): first-pass fusion,
+        as in ctc_beam_search and still ONE search launch.  The kernel prunes its candidates and every frame's beam by the transducer
+        score + ngram_weight * the n-gram's log-probability of the labels + length_bonus * their number + context_score * the phrase
+        credit (contexts open with SOS, the final order counts EOS and only earned credit), so a rare name survives the beam; the tables
+        go to the device once.  Every hypothesis then carries 'rnnt_score', 'ngram_score' (with the EOS term; 0 without ngram) and, with
+        context, 'context_credit', and score = rnnt_score + ngram_weight * ngram_score + length_bonus * labels + context_score *
+        context_credit goes into the ranking above.  Both None: the plain search, unchanged."""
         self._need_transducer()
+        a, beta, gamma = float(ngram_weight), float(length_bonus), float(context_score)
+        if ngram is not None:
+            ngram.check_labels(self.id2label)
+        if context is not None:
+            context.check_labels(self.id2label)
         W, S, K = int(beam_width), int(max_symbols), int(candidates)
         if not 1 <= W <= 16:
             raise ValueError("transducer_beam_search keeps beam_width hypotheses in the kernel's beam: 1..16, got %d" % W)
@@ -498,14 +511,28 @@ class Transformer(nn.Module):
         e = F_.linear(enc_out, self.rnnt_enc.weight, self.rnnt_enc.bias, False, True)
         cd = e.dtype
         tables = [P.linear_weight(m.weight, cd) for m in self.rnnt_embed]       # what _rnnt_predict's rows round to; fp32: the masters
+        fused = ngram is not None or context is not None
+        kw = dict(ngram=ngram, alpha=a, beta=beta, bos=constant.SOS_TOKEN, eos=constant.EOS_TOKEN, context=context, gamma=gamma) if fused else {}
         out = ops.rnnt_beam_search(e.contiguous(), tables, P.linear_weight(self.rnnt_out.weight, cd), self.rnnt_out.bias.data,
-                                   _lengths_to_device(lengths, e.device), W, K, S, W, constant.PAD_TOKEN, constant.SOS_TOKEN)
+                                   _lengths_to_device(lengths, e.device), W, K, S, W, constant.PAD_TOKEN, constant.SOS_TOKEN, **kw)
         L = T * S
-        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1), out["scores"].view(torch.int32).reshape(-1)]).cpu()
-        ids, lens, scores = torch.split(flat, [B * W * L, B * W, B * W])
+        parts = [out["scores"].view(torch.int32)] + ([out["lm"].view(torch.int32)] if fused else []) + (
+            [out["credit"]] if context is not None else [])
+        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1)] + [p.reshape(-1) for p in parts]).cpu()
+        ids, lens, scores, *extra = torch.split(flat, [B * W * L, B * W] + [B * W] * len(parts))
         ids, lens, scores = ids.view(B, W, L).tolist(), lens.view(B, W).tolist(), scores.view(torch.float32).view(B, W).tolist()
         ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n], 'rnnt_score': scores[b][n]} for n in range(W) if lens[b][n] >= 0]
                  for b in range(B)]
+        if fused:
+            lm_scores = extra[0].view(torch.float32).view(B, W).tolist()
+            credits = extra[1].view(B, W).tolist() if context is not None else None
+            for b, hs in enumerate(ended):
+                for h, n in zip(hs, [n for n in range(W) if lens[b][n] >= 0]):
+                    h['ngram_score'] = lm_scores[b][n]
+                    h['score'] = h['rnnt_score'] + a * h['ngram_score'] + beta * len(h['yseq'])
+                    if context is not None:
+                        h['context_credit'] = credits[b][n]
+                        h['score'] += gamma * h['context_credit']
         hyp_ids = [[h['yseq'] for h in hs] for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight)]
         strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
         return (strs, hyp_ids) if return_ids else strs
@@ -707,7 +734,9 @@ class Transformer(nn.Module):
                  lm_rescoring=False, lm_weight=0.1, c_weight=1, verbose=False, ctc_logits=None, ctc_lengths=None, ctc_weight=0.0,
                  ctc_candidates=0, ctc_greedy=False, align_source=None, target_lengths=None, ctc_beam=False,
                  attention_rescoring_weight=0.0, ngram=None, ngram_weight=0.0, length_bonus=0.0, context=None, context_score=0.0,
-                 transducer_greedy=False, transducer_max_symbols=5, transducer_beam=False, transducer_candidates=0):
+                 transducer_greedy=False, transducer_max_symbols=5, transducer_beam=False, transducer_candidates=0,
+                 transducer_ngram=None, transducer_ngram_weight=0.0, transducer_length_bonus=0.0, transducer_context=None,
+                 transducer_context_score=0.0):
         """-> (_, strs_hyps, strs_gold)   (reference: transformer.py:87-124).  ctc_weight > 0 (beam search only): joint CTC / attention
         scoring with the encoder CTC head (ctc_logits / ctc_lengths default to the head's logits and the true encoder frames);
         ctc_greedy: best-path decoding from the head alone; ctc_beam: prefix beam search over the head's posteriors alone
@@ -721,7 +750,15 @@ class Transformer(nn.Module):
         re-tokenised string).  transducer_greedy: time-synchronous greedy search of the transducer head (transducer_greedy, at most
         transducer_max_symbols labels per frame), not together with any other decoding mode or with align_source.  transducer_beam: beam
         search over the transducer head (transducer_beam_search: beam_width hypotheses, transducer_candidates labels per hypothesis and
-        step, transducer_max_symbols per frame, the beam_nbest best re-ranked with lm when lm_rescoring), under the same exclusions."""
+        step, transducer_max_symbols per frame, the beam_nbest best re-ranked with lm when lm_rescoring), under the same exclusions.
+        transducer_ngram / transducer_ngram_weight / transducer_length_bonus and transducer_context / transducer_context_score
+        (transducer_beam only; an error before any launch otherwise): the n-gram LM and the phrase list fused into THAT search's pruning
+        (transducer_beam_search's ngram / ngram_weight / length_bonus / context / context_score); ngram and context stay ctc_beam's."""
+        if transducer_ngram is not None and not transducer_beam:
+            raise ValueError("--transducer-ngram-path needs --transducer-beam-search: the n-gram LM is fused into the transducer beam search")
+        if transducer_context is not None and not transducer_beam:
+            raise ValueError("--transducer-context-path needs --transducer-beam-search: the phrase list biases the transducer beam "
+                             "search's pruning")
         if transducer_beam:
             if transducer_greedy or beam_search or ctc_greedy or ctc_beam or ctc_weight > 0 or attention_rescoring_weight > 0 \
                     or align_source is not None or ngram is not None or context is not None:
@@ -736,6 +773,10 @@ class Transformer(nn.Module):
                                  % int(beam_width))
             if lm_rescoring and lm is None:
                 raise ValueError("lm_rescoring=True needs lm (utils.lstm_utils.LM)")
+            if transducer_ngram is not None:
+                transducer_ngram.check_labels(self.id2label)
+            if transducer_context is not None:
+                transducer_context.check_labels(self.id2label)
         if transducer_greedy:
             if beam_search or ctc_greedy or ctc_beam or ctc_weight > 0 or attention_rescoring_weight > 0 or align_source is not None \
                     or ngram is not None or context is not None:
@@ -783,7 +824,9 @@ class Transformer(nn.Module):
             nbest_strs = self.transducer_beam_search(enc_out, self.ctc_frame_lengths(input_lengths, enc_out.shape[1]), beam_width,
                                                      nbest=max(1, int(beam_nbest)), candidates=transducer_candidates,
                                                      max_symbols=int(transducer_max_symbols), lm=lm if lm_rescoring else None,
-                                                     lm_weight=lm_weight, c_weight=c_weight)
+                                                     lm_weight=lm_weight, c_weight=c_weight, ngram=transducer_ngram,
+                                                     ngram_weight=transducer_ngram_weight, length_bonus=transducer_length_bonus,
+                                                     context=transducer_context, context_score=transducer_context_score)
             strs_hyps = [rows[0] if rows else "" for rows in nbest_strs]
         elif transducer_greedy:
             strs_hyps = self.transducer_greedy(enc_out, self.ctc_frame_lengths(input_lengths, enc_out.shape[1]),

@@ -2,7 +2,8 @@
 every test utterance (greedy, beam search with --beam-search, from the transducer head alone with --transducer-greedy /
 --transducer-beam-search, or from the encoder
 CTC head alone with --ctc-greedy / --ctc-beam-search,
-the latter's n-best rescored by the decoder with --attention-rescoring-weight, its pruning guided by a label n-gram LM with --ngram-path and biased towards the phrases of --context-path)
+the latter's n-best rescored by the decoder with --attention-rescoring-weight, its pruning guided by a label n-gram LM with --ngram-path and biased towards the phrases of --context-path;
+--transducer-ngram-path and --transducer-context-path do the same for --transducer-beam-search)
 and reports CER / WER.  --align-out PATH also writes label and word
 timestamps from the encoder CTC head (forced alignment of the transcript, or of the hypothesis with --align-source hyp)."""
 import torch
@@ -12,14 +13,20 @@ from utils import constant
 from utils.metrics import calculate_cer, calculate_cer_en_zh, calculate_wer
 
 
-def evaluate(model, test_loader, lm=None, noise_dir=None, ngram=None, context=None):
+def evaluate(model, test_loader, lm=None, noise_dir=None, ngram=None, context=None, transducer_ngram=None, transducer_context=None):
     """reference: test.py:19-62.  noise_dir: the checkpoint's --noise-dir (the reference injects noise into the test set too); ngram: the
-    NgramLM of --ngram-path, context: the ContextGraph of --context-path (None: the plain search, no table and no further launch)."""
+    NgramLM of --ngram-path, context: the ContextGraph of --context-path (None: the plain search, no table and no further launch);
+    transducer_ngram / transducer_context: those of --transducer-ngram-path / --transducer-context-path, for --transducer-beam-search."""
     args = constant.args
     fusion = {} if ngram is None else dict(ngram=ngram, ngram_weight=getattr(args, "ngram_weight", 0.3),
                                            length_bonus=getattr(args, "ngram_length_bonus", 0.0))
     if context is not None:
         fusion.update(context=context, context_score=getattr(args, "context_score", 3.0))
+    if transducer_ngram is not None:
+        fusion.update(transducer_ngram=transducer_ngram, transducer_ngram_weight=getattr(args, "transducer_ngram_weight", 0.3),
+                      transducer_length_bonus=getattr(args, "transducer_ngram_length_bonus", 0.0))
+    if transducer_context is not None:
+        fusion.update(transducer_context=transducer_context, transducer_context_score=getattr(args, "transducer_context_score", 3.0))
     model.eval()
     total_word = total_char = total_cer = total_wer = 0
     total_en_cer = total_zh_cer = total_en_char = total_zh_char = 0
@@ -127,8 +134,14 @@ def check_transducer_decoding(args, model):
     from that head alone (no --beam-search, --ctc-greedy, --ctc-beam-search, --ctc-decode-weight, --attention-rescoring-weight,
     --ngram-path, --context-path or --align-out, and not each other) and emit 1 <= --transducer-max-symbols labels per frame at the most.
     --transducer-beam-search keeps --beam-width in 1..16 hypotheses and tries --transducer-candidates in 0..16 labels (0: min(V - 1, 16)).
-    Without either flag nothing is checked.  All of it before any launch."""
+    --transducer-ngram-path and --transducer-context-path need --transducer-beam-search (--transducer-greedy does not take them).
+    Without any of these flags nothing is checked.  All of it before any launch."""
     greedy, beam = getattr(args, "transducer_greedy", False), getattr(args, "transducer_beam_search", False)
+    if getattr(args, "transducer_ngram_path", None) and not beam:
+        raise ValueError("--transducer-ngram-path needs --transducer-beam-search: the n-gram LM is fused into the transducer beam search")
+    if getattr(args, "transducer_context_path", None) and not beam:
+        raise ValueError("--transducer-context-path needs --transducer-beam-search: the phrase list biases the transducer beam search's "
+                         "pruning")
     if not greedy and not beam:
         return
     name = "--transducer-beam-search" if beam else "--transducer-greedy"
@@ -198,5 +211,12 @@ if __name__ == '__main__':
     if getattr(args, "context_path", None):   # --ctc-beam-search only (check_ctc_decoding); a character that is no label is refused here
         from utils.context import ContextGraph
         context = ContextGraph.from_file(args.context_path, label2id)
+    fused = {}
+    if getattr(args, "transducer_ngram_path", None):      # --transducer-beam-search only (check_transducer_decoding)
+        from utils.ngram import NgramLM
+        fused["transducer_ngram"] = NgramLM.load(args.transducer_ngram_path, id2label)
+    if getattr(args, "transducer_context_path", None):
+        from utils.context import ContextGraph
+        fused["transducer_context"] = ContextGraph.from_file(args.transducer_context_path, label2id)
     print(model)
-    evaluate(model, test_loader, lm=lm, noise_dir=getattr(loaded_args, "noise_dir", None), ngram=ngram, context=context)
+    evaluate(model, test_loader, lm=lm, noise_dir=getattr(loaded_args, "noise_dir", None), ngram=ngram, context=context, **fused)

@@ -36,7 +36,9 @@ Differences that do not change old command lines:
     output, L = (1 - r) L_existing + r L_rnnt (csrc/rnnt.hip, DESIGN.md section 7); `--transducer-greedy` (+ `--transducer-max-symbols`;
     test.py): time-synchronous greedy decoding from that head alone; `--transducer-beam-search` (+ `--beam-width`, `--beam-nbest`,
     `--transducer-candidates`, `--transducer-max-symbols`, `--lm-rescoring`; test.py): beam search over that head, one fused search
-    kernel per utterance (csrc/rnnt_beam.hip, DESIGN.md section 7);
+    kernel per utterance (csrc/rnnt_beam.hip); `--transducer-ngram-path FILE` (+ `--transducer-ngram-weight`,
+    `--transducer-ngram-length-bonus`) and `--transducer-context-path FILE` (+ `--transducer-context-score`; test.py
+    --transducer-beam-search): the n-gram LM and the phrase list fused into that search's pruning;
   * `--transducer-prune-range S` (+ `--transducer-simple-scale c`; train.py with --transducer-weight > 0): pruned transducer training, the
     joint and the loss on a band of S label positions per frame chosen by a simple joiner am + lm, L_rnnt = L_pruned + c L_simple
     (csrc/rnnt_pruned.hip).
@@ -179,6 +181,12 @@ _FLAGS = [
     # labels; every label that advances a listed phrase adds --context-score to a prefix' pruning key, a phrase that breaks off gives it
     # back; combines with --ngram-path, --attention-rescoring-weight and --lm-rescoring; without the path nothing changes
     (("--context-path",), dict(type=_S, default=None)), (("--context-score",), dict(default=3.0, type=_F)),
+    # --transducer-ngram-path / --transducer-context-path FILE (test.py --transducer-beam-search): the same two
+    # structures fused into the transducer beam search's pruning, with weights of their own (a transducer's blank-heavy posteriors want
+    # other values than CTC's; the defaults are the CTC flags' and are not tuned); without the paths nothing changes
+    (("--transducer-ngram-path",), dict(type=_S, default=None)), (("--transducer-ngram-weight",), dict(default=0.3, type=_F)),
+    (("--transducer-ngram-length-bonus",), dict(default=0.0, type=_F)),
+    (("--transducer-context-path",), dict(type=_S, default=None)), (("--transducer-context-score",), dict(default=3.0, type=_F)),
     # CTC forced alignment (test.py): --align-out PATH writes one JSON line per test utterance with label and word
     # timestamps from the CTC head; --align-source gold aligns the transcript, hyp the label ids the decoder produced
     (("--align-out",), dict(default=None, type=_S)), (("--align-source",), dict(default="gold", choices=["gold", "hyp"])),

@@ -36,7 +36,7 @@ enum { ASR_GEMM_RELU = 1, ASR_GEMM_ACCUMULATE = 2 };
 enum {
   ASR_OP_GEMM = 0, ASR_OP_CONV_IGEMM = 1, ASR_OP_CONV_WGRAD = 2, ASR_OP_ATTN_FWD = 3, ASR_OP_ATTN_BWD = 4,
   ASR_OP_ADD_LN = 5, ASR_OP_CE = 6, ASR_OP_ADAM = 7, ASR_OP_CONV1 = 8, ASR_OP_POOL = 9, ASR_OP_LAYOUT = 10,
-  ASR_OP_SEARCH = 11,      /* asr_rnnt_beam_search */
+  ASR_OP_SEARCH = 11,      /* asr_rnnt_beam_search[_lm|_ctx] */
   ASR_OP_COUNT = 16
 };
 
@@ -341,6 +341,33 @@ int asr_rnnt_beam_search(const void* e, const void* table0, const void* table1, 
                          const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank, int sos,
                          int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
                          asr_stream_t stream);
+/* The fused arms of the same kernel: an n-gram LM and phrase biasing have their say WHILE the beam is pruned.  The
+ * arguments before `scores` are asr_rnnt_beam_search's; the tables and their conventions are those of asr_ctc_beam_search_lm / _ctx
+ * (NgramLM.device_table, ContextGraph.device_table; the n-gram table holds a unigram for every label 0..V-1).  Every entry of the search
+ * also carries lm (the fp32 sum of q over its labels), len, the n-gram context (order - 1 labels, opened by `bos`), the automaton's
+ * state and its credit: functions of the label sequence alone, so two alignments of a sequence still merge by logaddexp on the score.
+ * Candidates and D are ranked by f = score + (double)(alpha lm + beta len [+ gamma credit]) (fp32 in this order, csrc/beam_bonus.h);
+ * the K candidates of a row stay the K best by logit.  The result is ordered again by score + bonus(lm + q(context, eos), len, earned),
+ * earned = credit - hold(state) (an unfinished phrase earns nothing), the place in the beam first among equals; eos -1: no end term.
+ * scores stays the acoustic log-probability; lm (B,nbest) fp32 = the LM sum with the end term (0 without a table), credit (B,nbest) int32
+ * = earned; missing entries: lm 0, credit 0.  T_b == 0: the empty sequence, score 0, lm = q([bos], eos), credit 0.
+ * asr_rnnt_beam_search_ctx with ng_keys NULL: phrases only -- alpha, bos and eos are not looked at and beta still counts.
+ * With alpha = beta = gamma = 0 ids, lengths and scores are asr_rnnt_beam_search's bits.  Refused as asr_rnnt_beam_search refuses, and:
+ * ASR_EINVAL for a table asr_ctc_beam_search_lm / _ctx would refuse, bos outside [0,V), eos outside [-1,V), a null lm / credit;
+ * ASR_EUNSUPPORTED for V > 65535, and for 16 z rows beyond 120 KB - 33 728 bytes of LDS (the entries' extra state sits behind the z
+ * rows: fp32 J <= 1384, bf16 J <= 2776). */
+int asr_rnnt_beam_search_lm(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out,
+                            const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank, int sos,
+                            int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+                            const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order, int bos, int eos,
+                            float alpha, float beta, float* lm, asr_stream_t stream);
+int asr_rnnt_beam_search_ctx(const void* e, const void* table0, const void* table1, const void* w_out, const float* b_out,
+                             const int32_t* frame_lengths, int B, int T, int J, int V, int W, int K, int S, int nbest, int blank, int sos,
+                             int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths, float* scores,
+                             const uint64_t* ng_keys, const float* ng_vals, int64_t ng_capacity, int ng_max_probe, int ng_order, int bos,
+                             int eos, float alpha, float beta, const uint64_t* cx_keys, const int32_t* cx_vals, int64_t cx_capacity,
+                             int cx_max_probe, const int32_t* cx_hold, int cx_states, float gamma, float* lm, int32_t* credit,
+                             asr_stream_t stream);
 
 /* ---- CTC prefix scorer for joint CTC / attention beam search (csrc/ctc_prefix.hip has the recursion; blank = `blank`).
  * asr_ctc_prefix_init: logits (B,T,ld) fp32 = the encoder's CTC logits, frames (B) int32 = true frames T_b per utterance, row_utt (R)
