@@ -894,19 +894,28 @@ def rnnt_beam_search(e, tables, w_out, b_out, lengths, beam_width, candidates=0,
     if ngram is None and context is None:
         L.call("asr_rnnt_beam_search", *args, L.stream())
         return out
-    out["lm"] = torch.empty((B, rows), device=dev, dtype=torch.float32)
+    ng, cx = _beam_fuse_args(out, ngram, context, bos, eos, alpha, beta, gamma)
     if context is None:
-        t = ngram.device_table(dev)
-        L.call("asr_rnnt_beam_search_lm", *args, L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"], t["max_probe"], t["order"], int(bos),
-               int(eos), float(alpha), float(beta), L.ptr(out["lm"]), L.stream())
-        return out
-    c = context.device_table(dev)
-    t = ngram.device_table(dev) if ngram is not None else dict(keys=None, vals=None, capacity=0, max_probe=0, order=0)
-    out["credit"] = torch.empty((B, rows), device=dev, dtype=torch.int32)
-    L.call("asr_rnnt_beam_search_ctx", *args, L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"], t["max_probe"], t["order"], int(bos),
-           int(eos), float(alpha), float(beta), L.ptr(c["keys"]), L.ptr(c["vals"]), c["capacity"], c["max_probe"], L.ptr(c["hold"]),
-           c["states"], float(gamma), L.ptr(out["lm"]), L.ptr(out["credit"]), L.stream())
+        L.call("asr_rnnt_beam_search_lm", *args, *ng, L.ptr(out["lm"]), L.stream())
+    else:
+        L.call("asr_rnnt_beam_search_ctx", *args, *ng, *cx, L.ptr(out["lm"]), L.ptr(out["credit"]), L.stream())
     return out
+
+
+def _beam_fuse_args(out, ngram, context, bos, eos, alpha, beta, gamma):
+    """What the fused entries of both beam searches take beside the plain entry's arguments -> (the n-gram arguments: keys, vals,
+    capacity, max_probe, order, bos, eos, alpha, beta -- the empty table without ngram --, the phrase arguments: keys, vals, capacity,
+    max_probe, hold, states, gamma -- None without context).  out, the plain search's outputs, gets lm and, with context, credit, of
+    the shape of its scores; each entry takes them at its own place.  The tables go to the device once per object."""
+    dev = out["scores"].device
+    t = ngram.device_table(dev) if ngram is not None else dict(keys=None, vals=None, capacity=0, max_probe=0, order=0)
+    ng = (L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"], t["max_probe"], t["order"], int(bos), int(eos), float(alpha), float(beta))
+    out["lm"] = torch.empty_like(out["scores"])
+    if context is None:
+        return ng, None
+    c = context.device_table(dev)
+    out["credit"] = torch.empty_like(out["lengths"])
+    return ng, (L.ptr(c["keys"]), L.ptr(c["vals"]), c["capacity"], c["max_probe"], L.ptr(c["hold"]), c["states"], float(gamma))
 
 
 def ctc_align(logits, targets, input_lengths, target_lengths, blank=0):
@@ -979,31 +988,21 @@ def ctc_beam_search(logits, lengths, beam_width, candidates=0, nbest=1, blank=0,
     rows = max(nbest, 1)
     out = dict(ids=torch.empty((B, rows, T), device=dev, dtype=torch.int32), lengths=torch.empty((B, rows), device=dev, dtype=torch.int32),
                scores=torch.empty((B, rows), device=dev, dtype=torch.float32))
-    if context is not None:
-        if context.V != V or (ngram is not None and ngram.V != V):
-            raise ValueError("the phrase list has %d labels%s, the logits %d" % (
-                context.V, "" if ngram is None else ", the n-gram LM %d" % ngram.V, V))
-        c = context.device_table(dev)
-        t = ngram.device_table(dev) if ngram is not None else dict(keys=None, vals=None, capacity=0, max_probe=0, order=0)
-        out["lm"] = torch.empty((B, rows), device=dev, dtype=torch.float32)
-        out["credit"] = torch.empty((B, rows), device=dev, dtype=torch.int32)
-        L.call("asr_ctc_beam_search_ctx", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
-               L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"],
-               t["max_probe"], t["order"], int(bos), int(eos), float(alpha), float(beta), L.ptr(out["lm"]), L.ptr(c["keys"]),
-               L.ptr(c["vals"]), c["capacity"], c["max_probe"], L.ptr(c["hold"]), c["states"], float(gamma), L.ptr(out["credit"]),
-               L.stream())
-        return out
-    if ngram is None:
-        L.call("asr_ctc_beam_search", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
-               L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.stream())
-        return out
-    if ngram.V != V:
+    if context is not None and (context.V != V or (ngram is not None and ngram.V != V)):
+        raise ValueError("the phrase list has %d labels%s, the logits %d" % (
+            context.V, "" if ngram is None else ", the n-gram LM %d" % ngram.V, V))
+    if context is None and ngram is not None and ngram.V != V:
         raise ValueError("the n-gram LM has %d labels, the logits %d" % (ngram.V, V))
-    t = ngram.device_table(dev)
-    out["lm"] = torch.empty((B, rows), device=dev, dtype=torch.float32)
-    L.call("asr_ctc_beam_search_lm", L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n,
-           L.ptr(out["ids"]), L.ptr(out["lengths"]), L.ptr(out["scores"]), L.ptr(t["keys"]), L.ptr(t["vals"]), t["capacity"],
-           t["max_probe"], t["order"], int(bos), int(eos), float(alpha), float(beta), L.ptr(out["lm"]), L.stream())
+    args = (L.ptr(logits), logits.stride(1), L.ptr(lengths), B, T, V, W, C, nbest, int(blank), L.ptr(ws), n, L.ptr(out["ids"]),
+            L.ptr(out["lengths"]), L.ptr(out["scores"]))
+    if ngram is None and context is None:
+        L.call("asr_ctc_beam_search", *args, L.stream())
+        return out
+    ng, cx = _beam_fuse_args(out, ngram, context, bos, eos, alpha, beta, gamma)
+    if context is None:
+        L.call("asr_ctc_beam_search_lm", *args, *ng, L.ptr(out["lm"]), L.stream())
+    else:
+        L.call("asr_ctc_beam_search_ctx", *args, *ng, L.ptr(out["lm"]), *cx, L.ptr(out["credit"]), L.stream())
     return out
 
 

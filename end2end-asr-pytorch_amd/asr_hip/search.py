@@ -154,6 +154,39 @@ def rank_ended(ended, nbest, c_weight, id2label, lm=None, lm_weight=0.1):
     return [sorted(hs, key=lambda h: h['final_score'], reverse=True)[:min(len(hs), nbest)] for hs in ended]
 
 
+# ---------------------------------------------------------------------------------------------------- the kernel searches' n-best
+def nbest_to_host(out, B, W, L, fused, has_context):
+    """The output dict of ops.ctc_beam_search / ops.rnnt_beam_search (nbest = W, rows of L ids) in ONE device-to-host copy -> per
+    utterance its found hypotheses, best first, as {'yseq', 'score'} with the kernel's raw 'lm' (fused) and 'credit' (has_context)."""
+    parts = [out["scores"]] + ([out["lm"]] if fused else []) + ([out["credit"]] if has_context else [])
+    flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1)] + [p.view(torch.int32).reshape(-1) for p in parts]).cpu()
+    ids, lens, *parts = torch.split(flat, [B * W * L, B * W] + [B * W] * len(parts))
+    ids, lens = ids.view(B, W, L).tolist(), lens.view(B, W).tolist()
+    cols = [(k, (p if k == 'credit' else p.view(torch.float32)).view(B, W).tolist()) for k, p in zip(('score', 'lm', 'credit'), parts)]
+    return [[dict([('yseq', ids[b][n][:lens[b][n]])] + [(k, v[b][n]) for k, v in cols]) for n in range(W) if lens[b][n] >= 0]
+            for b in range(B)]
+
+
+def fuse_scores(ended, base, a, beta, gamma):
+    """The fusion terms on the hypotheses of a fused search (nbest_to_host): h[base] = the kernel's score, 'ngram_score' its lm,
+    'context_credit' its credit where there is one, and score = h[base] + a * ngram_score + beta * len(yseq) + gamma * context_credit,
+    added in this order."""
+    for hs in ended:
+        for h in hs:
+            h[base], h['ngram_score'] = h['score'], h.pop('lm')
+            h['score'] = h[base] + a * h['ngram_score'] + beta * len(h['yseq'])
+            if 'credit' in h:
+                h['context_credit'] = h.pop('credit')
+                h['score'] += gamma * h['context_credit']
+
+
+def render_nbest(ended, nbest, c_weight, id2label, lm, lm_weight, return_ids):
+    """rank_ended, then the label ids of every utterance's n-best as strings -> strings, or (strings, ids) with return_ids."""
+    hyp_ids = [[h['yseq'] for h in hs] for hs in rank_ended(ended, nbest, c_weight, id2label, lm, lm_weight)]
+    strs = [["".join(id2label[x] for x in row) for row in rows] for rows in hyp_ids]
+    return (strs, hyp_ids) if return_ids else strs
+
+
 # ---------------------------------------------------------------------------------------------------- greedy
 def greedy_rerun(decoder, encoder_padded_outputs):
     """Token ids (B, 300) of the reference's greedy loop as it stands: the whole decoder over the growing prefix at every step."""

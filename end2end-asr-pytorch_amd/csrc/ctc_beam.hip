@@ -33,10 +33,8 @@
 //
 // The fused arm (asr_ctc_beam_search_lm, template <true>): a label n-gram LM has its say while the beam is pruned.  q(h, c) is the query
 // of csrc/ngram.h; tests/ctc_beam_lm_reference.py restates the arm.  Added to the definition above:
-//   state                   every list entry also carries lm = the fp32 sum of q over its labels, len = their number, and ctx = the key of
-//                           the last N - 1 symbols of [bos] + prefix.  Before frame 0: lm 0, len 0, ctx [bos]
-//   step                    a stay slot keeps the three; the extension of h by c gets lm(h) + q(ctx(h), c), len(h) + 1 and the shifted
-//                           context.  They depend on the label sequence alone: a prefix pruned and created again gets the same bits
+//   state, step             every list entry also carries the BeamExt of csrc/beam_fuse.h (lm, len, ctx; root and extension are defined
+//                           there, once for both searches); a stay slot keeps it
 //   prune                   slots ranked by f = tot + (alpha lm + beta (float)len) in fp32, tot = lae2(p_b', p_nb'); greater first, lower
 //                           slot index first among equals; a slot is live iff tot is finite
 //   result                  the W entries ordered by f + alpha q(ctx, eos) (f alone for eos = -1), the list place first among equals; the
@@ -48,24 +46,19 @@
 // The phrase arms (asr_ctc_beam_search_ctx, template <LM, true>): hypotheses that spell a listed phrase get a bonus while the beam is
 // pruned.  state(y), credit(y), hold(s) and earned(y) are those of utils/context.py, step(s, c) -> (next, delta) the lookup of
 // csrc/context.h; tests/ctc_beam_ctx_reference.py restates the arms.  Added to the definitions above:
-//   state                   every list entry also carries cst = state(prefix) and cnt = credit(prefix), both int32.  Before frame 0: eps, 0
-//   step                    a stay slot keeps them; the extension of h by c gets (next, cnt(h) + delta) of step(cst(h), c).  Functions of
-//                           the label sequence alone, like lm, len and ctx
+//   state, step             BeamExt's cst = state(prefix) and cnt = credit(prefix) are live; a stay slot keeps them
 //   prune                   slots ranked by f = tot + ((alpha lm + beta (float)len) + gamma (float)cnt) in fp32, in this order; without an
 //                           n-gram table lm = 0.f and len is still counted; liveness and the tie rules as above
 //   result                  ordered by the fused arm's final key with gamma (float)earned in place of gamma (float)cnt, earned = cnt -
 //                           hold(cst): a phrase left unfinished at the end of the utterance gets nothing.  Written: scores = tot, lm as in
 //                           the fused arm (0 for found hypotheses without a table, -inf for missing ones), credit = earned (-1: missing)
 // gamma times an integer: both arms and the host form the same bits from the same count.  The lookup sits where ngram_query sits, a live
-// extension that is no merge; with both, the first probes of both tables are issued before either is consumed.  The arms without
-// phrases instantiate none of it.
+// extension that is no merge.  The arms without phrases instantiate none of it.
 #include <type_traits>
 
 #include "ctc_common.h"      // NEG_INF, lae2, ctc_lse_kernel
-#include "ngram.h"           // NgramTable, ngram_query, ngram_shift
-#include "context.h"         // CtxTable, ctx_probe, ctx_finish
 #include "beam_key.h"        // beam_key, BEAM_ROOT_KEY_LO / _HI (shared with csrc/rnnt_beam.hip)
-#include "beam_bonus.h"      // beam_bonus (shared with csrc/rnnt_beam.hip)
+#include "beam_fuse.h"       // BeamExt and its lookups, the table checks (shared with csrc/rnnt_beam.hip; no lse.h before it)
 
 namespace {
 
@@ -87,9 +80,6 @@ __device__ __forceinline__ void beam_row16(const int* p, int (&a)[BEAM_MAX]) {
   }
 }
 
-// The key of a prefix (beam_key, BEAM_ROOT_KEY_*): csrc/beam_key.h.  Its children still in the list point at the old node of a prefix
-// that was pruned and re-created, which is why entries are matched by key.
-
 // What the fused arm adds to the plain search's arguments; the plain arm takes the empty BeamNoLm
 struct BeamLm {
   NgramTable tab;
@@ -105,8 +95,6 @@ struct BeamCtx {
   int32_t* credit;          // (B,nbest)
 };
 struct BeamNoCtx {};
-
-// the fused arms' addend to tot in a slot's rank key: beam_bonus of csrc/beam_bonus.h (without an LM, lm is 0.f and alpha is not looked at)
 
 // blockDim.x = 256, or 320 when W + W C > 256: one slot per thread; the first 256 threads stage the chunks.  LM: the fused arm;
 // CTX: the phrase arm, with or without it
@@ -130,13 +118,15 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
   __shared__ float f_lpb[BEAM_CHUNK], f_lse[BEAM_CHUNK];
   __shared__ __attribute__((aligned(16))) float sc[BEAM_SLOTS];
   __shared__ int o_len[BEAM_MAX];
-  // the fused arm: the float32 sum of q over the prefix' labels, their number, and the key of the last order - 1 symbols of [bos] + prefix
-  // (functions of the label sequence alone: a stay slot keeps them, a merge needs no rule); o_src: the list place of final rank r
+  // the fused arms: the entries' BeamExt (csrc/beam_fuse.h: a stay slot keeps it, a merge needs no rule) as five parallel arrays, cst and
+  // cnt for the phrase arms alone; `ext` views them: entry i of list buffer c is cell c * BEAM_MAX + i.  o_src: the list place of final rank r
   __shared__ float l_lm[2][BEAM_MAX], o_lm[BEAM_MAX];
   __shared__ uint64_t l_ctx[2][BEAM_MAX];
   __shared__ int l_len[2][BEAM_MAX], o_src[BEAM_MAX];
-  // the phrase arms: the automaton's state and the credit of the prefix (functions of the label sequence alone, as above)
   __shared__ int l_cst[2][BEAM_MAX], l_cnt[2][BEAM_MAX], o_cr[BEAM_MAX];
+  BeamExtSoa ext{}; CtxTable cx{};
+  if constexpr (FUSED) ext = BeamExtSoa{&l_lm[0][0], &l_len[0][0], &l_ctx[0][0], &l_cst[0][0], &l_cnt[0][0]};
+  if constexpr (CTX) cx = bias.tab;
   const int tid = threadIdx.x, b = blockIdx.x, nthr = blockDim.x;
   int Tb = in_len[b];
   Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
@@ -159,13 +149,7 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     l_pb[0][tid] = tid == 0 ? 0.f : NEG_INF;
     l_pnb[0][tid] = NEG_INF;
     l_tot[0][tid] = tid == 0 ? 0.f : NEG_INF;          // lae2(0, -inf) = 0
-    if constexpr (LM) l_lm[0][tid] = 0.f;
-    if constexpr (FUSED) l_len[0][tid] = 0;
-    if constexpr (LM) l_ctx[0][tid] = ngram_shift(0, fuse.bos, fuse.tab.order);
-    if constexpr (CTX) {
-      l_cst[0][tid] = 0;
-      l_cnt[0][tid] = 0;
-    }
+    if constexpr (FUSED) ext.put<LM, CTX>(tid, beam_ext_root<LM>(fuse.tab, fuse.bos));
   }
   for (int y = tid; y < BEAM_SLOTS; y += nthr) sc[y] = NEG_INF;         // (slots >= NS are never written: they never count)
 
@@ -200,9 +184,8 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
       float npb = NEG_INF, npnb = NEG_INF, sx = NEG_INF;
       int ext_c = -1;
       // fused arm: the slot's rank key f = tot + (alpha lm + beta len) (the plain arm ranks by sx = tot itself) and what its entry carries
-      float fx = NEG_INF, elm = 0.f;
-      int elen = 0, ecst = 0, ecnt = 0;
-      uint64_t ectx = 0;
+      float fx = NEG_INF;
+      BeamExt ex{0.f, 0, 0, 0, 0};
       if (x < W) {
         int cid[BEAM_MAX], klo[BEAM_MAX], khi[BEAM_MAX];
         beam_row16(c_id[f], cid);
@@ -226,15 +209,9 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
           }
         }
         sx = lae2(npb, npnb);
-        if constexpr (FUSED) {
-          if constexpr (LM) elm = l_lm[cur][x];
-          elen = l_len[cur][x];
-          if constexpr (LM) ectx = l_ctx[cur][x];
-          if constexpr (CTX) {
-            ecst = l_cst[cur][x];
-            ecnt = l_cnt[cur][x];
-          }
-          if (sx > NEG_INF) fx = sx + beam_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, elm, elen, ecnt);
+        if constexpr (FUSED) {                               // a stay slot keeps its state
+          ex = ext.get<LM, CTX>(cur * BEAM_MAX + x);
+          if (sx > NEG_INF) fx = sx + beam_ext_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, ex);
         }
         sc[x] = FUSED ? fx : sx;
       } else if (x < NS) {
@@ -254,21 +231,8 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
             ext_c = c;
             if constexpr (FUSED) {
               if (sx > NEG_INF) {                          // a live extension that is no merge: the one lookup of the step
-                CtxProbe probe;                            // (both structures' first probes are in flight before either is consumed)
-                if constexpr (CTX) probe = ctx_probe(bias.tab, l_cst[cur][sj], c);
-                uint64_t hctx = 0;
-                if constexpr (LM) {
-                  hctx = l_ctx[cur][sj];
-                  elm = l_lm[cur][sj] + ngram_query(fuse.tab, hctx, c);
-                }
-                elen = l_len[cur][sj] + 1;
-                if constexpr (LM) ectx = ngram_shift(hctx, c, fuse.tab.order);
-                if constexpr (CTX) {
-                  const int2 tr = ctx_finish(bias.tab, probe);
-                  ecst = tr.x;
-                  ecnt = l_cnt[cur][sj] + tr.y;
-                }
-                fx = sx + beam_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, elm, elen, ecnt);
+                ex = beam_ext_extend<LM, CTX>(fuse.tab, cx, ext.get<LM, CTX>(cur * BEAM_MAX + sj), c);
+                fx = sx + beam_ext_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, ex);
               }
             }
           }
@@ -322,13 +286,7 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
           l_pb[nxt][rank] = npb;
           l_pnb[nxt][rank] = npnb;
           l_tot[nxt][rank] = sx;
-          if constexpr (LM) l_lm[nxt][rank] = elm;
-          if constexpr (FUSED) l_len[nxt][rank] = elen;
-          if constexpr (LM) l_ctx[nxt][rank] = ectx;
-          if constexpr (CTX) {
-            l_cst[nxt][rank] = ecst;
-            l_cnt[nxt][rank] = ecnt;
-          }
+          if constexpr (FUSED) ext.put<LM, CTX>(nxt * BEAM_MAX + rank, ex);
         }
       }
       __syncthreads();
@@ -341,16 +299,13 @@ __global__ __launch_bounds__(320) void ctc_beam_kernel(const float* __restrict__
     float fk = NEG_INF, lmv = NEG_INF;
     int cr = -1;
     if (live) {
-      lmv = 0.f;
-      if constexpr (LM) lmv = l_lm[cur][tid];
-      if constexpr (CTX) {
-        const int st = l_cst[cur][tid];
-        cr = l_cnt[cur][tid] - bias.tab.hold[st >= 0 && st < bias.tab.states ? st : 0];
-      }
-      fk = l_tot[cur][tid] + beam_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, lmv, l_len[cur][tid], cr);
+      BeamExt e = ext.get<LM, CTX>(cur * BEAM_MAX + tid);
+      lmv = e.lm;
+      if constexpr (CTX) e.cnt = cr = beam_ext_earned(cx, e);
+      fk = l_tot[cur][tid] + beam_ext_bonus<LM, CTX>(fuse.alpha, fuse.beta, gamma, e);
       if constexpr (LM) {
         if (fuse.eos >= 0) {
-          const float qe = ngram_query(fuse.tab, l_ctx[cur][tid], fuse.eos);
+          const float qe = ngram_query(fuse.tab, e.ctx, fuse.eos);
           fk = fk + fuse.alpha * qe;
           lmv = lmv + qe;
         }
@@ -453,14 +408,12 @@ extern "C" int asr_ctc_beam_search_lm(const float* logits, int64_t ld, const int
                                       int nbest, int blank, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
                                       float* scores, const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order,
                                       int bos, int eos, float alpha, float beta, float* lm, hipStream_t s) {
-  const int rc = ngram_check_table(keys, vals, capacity, max_probe, order);
+  ASR_CHECK_ARG(lm);
+  NgramTable tab;
+  const int rc = beam_ngram_table(keys, vals, capacity, max_probe, order, bos, eos, V, &tab);
   if (rc != ASR_OK) return rc;
-  ASR_CHECK_ARG(lm && bos >= 0 && bos < V && eos >= -1 && eos < V);
-  if (V > NGRAM_MAX_ID + 1) return ASR_EUNSUPPORTED;          // ids + 1 in 16-bit key fields
-  const BeamLm fuse{NgramTable{keys, reinterpret_cast<const float2*>(vals), (uint32_t)(capacity - 1), max_probe, order}, bos, eos, alpha,
-                    beta, lm};
   return beam_search<true, false>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
-                                  scores, fuse, BeamNoCtx{}, s);
+                                  scores, BeamLm{tab, bos, eos, alpha, beta, lm}, BeamNoCtx{}, s);
 }
 
 // The phrase arms: the table of utils/context.py (ContextGraph.device_table).  ng_keys == NULL: no LM -- alpha, bos and eos are not looked
@@ -471,22 +424,16 @@ extern "C" int asr_ctc_beam_search_ctx(const float* logits, int64_t ld, const in
                                        int ng_max_probe, int ng_order, int bos, int eos, float alpha, float beta, float* lm,
                                        const uint64_t* cx_keys, const int32_t* cx_vals, int64_t cx_capacity, int cx_max_probe,
                                        const int32_t* cx_hold, int cx_states, float gamma, int32_t* credit, hipStream_t s) {
-  int rc = ctx_check_table(cx_keys, cx_vals, cx_capacity, cx_max_probe, cx_hold, cx_states);
-  if (rc != ASR_OK) return rc;
   ASR_CHECK_ARG(lm && credit);
-  if (V > CTX_MAX_ID + 1) return ASR_EUNSUPPORTED;            // labels + 1 in a 16-bit key field
-  const BeamCtx bias{CtxTable{cx_keys, reinterpret_cast<const int2*>(cx_vals), cx_hold, (uint32_t)(cx_capacity - 1), cx_max_probe,
-                              cx_states}, gamma, credit};
-  if (!ng_keys) {
-    const BeamLm fuse{NgramTable{nullptr, nullptr, 0, 1, 1}, 0, -1, 0.f, beta, lm};
-    return beam_search<false, true>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
-                                    scores, fuse, bias, s);
-  }
-  rc = ngram_check_table(ng_keys, ng_vals, ng_capacity, ng_max_probe, ng_order);
+  BeamCtx bias{CtxTable{}, gamma, credit};
+  int rc = beam_ctx_table(cx_keys, cx_vals, cx_capacity, cx_max_probe, cx_hold, cx_states, V, &bias.tab);
   if (rc != ASR_OK) return rc;
-  ASR_CHECK_ARG(bos >= 0 && bos < V && eos >= -1 && eos < V);
-  const BeamLm fuse{NgramTable{ng_keys, reinterpret_cast<const float2*>(ng_vals), (uint32_t)(ng_capacity - 1), ng_max_probe, ng_order},
-                    bos, eos, alpha, beta, lm};
+  if (!ng_keys)
+    return beam_search<false, true>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
+                                    scores, BeamLm{beam_no_ngram(), 0, -1, 0.f, beta, lm}, bias, s);
+  NgramTable tab;
+  rc = beam_ngram_table(ng_keys, ng_vals, ng_capacity, ng_max_probe, ng_order, bos, eos, V, &tab);
+  if (rc != ASR_OK) return rc;
   return beam_search<true, true>(logits, ld, input_lengths, B, T, V, W, C, nbest, blank, workspace, workspace_floats, ids, lengths,
-                                 scores, fuse, bias, s);
+                                 scores, BeamLm{tab, bos, eos, alpha, beta, lm}, bias, s);
 }

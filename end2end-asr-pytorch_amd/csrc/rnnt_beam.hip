@@ -41,14 +41,12 @@
 // The fused arms (asr_rnnt_beam_search_lm / _ctx, template <.., LM, CTX>): a label n-gram LM and a phrase list have their say while the
 // beam is pruned.  q(h, c) is the query of csrc/ngram.h, step(s, c) -> (next, delta) and hold(s) the automaton of csrc/context.h, bonus
 // the fp32 expression of csrc/beam_bonus.h; tests/rnnt_beam_fused_reference.py restates the arms in float64.  Added to the definition:
-//   state        every entry of C_s, D and A also carries lm = the fp32 sum of q over its labels, added in label order; len; nctx = the
-//                n-gram context key (order - 1 <= 3 labels: more than the predictor's, so it is carried and not rebuilt from l1 / l2),
-//                ngram_shift(0, bos, order) for the empty sequence; cst, the automaton's state, and cnt, the credit, both 0 for it.
-//                All five are functions of the label sequence alone
+//   state        every entry of C_s, D and A also carries the BeamExt of csrc/beam_fuse.h (lm, len, nctx = its ctx, cst, cnt; root and
+//                extension are defined there, once for both searches).  nctx holds order - 1 <= 3 labels, more than the predictor's l1 / l2
 //   key          f(h) = score(h) + (double)bonus(h), bonus = alpha lm + beta (float)len, then + gamma (float)cnt; without an LM lm = 0.f
 //   label step   the K candidates of a row stay the K best non-blank entries by logit (the acoustic model proposes); candidate (r, k)
-//                gets score_r + logp, lm_r + q(nctx_r, label), len_r + 1, the shifted context and (cst, cnt_r + delta) = step(cst_r,
-//                label); C_{s+1} = the W best by f descending, then the parent's place, then the label id
+//                gets score_r + logp and row r's state extended by its label; C_{s+1} = the W best by f descending, then the parent's
+//                place, then the label id
 //   blank step   the entry joins D with its whole state; a sequence D already holds merges score by rnnt_lae and keeps the rest, which
 //                is equal by construction
 //   frame end    A = the W best of D by f descending, then the order of first insertion
@@ -57,19 +55,16 @@
 //                = cnt - hold(cst): an unfinished phrase earns nothing; missing entries: lm 0, credit 0.  T_b = 0: the empty sequence,
 //                score 0, lm = q(ctx(bos), eos), credit 0
 // With alpha = beta = gamma = 0 every key is the score: ids, lengths and scores are the plain arms' bits.  The lookups sit in phase 4, one
-// candidate per thread (n K <= 256), the first probes of the n-gram and of the automaton issued together; the candidate's new state
-// stays in that thread's registers until phase 5 places it.  The per-entry state (24 bytes) of D's 1024 entries, D's rank keys and C_s
-// live in dynamic LDS behind the z rows (RB_FUSE_BYTES = 33 728), so the fused arms' J limit is lower (fp32 1384, bf16 2776) and the
-// plain arms' static LDS and limit are what they were.  <.., false, false> instantiates none of this: its frame loop is the same
-// instruction stream as before.
+// candidate per thread (n K <= 256); the candidate's new state stays in that thread's registers until phase 5 places it.  The per-entry
+// state (24 bytes) of D's 1024 entries, D's rank keys and C_s live in dynamic LDS behind the z rows (RB_FUSE_BYTES = 33 728), so the
+// fused arms' J limit is lower (fp32 1384, bf16 2776) and the plain arms' static LDS and limit are what they were.  <.., false, false>
+// instantiates none of this: its frame loop is the same instruction stream as before.
 #include "common.h"
 #include "lse.h"             // Lse, lse_row (no multiply-add contraction from here on)
 #include "rnnt_common.h"     // rnnt_lae, clampi
 #include "topk.h"            // MaxIdx, better, wave_best
 #include "beam_key.h"        // beam_key, BEAM_ROOT_KEY_LO / _HI
-#include "beam_bonus.h"      // beam_bonus (shared with csrc/ctc_beam.hip)
-#include "ngram.h"           // NgramTable, ngram_query, ngram_shift
-#include "context.h"         // CtxTable, ctx_probe, ctx_finish
+#include "beam_fuse.h"       // BeamExt and its lookups, the table checks (shared with csrc/ctc_beam.hip; behind lse.h)
 #include <type_traits>
 
 namespace {
@@ -241,26 +236,24 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
   const T* w = reinterpret_cast<const T*>(a.w);
   float* lg = a.ws + (int64_t)b * a.ws_stride;
   int2* trie = reinterpret_cast<int2*>(lg + (int64_t)RB_MAX * ldv);
-  // the fused arms' state of every entry of D (x_d*), of C_s (x_c*, [2][16]) and the final order, behind the z rows.  Functions of the label
-  // sequence alone: a merge in D keeps them, and a sequence created again gets the same bits
-  uint64_t *x_dctx = nullptr, *x_cctx = nullptr;
-  double* x_df = nullptr;                                      // D's rank keys at the end of a frame
-  float *x_dlm = nullptr, *x_clm = nullptr, *x_olm = nullptr;
-  int *x_dlen = nullptr, *x_dcst = nullptr, *x_dcnt = nullptr, *x_clen = nullptr, *x_ccst = nullptr, *x_ccnt = nullptr, *x_osrc = nullptr,
-      *x_ocr = nullptr;
+  // the fused arms' state (BeamExt, csrc/beam_fuse.h) of every entry of D (xd) and of C_s (xc: entry r of buffer c is cell c RB_MAX + r),
+  // D's rank keys at the end of a frame and the final order, behind the z rows
+  BeamExtSoa xd{}, xc{};
+  double* x_df = nullptr;
+  float* x_olm = nullptr; int *x_osrc = nullptr, *x_ocr = nullptr;
   if constexpr (FUSED) {
     unsigned char* q = rb_dyn + (size_t)RB_MAX * zld * sizeof(T);          // (a multiple of 16 bytes)
-    x_dctx = reinterpret_cast<uint64_t*>(q); q += RB_DMAX * 8;
+    xd.ctx = reinterpret_cast<uint64_t*>(q); q += RB_DMAX * 8;
     x_df = reinterpret_cast<double*>(q); q += RB_DMAX * 8;
-    x_cctx = reinterpret_cast<uint64_t*>(q); q += 2 * RB_MAX * 8;
-    x_dlm = reinterpret_cast<float*>(q); q += RB_DMAX * 4;
-    x_dlen = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
-    x_dcst = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
-    x_dcnt = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
-    x_clm = reinterpret_cast<float*>(q); q += 2 * RB_MAX * 4;
-    x_clen = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
-    x_ccst = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
-    x_ccnt = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
+    xc.ctx = reinterpret_cast<uint64_t*>(q); q += 2 * RB_MAX * 8;
+    xd.lm = reinterpret_cast<float*>(q); q += RB_DMAX * 4;
+    xd.len = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
+    xd.cst = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
+    xd.cnt = reinterpret_cast<int*>(q); q += RB_DMAX * 4;
+    xc.lm = reinterpret_cast<float*>(q); q += 2 * RB_MAX * 4;
+    xc.len = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
+    xc.cst = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
+    xc.cnt = reinterpret_cast<int*>(q); q += 2 * RB_MAX * 4;
     x_osrc = reinterpret_cast<int*>(q); q += RB_MAX * 4;
     x_olm = reinterpret_cast<float*>(q); q += RB_MAX * 4;
     x_ocr = reinterpret_cast<int*>(q);
@@ -273,14 +266,11 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
     c_node[0][tid] = tid == 0 ? 0 : -1;                        // node 0 is the empty sequence
     c_l1[0][tid] = a.sos;
     c_l2[0][tid] = a.sos;
-    if constexpr (FUSED) {                                     // the empty sequence: lm 0, len 0, context [bos], state eps, credit 0
-      x_clm[tid] = 0.f;
-      x_clen[tid] = 0;
-      x_ccst[tid] = 0;
-      x_ccnt[tid] = 0;
-      x_cctx[tid] = 0;
-      if constexpr (LM) x_cctx[tid] = ngram_shift(0, fz.bos, fz.ng.order);
-    }
+    // With phrases all five arrays are written: the moves below copy all five, and without an LM lm still enters the bonus as 0.f * lm.
+    // The LM-only arms leave cst and cnt unwritten: they are moved along and never read (every use is under CTX), and the one more
+    // store here measured 0.4 to 0.9 % of a batch in those arms (profiles/beam_fuse_refactor_isa.txt, 2a)
+    if constexpr (CTX) xc.put<true, true>(tid, beam_ext_root<LM>(fz.ng, fz.bos));
+    else if constexpr (LM) xc.put<true, false>(tid, beam_ext_root<LM>(fz.ng, fz.bos));
   }
   if (tid == 0) d_n = 0;
   __syncthreads();
@@ -375,13 +365,13 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
             d_node[pos] = c_node[cur][lane];
             d_l1[pos] = c_l1[cur][lane];
             d_l2[pos] = c_l2[cur][lane];
-            if constexpr (FUSED) {                             // the entry joins D with its whole state
+            if constexpr (FUSED) {                             // the entry joins D with its whole state (field by field: beam_fuse.h)
               const int ce = cur * RB_MAX + lane;
-              x_dctx[pos] = x_cctx[ce];
-              x_dlm[pos] = x_clm[ce];
-              x_dlen[pos] = x_clen[ce];
-              x_dcst[pos] = x_ccst[ce];
-              x_dcnt[pos] = x_ccnt[ce];
+              xd.ctx[pos] = xc.ctx[ce];
+              xd.lm[pos] = xc.lm[ce];
+              xd.len[pos] = xc.len[ce];
+              xd.cst[pos] = xc.cst[ce];
+              xd.cnt[pos] = xc.cnt[ce];
             }
           }
         }
@@ -390,28 +380,13 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
       const int nk = n * K;
       // fused arms: what candidate tid's entry would carry, kept in registers for phase 5 (the same thread places it)
       double e_ac = 0.0;
-      float e_lm = 0.f;
-      uint64_t e_ctx = 0;
-      int e_len = 0, e_cst = 0, e_cnt = 0;
+      BeamExt ex{0.f, 0, 0, 0, 0};
       if (s < S && tid < nk) {
         const int r = tid / K, k = tid - r * K;
-        if constexpr (FUSED) {                                 // the step's lookups: both structures' first probes are in flight together
-          const int label = k_lab[r][k], ce = cur * RB_MAX + r;
-          CtxProbe probe;
-          if constexpr (CTX) probe = ctx_probe(fz.cx, x_ccst[ce], label);
-          if constexpr (LM) {
-            const uint64_t hctx = x_cctx[ce];
-            e_lm = x_clm[ce] + ngram_query(fz.ng, hctx, label);
-            e_ctx = ngram_shift(hctx, label, fz.ng.order);
-          }
-          e_len = x_clen[ce] + 1;
-          if constexpr (CTX) {
-            const int2 tr = ctx_finish(fz.cx, probe);
-            e_cst = tr.x;
-            e_cnt = x_ccnt[ce] + tr.y;
-          }
+        if constexpr (FUSED) {                                 // the step's lookups
+          ex = beam_ext_extend<LM, CTX>(fz.ng, fz.cx, xc.get<LM, CTX>(cur * RB_MAX + r), k_lab[r][k]);
           e_ac = c_score[cur][r] + (double)k_lp[r][k];
-          sc[tid] = e_ac + (double)beam_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, e_lm, e_len, e_cnt);
+          sc[tid] = e_ac + (double)beam_ext_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, ex);
         } else {
           sc[tid] = c_score[cur][r] + (double)k_lp[r][k];
         }
@@ -442,11 +417,11 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
             c_l2[nxt][rank] = c_l1[cur][r];
             if constexpr (FUSED) {
               const int ne = nxt * RB_MAX + rank;
-              x_cctx[ne] = e_ctx;
-              x_clm[ne] = e_lm;
-              x_clen[ne] = e_len;
-              x_ccst[ne] = e_cst;
-              x_ccnt[ne] = e_cnt;
+              xc.ctx[ne] = ex.ctx;
+              xc.lm[ne] = ex.lm;
+              xc.len[ne] = ex.len;
+              xc.cst[ne] = ex.cst;
+              xc.cnt[ne] = ex.cnt;
             }
           }
         }
@@ -460,7 +435,7 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
     const double* d_rank = d_score;                            // what D is ranked by: the score, or f in the fused arms
     if constexpr (FUSED) {
       for (int i = tid; i < dn; i += RB_THREADS)
-        x_df[i] = d_score[i] + (double)beam_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, x_dlm[i], x_dlen[i], x_dcnt[i]);
+        x_df[i] = d_score[i] + (double)beam_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, xd.lm[i], xd.len[i], xd.cnt[i]);
       d_rank = x_df;
       __syncthreads();
     }
@@ -480,11 +455,11 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
         c_l2[nxt][rank] = d_l2[i];
         if constexpr (FUSED) {
           const int ne = nxt * RB_MAX + rank;
-          x_cctx[ne] = x_dctx[i];
-          x_clm[ne] = x_dlm[i];
-          x_clen[ne] = x_dlen[i];
-          x_ccst[ne] = x_dcst[i];
-          x_ccnt[ne] = x_dcnt[i];
+          xc.ctx[ne] = xd.ctx[i];
+          xc.lm[ne] = xd.lm[i];
+          xc.len[ne] = xd.len[i];
+          xc.cst[ne] = xd.cst[i];
+          xc.cnt[ne] = xd.cnt[i];
         }
       }
     }
@@ -500,16 +475,14 @@ __global__ __launch_bounds__(RB_THREADS) void rnnt_beam_kernel(RbArgs a, std::co
     float lmv = 0.f;
     int cr = 0;
     if (live) {
-      const int ce = cur * RB_MAX + tid;
+      BeamExt e = xc.get<LM, CTX>(cur * RB_MAX + tid);
       if constexpr (LM) {
-        lmv = x_clm[ce];
-        if (fz.eos >= 0) lmv = lmv + ngram_query(fz.ng, x_cctx[ce], fz.eos);
+        if (fz.eos >= 0) e.lm = e.lm + ngram_query(fz.ng, e.ctx, fz.eos);
       }
-      if constexpr (CTX) {
-        const int st = x_ccst[ce];
-        cr = x_ccnt[ce] - fz.cx.hold[st >= 0 && st < fz.cx.states ? st : 0];
-      }
-      fk = c_score[cur][tid] + (double)beam_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, lmv, x_clen[ce], cr);
+      if constexpr (CTX) e.cnt = beam_ext_earned(fz.cx, e);
+      lmv = e.lm;
+      cr = e.cnt;
+      fk = c_score[cur][tid] + (double)beam_ext_bonus<LM, CTX>(fz.alpha, fz.beta, fz.gamma, e);
     }
     if (tid < RB_MAX) { sc[tid] = fk; x_osrc[tid] = -1; }
     __syncthreads();
@@ -608,12 +581,10 @@ extern "C" int asr_rnnt_beam_search_lm(const void* e, const void* table0, const 
                                        int sos, int dtype, float* workspace, int64_t workspace_floats, int32_t* ids, int32_t* lengths,
                                        float* scores, const uint64_t* keys, const float* vals, int64_t capacity, int max_probe, int order,
                                        int bos, int eos, float alpha, float beta, float* lm, hipStream_t s) {
-  const int rc = ngram_check_table(keys, vals, capacity, max_probe, order);
+  ASR_CHECK_ARG(lm);
+  RbFuse fz{NgramTable{}, beam_no_ctx(), bos, eos, alpha, beta, 0.f, lm, nullptr};
+  const int rc = beam_ngram_table(keys, vals, capacity, max_probe, order, bos, eos, V, &fz.ng);
   if (rc != ASR_OK) return rc;
-  ASR_CHECK_ARG(lm && bos >= 0 && bos < V && eos >= -1 && eos < V);
-  if (V > NGRAM_MAX_ID + 1) return ASR_EUNSUPPORTED;          // ids + 1 in 16-bit key fields
-  const RbFuse fz{NgramTable{keys, reinterpret_cast<const float2*>(vals), (uint32_t)(capacity - 1), max_probe, order},
-                  CtxTable{nullptr, nullptr, nullptr, 0, 1, 1}, bos, eos, alpha, beta, 0.f, lm, nullptr};
   return rb_search<true, false>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
                                 workspace_floats, ids, lengths, scores, fz, s);
 }
@@ -627,21 +598,16 @@ extern "C" int asr_rnnt_beam_search_ctx(const void* e, const void* table0, const
                                         int ng_max_probe, int ng_order, int bos, int eos, float alpha, float beta,
                                         const uint64_t* cx_keys, const int32_t* cx_vals, int64_t cx_capacity, int cx_max_probe,
                                         const int32_t* cx_hold, int cx_states, float gamma, float* lm, int32_t* credit, hipStream_t s) {
-  int rc = ctx_check_table(cx_keys, cx_vals, cx_capacity, cx_max_probe, cx_hold, cx_states);
-  if (rc != ASR_OK) return rc;
   ASR_CHECK_ARG(lm && credit);
-  if (V > CTX_MAX_ID + 1) return ASR_EUNSUPPORTED;            // labels + 1 in a 16-bit key field
-  const CtxTable cx{cx_keys, reinterpret_cast<const int2*>(cx_vals), cx_hold, (uint32_t)(cx_capacity - 1), cx_max_probe, cx_states};
-  if (!ng_keys) {
-    const RbFuse fz{NgramTable{nullptr, nullptr, 0, 1, 1}, cx, 0, -1, 0.f, beta, gamma, lm, credit};
-    return rb_search<false, true>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
-                                  workspace_floats, ids, lengths, scores, fz, s);
-  }
-  rc = ngram_check_table(ng_keys, ng_vals, ng_capacity, ng_max_probe, ng_order);
+  CtxTable cx;
+  int rc = beam_ctx_table(cx_keys, cx_vals, cx_capacity, cx_max_probe, cx_hold, cx_states, V, &cx);
   if (rc != ASR_OK) return rc;
-  ASR_CHECK_ARG(bos >= 0 && bos < V && eos >= -1 && eos < V);
-  const RbFuse fz{NgramTable{ng_keys, reinterpret_cast<const float2*>(ng_vals), (uint32_t)(ng_capacity - 1), ng_max_probe, ng_order}, cx,
-                  bos, eos, alpha, beta, gamma, lm, credit};
+  if (!ng_keys)
+    return rb_search<false, true>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
+                                  workspace_floats, ids, lengths, scores, RbFuse{beam_no_ngram(), cx, 0, -1, 0.f, beta, gamma, lm, credit}, s);
+  RbFuse fz{NgramTable{}, cx, bos, eos, alpha, beta, gamma, lm, credit};
+  rc = beam_ngram_table(ng_keys, ng_vals, ng_capacity, ng_max_probe, ng_order, bos, eos, V, &fz.ng);
+  if (rc != ASR_OK) return rc;
   return rb_search<true, true>(e, table0, table1, w_out, b_out, frame_lengths, B, T, J, V, W, K, S, nbest, blank, sos, dtype, workspace,
                                workspace_floats, ids, lengths, scores, fz, s);
 }

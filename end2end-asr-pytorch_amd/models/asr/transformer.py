@@ -213,34 +213,14 @@ class Transformer(nn.Module):
             raise ValueError("nbest must be at least 1, got %d" % nbest)
         logits = self.ctc_logits(enc_out)
         B, T, V = logits.shape
+        fused = ngram is not None or context is not None
+        kw = dict(ngram=ngram, alpha=a, beta=beta, bos=constant.SOS_TOKEN, eos=constant.EOS_TOKEN) if fused else {}
         if context is not None:
-            out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN,
-                                      ngram=ngram, alpha=a, beta=beta, bos=constant.SOS_TOKEN, eos=constant.EOS_TOKEN, context=context,
-                                      gamma=gamma)
-            parts = [out["scores"], out["lm"], out["credit"].view(torch.float32)]
-        elif ngram is None:
-            out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN)
-            parts = [out["scores"]]
-        else:
-            out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN,
-                                      ngram=ngram, alpha=a, beta=beta, bos=constant.SOS_TOKEN, eos=constant.EOS_TOKEN)
-            parts = [out["scores"], out["lm"]]
-        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1)] + [p.view(torch.int32).reshape(-1) for p in parts]).cpu()
-        ids, lens, *parts = torch.split(flat, [B * W * T, B * W] + [B * W] * len(parts))
-        ids, lens = ids.view(B, W, T).tolist(), lens.view(B, W).tolist()
-        credits = parts.pop().view(B, W).tolist() if context is not None else None
-        scores, *lm_scores = [p.view(torch.float32).view(B, W).tolist() for p in parts]
-        ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n]} for n in range(W) if lens[b][n] >= 0] for b in range(B)]
-        if ngram is not None or context is not None:
-            for b, hs in enumerate(ended):
-                found = [n for n in range(W) if lens[b][n] >= 0]
-                for h, n in zip(hs, found):
-                    g = lm_scores[0][b][n]
-                    h['ctc_score'], h['ngram_score'] = h['score'], g
-                    h['score'] = h['ctc_score'] + a * g + beta * len(h['yseq'])
-                    if context is not None:
-                        h['context_credit'] = credits[b][n]
-                        h['score'] += gamma * h['context_credit']
+            kw.update(context=context, gamma=gamma)
+        out = ops.ctc_beam_search(logits, _lengths_to_device(lengths, logits.device), W, candidates, W, constant.PAD_TOKEN, **kw)
+        ended = search.nbest_to_host(out, B, W, T, fused, context is not None)
+        if fused:
+            search.fuse_scores(ended, 'ctc_score', a, beta, gamma)
         if lam > 0.0:
             att = self.decoder.score_hypotheses(enc_out, [[h['yseq'] for h in hs] for hs in ended])
             for hs, scores_b in zip(ended, att):
@@ -248,13 +228,11 @@ class Transformer(nn.Module):
                     h.setdefault('ctc_score', h['score'])
                     h['att_score'] = att_score
                     h['score'] = (1.0 - lam) * h['ctc_score'] + lam * att_score
-                    if ngram is not None or context is not None:
+                    if fused:
                         h['score'] += a * h['ngram_score'] + beta * len(h['yseq'])
                     if context is not None:
                         h['score'] += gamma * h['context_credit']
-        hyp_ids = [[h['yseq'] for h in hs] for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight)]
-        strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
-        return (strs, hyp_ids) if return_ids else strs
+        return search.render_nbest(ended, nbest, c_weight, self.id2label, lm, lm_weight, return_ids)
 
     @torch.no_grad()
     def ctc_align(self, enc_out, lengths, targets, target_lengths=None):
@@ -515,27 +493,14 @@ class Transformer(nn.Module):
         kw = dict(ngram=ngram, alpha=a, beta=beta, bos=constant.SOS_TOKEN, eos=constant.EOS_TOKEN, context=context, gamma=gamma) if fused else {}
         out = ops.rnnt_beam_search(e.contiguous(), tables, P.linear_weight(self.rnnt_out.weight, cd), self.rnnt_out.bias.data,
                                    _lengths_to_device(lengths, e.device), W, K, S, W, constant.PAD_TOKEN, constant.SOS_TOKEN, **kw)
-        L = T * S
-        parts = [out["scores"].view(torch.int32)] + ([out["lm"].view(torch.int32)] if fused else []) + (
-            [out["credit"]] if context is not None else [])
-        flat = torch.cat([out["ids"].reshape(-1), out["lengths"].reshape(-1)] + [p.reshape(-1) for p in parts]).cpu()
-        ids, lens, scores, *extra = torch.split(flat, [B * W * L, B * W] + [B * W] * len(parts))
-        ids, lens, scores = ids.view(B, W, L).tolist(), lens.view(B, W).tolist(), scores.view(torch.float32).view(B, W).tolist()
-        ended = [[{'yseq': ids[b][n][:lens[b][n]], 'score': scores[b][n], 'rnnt_score': scores[b][n]} for n in range(W) if lens[b][n] >= 0]
-                 for b in range(B)]
+        ended = search.nbest_to_host(out, B, W, T * S, fused, context is not None)
         if fused:
-            lm_scores = extra[0].view(torch.float32).view(B, W).tolist()
-            credits = extra[1].view(B, W).tolist() if context is not None else None
-            for b, hs in enumerate(ended):
-                for h, n in zip(hs, [n for n in range(W) if lens[b][n] >= 0]):
-                    h['ngram_score'] = lm_scores[b][n]
-                    h['score'] = h['rnnt_score'] + a * h['ngram_score'] + beta * len(h['yseq'])
-                    if context is not None:
-                        h['context_credit'] = credits[b][n]
-                        h['score'] += gamma * h['context_credit']
-        hyp_ids = [[h['yseq'] for h in hs] for hs in search.rank_ended(ended, nbest, c_weight, self.id2label, lm, lm_weight)]
-        strs = [["".join(self.id2label[x] for x in row) for row in rows] for rows in hyp_ids]
-        return (strs, hyp_ids) if return_ids else strs
+            search.fuse_scores(ended, 'rnnt_score', a, beta, gamma)
+        else:
+            for hs in ended:
+                for h in hs:
+                    h['rnnt_score'] = h['score']
+        return search.render_nbest(ended, nbest, c_weight, self.id2label, lm, lm_weight, return_ids)
 
     def forward(self, padded_input, input_lengths, padded_target, verbose=False, return_ctc=False):
         """-> (pred (B,Td,V) fp32, gold (B,Td), hyp_seq (B,Td), gold_seq)   (reference: transformer.py:59-85); with return_ctc also

@@ -140,3 +140,32 @@ def test_rank_ended_nests_per_utterance_and_orders_by_the_word_bonus():
             assert [h['final_score'] for h in out] == [final[n] for n in order]
     strs, ids = search.strings_up_to_eos([[a, sp, b, EOS, a], [b, b]], id2label)
     assert strs == ["a b", "bb"] and ids == [[a, sp, b], [b, b]]
+
+
+def test_nbest_bookkeeping_of_the_kernel_searches():
+    """nbest_to_host / fuse_scores / render_nbest on a hand-made output dict (CPU tensors): found hypotheses only, in place order, with
+    the float bits of the op's tensors; the fusion terms added in the order the model tests compare with ==; the fields per arm."""
+    B, W, L = 2, 3, 4
+    out = dict(ids=torch.tensor([[[3, 4, 0, 0], [4, 0, 0, 0], [0, 0, 0, 0]], [[0, 0, 0, 0]] * 3], dtype=torch.int32),
+               lengths=torch.tensor([[2, 1, -1], [0, -1, -1]], dtype=torch.int32),
+               scores=torch.tensor([[-1.25, -2.1, -math.inf], [0.0, -math.inf, -math.inf]]),
+               lm=torch.tensor([[-3.3, -0.7, 0.0], [-0.1, 0.0, 0.0]]), credit=torch.tensor([[2, 0, 0], [0, 0, 0]], dtype=torch.int32))
+    sc, lm = out["scores"].tolist(), out["lm"].tolist()
+    plain = search.nbest_to_host(out, B, W, L, False, False)
+    assert plain == [[{'yseq': [3, 4], 'score': sc[0][0]}, {'yseq': [4], 'score': sc[0][1]}], [{'yseq': [], 'score': 0.0}]]
+    a, beta, gamma = 0.3, 0.5, 1.5
+    for has_context in (False, True):
+        ended = search.nbest_to_host(out, B, W, L, True, has_context)
+        assert [[set(h) for h in hs] for hs in ended] == [[{'yseq', 'score', 'lm'} | ({'credit'} if has_context else set())] * n for n in (2, 1)]
+        search.fuse_scores(ended, 'ctc_score', a, beta, gamma)
+        h = ended[0][0]
+        assert set(h) == {'yseq', 'score', 'ctc_score', 'ngram_score'} | ({'context_credit'} if has_context else set())
+        want = sc[0][0] + a * lm[0][0] + beta * 2
+        if has_context:
+            want += gamma * 2
+            assert type(h['context_credit']) is int and h['context_credit'] == 2
+        assert h['score'] == want and h['ctc_score'] == sc[0][0] and h['ngram_score'] == lm[0][0]
+        assert ended[1][0]['score'] == 0.0 + a * lm[1][0] + beta * 0 + (gamma * 0 if has_context else 0.0)
+    id2label = dict(enumerate([constant.PAD_CHAR, constant.SOS_CHAR, constant.EOS_CHAR, "a", "b"]))
+    strs, ids = search.render_nbest(plain, 2, 0.0, id2label, None, 0.1, True)
+    assert ids == [[[3, 4], [4]], [[]]] and strs == [["ab", "b"], [""]] and search.render_nbest(plain, 1, 0.0, id2label, None, 0.1, False) == [["ab"], [""]]
