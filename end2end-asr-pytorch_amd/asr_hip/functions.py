@@ -17,6 +17,7 @@ Sub-layer -> reference code
   RnntSimpleFn, RnntJointPrunedFn, RnntPrunedFn  (no reference code: pruned transducer training, --transducer-prune-range)
 """
 import collections
+import functools
 import os
 import weakref
 
@@ -1036,6 +1037,41 @@ class EmbCNNFn(Function):
 
 
 # ================================================================================================ loss
+# The logit hand-over, stated once.  Every loss Function whose input may be the fp32 logits of a bf16 model's vocabulary projection
+# (CEFn, DistillFn, RnntFn, RnntPrunedFn, SeqLogProbFn) follows it:
+#   forward   _claim_logits(ctx, logits): if the input needs a gradient, claim the box LinearFn left for these logits (_Handover.claim:
+#             matched by a live weak reference plus address and size).  The claim EMPTIES the slot whoever makes it and whatever it
+#             finds -- the slot holds one box, for the projection that ran last -- so a Function must run right behind the projection
+#             whose logits it takes, before the next fp32 projection or claim.
+#   backward  _hand_back(ctx, bwd, shape): with a box, the gradient goes into it as bf16, zero padded to 64 columns (what the
+#             projection's data-gradient GEMM reads), and a stride-0 zero is the formal fp32 gradient -- that saves the fp32 tensor
+#             (56 MB at the benchmark's CE), its cast / pad launch and half of the kernel's stores; LinearFn.backward adds whatever a
+#             second consumer of the logits contributed.  Without a box (an fp32 model, logits from elsewhere) the fp32 gradient itself.
+def _claim_logits(ctx, logits):
+    ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+
+
+def _hand_back(ctx, bwd, shape):
+    """bwd(**kw) is the Function's ops.*_bwd call, open in out_dtype and pad; `shape` the formal shape of the input's gradient."""
+    if ctx.handover is None:
+        return bwd().reshape(shape)
+    dy = ctx.handover["dy"] = bwd(out_dtype=torch.bfloat16, pad=64)
+    return ops.zero_scalar(dy.device).expand(shape)
+
+
+def _f32c(t):
+    """fp32 and contiguous: what the loss kernels read."""
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
+
+
+def _lengths_i32(lengths, dev):
+    return torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _scalar_f32(dloss):
+    return dloss.reshape(1).float().contiguous()
+
+
 class CEFn(Function):
     """loss = sum over non-PAD rows of the (label smoothed) row loss / count        (reference: utils/metrics.py:102-132).
 
@@ -1050,10 +1086,7 @@ class CEFn(Function):
     def forward(ctx, pred, gold, smoothing, pad_id, global_count):
         ctx.set_materialize_grads(False)       # no zero-filled gradients for the two statistics outputs (one fill launch each per step)
         V = pred.shape[-1]
-        logits = pred.reshape(-1, V)
-        if logits.dtype != torch.float32:
-            logits = logits.float()
-        logits = logits.contiguous()
+        logits = _f32c(pred.reshape(-1, V))
         g = gold.reshape(-1).contiguous()
         red = P._state["reducer"]
         # (grad mode is always off inside Function.forward: "will backward run" is ctx.needs_input_grad)
@@ -1071,7 +1104,7 @@ class CEFn(Function):
             count = global_count if global_count is not None else sums[1:2]
         ctx.t = (logits, g, lse, count)
         ctx.smoothing, ctx.pad_id, ctx.shape = smoothing, pad_id, pred.shape
-        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        _claim_logits(ctx, logits)
         ctx.mark_non_differentiable(sums, am)
         return loss, sums, am
 
@@ -1080,15 +1113,9 @@ class CEFn(Function):
         logits, g, lse, count = ctx.t
         if count is None:
             count = ops.ones_scalar(logits.device)
-        go = dloss.reshape(1).float().contiguous()
-        if ctx.handover is not None:
-            # the logits come straight from a LinearFn of a bf16 model: hand it the gradient in bf16, padded to 64 columns (what its
-            # data-gradient GEMM reads), and return a stride-0 zero as the formal fp32 gradient -- saves the 56 MB fp32 tensor, its
-            # cast / pad launch and half of this kernel's stores (reference: loss.backward() through utils/metrics.py:118-130)
-            ctx.handover["dy"] = ops.ce_bwd(logits, g, lse, ctx.smoothing, ctx.pad_id, go, count, out_dtype=torch.bfloat16, pad=64)
-            return ops.zero_scalar(logits.device).expand(ctx.shape), None, None, None, None
-        dl = ops.ce_bwd(logits, g, lse, ctx.smoothing, ctx.pad_id, go, count)
-        return dl.view(ctx.shape), None, None, None, None
+        # (reference: loss.backward() through utils/metrics.py:118-130)
+        bwd = functools.partial(ops.ce_bwd, logits, g, lse, ctx.smoothing, ctx.pad_id, _scalar_f32(dloss), count)
+        return _hand_back(ctx, bwd, ctx.shape), None, None, None, None
 
 
 class DistillFn(Function):
@@ -1097,11 +1124,9 @@ class DistillFn(Function):
     live-row count.  with_ce=False: the KD term alone -- gold only marks the live rows
     and ce_scale is taken as 0.  -> (loss, sums (4,) = [sum ce, #live, #correct, sum kd], argmax (M,) or an empty tensor without with_ce),
     the last two not differentiable; the teacher logits never get a gradient.
-    backward: ONE asr_distill_bwd launch writes the combined CE + KD gradient.  The vocabulary projection's hand-over slot takes one
-    gradient per logits tensor, which is why the two terms share a Function: when the student logits come straight from the projection
-    of a bf16 model the gradient goes through the slot exactly as CEFn's does (bf16, zero padded to 64 columns, a stride-0 zero as the
-    formal gradient); otherwise the fp32 gradient is returned.  The claim empties the slot whoever makes it: of two DistillFn calls
-    in one step, the one on the projection's logits comes first."""
+    backward: ONE asr_distill_bwd launch writes the combined CE + KD gradient.  The logit hand-over (_claim_logits / _hand_back above)
+    takes one gradient per logits tensor, which is why the two terms share a Function; and since a claim empties the slot, of two
+    DistillFn calls in one step the one on the projection's logits comes first."""
 
     @staticmethod
     def forward(ctx, student_logits, teacher_logits, gold, smoothing, pad_id, temperature, ce_scale, kd_scale, with_ce):
@@ -1110,14 +1135,8 @@ class DistillFn(Function):
         if teacher_logits.shape != student_logits.shape:
             raise ValueError("DistillFn: student logits %s and teacher logits %s differ in shape"
                              % (tuple(student_logits.shape), tuple(teacher_logits.shape)))
-        logits = student_logits.reshape(-1, V)
-        if logits.dtype != torch.float32:
-            logits = logits.float()
-        logits = logits.contiguous()
-        teach = teacher_logits.detach().reshape(-1, V)
-        if teach.dtype != torch.float32:
-            teach = teach.float()
-        teach = teach.contiguous()
+        logits = _f32c(student_logits.reshape(-1, V))
+        teach = _f32c(teacher_logits.detach().reshape(-1, V))
         g = gold.reshape(-1).contiguous()
         if not with_ce:
             ce_scale = 0.0
@@ -1127,19 +1146,15 @@ class DistillFn(Function):
         ctx.t = (logits, teach, g, stats, sums[1:2])
         ctx.cfg = (float(smoothing), int(pad_id), float(temperature), float(ce_scale), float(kd_scale))
         ctx.shape = student_logits.shape
-        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        _claim_logits(ctx, logits)
         ctx.mark_non_differentiable(sums, am)
         return loss.reshape(()), sums, am
 
     @staticmethod
     def backward(ctx, dloss, *unused):
         logits, teach, g, stats, count = ctx.t
-        go = dloss.reshape(1).float().contiguous()
-        if ctx.handover is not None:
-            ctx.handover["dy"] = ops.distill_bwd(logits, teach, g, stats, *ctx.cfg, go, count, out_dtype=torch.bfloat16, pad=64)
-            return (ops.zero_scalar(logits.device).expand(ctx.shape),) + (None,) * 8
-        dl = ops.distill_bwd(logits, teach, g, stats, *ctx.cfg, go, count)
-        return (dl.view(ctx.shape),) + (None,) * 8
+        bwd = functools.partial(ops.distill_bwd, logits, teach, g, stats, *ctx.cfg, _scalar_f32(dloss), count)
+        return (_hand_back(ctx, bwd, ctx.shape),) + (None,) * 8
 
 
 class CTCFn(Function):
@@ -1148,12 +1163,10 @@ class CTCFn(Function):
 
     @staticmethod
     def forward(ctx, pred, gold, input_lengths, target_lengths, blank):
-        logits = pred if pred.dtype == torch.float32 else pred.float()
-        logits = logits.contiguous()
+        logits = _f32c(pred)
         dev = logits.device
         tg = gold.to(device=dev, dtype=torch.int64).contiguous()
-        il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        il, tl = _lengths_i32(input_lengths, dev), _lengths_i32(target_lengths, dev)
         loss, ws = ops.ctc_fwd(logits, tg, il, tl, blank)
         ctx.t = (logits, tg, il, tl, ws)
         ctx.blank = blank
@@ -1162,7 +1175,7 @@ class CTCFn(Function):
     @staticmethod
     def backward(ctx, dloss):
         logits, tg, il, tl, ws = ctx.t
-        dl = ops.ctc_bwd(logits, tg, il, tl, ws, dloss.reshape(1).float().contiguous(), ctx.blank)
+        dl = ops.ctc_bwd(logits, tg, il, tl, ws, _scalar_f32(dloss), ctx.blank)
         return dl, None, None, None, None
 
 
@@ -1194,13 +1207,12 @@ class RnntFn(Function):
     logits, gold (B,>=U) label ids without SOS / EOS, frame_lengths = true encoder frames T_b, target_lengths = U_b, blank = PAD.  The
     reduction is CTCFn's, so --ctc-weight and --transducer-weight compare.  An utterance without an alignment (T_b = 0, a label that
     is the blank or outside [0,V)) makes the loss +inf and gets zero gradient rows.
-    backward: ONE launch (ops.rnnt_bwd).  The logit hand-over slot: this Function CLAIMS it, as SeqLogProbFn does.  The model applies it
+    backward: ONE launch (ops.rnnt_bwd), through the logit hand-over (_claim_logits / _hand_back above).  The model applies this Function
     right behind the joint's vocabulary projection and before the decoder runs (Transformer.transducer_loss), so the slot it claims is
-    that projection's and the decoder's projection leaves a fresh one for CEFn afterwards.  In a bf16 model the gradient therefore
-    travels as bf16, zero padded to 64 columns, with a stride-0 zero as the formal gradient.  Memory at B 32, T' 75, V 4364: the fp32
+    that projection's and the decoder's projection leaves a fresh one for CEFn afterwards.  Memory at B 32, T' 75, V 4364: the fp32
     logits are B T' (U+1) V 4 bytes = 0.88 GB at U 20 and 1.72 GB at U 40 (kept for the backward), the handed-over gradient half of a
     4416-wide copy of that, 0.45 / 0.87 GB; returning the formal fp32 gradient instead would cost another 0.88 / 1.72 GB plus the cast
-    and pad launch.  Outside the slot (an fp32 model) the fp32 gradient is returned.
+    and pad launch.
     A shape whose fp32 logits (rows 64-column padded) reach 2^31 bytes is refused with a ValueError before any launch.  The new
     kernels index in 64 bits; the vocabulary projection then runs B T' (U+1) rows through the GEMM arms of _linear_fwd / _lin_bwd, whose
     row bases are 64 bit but whose M, tile counts and per-thread chunk offsets (csrc/gemm_tn.hip, csrc/gemm_nn.hip: offA / offB,
@@ -1213,8 +1225,7 @@ class RnntFn(Function):
             raise ValueError("RnntFn: joint logits (B,T,U+1,V) expected, got %s" % (tuple(pred.shape),))
         B, T, U1, V = pred.shape
         check_rnnt_shape(B, T, U1, V)
-        logits = pred if pred.dtype == torch.float32 else pred.float()
-        logits = logits.contiguous()
+        logits = _f32c(pred)
         dev = logits.device
         tg = torch.as_tensor(gold).to(device=dev, dtype=torch.int64)
         if U1 == 1 and tg.shape[1] == 0:
@@ -1222,23 +1233,18 @@ class RnntFn(Function):
         if tg.shape[1] < max(U1 - 1, 1):
             raise ValueError("RnntFn: %d label columns for logits with U + 1 = %d" % (tg.shape[1], U1))
         tg = tg[:, :max(U1 - 1, 1)].contiguous()
-        fl = torch.as_tensor(frame_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        fl, tl = _lengths_i32(frame_lengths, dev), _lengths_i32(target_lengths, dev)
         loss, ws = ops.rnnt_fwd(logits, tg, fl, tl, blank)
         ctx.t = (logits, tg, fl, tl, ws)
         ctx.blank, ctx.shape = blank, pred.shape
-        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        _claim_logits(ctx, logits)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, dloss):
         logits, tg, fl, tl, ws = ctx.t
-        go = dloss.reshape(1).float().contiguous()
-        if ctx.handover is not None:
-            ctx.handover["dy"] = ops.rnnt_bwd(logits, tg, fl, tl, ws, go, ctx.blank, out_dtype=torch.bfloat16, pad=64)
-            return ops.zero_scalar(logits.device).expand(ctx.shape), None, None, None, None
-        dl = ops.rnnt_bwd(logits, tg, fl, tl, ws, go, ctx.blank)
-        return dl.reshape(ctx.shape), None, None, None, None
+        bwd = functools.partial(ops.rnnt_bwd, logits, tg, fl, tl, ws, _scalar_f32(dloss), ctx.blank)
+        return _hand_back(ctx, bwd, ctx.shape), None, None, None, None
 
 
 def check_rnnt_shape(B, T, U1, V):
@@ -1273,12 +1279,10 @@ class RnntSimpleFn(Function):
         if am.dim() != 3 or lm.dim() != 3 or am.shape[0] != lm.shape[0] or am.shape[2] != lm.shape[2]:
             raise ValueError("RnntSimpleFn: am (B,T,V) and lm (B,U+1,V) expected, got %s and %s" % (tuple(am.shape), tuple(lm.shape)))
         B, U = am.shape[0], lm.shape[1] - 1
-        a = (am if am.dtype == torch.float32 else am.float()).contiguous()
-        l = (lm if lm.dtype == torch.float32 else lm.float()).contiguous()
+        a, l = _f32c(am), _f32c(lm)
         dev = a.device
         tg = _rnnt_labels(gold, B, U, dev)
-        fl = torch.as_tensor(frame_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        fl, tl = _lengths_i32(frame_lengths, dev), _lengths_i32(target_lengths, dev)
         loss, ws, gb, gl = ops.rnnt_simple_fwd(a, l, tg, fl, tl, blank)
         ctx.t = (tg, fl, tl, ws)
         ctx.blank, ctx.shapes = blank, (am.shape, lm.shape)
@@ -1288,7 +1292,7 @@ class RnntSimpleFn(Function):
     @staticmethod
     def backward(ctx, dloss, *unused):
         tg, fl, tl, ws = ctx.t
-        dam, dlm = ops.rnnt_simple_bwd(ctx.shapes[0], ctx.shapes[1], tg, fl, tl, ws, dloss.reshape(1).float().contiguous(), ctx.blank)
+        dam, dlm = ops.rnnt_simple_bwd(ctx.shapes[0], ctx.shapes[1], tg, fl, tl, ws, _scalar_f32(dloss), ctx.blank)
         return dam, dlm, None, None, None, None
 
 
@@ -1316,8 +1320,8 @@ class RnntPrunedFn(Function):
     """RnntFn on a band (ops.rnnt_pruned_fwd): pred (B,T,W,V) fp32 logits whose row (b,t,w) is lattice cell
     (t, s_begin[b,t] + w) of the T x (U + 1) lattice, U = `umax`; every node outside the band has no outgoing arc.  An utterance without a
     complete path inside its band makes the loss +inf and gets zero gradient rows, like any utterance without an alignment.
-    backward: ONE launch.  This Function CLAIMS the logit hand-over slot exactly as RnntFn does: rnnt_out on the banded z must be the
-    last fp32 projection before it, and both must run before the decoder.  check_rnnt_shape(B, T, W, V) applies."""
+    backward: ONE launch, through the logit hand-over as RnntFn's: rnnt_out on the banded z must be the last fp32 projection before
+    this Function, and both must run before the decoder.  check_rnnt_shape(B, T, W, V) applies."""
 
     @staticmethod
     def forward(ctx, pred, gold, frame_lengths, target_lengths, s_begin, umax, blank):
@@ -1328,55 +1332,44 @@ class RnntPrunedFn(Function):
         if not 1 <= W <= U + 1:
             raise ValueError("RnntPrunedFn: a band of %d label positions for U + 1 = %d" % (W, U + 1))
         check_rnnt_shape(B, T, W, V)
-        logits = pred if pred.dtype == torch.float32 else pred.float()
-        logits = logits.contiguous()
+        logits = _f32c(pred)
         dev = logits.device
         tg = _rnnt_labels(gold, B, U, dev)
-        fl = torch.as_tensor(frame_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+        fl, tl = _lengths_i32(frame_lengths, dev), _lengths_i32(target_lengths, dev)
         loss, ws = ops.rnnt_pruned_fwd(logits, tg, fl, tl, s_begin, U, blank)
         ctx.t = (logits, tg, fl, tl, s_begin, ws)
         ctx.blank, ctx.shape, ctx.U = blank, pred.shape, U
-        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        _claim_logits(ctx, logits)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, dloss):
         logits, tg, fl, tl, s, ws = ctx.t
-        go = dloss.reshape(1).float().contiguous()
-        if ctx.handover is not None:
-            ctx.handover["dy"] = ops.rnnt_pruned_bwd(logits, tg, fl, tl, s, ctx.U, ws, go, ctx.blank, out_dtype=torch.bfloat16, pad=64)
-            return (ops.zero_scalar(logits.device).expand(ctx.shape),) + (None,) * 6
-        dl = ops.rnnt_pruned_bwd(logits, tg, fl, tl, s, ctx.U, ws, go, ctx.blank)
-        return (dl.reshape(ctx.shape),) + (None,) * 6
+        bwd = functools.partial(ops.rnnt_pruned_bwd, logits, tg, fl, tl, s, ctx.U, ws, _scalar_f32(dloss), ctx.blank)
+        return (_hand_back(ctx, bwd, ctx.shape),) + (None,) * 6
 
 
 # ================================================================================================ MWER over the n-best
 class SeqLogProbFn(Function):
     """score[r] = sum over the rows of segment r of log_softmax(logits)[m, tgt[m]] (ops.seq_logprob), differentiable in the logits
     (MWER training).  -> (score (R,) fp32, tok (M,) fp32, not differentiable).
-    backward: ONE launch of asr_seq_logprob_bwd with the incoming gradient of `score` as the per-segment coefficients.  When the logits
-    come straight from the vocabulary projection of a bf16 model, its part of the gradient goes through the logit hand-over slot exactly
-    as CEFn's does (bf16, zero padded to 64 columns, a stride-0 zero as the formal gradient); otherwise the formal fp32 gradient is
-    returned."""
+    backward: ONE launch of asr_seq_logprob_bwd with the incoming gradient of `score` as the per-segment coefficients, through the
+    logit hand-over (_claim_logits / _hand_back above)."""
 
     @staticmethod
     def forward(ctx, logits, tgt, seg_off):
         assert logits.dim() == 2 and logits.dtype == torch.float32
         out = ops.seq_logprob(logits, tgt, seg_off)
         ctx.t = (logits, tgt, seg_off)
-        ctx.handover = _logit_handover.claim(logits) if ctx.needs_input_grad[0] else None
+        _claim_logits(ctx, logits)
         ctx.mark_non_differentiable(out["tok"])
         return out["score"], out["tok"]
 
     @staticmethod
     def backward(ctx, dscore, *unused):
         logits, tgt, seg_off = ctx.t
-        coef = dscore.float().contiguous()
-        if ctx.handover is not None:
-            ctx.handover["dy"] = ops.seq_logprob_bwd(logits, tgt, seg_off, coef, out_dtype=torch.bfloat16, pad=64)
-            return ops.zero_scalar(logits.device).expand(logits.shape), None, None
-        return ops.seq_logprob_bwd(logits, tgt, seg_off, coef), None, None
+        bwd = functools.partial(ops.seq_logprob_bwd, logits, tgt, seg_off, dscore.float().contiguous())
+        return _hand_back(ctx, bwd, logits.shape), None, None
 
 
 class MwerLossFn(Function):

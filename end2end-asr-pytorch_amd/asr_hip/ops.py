@@ -562,6 +562,24 @@ def embed_bwd(tok, dout, dtable, scale, p, seed, pad_id):
 
 
 # ------------------------------------------------------------------------------------------------ loss
+# A logit gradient (ce_bwd, distill_bwd, rnnt_bwd, rnnt_pruned_bwd, seq_logprob_bwd) is written into an (M, ldd) buffer, ldd = V rounded up
+# to `pad` columns, whose pad columns the kernel zeroes.  The wrapper returns its (M,V) view -- or, with pad=64, the WHOLE buffer: what the
+# vocabulary projection's data-gradient GEMM contracts (functions._hand_back).
+def _grad_rows(M, V, pad, device, dtype):
+    ldd = (V + pad - 1) // pad * pad
+    return torch.empty((M, ldd), device=device, dtype=dtype), ldd
+
+
+def _grad_view(dl, V, pad):
+    return dl if pad == 64 else dl[:, :V]
+
+
+def _check_lengths(B, *lengths):
+    """Every per-utterance length vector: int32, B elements, contiguous (the kernels read them on the device)."""
+    for t in lengths:
+        assert t.dtype == torch.int32 and t.numel() == B and t.is_contiguous()
+
+
 def ce_fwd(logits, gold, smoothing, pad_id, sums=None):
     """logits (M,V) fp32 -> (row_lse (M), argmax (M) int64, sums (3) fp32 = [loss_sum, count, num_correct]).
     sums: optional ZEROED fp32 destination (>= 3 elements) the kernel adds into, e.g. FlatParams.stats."""
@@ -691,8 +709,7 @@ def _rnnt_args(logits, targets, frame_lengths, target_lengths):
     ld = logits.stride(2)
     assert logits.stride(1) == U1 * ld and logits.stride(0) == T * U1 * ld, "rnnt: logits rows at one stride"
     assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (B, max(U1 - 1, 1))
-    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
-    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    _check_lengths(B, frame_lengths, target_lengths)
     return B, T, U1 - 1, V, ld
 
 
@@ -709,15 +726,13 @@ def rnnt_fwd(logits, targets, frame_lengths, target_lengths, blank=0):
 
 
 def rnnt_bwd(logits, targets, frame_lengths, target_lengths, ws, grad_out=None, blank=0, out_dtype=torch.float32, pad=8):
-    """grad_out * d loss / d logits of rnnt_fwd, ONE launch.  Returned like ce_bwd's: a (B T (U+1), V) view of a buffer V rounded up to
-    `pad` wide whose pad columns are zero, the WHOLE buffer with pad=64 (what the data-gradient GEMM contracts)."""
+    """grad_out * d loss / d logits of rnnt_fwd, ONE launch, as B T (U+1) logit-gradient rows (_grad_rows / _grad_view)."""
     B, T, U, V, ld = _rnnt_args(logits, targets, frame_lengths, target_lengths)
     assert grad_out is None or (grad_out.dtype == torch.float32 and grad_out.numel() == 1)
-    ldd = (V + pad - 1) // pad * pad
-    dl = torch.empty((B * T * (U + 1), ldd), device=logits.device, dtype=out_dtype)
+    dl, ldd = _grad_rows(B * T * (U + 1), V, pad, logits.device, out_dtype)
     L.call("asr_rnnt_bwd", L.ptr(logits), ld, L.ptr(targets), L.ptr(frame_lengths), L.ptr(target_lengths), B, T, U, V, int(blank),
            L.ptr(ws), L.ptr(grad_out), L.ptr(dl), ldd, L.dt(dl), L.stream())
-    return dl if pad == 64 else dl[:, :V]
+    return _grad_view(dl, V, pad)
 
 
 # ------------------------------------------------------------------------------------------------ pruned transducer (csrc/rnnt_pruned.hip)
@@ -729,8 +744,7 @@ def _rnnt_simple_args(am, lm, targets, frame_lengths, target_lengths):
         assert x.dtype == torch.float32 and (x.stride(2) == 1 or V == 1) and x.stride(0) == x.shape[1] * x.stride(1), \
             "rnnt_simple: fp32 rows at one stride"
     assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (B, max(U1 - 1, 1))
-    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
-    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    _check_lengths(B, frame_lengths, target_lengths)
     return B, T, U1 - 1, V
 
 
@@ -769,8 +783,7 @@ def rnnt_prune_ranges(gb, gl, frame_lengths, target_lengths, prune_range):
     gl (B,T,U+1) fp32 of rnnt_simple_fwd (the rule: csrc/rnnt_pruned.hip).  One launch, nothing copied to the host."""
     B, T, U1 = gb.shape
     assert gl.shape == gb.shape and gb.dtype == gl.dtype == torch.float32 and gb.is_contiguous() and gl.is_contiguous()
-    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
-    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    _check_lengths(B, frame_lengths, target_lengths)
     s = torch.empty((B, T), device=gb.device, dtype=torch.int32)
     L.call("asr_rnnt_prune_ranges", L.ptr(gb), L.ptr(gl), L.ptr(frame_lengths), L.ptr(target_lengths), B, T, U1 - 1, int(prune_range),
            L.ptr(s), L.stream())
@@ -817,8 +830,7 @@ def _rnnt_pruned_args(logits, targets, frame_lengths, target_lengths, s_begin, U
     ld = logits.stride(2)
     assert logits.stride(1) == W * ld and logits.stride(0) == T * W * ld, "rnnt_pruned: logits rows at one stride"
     assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (B, max(U, 1))
-    assert frame_lengths.dtype == torch.int32 and frame_lengths.numel() == B and frame_lengths.is_contiguous()
-    assert target_lengths.dtype == torch.int32 and target_lengths.numel() == B and target_lengths.is_contiguous()
+    _check_lengths(B, frame_lengths, target_lengths)
     _band_args(s_begin, B, T, U + 1, W)
     return B, T, U, W, V, ld
 
@@ -836,15 +848,13 @@ def rnnt_pruned_fwd(logits, targets, frame_lengths, target_lengths, s_begin, U, 
 
 
 def rnnt_pruned_bwd(logits, targets, frame_lengths, target_lengths, s_begin, U, ws, grad_out=None, blank=0, out_dtype=torch.float32, pad=8):
-    """grad_out * d loss / d logits of rnnt_pruned_fwd, ONE launch, returned like rnnt_bwd's: a (B T W, V) view of a buffer V rounded up to
-    `pad` wide whose pad columns are zero, the WHOLE buffer with pad=64."""
+    """grad_out * d loss / d logits of rnnt_pruned_fwd, ONE launch, as B T W logit-gradient rows (_grad_rows / _grad_view)."""
     B, T, U, W, V, ld = _rnnt_pruned_args(logits, targets, frame_lengths, target_lengths, s_begin, int(U))
     assert grad_out is None or (grad_out.dtype == torch.float32 and grad_out.numel() == 1)
-    ldd = (V + pad - 1) // pad * pad
-    dl = torch.empty((B * T * W, ldd), device=logits.device, dtype=out_dtype)
+    dl, ldd = _grad_rows(B * T * W, V, pad, logits.device, out_dtype)
     L.call("asr_rnnt_pruned_bwd", L.ptr(logits), ld, L.ptr(targets), L.ptr(frame_lengths), L.ptr(target_lengths), L.ptr(s_begin), B, T, U, W,
            V, int(blank), L.ptr(ws), L.ptr(grad_out), L.ptr(dl), ldd, L.dt(dl), L.stream())
-    return dl if pad == 64 else dl[:, :V]
+    return _grad_view(dl, V, pad)
 
 
 def rnnt_beam_search(e, tables, w_out, b_out, lengths, beam_width, candidates=0, max_symbols=5, nbest=1, blank=0, sos=1, ngram=None,
@@ -1278,9 +1288,8 @@ def seq_logprob(logits, tgt, seg_off):
 
 def seq_logprob_bwd(logits, tgt, seg_off, coef, grad_out=None, out_dtype=torch.float32, pad=8):
     """The backward of seq_logprob (csrc/mwer.hip): row m of segment r gets c * ([v == tgt[m]] - softmax(logits[m])[v]) with c = grad_out
-    * coef[r]; coef (R,) fp32 on the device, grad_out a device scalar or None (= 1).  Returned like ce_bwd's: an (M,V) view of an (M, V
-    rounded up to `pad`) buffer whose pad columns are zero, the WHOLE buffer with pad=64 (what the data-gradient GEMM contracts).  Rows
-    with c == 0, a tgt outside [0,V) or no segment are zero and their logits are not read."""
+    * coef[r]; coef (R,) fp32 on the device, grad_out a device scalar or None (= 1).  Returned as logit-gradient rows (_grad_rows /
+    _grad_view).  Rows with c == 0, a tgt outside [0,V) or no segment are zero and their logits are not read."""
     M, V = logits.shape
     R = seg_off.numel() - 1
     assert logits.dtype == torch.float32 and (logits.stride(1) == 1 or V == 1 or M == 0)
@@ -1288,11 +1297,10 @@ def seq_logprob_bwd(logits, tgt, seg_off, coef, grad_out=None, out_dtype=torch.f
     assert seg_off.dtype == torch.int32 and R >= 0 and seg_off.is_contiguous()
     assert coef.dtype == torch.float32 and coef.numel() == R and coef.is_contiguous()
     assert grad_out is None or (grad_out.dtype == torch.float32 and grad_out.numel() == 1)
-    ld = (V + pad - 1) // pad * pad
-    dl = torch.empty((M, ld), device=logits.device, dtype=out_dtype)
+    dl, ldd = _grad_rows(M, V, pad, logits.device, out_dtype)
     L.call("asr_seq_logprob_bwd", L.ptr(logits), logits.stride(0) if M else V, L.ptr(tgt), L.ptr(seg_off), L.ptr(coef), L.ptr(grad_out),
-           R, M, V, L.ptr(dl), ld, L.dt(dl), L.stream())
-    return dl if pad == 64 else dl[:, :V]
+           R, M, V, L.ptr(dl), ldd, L.dt(dl), L.stream())
+    return _grad_view(dl, V, pad)
 
 
 MWER_NBEST_MAX = 16          # hypotheses per utterance asr_mwer_loss is specified for (= the CTC prefix beam search's widest beam)
@@ -1315,14 +1323,12 @@ def mwer_loss(score, err, utt_off, risk_scale, gold_scale):
 
 
 def ce_bwd(logits, gold, lse, smoothing, pad_id, grad_out, count, out_dtype=torch.float32, pad=8):
-    """Returns dlogits as an (M,V) view of an (M, V rounded up to `pad`) buffer whose pad columns are zero; with a 64-column pad
-    the WHOLE padded buffer is returned (the data-gradient GEMM contracts the padded width)."""
+    """dlogits of ce_fwd / ce_fwd_det as logit-gradient rows (_grad_rows / _grad_view); grad_out and count are device scalars."""
     M, V = logits.shape
-    ld = (V + pad - 1) // pad * pad
-    dl = torch.empty((M, ld), device=logits.device, dtype=out_dtype)
+    dl, ldd = _grad_rows(M, V, pad, logits.device, out_dtype)
     L.call("asr_ce_bwd", L.ptr(logits), logits.stride(0), L.ptr(gold), L.ptr(lse), M, V, float(smoothing), int(pad_id),
-           L.ptr(grad_out), L.ptr(count), L.ptr(dl), ld, L.dt(dl), L.stream())
-    return dl if pad == 64 else dl[:, :V]
+           L.ptr(grad_out), L.ptr(count), L.ptr(dl), ldd, L.dt(dl), L.stream())
+    return _grad_view(dl, V, pad)
 
 
 def _distill_args(student, teacher, gold):
@@ -1356,16 +1362,14 @@ def distill_fwd(student, teacher, gold, smoothing, pad_id, temperature, ce_scale
 def distill_bwd(student, teacher, gold, row_stats, smoothing, pad_id, temperature, ce_scale, kd_scale, grad_out, count,
                 out_dtype=torch.float32, pad=8):
     """The combined CE + KD logit gradient of distill_fwd, one launch: c (ce_scale (softmax(s) sum_q - q) + kd_scale tau (pS - pT)) with
-    c = grad_out / count (device scalars) on live rows, zero on dead ones.  Returned like ce_bwd's: an (M,V) view of an (M, V rounded up
-    to `pad`) buffer whose pad columns are zero, the WHOLE buffer with pad=64."""
+    c = grad_out / count (device scalars) on live rows, zero on dead ones.  Returned as logit-gradient rows (_grad_rows / _grad_view)."""
     M, V = _distill_args(student, teacher, gold)
     assert row_stats.dtype == torch.float32 and row_stats.shape == (M, 4) and row_stats.is_contiguous()
-    ld = (V + pad - 1) // pad * pad
-    dl = torch.empty((M, ld), device=student.device, dtype=out_dtype)
+    dl, ldd = _grad_rows(M, V, pad, student.device, out_dtype)
     L.call("asr_distill_bwd", L.ptr(student), student.stride(0), L.ptr(teacher), teacher.stride(0), L.ptr(gold), L.ptr(row_stats), M, V,
            float(smoothing), int(pad_id), float(temperature), float(ce_scale), float(kd_scale), L.ptr(grad_out), L.ptr(count), L.ptr(dl),
-           ld, L.dt(dl), L.stream())
-    return dl if pad == 64 else dl[:, :V]
+           ldd, L.dt(dl), L.stream())
+    return _grad_view(dl, V, pad)
 
 
 # ------------------------------------------------------------------------------------------------ optimiser

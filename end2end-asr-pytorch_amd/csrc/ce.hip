@@ -3,7 +3,8 @@
 // HBM-bound: forward reads M*V*4 bytes once (second pass is L2-resident), backward reads M*V*4 and writes
 // M*ldd*sizeof(T).
 #include "common.h"
-#include "topk.h"            // MaxIdx, better: the arg-max order (shared with csrc/rnnt_beam.hip)
+#include "topk.h"            // MaxIdx, wave_best, block_best: the arg-max order (shared with csrc/rnnt_beam.hip)
+#include "loss_rows.h"       // Smoothing, smoothed_row_loss, finish_sums (shared with csrc/distill.hip)
 
 namespace {
 
@@ -39,11 +40,7 @@ __global__ __launch_bounds__(64 * CE_ROWS) void ce_fwd_kernel(const float* __res
       sum += x;
       if (x > mi.v) { mi.v = x; mi.i = v; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      MaxIdx t{__shfl_xor(mi.v, o, 64), __shfl_xor(mi.i, o, 64)};
-      mi = better(mi, t);
-    }
+    mi = wave_best(mi);
     sum = wave_sum(sum);
     float e = 0.f;
 #pragma unroll 4
@@ -60,14 +57,7 @@ __global__ __launch_bounds__(64 * CE_ROWS) void ce_fwd_kernel(const float* __res
       const int64_t g = gold[row];
       if (g != pad_id) {
         const float lpg = l[g] - lse;
-        float loss;
-        if (eps > 0.f) {
-          const float sum_lp = sum - (float)V * lse;
-          loss = -((1.f - eps) * lpg + (eps / (float)V) * (sum_lp - lpg));
-        } else {
-          loss = -lpg;
-        }
-        part[0] = loss;
+        part[0] = smoothed_row_loss(lpg, sum, V, lse, eps);
         part[1] = 1.f;
         part[2] = mi.i == g ? 1.f : 0.f;
       }
@@ -86,33 +76,19 @@ __global__ __launch_bounds__(64 * CE_ROWS) void ce_fwd_kernel(const float* __res
   }
 }
 
-// sums[k] = the blocks' partial sums added in a fixed order (thread t takes blocks t, t + 256, ...; then a tree over the threads);
-// loss = sums[0] / (den ? den[0] : sums[1])
+// sums[k] = the blocks' partial sums added in a fixed order (finish_sums of csrc/loss_rows.h); loss = sums[0] / (den ? den[0] : sums[1])
 __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict__ partials, int nblocks, const float* __restrict__ den,
                                                         float* __restrict__ sums, float* __restrict__ loss) {
   __shared__ float red[3][256];
   const int tid = threadIdx.x;
-  float a[3] = {0.f, 0.f, 0.f};
-  for (int b = tid; b < nblocks; b += 256)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] += partials[(int64_t)b * 3 + k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) red[k][tid] = a[k];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k][tid] += red[k][tid + o];
-    __syncthreads();
-  }
+  finish_sums<3>(partials, nblocks, red);
   if (tid < 3) sums[tid] = red[tid][0];
   if (tid == 0) loss[0] = red[0][0] / (den ? den[0] : red[1][0]);
 }
 
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ logits, int64_t ld, int V,
                                                           int64_t* __restrict__ out) {
-  __shared__ float s_v[4]; __shared__ int s_i[4];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row = blockIdx.x, tid = threadIdx.x;
   const float* l = logits + (int64_t)row * ld;
   MaxIdx mi{-INFINITY, 0x7fffffff};
   const int V4 = ((((uintptr_t)l) & 15) == 0) ? (V & ~3) : 0;
@@ -128,19 +104,8 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     const float x = l[v];
     if (x > mi.v) { mi.v = x; mi.i = v; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    MaxIdx t{__shfl_xor(mi.v, o, 64), __shfl_xor(mi.i, o, 64)};
-    mi = better(mi, t);
-  }
-  if (lane == 0) { s_v[wave] = mi.v; s_i[wave] = mi.i; }
-  __syncthreads();
-  if (tid == 0) {
-    MaxIdx m{s_v[0], s_i[0]};
-#pragma unroll
-    for (int w = 1; w < 4; ++w) m = better(m, MaxIdx{s_v[w], s_i[w]});
-    out[row] = m.i == 0x7fffffff ? 0 : m.i;
-  }
+  const MaxIdx m = block_best(mi);
+  if (tid == 0) out[row] = m.i == 0x7fffffff ? 0 : m.i;
 }
 
 // Beam-search scoring (reference: transformer.py:446-449, F.log_softmax + torch.topk per hypothesis): the k best log-probabilities
@@ -149,8 +114,6 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
 constexpr int TOPK_MAX = 16;
 __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __restrict__ logits, int64_t ld, int V, int k,
                                                               float* __restrict__ vals, int64_t* __restrict__ idx) {
-  __shared__ float s_v[4];
-  __shared__ int s_i[4];
   __shared__ float s_red[2][4];
   __shared__ int taken[TOPK_MAX];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -175,17 +138,8 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __res
       const float x = l[v];
       if (!used && (x > mi.v || (x == mi.v && v < mi.i))) { mi.v = x; mi.i = v; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      MaxIdx t{__shfl_xor(mi.v, o, 64), __shfl_xor(mi.i, o, 64)};
-      mi = better(mi, t);
-    }
-    if (lane == 0) { s_v[wave] = mi.v; s_i[wave] = mi.i; }
-    __syncthreads();
+    const MaxIdx m = block_best(mi);
     if (tid == 0) {
-      MaxIdx m{s_v[0], s_i[0]};
-#pragma unroll
-      for (int w = 1; w < 4; ++w) m = better(m, MaxIdx{s_v[w], s_i[w]});
       taken[j] = m.i;
       vals[(int64_t)row * k + j] = m.v - lse;
       idx[(int64_t)row * k + j] = m.i == 0x7fffffff ? 0 : m.i;
@@ -209,12 +163,10 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
   const float coef = (*grad_out) / (*count);
   const float* l = logits + (int64_t)row * ld;
   const float lse = row_lse[row];
-  const float q_other = eps > 0.f ? eps / (float)V : 0.f;
-  const float q_gold = eps > 0.f ? 1.f - eps : 1.f;
-  const float sum_q = q_gold + (float)(V - 1) * q_other;
+  const Smoothing q(eps, V);
   for (int v = threadIdx.x; v < ldd; v += 256) {
     float o = 0.f;
-    if (v < V) o = coef * (expf(l[v] - lse) * sum_q - (v == g ? q_gold : q_other));
+    if (v < V) o = coef * (expf(l[v] - lse) * q.sum_q - (v == g ? q.q_gold : q.q_other));
     DT<T>::st(d + v, o);
   }
 }
@@ -226,10 +178,8 @@ extern "C" int asr_ce_fwd(const float* logits, int64_t ld, const int64_t* gold, 
   ASR_CHECK_ARG(logits && gold && row_lse && argmax && sums && M >= 0 && V > 0 && ld >= V && smoothing >= 0.f);
   if (M == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_CE, s);
-  hipLaunchKernelGGL(ce_fwd_kernel, dim3((M + CE_ROWS - 1) / CE_ROWS), dim3(64 * CE_ROWS), 0, s, logits, ld, gold, M, V, smoothing, pad_id,
-                     row_lse, argmax, sums, (float*)nullptr);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<ce_fwd_kernel>(dim3((M + CE_ROWS - 1) / CE_ROWS), dim3(64 * CE_ROWS), 0, s, logits, ld, gold, M, V, smoothing, pad_id,
+                                   row_lse, argmax, sums, (float*)nullptr);
 }
 
 extern "C" int asr_ce_partial_blocks(int M) { return M > 0 ? (M + CE_ROWS - 1) / CE_ROWS : 0; }
@@ -239,17 +189,13 @@ extern "C" int asr_ce_fwd_partials(const float* logits, int64_t ld, const int64_
   ASR_CHECK_ARG(logits && gold && row_lse && argmax && partials && M >= 0 && V > 0 && ld >= V && smoothing >= 0.f);
   if (M == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_CE, s);
-  hipLaunchKernelGGL(ce_fwd_kernel, dim3((M + CE_ROWS - 1) / CE_ROWS), dim3(64 * CE_ROWS), 0, s, logits, ld, gold, M, V, smoothing, pad_id,
-                     row_lse, argmax, (float*)nullptr, partials);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<ce_fwd_kernel>(dim3((M + CE_ROWS - 1) / CE_ROWS), dim3(64 * CE_ROWS), 0, s, logits, ld, gold, M, V, smoothing, pad_id,
+                                   row_lse, argmax, (float*)nullptr, partials);
 }
 
 extern "C" int asr_ce_finish(const float* partials, int nblocks, const float* den, float* sums, float* loss, hipStream_t s) {
   ASR_CHECK_ARG(sums && loss && nblocks >= 0 && (partials || nblocks == 0));
-  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, s, partials, nblocks, den, sums, loss);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<ce_finish_kernel>(dim3(1), dim3(256), 0, s, partials, nblocks, den, sums, loss);
 }
 
 extern "C" int asr_ce_bwd(const float* logits, int64_t ld, const int64_t* gold, const float* row_lse, int M, int V,
@@ -258,30 +204,22 @@ extern "C" int asr_ce_bwd(const float* logits, int64_t ld, const int64_t* gold, 
   ASR_CHECK_ARG(logits && gold && row_lse && grad_out && count && dlogits && M >= 0 && V > 0 && ld >= V && ldd >= V);
   if (M == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_CE, s);
-  if (out_dtype == ASR_F32)
-    hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3(M), dim3(256), 0, s, logits, ld, gold, row_lse, V, smoothing, pad_id,
-                       grad_out, count, (float*)dlogits, ldd);
-  else if (out_dtype == ASR_BF16)
-    hipLaunchKernelGGL((ce_bwd_kernel<bf16_t>), dim3(M), dim3(256), 0, s, logits, ld, gold, row_lse, V, smoothing, pad_id,
-                       grad_out, count, (bf16_t*)dlogits, ldd);
-  else return ASR_EINVAL;
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return asr_launch<ce_bwd_kernel<T>>(dim3(M), dim3(256), 0, s, logits, ld, gold, row_lse, V, smoothing, pad_id, grad_out, count,
+                                        (T*)dlogits, ldd);
+  });
 }
 
 extern "C" int asr_argmax_rows(const float* logits, int64_t ld, int M, int V, int64_t* out, hipStream_t s) {
   ASR_CHECK_ARG(logits && out && M >= 0 && V > 0 && ld >= V);
   if (M == 0) return ASR_OK;
-  hipLaunchKernelGGL(argmax_rows_kernel, dim3(M), dim3(256), 0, s, logits, ld, V, out);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<argmax_rows_kernel>(dim3(M), dim3(256), 0, s, logits, ld, V, out);
 }
 
 extern "C" int asr_logsoftmax_topk(const float* logits, int64_t ld, int M, int V, int k, float* vals, int64_t* idx, hipStream_t s) {
   ASR_CHECK_ARG(logits && vals && idx && M >= 0 && V > 0 && ld >= V && k > 0 && k <= V);
   if (k > TOPK_MAX) return ASR_EUNSUPPORTED;
   if (M == 0) return ASR_OK;
-  hipLaunchKernelGGL(logsoftmax_topk_kernel, dim3(M), dim3(256), 0, s, logits, ld, V, k, vals, idx);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<logsoftmax_topk_kernel>(dim3(M), dim3(256), 0, s, logits, ld, V, k, vals, idx);
 }

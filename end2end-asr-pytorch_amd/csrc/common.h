@@ -194,6 +194,13 @@ static inline uint32_t asr_drop_threshold(float p) {
     if (hipGetLastError() != hipSuccess) return ASR_ELAUNCH;   \
   } while (0)
 
+// an entry of several launches: return the first status that is not ASR_OK (variadic: a template argument list has commas)
+#define ASR_TRY(...)                        \
+  do {                                      \
+    const int rc_ = (__VA_ARGS__);          \
+    if (rc_ != ASR_OK) return rc_;          \
+  } while (0)
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline bool aligned8(const void* p) { return (((uintptr_t)p) & 7) == 0; }

@@ -4,20 +4,17 @@
 // takes one gradient per logits tensor).  One wave per row, DS_ROWS rows per block, no atomics: the results are a function of the
 // inputs alone.  Forward reads 2*M*V*4 bytes (its second pass is L2-resident), backward the same and writes M*ldd elements.
 #include "common.h"
+#include "topk.h"            // MaxIdx, wave_best: the arg-max order of csrc/ce.hip
 
 // The two load arms of a row pass (16-byte loads / one by one) feed the same values in the same order through the same arithmetic; without
 // multiply-add contraction the compiler cannot round the two differently.
 #pragma clang fp contract(off)
 
+#include "loss_rows.h"       // Smoothing, smoothed_row_loss, finish_sums: behind the pragma, so they round as this file does
+
 namespace {
 
 constexpr int DS_ROWS = 8;
-
-struct MaxIdx { float v; int i; };
-__device__ __forceinline__ MaxIdx better(MaxIdx a, MaxIdx b) {     // greater value, lowest index on ties
-  if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
 
 __device__ __forceinline__ float4 ld4(const float* __restrict__ p, bool vec) {
   if (vec) return *reinterpret_cast<const float4*>(p);
@@ -72,11 +69,7 @@ __global__ __launch_bounds__(64 * DS_ROWS) void distill_fwd_kernel(const float* 
         if (a > mi.v) { mi.v = a; mi.i = v; }              // strictly greater, ascending v: the lowest index per lane
         mt = fmaxf(mt, b);
       });
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        MaxIdx t{__shfl_xor(mi.v, o, 64), __shfl_xor(mi.i, o, 64)};
-        mi = better(mi, t);
-      }
+      mi = wave_best(mi);
       mt = wave_max(mt);
       if (CE) sum = wave_sum(sum);
       // x -> x / tau is monotone (tau > 0, correctly rounded), so the maxima of the softened rows are the softened maxima
@@ -107,14 +100,7 @@ __global__ __launch_bounds__(64 * DS_ROWS) void distill_fwd_kernel(const float* 
         st[0] = lse;
         am = mi.i == 0x7fffffff ? 0 : mi.i;
         const float lpg = (g >= 0 && g < V) ? ls[g] - lse : 0.f;
-        float loss;
-        if (eps > 0.f) {
-          const float sum_lp = sum - (float)V * lse;
-          loss = -((1.f - eps) * lpg + (eps / (float)V) * (sum_lp - lpg));
-        } else {
-          loss = -lpg;
-        }
-        part[0] = loss;
+        part[0] = smoothed_row_loss(lpg, sum, V, lse, eps);
         part[2] = mi.i == g ? 1.f : 0.f;
       }
     }
@@ -131,30 +117,20 @@ __global__ __launch_bounds__(64 * DS_ROWS) void distill_fwd_kernel(const float* 
   }
 }
 
-// sums[k] = the blocks' partial sums added in a fixed order (thread t takes blocks t, t + 256, ...; then a tree over the threads);
+// sums[k] = the blocks' partial sums added in a fixed order (finish_sums of csrc/loss_rows.h);
 // loss = (ce_scale sums[0] + kd_scale sums[3]) / (den ? den[0] : sums[1])
 __global__ __launch_bounds__(256) void distill_finish_kernel(const float* __restrict__ partials, int nblocks, const float* __restrict__ den,
                                                              float ce_scale, float kd_scale, float* __restrict__ sums,
                                                              float* __restrict__ loss) {
   __shared__ float red[4][256];
   const int tid = threadIdx.x;
-  float a[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int b = tid; b < nblocks; b += 256)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] += partials[(int64_t)b * 4 + k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) red[k][tid] = a[k];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + o];
-    __syncthreads();
-  }
+  finish_sums<4>(partials, nblocks, red);
   if (tid < 4) sums[tid] = red[tid][0];
   if (tid == 0) loss[0] = (ce_scale * red[0][0] + kd_scale * red[3][0]) / (den ? den[0] : red[1][0]);
 }
 
+// (its own four-wide store and one-by-one dead-row loop, not store4 / GradRow::zero of csrc/loss_rows.h: with those both arms gained a VGPR
+// and the bf16 arm 36 instructions, and it measured at the upper edge of the parent's range; profiles/loss_rows_refactor.txt)
 struct alignas(8) bf16x4_t { bf16_t v[4]; };
 __device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) {
   if ((((uintptr_t)p) & 15) == 0) { *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d); return; }
@@ -186,9 +162,7 @@ __global__ __launch_bounds__(64 * DS_ROWS) void distill_bwd_kernel(const float* 
   const float* ls = student + (int64_t)row * ld_s;
   const float* lt = teacher + (int64_t)row * ld_t;
   const float lse = row_stats[(int64_t)row * 4], lse_s = row_stats[(int64_t)row * 4 + 1], lse_t = row_stats[(int64_t)row * 4 + 2];
-  const float q_other = eps > 0.f ? eps / (float)V : 0.f;
-  const float q_gold = eps > 0.f ? 1.f - eps : 1.f;
-  const float sum_q = q_gold + (float)(V - 1) * q_other;
+  const Smoothing q(eps, V);
   const float kt = kd_scale * tau;
   const bool ce = ce_scale != 0.f;
   // The fp32 arm (parity mode, and the CTC head's frame-level term) first sums each distribution as it will be formed, exp(x - lse), and
@@ -209,9 +183,10 @@ __global__ __launch_bounds__(64 * DS_ROWS) void distill_bwd_kernel(const float* 
   }
   auto grad = [&](int v, float a, float b) {
     float o = kt * (soft_prob(a, tau, lse_s) / zs - soft_prob(b, tau, lse_t) / zt);
-    if (ce) o = ce_scale * (expf(a - lse) / zc * sum_q - (v == g ? q_gold : q_other)) + o;
+    if (ce) o = ce_scale * (expf(a - lse) / zc * q.sum_q - (v == g ? q.q_gold : q.q_other)) + o;
     return coef * o;
   };
+  // this kernel stays off GradRow (csrc/loss_rows.h): it reads two tensors and owns its columns by V4 as row_pairs does, not by ldd4
   const bool vs = (((uintptr_t)ls) & 15) == 0, vt = (((uintptr_t)lt) & 15) == 0;
   const int V4 = V & ~3;
 #pragma unroll 2
@@ -235,22 +210,16 @@ extern "C" int asr_distill_fwd(const float* student, int64_t ld_s, const float* 
                 temperature <= 16.f);
   AsrProfScope prof(ASR_OP_CE, s);
   const dim3 grid((M + DS_ROWS - 1) / DS_ROWS), block(64 * DS_ROWS);
-  if (with_ce)
-    hipLaunchKernelGGL((distill_fwd_kernel<true>), grid, block, 0, s, student, ld_s, teacher, ld_t, gold, M, V, smoothing, pad_id,
-                       temperature, row_stats, argmax, partials);
-  else
-    hipLaunchKernelGGL((distill_fwd_kernel<false>), grid, block, 0, s, student, ld_s, teacher, ld_t, gold, M, V, smoothing, pad_id,
-                       temperature, row_stats, argmax, partials);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return with_ce ? asr_launch<distill_fwd_kernel<true>>(grid, block, 0, s, student, ld_s, teacher, ld_t, gold, M, V, smoothing, pad_id,
+                                                        temperature, row_stats, argmax, partials)
+                 : asr_launch<distill_fwd_kernel<false>>(grid, block, 0, s, student, ld_s, teacher, ld_t, gold, M, V, smoothing, pad_id,
+                                                         temperature, row_stats, argmax, partials);
 }
 
 extern "C" int asr_distill_finish(const float* partials, int nblocks, const float* den, float ce_scale, float kd_scale, float* sums,
                                   float* loss, hipStream_t s) {
   ASR_CHECK_ARG(sums && loss && nblocks >= 0 && (partials || nblocks == 0));
-  hipLaunchKernelGGL(distill_finish_kernel, dim3(1), dim3(256), 0, s, partials, nblocks, den, ce_scale, kd_scale, sums, loss);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<distill_finish_kernel>(dim3(1), dim3(256), 0, s, partials, nblocks, den, ce_scale, kd_scale, sums, loss);
 }
 
 extern "C" int asr_distill_bwd(const float* student, int64_t ld_s, const float* teacher, int64_t ld_t, const int64_t* gold,
@@ -263,12 +232,9 @@ extern "C" int asr_distill_bwd(const float* student, int64_t ld_s, const float* 
   if (out_dtype != ASR_F32 && out_dtype != ASR_BF16) return ASR_EINVAL;
   AsrProfScope prof(ASR_OP_CE, s);
   const dim3 grid((M + DS_ROWS - 1) / DS_ROWS), block(64 * DS_ROWS);
-  if (out_dtype == ASR_F32)
-    hipLaunchKernelGGL((distill_bwd_kernel<float>), grid, block, 0, s, student, ld_s, teacher, ld_t, gold, row_stats, M, V, smoothing,
-                       pad_id, temperature, ce_scale, kd_scale, grad_out, count, (float*)dlogits, ldd);
-  else
-    hipLaunchKernelGGL((distill_bwd_kernel<bf16_t>), grid, block, 0, s, student, ld_s, teacher, ld_t, gold, row_stats, M, V, smoothing,
-                       pad_id, temperature, ce_scale, kd_scale, grad_out, count, (bf16_t*)dlogits, ldd);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return asr_launch<distill_bwd_kernel<T>>(grid, block, 0, s, student, ld_s, teacher, ld_t, gold, row_stats, M, V, smoothing, pad_id,
+                                             temperature, ce_scale, kd_scale, grad_out, count, (T*)dlogits, ldd);
+  });
 }

@@ -1,5 +1,5 @@
-// Online log-sum-exp of a logits row, one wave per row: shared by csrc/seq_logprob.hip (forward) and csrc/mwer.hip (its backward), so the
-// backward recomputes the forward's normaliser with the forward's code and the forward's bits.
+// Online log-sum-exp of a logits row, one wave per row: shared by csrc/seq_logprob.hip (forward), csrc/mwer.hip (its backward) and the
+// transducer's row pass (csrc/rnnt_lattice.h), so a backward recomputes the forward's normaliser with the forward's code and the forward's bits.
 // A file that includes this compiles WITHOUT multiply-add contraction from here on: the compiler chooses where to fuse loop by loop, and
 // the two load arms of the row pass must round the same sums at the same places.
 #pragma once
@@ -21,6 +21,10 @@ __device__ __forceinline__ Lse lse_merge(Lse a, Lse b) {
   if (lo.m == -INFINITY) return hi;
   return Lse{hi.m, hi.s1 + (lo.s1 + 1.f) * expf(lo.m - hi.m)};
 }
+
+// log softmax of a logit x of a set with maximum m and lz = log1pf(s1) (computed once per row by the caller): (x - max) - log(sum),
+// exact 0 - 0 when x holds all the mass.  x = -inf gives -inf.
+__device__ __forceinline__ float lse_logprob(float x, float m, float lz) { return (x - m) - lz; }
 
 // one logit into a lane's state: one expf whichever of the two is larger, and no branch.  Both load arms of the row pass feed the same
 // values in the same order through this, which is what makes their results the same bits.

@@ -162,16 +162,14 @@ extern "C" int asr_rnnt_fwd(const float* logits, int64_t ld, const int64_t* targ
   float* lpl = lpb + rows;
   float* nll = lpl + rows;
   AsrProfScope prof(ASR_OP_CE, s);
-  hipLaunchKernelGGL(rnnt_row_kernel<false>, dim3((unsigned)ceil_div64(rows, RNNT_ROWS)), dim3(64 * RNNT_ROWS), 0, s, logits, ld, targets, frame_lengths,
-                     target_lengths, T, Umax, V, blank, rows, lse, lpb, lpl, (const int32_t*)nullptr, Umax + 1);
-  ASR_LAUNCH_CHECK();
+  ASR_TRY(asr_launch<rnnt_row_kernel<false>>(dim3((unsigned)ceil_div64(rows, RNNT_ROWS)), dim3(64 * RNNT_ROWS), 0, s, logits, ld, targets, frame_lengths,
+                                             target_lengths, T, Umax, V, blank, rows, lse, lpb, lpl, (const int32_t*)nullptr, Umax + 1));
+  // the whole 64 KB at the first need (asr_launch would grant `lds`): a later batch with a longer U then asks for no second grant, which
+  // must not run inside a stream capture
   if (lds > 48 * 1024) (void)asr_grant_lds<rnnt_lattice_kernel>(64 * 1024);
-  hipLaunchKernelGGL(rnnt_lattice_kernel, dim3(B, 2), dim3(256), lds, s, targets, frame_lengths, target_lengths, T, Umax, V, blank, lpb, lpl,
-                     alpha, beta, nll_d, nll);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rnnt_finish_kernel, dim3(1), dim3(64), 0, s, nll_d, target_lengths, B, Umax, loss);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  ASR_TRY(asr_launch<rnnt_lattice_kernel>(dim3(B, 2), dim3(256), lds, s, targets, frame_lengths, target_lengths, T, Umax, V, blank, lpb, lpl,
+                                          alpha, beta, nll_d, nll));
+  return asr_launch<rnnt_finish_kernel>(dim3(1), dim3(64), 0, s, nll_d, target_lengths, B, Umax, loss);
 }
 
 extern "C" int asr_rnnt_bwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* frame_lengths,
@@ -190,13 +188,11 @@ extern "C" int asr_rnnt_bwd(const float* logits, int64_t ld, const int64_t* targ
   const float* lpl = lpb + rows;
   const dim3 grid((unsigned)ceil_div64(rows, RNNT_ROWS)), block(64 * RNNT_ROWS);
   AsrProfScope prof(ASR_OP_CE, s);
-  if (out_dtype == ASR_F32)
-    hipLaunchKernelGGL((rnnt_bwd_kernel<float, false>), grid, block, 0, s, logits, ld, targets, frame_lengths, target_lengths, B, T, Umax, V, blank, rows,
-                       lse, lpb, lpl, alpha, beta, nll_d, grad_out, (float*)dlogits, ldd, (const int32_t*)nullptr, Umax + 1);
-  else
-    hipLaunchKernelGGL((rnnt_bwd_kernel<bf16_t, false>), grid, block, 0, s, logits, ld, targets, frame_lengths, target_lengths, B, T, Umax, V, blank, rows,
-                       lse, lpb, lpl, alpha, beta, nll_d, grad_out, (bf16_t*)dlogits, ldd, (const int32_t*)nullptr, Umax + 1);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(out_dtype, [&](auto tag) {
+    using E = decltype(tag);
+    return asr_launch<rnnt_bwd_kernel<E, false>>(grid, block, 0, s, logits, ld, targets, frame_lengths, target_lengths, B, T, Umax, V, blank, rows,
+                                                 lse, lpb, lpl, alpha, beta, nll_d, grad_out, (E*)dlogits, ldd, (const int32_t*)nullptr,
+                                                 Umax + 1);
+  });
 }
 

@@ -5,7 +5,8 @@
 // outside the band has no outgoing arc.  With W = U + 1 and s_begin = 0 the two are the same bits.
 #pragma once
 #include "common.h"
-#include "lse.h"        // Lse, lse_row (no multiply-add contraction from here on: a row gives the same bits through either load arm)
+#include "lse.h"        // Lse, lse_row, lse_logprob (no multiply-add contraction from here on: a row gives the same bits through either load arm)
+#include "loss_rows.h"  // GradRow: the gradient rows (shared with csrc/mwer.hip)
 #include "rnnt_common.h"      // rnnt_lae, clampi
 
 namespace {
@@ -52,11 +53,11 @@ __global__ __launch_bounds__(64 * RNNT_ROWS) void rnnt_row_kernel(const float* _
   if (lane == 0) {
     const float lz = log1pf(st.s1);
     lse[row] = st.m + lz;
-    lpb[cell] = (l[blank] - st.m) - lz;
+    lpb[cell] = lse_logprob(l[blank], st.m, lz);
     float ll = -INFINITY;
     if (u < Ub) {
       const int64_t y = targets[(int64_t)b * Umax + u];
-      if (y >= 0 && y < V && y != blank) ll = (l[y] - st.m) - lz;
+      if (y >= 0 && y < V && y != blank) ll = lse_logprob(l[y], st.m, lz);
     }
     lpl[cell] = ll;
   }
@@ -134,15 +135,7 @@ __global__ __launch_bounds__(64) void rnnt_finish_kernel(const double* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ loss: gradient
-template <typename T> struct RVec4;            // four output elements of one lane: a 16-byte (fp32) or 8-byte (bf16) store
-template <> struct RVec4<float> { typedef float4 type; };
-template <> struct RVec4<bf16_t> { typedef ushort4 type; };
-__device__ __forceinline__ float4 rpack4(const float (&o)[4], float*) { return make_float4(o[0], o[1], o[2], o[3]); }
-__device__ __forceinline__ ushort4 rpack4(const float (&o)[4], bf16_t*) {
-  return make_ushort4(f32_to_bf16(o[0]), f32_to_bf16(o[1]), f32_to_bf16(o[2]), f32_to_bf16(o[3]));
-}
-
-// one wave per row; lane `lane` owns columns 4 lane + 256 k .. + 3 up to ldd4, then column ldd4 + lane (seq_bwd_kernel's shape, csrc/mwer.hip)
+// one wave per row, written through GradRow of csrc/loss_rows.h (seq_bwd_kernel's shape, csrc/mwer.hip)
 template <typename T, bool BAND>
 __global__ __launch_bounds__(64 * RNNT_ROWS) void rnnt_bwd_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ targets,
                                                                   const int32_t* __restrict__ frames, const int32_t* __restrict__ tg_len,
@@ -152,7 +145,6 @@ __global__ __launch_bounds__(64 * RNNT_ROWS) void rnnt_bwd_kernel(const float* _
                                                                   const double* __restrict__ beta, const double* __restrict__ nll_d,
                                                                   const float* __restrict__ grad_out, T* __restrict__ dl, int64_t ldd,
                                                                   const int32_t* __restrict__ s_begin, int W) {
-  typedef typename RVec4<T>::type V4T;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * RNNT_ROWS + wave;
   if (row >= rows) return;
@@ -163,9 +155,7 @@ __global__ __launch_bounds__(64 * RNNT_ROWS) void rnnt_bwd_kernel(const float* _
   const int t = (int)(bt % Tn);
   const int b = (int)(bt / Tn);
   const int Tb = clampi(frames[b], 0, Tn), Ub = clampi(tg_len[b], 0, Umax);
-  T* d = dl + row * ldd;
-  const int ldd4 = (int)(ldd & ~(int64_t)3);
-  const bool vst = (((uintptr_t)d) & (sizeof(V4T) - 1)) == 0;
+  const GradRow<T> out(dl + row * ldd, ldd);
   // everything up to here and the values below are the same in all lanes of the wave (a row per wave)
   float gb = 0.f, gl = 0.f, c = 0.f;
   int ycol = -1;
@@ -185,42 +175,16 @@ __global__ __launch_bounds__(64 * RNNT_ROWS) void rnnt_bwd_kernel(const float* _
     }
   }
   if (!live) {                                 // a dead row, or an utterance without an alignment: zeros, its logits are not read
-    const float z[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int v = lane * 4; v < ldd4; v += 256) {
-      if (vst) *reinterpret_cast<V4T*>(d + v) = rpack4(z, d);
-      else { DT<T>::st(d + v, 0.f); DT<T>::st(d + v + 1, 0.f); DT<T>::st(d + v + 2, 0.f); DT<T>::st(d + v + 3, 0.f); }
-    }
-    if (ldd4 + lane < ldd) DT<T>::st(d + ldd4 + lane, 0.f);
+    out.zero(lane);
     return;
   }
   const float* l = logits + row * ld;
   const float ls = lse[row];
   const float g = gb + gl;
-  const bool vld = (((uintptr_t)l) & 15) == 0;
-  for (int v = lane * 4; v < ldd4; v += 256) {
-    float x[4];
-    if (vld && v + 3 < V) {
-      const float4 q = *reinterpret_cast<const float4*>(l + v);
-      x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = v + j < V ? l[v + j] : -INFINITY;            // columns >= V are never read
-    }
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float sm = expf(x[j] - ls);                                               // exp(-inf) = 0: a -inf logit, a pad column
-      o[j] = v + j < V ? c * ((g * sm - (v + j == blank ? gb : 0.f)) - (v + j == ycol ? gl : 0.f)) : 0.f;
-    }
-    if (vst) *reinterpret_cast<V4T*>(d + v) = rpack4(o, d);
-    else { DT<T>::st(d + v, o[0]); DT<T>::st(d + v + 1, o[1]); DT<T>::st(d + v + 2, o[2]); DT<T>::st(d + v + 3, o[3]); }
-  }
-  const int v = ldd4 + lane;
-  if (v < ldd) {
-    float o = 0.f;
-    if (v < V) o = c * ((g * expf(l[v] - ls) - (v == blank ? gb : 0.f)) - (v == ycol ? gl : 0.f));
-    DT<T>::st(d + v, o);
-  }
+  out.write(l, V, lane, [&](int v, float x) {
+    const float sm = expf(x - ls);
+    return c * ((g * sm - (v == blank ? gb : 0.f)) - (v == ycol ? gl : 0.f));
+  });
 }
 
 bool rnnt_rows_ok(int B, int T, int Umax, int64_t* rows) {

@@ -387,26 +387,20 @@ extern "C" int asr_rnnt_simple_fwd(const float* am, int64_t lda, const float* lm
   if (lds > 64 * 1024 || B > 65535 || ceil_div64(T, CT_MN) > 65535 || !grid_ok(ceil_div64(cells, 256))) return ASR_EUNSUPPORTED;
   const SimpleWs w(workspace, B, T, Umax, V);
   AsrProfScope prof(ASR_OP_CE, s);
-  hipLaunchKernelGGL(simple_rows_kernel, dim3((unsigned)ceil_div64(rows, RNNT_ROWS)), dim3(64 * RNNT_ROWS), 0, s, am, lda, lm, ldl, frame_lengths,
-                     target_lengths, B, T, Umax, V, w.ma, w.ml, w.Ea, w.El);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL((rnnt_contract_kernel<false, false, 0>), dim3((U1 + CT_MN - 1) / CT_MN, (T + CT_MN - 1) / CT_MN, B), dim3(256), 0, s, w.Ea,
-                     (int64_t)V, (int64_t)T * V, w.El, (int64_t)V, (int64_t)U1 * V, w.dot, (int64_t)U1, (int64_t)T * U1, T, U1, V,
-                     (const float*)nullptr, (const int32_t*)nullptr, 0, B, (const float*)nullptr);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(simple_cell_kernel, dim3((unsigned)ceil_div64(cells, 256)), dim3(256), 0, s, am, lda, lm, ldl, targets, frame_lengths,
-                     target_lengths, T, Umax, V, blank, cells, w.ma, w.ml, w.dot, w.lpb, w.lpl);
-  ASR_LAUNCH_CHECK();
+  ASR_TRY(asr_launch<simple_rows_kernel>(dim3((unsigned)ceil_div64(rows, RNNT_ROWS)), dim3(64 * RNNT_ROWS), 0, s, am, lda, lm, ldl, frame_lengths,
+                                         target_lengths, B, T, Umax, V, w.ma, w.ml, w.Ea, w.El));
+  ASR_TRY(asr_launch<rnnt_contract_kernel<false, false, 0>>(dim3((U1 + CT_MN - 1) / CT_MN, (T + CT_MN - 1) / CT_MN, B), dim3(256), 0, s, w.Ea,
+                                                            (int64_t)V, (int64_t)T * V, w.El, (int64_t)V, (int64_t)U1 * V, w.dot, (int64_t)U1,
+                                                            (int64_t)T * U1, T, U1, V, (const float*)nullptr, (const int32_t*)nullptr, 0, B, (const float*)nullptr));
+  ASR_TRY(asr_launch<simple_cell_kernel>(dim3((unsigned)ceil_div64(cells, 256)), dim3(256), 0, s, am, lda, lm, ldl, targets, frame_lengths,
+                                         target_lengths, T, Umax, V, blank, cells, w.ma, w.ml, w.dot, w.lpb, w.lpl));
+  // (64 KB at once, as asr_rnnt_fwd)
   if (lds > 48 * 1024) (void)asr_grant_lds<rnnt_lattice_kernel>(64 * 1024);
-  hipLaunchKernelGGL(rnnt_lattice_kernel, dim3(B, 2), dim3(256), lds, s, targets, frame_lengths, target_lengths, T, Umax, V, blank, w.lpb, w.lpl,
-                     w.alpha, w.beta, w.nll_d, w.nll);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rnnt_finish_kernel, dim3(1), dim3(64), 0, s, w.nll_d, target_lengths, B, Umax, loss);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(simple_occ_kernel, dim3((unsigned)ceil_div64(cells, 256)), dim3(256), 0, s, frame_lengths, target_lengths, T, Umax, cells,
-                     w.lpb, w.lpl, w.alpha, w.beta, w.nll_d, w.dot, w.gb, w.gl, w.G);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  ASR_TRY(asr_launch<rnnt_lattice_kernel>(dim3(B, 2), dim3(256), lds, s, targets, frame_lengths, target_lengths, T, Umax, V, blank, w.lpb, w.lpl,
+                                          w.alpha, w.beta, w.nll_d, w.nll));
+  ASR_TRY(asr_launch<rnnt_finish_kernel>(dim3(1), dim3(64), 0, s, w.nll_d, target_lengths, B, Umax, loss));
+  return asr_launch<simple_occ_kernel>(dim3((unsigned)ceil_div64(cells, 256)), dim3(256), 0, s, frame_lengths, target_lengths, T, Umax, cells,
+                                       w.lpb, w.lpl, w.alpha, w.beta, w.nll_d, w.dot, w.gb, w.gl, w.G);
 }
 
 extern "C" int asr_rnnt_simple_bwd(const int64_t* targets, const int32_t* frame_lengths, const int32_t* target_lengths, int B, int T, int Umax,
@@ -420,26 +414,22 @@ extern "C" int asr_rnnt_simple_bwd(const int64_t* targets, const int32_t* frame_
   AsrProfScope prof(ASR_OP_CE, s);
   const unsigned nt = (V + CT_MN - 1) / CT_MN;
   // d am (B,T,V) = c Ea (G El): A = G (T x U1, k minor), B = El (U1 x V, k major)
-  hipLaunchKernelGGL((rnnt_contract_kernel<false, true, 1>), dim3(nt, (T + CT_MN - 1) / CT_MN, B), dim3(256), 0, s, w.G, (int64_t)U1, (int64_t)T * U1,
-                     w.El, (int64_t)V, (int64_t)U1 * V, dam, (int64_t)V, (int64_t)T * V, T, V, U1, w.Ea, target_lengths, Umax, B, grad_out);
-  ASR_LAUNCH_CHECK();
+  ASR_TRY(asr_launch<rnnt_contract_kernel<false, true, 1>>(dim3(nt, (T + CT_MN - 1) / CT_MN, B), dim3(256), 0, s, w.G, (int64_t)U1, (int64_t)T * U1,
+                                                           w.El, (int64_t)V, (int64_t)U1 * V, dam, (int64_t)V, (int64_t)T * V, T, V, U1, w.Ea,
+                                                           target_lengths, Umax, B, grad_out));
   // d lm (B,U1,V) = c El (G^T Ea): A = G (stored T x U1: k major), B = Ea (T x V, k major)
-  hipLaunchKernelGGL((rnnt_contract_kernel<true, true, 1>), dim3(nt, (U1 + CT_MN - 1) / CT_MN, B), dim3(256), 0, s, w.G, (int64_t)U1, (int64_t)T * U1,
-                     w.Ea, (int64_t)V, (int64_t)T * V, dlm, (int64_t)V, (int64_t)U1 * V, U1, V, T, w.El, target_lengths, Umax, B, grad_out);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(simple_onehot_kernel, dim3((unsigned)ceil_div64(rows, 256)), dim3(256), 0, s, targets, frame_lengths, target_lengths, B, T,
-                     Umax, V, blank, w.gb, w.gl, w.nll_d, grad_out, dam, dlm);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  ASR_TRY(asr_launch<rnnt_contract_kernel<true, true, 1>>(dim3(nt, (U1 + CT_MN - 1) / CT_MN, B), dim3(256), 0, s, w.G, (int64_t)U1, (int64_t)T * U1,
+                                                          w.Ea, (int64_t)V, (int64_t)T * V, dlm, (int64_t)V, (int64_t)U1 * V, U1, V, T, w.El,
+                                                          target_lengths, Umax, B, grad_out));
+  return asr_launch<simple_onehot_kernel>(dim3((unsigned)ceil_div64(rows, 256)), dim3(256), 0, s, targets, frame_lengths, target_lengths, B, T,
+                                          Umax, V, blank, w.gb, w.gl, w.nll_d, grad_out, dam, dlm);
 }
 
 extern "C" int asr_rnnt_prune_ranges(const float* gb, const float* gl, const int32_t* frame_lengths, const int32_t* target_lengths, int B,
                                      int T, int Umax, int S, int32_t* s_begin, hipStream_t s) {
   ASR_CHECK_ARG(gb && gl && frame_lengths && target_lengths && s_begin && B > 0 && T > 0 && Umax >= 0 && S >= 1);
   const int W = S < Umax + 1 ? S : Umax + 1;
-  hipLaunchKernelGGL(prune_ranges_kernel, dim3(B), dim3(256), 0, s, gb, gl, frame_lengths, target_lengths, T, Umax, W, s_begin);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<prune_ranges_kernel>(dim3(B), dim3(256), 0, s, gb, gl, frame_lengths, target_lengths, T, Umax, W, s_begin);
 }
 
 extern "C" int asr_rnnt_joint_pruned_fwd(const void* e, const void* p, const int32_t* s_begin, void* z, int B, int T, int U1, int W, int J,
@@ -495,18 +485,14 @@ extern "C" int asr_rnnt_pruned_fwd(const float* logits, int64_t ld, const int64_
   float* lpl = lpb + cells;
   float* nll = lpl + cells;
   AsrProfScope prof(ASR_OP_CE, s);
-  hipLaunchKernelGGL(fill_ninf_kernel, dim3((unsigned)ceil_div64(2 * cells, 256)), dim3(256), 0, s, lpb, 2 * cells);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rnnt_row_kernel<true>, dim3((unsigned)ceil_div64(rows, RNNT_ROWS)), dim3(64 * RNNT_ROWS), 0, s, logits, ld, targets,
-                     frame_lengths, target_lengths, T, Umax, V, blank, rows, lse, lpb, lpl, s_begin, W);
-  ASR_LAUNCH_CHECK();
+  ASR_TRY(asr_launch<fill_ninf_kernel>(dim3((unsigned)ceil_div64(2 * cells, 256)), dim3(256), 0, s, lpb, 2 * cells));
+  ASR_TRY(asr_launch<rnnt_row_kernel<true>>(dim3((unsigned)ceil_div64(rows, RNNT_ROWS)), dim3(64 * RNNT_ROWS), 0, s, logits, ld, targets,
+                                            frame_lengths, target_lengths, T, Umax, V, blank, rows, lse, lpb, lpl, s_begin, W));
+  // (64 KB at once, as asr_rnnt_fwd)
   if (lds > 48 * 1024) (void)asr_grant_lds<rnnt_lattice_kernel>(64 * 1024);
-  hipLaunchKernelGGL(rnnt_lattice_kernel, dim3(B, 2), dim3(256), lds, s, targets, frame_lengths, target_lengths, T, Umax, V, blank, lpb, lpl,
-                     alpha, beta, nll_d, nll);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rnnt_finish_kernel, dim3(1), dim3(64), 0, s, nll_d, target_lengths, B, Umax, loss);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  ASR_TRY(asr_launch<rnnt_lattice_kernel>(dim3(B, 2), dim3(256), lds, s, targets, frame_lengths, target_lengths, T, Umax, V, blank, lpb, lpl,
+                                          alpha, beta, nll_d, nll));
+  return asr_launch<rnnt_finish_kernel>(dim3(1), dim3(64), 0, s, nll_d, target_lengths, B, Umax, loss);
 }
 
 extern "C" int asr_rnnt_pruned_bwd(const float* logits, int64_t ld, const int64_t* targets, const int32_t* frame_lengths,
@@ -526,12 +512,9 @@ extern "C" int asr_rnnt_pruned_bwd(const float* logits, int64_t ld, const int64_
   const float* lpl = lpb + cells;
   const dim3 grid((unsigned)ceil_div64(rows, RNNT_ROWS)), block(64 * RNNT_ROWS);
   AsrProfScope prof(ASR_OP_CE, s);
-  if (out_dtype == ASR_F32)
-    hipLaunchKernelGGL((rnnt_bwd_kernel<float, true>), grid, block, 0, s, logits, ld, targets, frame_lengths, target_lengths, B, T, Umax, V, blank,
-                       rows, lse, lpb, lpl, alpha, beta, nll_d, grad_out, (float*)dlogits, ldd, s_begin, W);
-  else
-    hipLaunchKernelGGL((rnnt_bwd_kernel<bf16_t, true>), grid, block, 0, s, logits, ld, targets, frame_lengths, target_lengths, B, T, Umax, V, blank,
-                       rows, lse, lpb, lpl, alpha, beta, nll_d, grad_out, (bf16_t*)dlogits, ldd, s_begin, W);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_with_dtype(out_dtype, [&](auto tag) {
+    using E = decltype(tag);
+    return asr_launch<rnnt_bwd_kernel<E, true>>(grid, block, 0, s, logits, ld, targets, frame_lengths, target_lengths, B, T, Umax, V, blank, rows,
+                                                lse, lpb, lpl, alpha, beta, nll_d, grad_out, (E*)dlogits, ldd, s_begin, W);
+  });
 }

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64 * SEQ_ROWS) void seq_row_kernel(const float* __r
     float lp = -INFINITY;                      // a target outside [0, V): -inf, nothing read
     if (t >= 0 && t < V) {
       const float xt = l[t];
-      if (xt > -INFINITY) lp = (xt - st.m) - log1pf(st.s1);      // (x - max) - log(sum): exact 0 - 0 when the target holds all the mass
+      if (xt > -INFINITY) lp = (xt - st.m) - log1pf(st.s1);      // lse_logprob of csrc/lse.h written out: the logarithm only where the target has mass
     }
     tok_lp[row] = lp;
   }
@@ -53,9 +53,6 @@ extern "C" int asr_seq_logprob(const float* logits, int64_t ld, const int64_t* t
     if (R > 0 && hipMemsetAsync(score, 0, sizeof(float) * (size_t)R, s) != hipSuccess) return ASR_ERUNTIME;
     return ASR_OK;
   }
-  hipLaunchKernelGGL(seq_row_kernel, dim3((M + SEQ_ROWS - 1) / SEQ_ROWS), dim3(64 * SEQ_ROWS), 0, s, logits, ld, tgt, M, V, tok_lp);
-  ASR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(seq_sum_kernel, dim3((R + 63) / 64), dim3(64), 0, s, tok_lp, seg_off, R, M, score);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  ASR_TRY(asr_launch<seq_row_kernel>(dim3((M + SEQ_ROWS - 1) / SEQ_ROWS), dim3(64 * SEQ_ROWS), 0, s, logits, ld, tgt, M, V, tok_lp));
+  return asr_launch<seq_sum_kernel>(dim3((R + 63) / 64), dim3(64), 0, s, tok_lp, seg_off, R, M, score);
 }
