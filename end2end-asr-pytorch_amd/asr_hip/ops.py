@@ -1866,38 +1866,46 @@ def fbank_upload(bank, device):
     return FbankDevice(first.to(torch.int32).to(device), count.to(torch.int32).to(device), weights.contiguous().to(device), int(K))
 
 
+def _finish_features(reim, ld, lengths, B, F, Tmax, hop, normalize, spec, max_frames, stats, bank=None, floor=FBANK_FLOOR):
+    """What log_spectrogram and fbank_finish end in (features_finish, csrc/spectrogram.hip): the DFT rows reim (B * Tmax, ld) -> (features
+    (B, 1, F, T_out), n_frames (B) int32 clamped to T_out = Tmax, or with `spec` min(Tmax, max_frames)): log-mel through the uploaded
+    `bank`, log-magnitudes of the F bins without one.  stats: "sums", "sqdev" (B) and "raw" (B, 1, F, Tmax), None where normalize overwrote it."""
+    from utils.audio import spec_frames
+    dev = reim.device
+    feat = torch.empty((B, 1, F, Tmax), device=dev, dtype=torch.float32)
+    scratch = torch.zeros((2, B), device=dev, dtype=torch.float32)
+    head = (L.ptr(reim), ld, L.ptr(lengths), L.ptr(feat), L.ptr(scratch[0]), L.ptr(scratch[1]))
+    name, dims, tail = "asr_spect_finish", (B, F), ()
+    if bank is not None:
+        name, dims = "asr_fbank_finish", (B, bank.n_bins, F)
+        tail = (L.ptr(bank.first), L.ptr(bank.count), L.ptr(bank.weights), bank.weights.numel(), float(floor))
+    if spec is not None:
+        if not normalize:
+            raise ValueError("%s: SpecAugment is defined on the normalised features" % ("log_spectrogram" if bank is None else "fbank_finish"))
+        T_out = Tmax if max_frames is None else min(Tmax, int(max_frames))
+        prm = _spec_params(spec, B, T_out, dev)
+        out, raw = torch.empty((B, 1, F, T_out), device=dev, dtype=torch.float32), feat
+        L.call(name + "_aug", *head, L.ptr(out), L.ptr(prm), *dims, Tmax, T_out, hop, *tail, L.stream())
+    else:
+        T_out, out, raw = Tmax, feat, None if normalize else feat
+        L.call(name, *head, *dims, Tmax, hop, int(normalize), *tail, L.stream())
+    if stats is not None:
+        stats.update(raw=raw, sums=scratch[0], sqdev=scratch[1])
+    return out, spec_frames(lengths, hop, T_out).to(torch.int32)
+
+
 def fbank_finish(reim, lengths, bank, hop, normalize=True, spec=None, max_frames=None, stats=None, floor=FBANK_FLOOR):
     """Log-mel filterbank features (asr_fbank_finish) of caller-supplied DFT rows: reim (B * Tmax, >= 2 K) fp32 on
     the device, [re (K) | im (K)] per frame, rows evenly strided; lengths (B) int32 samples; bank: utils.audio.mel_filterbank's arrays
     (host) or an fbank_upload of them.  Returns (feat (B, 1, M, Tmax), n_frames (B) int32) as log_spectrogram does, frames past an
-    utterance's 1 + max(len, 2) // hop zero.  normalize / spec / max_frames: as log_spectrogram; stats also without spec (then "raw" is
+    utterance's utils.audio.spec_frames zero.  normalize / spec / max_frames: as log_spectrogram; stats also without spec (then "raw" is
     None when normalize overwrote it)."""
     assert reim.dim() == 2 and reim.dtype == torch.float32 and reim.stride(1) == 1 and lengths.dtype == torch.int32
     bank = fbank_upload(bank, reim.device)
     B, K, M = lengths.numel(), bank.n_bins, bank.first.numel()
     if B == 0 or reim.shape[0] % B or reim.shape[1] < 2 * K:
         raise ValueError("fbank_finish: reim must hold B * Tmax rows of at least %d columns, got %s for B = %d" % (2 * K, tuple(reim.shape), B))
-    Tmax, ld = reim.shape[0] // B, reim.stride(0)
-    feat = torch.empty((B, 1, M, Tmax), device=reim.device, dtype=torch.float32)
-    scratch = torch.zeros((2, B), device=reim.device, dtype=torch.float32)
-    n_frames = torch.clamp(1 + torch.clamp(lengths, min=2) // hop, max=Tmax).to(torch.int32)
-    tail = (L.ptr(bank.first), L.ptr(bank.count), L.ptr(bank.weights), bank.weights.numel(), float(floor), L.stream())
-    if spec is not None:
-        if not normalize:
-            raise ValueError("fbank_finish: SpecAugment is defined on the normalised features")
-        T_out = Tmax if max_frames is None else min(Tmax, int(max_frames))
-        prm = _spec_params(spec, B, T_out, reim.device)
-        out = torch.empty((B, 1, M, T_out), device=reim.device, dtype=torch.float32)
-        L.call("asr_fbank_finish_aug", L.ptr(reim), ld, L.ptr(lengths), L.ptr(feat), L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(out),
-               L.ptr(prm), B, K, M, Tmax, T_out, hop, *tail)
-        if stats is not None:
-            stats.update(raw=feat, sums=scratch[0], sqdev=scratch[1])
-        return out, torch.clamp(n_frames, max=T_out)
-    L.call("asr_fbank_finish", L.ptr(reim), ld, L.ptr(lengths), L.ptr(feat), L.ptr(scratch[0]), L.ptr(scratch[1]), B, K, M, Tmax, hop,
-           int(normalize), *tail)
-    if stats is not None:               # the normalisation is in place: the raw values survive only without it
-        stats.update(raw=None if normalize else feat, sums=scratch[0], sqdev=scratch[1])
-    return feat, n_frames
+    return _finish_features(reim, reim.stride(0), lengths, B, M, reim.shape[0] // B, hop, normalize, spec, max_frames, stats, bank, floor)
 
 
 def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="hamming", spec=None, max_frames=None, stats=None,
@@ -1908,20 +1916,21 @@ def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="ha
     log1p / mean / unbiased std kernels.  window: --window (hamming, hann, blackman, bartlett; symmetric).
     spec: (B, 40) SpecAugment rows (spec_augment) -- the normalisation, the cut to max_frames frames and the augmentation are then
     one launch (asr_spect_finish_aug) and the result is (B, 1, F, min(Tmax, max_frames)) with n_frames clamped to it (host rows,
-    as for spec_augment).  stats: a dict that receives what that launch normalised with -- "raw" (B, 1, F, Tmax) log-magnitudes and
+    as for spec_augment).  stats: a dict that receives what the launch normalised with -- "raw" (B, 1, F, Tmax) log-magnitudes and
     "sums", "sqdev" (B) -- for tests and diagnostics: the reductions add with float atomics, so another launch may see other bits.
+    As fbank_finish promises, it is filled without spec too: "raw" is then None when normalize overwrote the values in place.
     features: "spect" (the above) or "fbank": log-mel filterbank features (B, 1, M, Tmax) of the same DFT through the bank `mel`
     (fbank_finish)."""
     if features not in ("spect", "fbank") or (features == "fbank") != (mel is not None):
         raise ValueError("log_spectrogram: features is 'spect', or 'fbank' with its filter bank mel=")
     assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1 and lengths.dtype == torch.int32
+    from utils.audio import spec_frames
     B, Lmax = wav.shape
     F = n_fft // 2 + 1
-    Tmax = 1 + max(Lmax, 2) // hop
+    Tmax = spec_frames(Lmax, hop)
     win, basis = _stft_constants(n_fft, wav.device, window)
     frames = torch.empty((B * Tmax, n_fft), device=wav.device, dtype=torch.float32)
-    L.call("asr_stft_frames", L.ptr(wav), wav.stride(0), L.ptr(lengths), L.ptr(win), L.ptr(frames), B, Tmax, n_fft, hop,
-           L.stream())
+    L.call("asr_stft_frames", L.ptr(wav), wav.stride(0), L.ptr(lengths), L.ptr(win), L.ptr(frames), B, Tmax, n_fft, hop, L.stream())
     ld = (2 * F + 3) // 4 * 4
     reim = torch.empty((B * Tmax, ld), device=wav.device, dtype=torch.float32)
     gemm_nt(frames, basis, out=reim[:, :2 * F])
@@ -1930,23 +1939,28 @@ def log_spectrogram(wav, lengths, n_fft=320, hop=160, normalize=True, window="ha
         if mel.n_bins != F:
             raise ValueError("log_spectrogram: the filter bank is not one of %d bins" % F)
         return fbank_finish(reim, lengths, mel, hop, normalize=normalize, spec=spec, max_frames=max_frames, stats=stats)
-    spect = torch.empty((B, 1, F, Tmax), device=wav.device, dtype=torch.float32)
-    scratch = torch.zeros((2, B), device=wav.device, dtype=torch.float32)
-    n_frames = (1 + torch.clamp(lengths, min=2) // hop).to(torch.int32)
-    if spec is not None:
-        if not normalize:
-            raise ValueError("log_spectrogram: SpecAugment is defined on the normalised features")
-        T_out = Tmax if max_frames is None else min(Tmax, int(max_frames))
-        prm = _spec_params(spec, B, T_out, wav.device)
-        out = torch.empty((B, 1, F, T_out), device=wav.device, dtype=torch.float32)
-        L.call("asr_spect_finish_aug", L.ptr(reim), ld, L.ptr(lengths), L.ptr(spect), L.ptr(scratch[0]), L.ptr(scratch[1]),
-               L.ptr(out), L.ptr(prm), B, F, Tmax, T_out, hop, L.stream())
-        if stats is not None:
-            stats.update(raw=spect, sums=scratch[0], sqdev=scratch[1])
-        return out, torch.clamp(n_frames, max=T_out)
-    L.call("asr_spect_finish", L.ptr(reim), ld, L.ptr(lengths), L.ptr(spect), L.ptr(scratch[0]), L.ptr(scratch[1]), B, F, Tmax,
-           hop, int(normalize), L.stream())
-    return spect, n_frames
+    return _finish_features(reim, ld, lengths, B, F, Tmax, hop, normalize, spec, max_frames, stats)
+
+
+def _wave_lens(name, lens, B, Lmax):
+    """The lengths (B) of padded waveforms (B, Lmax) as int64 on the host; one the kernel would have to clamp is a caller's mistake."""
+    import numpy as np
+    n = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
+    if (n < 0).any() or (n > Lmax).any():
+        raise ValueError("%s: lengths outside [0, %d]" % (name, Lmax))
+    return n
+
+
+def _row_stride(t, cols):
+    """The row stride of (B, cols) rows as the entry points check it (>= cols): a single row's stride is arbitrary."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), cols)
+
+
+def _check_out_rows(name, out, B, min_cols, device):
+    """A caller's output buffer of a waveform launch, every column of which is written."""
+    if out.dim() != 2 or out.dtype != torch.float32 or out.device != device or out.shape[0] != B or out.shape[1] < min_cols or \
+            (out.shape[1] > 1 and out.stride(1) != 1) or (B > 1 and out.stride(0) < out.shape[1]):
+        raise ValueError("%s: out must be (%d, >= %d) fp32 on %s with unit column stride and rows that do not overlap" % (name, B, min_cols, device))
 
 
 def augment_wave(wav, lens, params, bank, sample_rate=16000, offsets=False):
@@ -1960,9 +1974,7 @@ def augment_wave(wav, lens, params, bank, sample_rate=16000, offsets=False):
     assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1
     B, Lmax = wav.shape
     P = torch.as_tensor(params, dtype=torch.float64).cpu().numpy().reshape(B, -1)
-    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
-    if (n_in < 0).any() or (n_in > Lmax).any():
-        raise ValueError("augment_wave: lengths outside [0, %d]" % Lmax)
+    n_in = _wave_lens("augment_wave", lens, B, Lmax)
     S, search, O = wsola_constants(sample_rate)
     kp = np.zeros((B, 8), dtype=np.float64)
     nclips = 0 if bank is None else int(bank.lengths.size)
@@ -1989,10 +2001,7 @@ def augment_wave(wav, lens, params, bank, sample_rate=16000, offsets=False):
     offs = torch.zeros((B, nseg), device=dev, dtype=torch.int32) if offsets else None
     lens_in = torch.from_numpy(n_in.astype(np.int32)).to(dev)
     kp_dev = torch.from_numpy(kp).to(dev)
-    if bank is not None:
-        bdata, boff, blen = bank.data, bank.offsets, bank.lens
-    else:
-        bdata = boff = blen = None
+    bdata, boff, blen = (None, None, None) if bank is None else (bank.data, bank.offsets, bank.lens)
     L.call("asr_augment_wave", L.ptr(wav), wav.stride(0), L.ptr(lens_in), L.ptr(kp_dev), L.ptr(bdata), L.ptr(boff), L.ptr(blen),
            nclips, L.ptr(out), out.stride(0), L.ptr(offs), nseg, B, S, search, O, L.stream())
     lens_out = torch.from_numpy(n_outs.astype(np.int32)).to(dev)
@@ -2010,15 +2019,11 @@ def resample_launch(wav, lens, plan, table, out):
     upload -- the kernel clamps what it reads; a plan it would have to clamp is a caller's mistake."""
     import numpy as np
     assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1
-    assert out.dim() == 2 and out.dtype == torch.float32 and (out.shape[1] <= 1 or out.stride(1) == 1) and out.device == wav.device
     B, Lmax = wav.shape
+    _check_out_rows("resample", out, B, 0, wav.device)
     out_cols = out.shape[1]
     plan = np.ascontiguousarray(torch.as_tensor(plan).cpu().numpy().astype(np.int64).reshape(B, 8))
-    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
-    if out.shape[0] != B or (B > 1 and out.stride(0) < out_cols):
-        raise ValueError("resample: out must be (%d, out_cols) with rows that do not overlap" % B)
-    if (n_in < 0).any() or (n_in > Lmax).any():
-        raise ValueError("resample: lengths outside [0, %d]" % Lmax)
+    n_in = _wave_lens("resample", lens, B, Lmax)
     floats = 0 if table is None else table.numel()
     if table is not None:
         assert table.dim() == 1 and table.dtype == torch.float32 and table.is_contiguous() and table.device == wav.device
@@ -2034,9 +2039,8 @@ def resample_launch(wav, lens, plan, table, out):
         return out
     dev = wav.device
     lens_dev, plan_dev = torch.from_numpy(n_in.astype(np.int32)).to(dev), torch.from_numpy(plan.astype(np.int32)).to(dev)
-    ld_out = out.stride(0) if B > 1 else max(out.stride(0), out_cols)           # a single row's stride is arbitrary
-    L.call("asr_resample", L.ptr(wav), wav.stride(0), L.ptr(lens_dev), L.ptr(plan_dev), L.ptr(table), floats, L.ptr(out), ld_out,
-           out_cols, B, L.stream())
+    L.call("asr_resample", L.ptr(wav), wav.stride(0), L.ptr(lens_dev), L.ptr(plan_dev), L.ptr(table), floats, L.ptr(out),
+           _row_stride(out, out_cols), out_cols, B, L.stream())
     return out
 
 
@@ -2050,12 +2054,10 @@ def resample(wav, lens, p, tables=None, out=None):
     from utils.audio import SPEED_RANGE, device_resample_tables, speed_length, speed_ratio
     assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.stride(1) == 1
     B, Lmax = wav.shape
-    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
     ps = [int(v) for v in torch.as_tensor(p).cpu().reshape(B).tolist()]
     if any(v != 0 and not SPEED_RANGE[0] <= v <= SPEED_RANGE[1] for v in ps):
         raise ValueError("resample: speed factors are 0 (none) or %d .. %d thousandths, got %s" % (SPEED_RANGE + (ps,)))
-    if (n_in < 0).any() or (n_in > Lmax).any():
-        raise ValueError("resample: lengths outside [0, %d]" % Lmax)
+    n_in = _wave_lens("resample", lens, B, Lmax)
     dev = wav.device
     live = sorted(set(v for v in ps if v not in (0, 1000)))
     if not live and out is None:
@@ -2104,10 +2106,8 @@ def reverb(wav, lens, rir, bank, out=None):
         raise ValueError("reverb: the waveforms must be a contiguous (B, L) fp32 tensor, got %s %s with strides %s"
                          % (tuple(wav.shape), wav.dtype, wav.stride()))
     B, Lmax = wav.shape
-    n_in = torch.as_tensor(lens).cpu().numpy().astype(np.int64).reshape(B)
+    n_in = _wave_lens("reverb", lens, B, Lmax)
     idx = torch.as_tensor(rir).cpu().numpy().astype(np.int64).reshape(B)
-    if (n_in < 0).any() or (n_in > Lmax).any():
-        raise ValueError("reverb: lengths outside [0, %d]" % Lmax)
     count = 0 if bank is None else len(bank)
     if (idx < -1).any() or (idx >= count).any():
         raise ValueError("reverb: RIR indices are -1 (none) or 0 .. %d, got %s" % (count - 1, idx.tolist()))
@@ -2118,19 +2118,15 @@ def reverb(wav, lens, rir, bank, out=None):
         return wav
     if out is None:
         out = torch.empty((B, max(Lmax, 1)), device=dev, dtype=torch.float32)[:, :Lmax]
-    if out.dim() != 2 or out.dtype != torch.float32 or out.device != dev or out.shape[0] != B or out.shape[1] < Lmax or \
-            (out.shape[1] > 1 and out.stride(1) != 1) or (B > 1 and out.stride(0) < out.shape[1]):
-        raise ValueError("reverb: out must be (%d, >= %d) fp32 on %s with unit column stride and rows that do not overlap" % (B, Lmax, dev))
+    _check_out_rows("reverb", out, B, Lmax, dev)
     if out.untyped_storage().data_ptr() == wav.untyped_storage().data_ptr():
         raise ValueError("reverb: out must be another buffer than the waveforms (an output depends on thousands of earlier samples)")
     if B == 0 or out.shape[1] == 0:
         return out
     lens_dev, idx_dev = torch.from_numpy(n_in.astype(np.int32)).to(dev), torch.from_numpy(idx.astype(np.int32)).to(dev)
-    ld_out = out.stride(0) if B > 1 else max(out.stride(0), out.shape[1])       # a single row's stride is arbitrary
-    ld_in = wav.stride(0) if B > 1 else max(wav.stride(0), Lmax)
     taps, offs, counts = (None, None, None) if bank is None else (bank.data, bank.offsets, bank.lens)     # no bank: every row is copied
-    L.call("asr_reverb", L.ptr(wav), ld_in, L.ptr(lens_dev), L.ptr(idx_dev), L.ptr(taps), 0 if taps is None else taps.numel(),
-           L.ptr(offs), L.ptr(counts), count, L.ptr(out), ld_out, out.shape[1], B, L.stream())
+    L.call("asr_reverb", L.ptr(wav), _row_stride(wav, Lmax), L.ptr(lens_dev), L.ptr(idx_dev), L.ptr(taps), 0 if taps is None else taps.numel(),
+           L.ptr(offs), L.ptr(counts), count, L.ptr(out), _row_stride(out, out.shape[1]), out.shape[1], B, L.stream())
     return out
 
 

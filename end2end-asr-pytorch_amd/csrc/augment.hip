@@ -219,8 +219,6 @@ extern "C" int asr_augment_wave(const float* wav, int64_t wav_stride, const int3
   const size_t lds = (size_t)(2 * Wn + 2 * O) * sizeof(float);
   if (lds > 64 * 1024) return ASR_EINVAL;
   AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  augment_wave_kernel<<<B, kThreads, lds, stream>>>(wav, wav_stride, lens, params, bank, bank_off, bank_len, nclips, out, out_stride,
-                                                    offsets, off_stride, S, search, O);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<augment_wave_kernel>(dim3(B), dim3(kThreads), lds, stream, wav, wav_stride, lens, params, bank, bank_off, bank_len, nclips,
+                                         out, out_stride, offsets, off_stride, S, search, O);
 }

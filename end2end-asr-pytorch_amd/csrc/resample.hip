@@ -9,14 +9,14 @@
 // lanes 4 num / den apart: a 4-way conflict on every tap) and its stores are one contiguous 256-byte run.  The taps come from the table
 // through the cache: den x 2R floats, ~0.5 KB for the factors 0.9 / 1.1, at most 104 KB (den = 1000, R = 13).  Rows that are copied
 // (num == den) and tiles behind n_out move 16 bytes per lane.  No atomics: the same inputs give the same bits.
-#include "common.h"
+#include "wave_rows.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kPer = 4;                          // outputs per lane
 constexpr int kTile = ASR_RESAMPLE_TILE;         // outputs per workgroup
-constexpr int kLds = 2304;                       // staged input samples: kTile * 2 + 2 * 13 + alignment (factors down to 0.5 ... up to 2)
+constexpr int kLds = 2304;                       // staged input samples: kTile * 2 + 2 * 13 + alignment (factors 0.5 .. 2); tests/test_gpu_frontend_golden.py repeats it
 constexpr int kMaxDen = 1000;
 static_assert(kTile == kThreads * kPer, "one tile is kPer outputs per lane");
 
@@ -38,29 +38,6 @@ __device__ __forceinline__ ResamplePlan load_plan(const int32_t* __restrict__ pl
                              p.off + (int64_t)p.den * 2 * (int64_t)p.R <= table_floats);
   if (!ok) p.n_out = 0;
   return p;
-}
-
-// columns [m, m + 4) of a row that is copied or zero: x below `live` (<= n, <= n_out), +0.0 from there on
-__device__ __forceinline__ void copy_or_zero4(const float* __restrict__ x, float* __restrict__ y, int m, int live, int out_cols,
-                                              bool vec_in, bool vec_out) {
-  if (m >= out_cols) return;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (vec_in && m + 3 < live) {
-    v = *reinterpret_cast<const float4*>(x + m);
-  } else {
-    if (m < live) v.x = x[m];
-    if (m + 1 < live) v.y = x[m + 1];
-    if (m + 2 < live) v.z = x[m + 2];
-    if (m + 3 < live) v.w = x[m + 3];
-  }
-  if (vec_out && m + 3 < out_cols) {
-    *reinterpret_cast<float4*>(y + m) = v;
-  } else {
-    y[m] = v.x;
-    if (m + 1 < out_cols) y[m + 1] = v.y;
-    if (m + 2 < out_cols) y[m + 2] = v.z;
-    if (m + 3 < out_cols) y[m + 3] = v.w;
-  }
 }
 
 __global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restrict__ wav, int64_t wav_stride,
@@ -92,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restr
   const int64_t span = i_last + p.R - a0 + 1;                                    // input samples [a0, a0 + span) feed the tile
   const bool staged = span <= kLds;
   if (staged) {
-    for (int c = kPer * tid; c < (int)span; c += kTile) {
+    for (int c = kPer * tid; c < (int)span; c += kTile) {          // written out here and in reverb.hip: see wave_rows.h
       const int64_t j = a0 + c;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (vec_in && j >= 0 && j + 3 < n) {
@@ -161,15 +138,11 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restr
 
 extern "C" int asr_resample(const float* wav, int64_t wav_stride, const int32_t* lens, const int32_t* plan, const float* table,
                             int64_t table_floats, float* out, int64_t out_stride, int out_cols, int B, hipStream_t stream) {
-  ASR_CHECK_ARG(wav && lens && plan && out && B >= 0 && B <= 65535 && wav_stride >= 0 && table_floats >= 0);
-  ASR_CHECK_ARG(table || table_floats == 0);
-  ASR_CHECK_ARG(out_cols >= 0 && out_stride >= out_cols && out_cols <= 0x7fffffff - kTile);
+  WaveRowsLaunch l;
+  ASR_CHECK_ARG(wave_rows_launch(wav, wav_stride, out, out_stride, out_cols, B, kTile, &l));
+  ASR_CHECK_ARG(lens && plan && table_floats >= 0 && (table || table_floats == 0));
   if (B == 0 || out_cols == 0) return ASR_OK;
-  const int vec_in = aligned16(wav) && wav_stride % 4 == 0, vec_out = aligned16(out) && out_stride % 4 == 0;
   AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  const dim3 grid((unsigned)((out_cols + kTile - 1) / kTile), (unsigned)B);
-  resample_kernel<<<grid, kThreads, 0, stream>>>(wav, wav_stride, lens, plan, table, table_floats, out, out_stride, out_cols, vec_in,
-                                                 vec_out);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<resample_kernel>(l.grid, dim3(kThreads), 0, stream, wav, wav_stride, lens, plan, table, table_floats, out, out_stride,
+                                     out_cols, l.vec_in, l.vec_out);
 }

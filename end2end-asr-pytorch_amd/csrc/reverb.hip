@@ -22,7 +22,7 @@
 // a uniform address, which the compiler turns into scalar loads (nothing is ever stored through the scalar path).
 // Copied rows, rows the kernel refuses (written as zeros) and tiles behind n move 16 bytes per lane.  No atomics, no workspace: the
 // bits of a row depend on its samples, its taps and n alone -- not on the batch, the row's position in it, alignment, or the run.
-#include "common.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -33,29 +33,6 @@ constexpr int kQ = kPer / 4;                     // ... in float4
 constexpr int kChunk = ASR_REVERB_CHUNK;         // taps per staged span
 constexpr int kSpan = kTile + kChunk;            // staged samples
 static_assert(kTile == kPer * kThreads && kPer % 4 == 0 && kChunk % 4 == 0, "whole float4 per lane and per chunk");
-
-// columns [m, m + 4) of a row that is copied or zero: x below `live`, +0.0 from there on
-__device__ __forceinline__ void copy_or_zero4(const float* __restrict__ x, float* __restrict__ y, int m, int live, int out_cols,
-                                              bool vec_in, bool vec_out) {
-  if (m >= out_cols) return;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (vec_in && m + 3 < live) {
-    v = *reinterpret_cast<const float4*>(x + m);
-  } else {
-    if (m < live) v.x = x[m];
-    if (m + 1 < live) v.y = x[m + 1];
-    if (m + 2 < live) v.z = x[m + 2];
-    if (m + 3 < live) v.w = x[m + 3];
-  }
-  if (vec_out && m + 3 < out_cols) {
-    *reinterpret_cast<float4*>(y + m) = v;
-  } else {
-    y[m] = v.x;
-    if (m + 1 < out_cols) y[m + 1] = v.y;
-    if (m + 2 < out_cols) y[m + 2] = v.z;
-    if (m + 3 < out_cols) y[m + 3] = v.w;
-  }
-}
 
 // outputs [m, m + 4), m < n somewhere in the run: the sums below n, +0.0 from there on
 __device__ __forceinline__ void store4(float* __restrict__ y, int m, int n, int out_cols, const float (&a)[4], bool vec_out) {
@@ -118,12 +95,7 @@ __device__ __forceinline__ ReverbRow load_row(int b, const int32_t* __restrict__
 // inclusive prefix sum of v over the workgroup's 256 threads; *total = the sum
 __device__ __forceinline__ int block_scan(int v, int* wave_sums, int* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += u;
-  }
+  const int incl = wave_scan_incl(v);
   if (lane == 63) wave_sums[wave] = incl;
   __syncthreads();
   const int s0 = wave_sums[0], s1 = wave_sums[1], s2 = wave_sums[2], s3 = wave_sums[3];
@@ -187,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void reverb_kernel(const float* __restric
     // xs[i] = x[j0 + i]: the samples under the tile for the taps [c0, c0 + kChunk); j0 is a multiple of 4
     const int j0 = m0 - c0 - kChunk;
     if (c0) __syncthreads();
-    for (int c = 4 * tid; c < kSpan; c += 4 * kThreads) {
+    for (int c = 4 * tid; c < kSpan; c += 4 * kThreads) {               // written out here and in resample.hip: see wave_rows.h
       const int j = j0 + c;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (vec_in && j >= 0 && j + 3 < n) {
@@ -233,15 +205,11 @@ __global__ __launch_bounds__(kThreads) void reverb_kernel(const float* __restric
 extern "C" int asr_reverb(const float* wav, int64_t wav_stride, const int32_t* lens, const int32_t* rir, const float* bank,
                           int64_t bank_floats, const int64_t* rir_off, const int64_t* rir_len, int nrir, float* out,
                           int64_t out_stride, int out_cols, int B, hipStream_t stream) {
-  ASR_CHECK_ARG(wav && lens && rir && out && B >= 0 && B <= 65535 && wav_stride >= 0 && bank_floats >= 0 && nrir >= 0);
-  ASR_CHECK_ARG((bank && rir_off && rir_len) || nrir == 0);
-  ASR_CHECK_ARG(out_cols >= 0 && out_stride >= out_cols && out_cols <= 0x7fffffff - kTile);
+  WaveRowsLaunch l;
+  ASR_CHECK_ARG(wave_rows_launch(wav, wav_stride, out, out_stride, out_cols, B, kTile, &l));
+  ASR_CHECK_ARG(lens && rir && bank_floats >= 0 && nrir >= 0 && ((bank && rir_off && rir_len) || nrir == 0));
   if (B == 0 || out_cols == 0) return ASR_OK;
-  const int vec_in = aligned16(wav) && wav_stride % 4 == 0, vec_out = aligned16(out) && out_stride % 4 == 0;
   AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  const dim3 grid((unsigned)((out_cols + kTile - 1) / kTile), (unsigned)B);
-  reverb_kernel<<<grid, kThreads, 0, stream>>>(wav, wav_stride, lens, rir, bank, bank_floats, rir_off, rir_len, nrir, out, out_stride,
-                                               out_cols, vec_in, vec_out);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<reverb_kernel>(l.grid, dim3(kThreads), 0, stream, wav, wav_stride, lens, rir, bank, bank_floats, rir_off, rir_len, nrir, out,
+                                   out_stride, out_cols, l.vec_in, l.vec_out);
 }

@@ -9,6 +9,20 @@ constexpr int kSpecMaxMasks = 8;
 // (2u+1) s - d of the time warp stays below 2^31 for n <= 16384 frames; longer utterances take the same expressions in 64-bit integers
 constexpr int kSpecWarp32 = 16384;
 
+// frames of an utterance of `len` samples: 1 + (len + n_fft - n_fft) / hop of the centred STFT; the host path pads utterances shorter
+// than 2 samples (utils/audio.py spec_frames)
+__host__ __device__ __forceinline__ int spect_frames(int len, int hop) { return 1 + (len > 2 ? len : 2) / hop; }
+
+// what a thread of a (B * F * ceil(Tmax / 256)) x 256 grid works on: frame t (Tmax and beyond in the last block of a row) of row (b, f)
+struct SpectPos {
+  int b, f, t;
+};
+__device__ __forceinline__ SpectPos spect_pos(int F, int Tmax) {
+  const int tb = (Tmax + 255) / 256;
+  const int tblk = blockIdx.x % tb, f = (blockIdx.x / tb) % F, b = blockIdx.x / (tb * F);
+  return {b, f, (int)(tblk * 256 + threadIdx.x)};
+}
+
 struct SpectNorm {
   float mean, rstd;
 };
@@ -24,7 +38,7 @@ __device__ __forceinline__ SpectNorm spect_norm_of(const float* __restrict__ sum
 __device__ __forceinline__ float spect_norm_apply(float v, const SpectNorm& s) { return (v - s.mean) * s.rstd; }
 
 // out (B, F, T_out) <- warp + masks of x (B, F, >= T_out), rows ldx_row / ldo_row floats apart.  lengths != nullptr: x is the raw
-// log-magnitude and is normalised on load with (sums, sq) over the 1 + max(lengths[b], 2) / hop frames of the utterance.
+// log-magnitude and is normalised on load with (sums, sq) over the spect_frames(lengths[b], hop) frames of the utterance.
 __attribute__((visibility("hidden"))) int spec_augment_launch(const float* x, int64_t ldx_row, float* out, int64_t ldo_row,
                                                               const int32_t* params, const int32_t* lengths, const float* sums,
                                                               const float* sq, int hop, int B, int F, int T_out, hipStream_t stream);

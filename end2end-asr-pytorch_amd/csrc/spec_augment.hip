@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kThreads) void spec_augment_kernel(const float* __r
   int n = min(max(prm[0], 0), T_out);
   SpectNorm nm = {0.f, 1.f};
   if (NORM) {
-    const int nfr = 1 + max(lengths[b], 2) / hop;
+    const int nfr = spect_frames(lengths[b], hop);
     n = min(n, nfr);
     nm = spect_norm_of(sums, sq, b, nfr, F);
   }
@@ -124,10 +124,8 @@ int launch(const float* x, int64_t ldx_row, float* out, int64_t ldo_row, const i
   const bool vec = aligned16(out) && ldo_row % 4 == 0 && T_out % 4 == 0;
   const int per = kThreads * (vec ? 4 : 1);
   const dim3 grid((unsigned)((T_out + per - 1) / per), (unsigned)((F + kRows - 1) / kRows), (unsigned)B);
-  if (vec) spec_augment_kernel<NORM, 4><<<grid, kThreads, 0, stream>>>(x, ldx_row, out, ldo_row, params, lengths, sums, sq, hop, F, T_out);
-  else spec_augment_kernel<NORM, 1><<<grid, kThreads, 0, stream>>>(x, ldx_row, out, ldo_row, params, lengths, sums, sq, hop, F, T_out);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  if (vec) return asr_launch<spec_augment_kernel<NORM, 4>>(grid, dim3(kThreads), 0, stream, x, ldx_row, out, ldo_row, params, lengths, sums, sq, hop, F, T_out);
+  return asr_launch<spec_augment_kernel<NORM, 1>>(grid, dim3(kThreads), 0, stream, x, ldx_row, out, ldo_row, params, lengths, sums, sq, hop, F, T_out);
 }
 
 }  // namespace

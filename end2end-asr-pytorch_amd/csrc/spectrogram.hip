@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void stft_frames_kernel(const float* __restric
   const int64_t ft = i / n_fft;
   const int t = (int)(ft % Tmax), b = (int)(ft / Tmax);
   const int len = max(lengths[b], 2);                 // the host path pads utterances shorter than 2 samples (audio.py)
-  const int nfr = 1 + len / hop;                      // frames of this utterance: 1 + (len + n_fft - n_fft) / hop
+  const int nfr = spect_frames(lengths[b], hop);
   float v = 0.f;
   if (t < nfr) {
     const int pad = n_fft / 2;
@@ -63,10 +63,8 @@ __global__ __launch_bounds__(256) void spect_logmag_kernel(const float* __restri
                                                            float* __restrict__ spect, float* __restrict__ sums, int B, int F,
                                                            int Tmax, int hop) {
   __shared__ float red[4];
-  const int tb = (Tmax + 255) / 256;
-  const int tblk = blockIdx.x % tb, f = (blockIdx.x / tb) % F, b = blockIdx.x / (tb * F);
-  const int t = tblk * 256 + threadIdx.x;
-  const int nfr = 1 + max(lengths[b], 2) / hop;
+  const auto [b, f, t] = spect_pos(F, Tmax);
+  const int nfr = spect_frames(lengths[b], hop);
   float v = 0.f;
   if (t < Tmax) {
     if (t < nfr) {
@@ -84,10 +82,8 @@ __global__ __launch_bounds__(256) void spect_sqdev_kernel(const float* __restric
                                                           const float* __restrict__ sums, float* __restrict__ sq, int B, int F, int Tmax,
                                                           int hop) {
   __shared__ float red[4];
-  const int tb = (Tmax + 255) / 256;
-  const int tblk = blockIdx.x % tb, f = (blockIdx.x / tb) % F, b = blockIdx.x / (tb * F);
-  const int t = tblk * 256 + threadIdx.x;
-  const int nfr = 1 + max(lengths[b], 2) / hop;
+  const auto [b, f, t] = spect_pos(F, Tmax);
+  const int nfr = spect_frames(lengths[b], hop);
   const float mean = sums[b] / ((float)nfr * (float)F);
   float v = 0.f;
   if (t < nfr && t < Tmax) {
@@ -101,10 +97,8 @@ __global__ __launch_bounds__(256) void spect_sqdev_kernel(const float* __restric
 __global__ __launch_bounds__(256) void spect_normalize_kernel(float* __restrict__ spect, const int32_t* __restrict__ lengths,
                                                               const float* __restrict__ sums, const float* __restrict__ sq, int B, int F,
                                                               int Tmax, int hop) {
-  const int tb = (Tmax + 255) / 256;
-  const int tblk = blockIdx.x % tb, f = (blockIdx.x / tb) % F, b = blockIdx.x / (tb * F);
-  const int t = tblk * 256 + threadIdx.x;
-  const int nfr = 1 + max(lengths[b], 2) / hop;
+  const auto [b, f, t] = spect_pos(F, Tmax);
+  const int nfr = spect_frames(lengths[b], hop);
   if (t >= nfr || t >= Tmax) return;
   const SpectNorm nm = spect_norm_of(sums, sq, b, nfr, F);
   float* p = spect + ((int64_t)b * F + f) * Tmax + t;
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(256) void spect_normalize_kernel(float* __restrict_
 // that in the second half, where each lane owns a frame and reads its own row, the 32 lanes of an LDS access fall on 32 banks.  Each
 // wave then walks every fourth filter: first / count / weights are wave-uniform (scalar loads), the store is 256 contiguous bytes
 // along T.  Filters are clamped to the K bins and the nw weights: nothing outside the staged tile or the arrays is read.
-constexpr int kFbankTile = 64;
+constexpr int kFbankTile = 64;                   // tests/test_gpu_frontend_golden.py repeats it (FBANK_TILE)
 
 __global__ __launch_bounds__(256) void fbank_logmel_kernel(const float* __restrict__ reim, int64_t ld, const int32_t* __restrict__ lengths,
                                                            const int32_t* __restrict__ first, const int32_t* __restrict__ count,
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(256) void fbank_logmel_kernel(const float* __restri
   const int tiles = (Tmax + kFbankTile - 1) / kFbankTile;
   const int b = blockIdx.x / tiles, t0 = (blockIdx.x % tiles) * kFbankTile;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nfr = 1 + max(lengths[b], 2) / hop;
+  const int nfr = spect_frames(lengths[b], hop);
   const int nv = min(min(nfr, Tmax) - t0, kFbankTile);                    // frames of this tile that belong to the utterance
   const int t = t0 + lane;
   float* out = feat + (int64_t)b * M * Tmax + t;
@@ -144,12 +138,7 @@ __global__ __launch_bounds__(256) void fbank_logmel_kernel(const float* __restri
     for (int m0 = 0; m0 < M; m0 += 64) {
       const int m = m0 + lane;
       const int c = m < M ? min(max(count[m], 0), K) : 0;
-      int incl = c;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-      }
+      const int incl = wave_scan_incl(c);
       if (m < M) offs[m] = carry + incl - c;
       carry += __shfl(incl, 63, 64);
     }
@@ -179,13 +168,42 @@ __global__ __launch_bounds__(256) void fbank_logmel_kernel(const float* __restri
   if (threadIdx.x == 0) atomicAdd(sums + b, s);
 }
 
-int fbank_first_pass(const float* reim, int64_t ld, const int32_t* lengths, float* feat, float* sums, int B, int K, int M, int Tmax, int hop,
-                     const int32_t* first, const int32_t* count, const float* weights, int nw, float floor_v, hipStream_t stream) {
-  const size_t lds = ((size_t)kFbankTile * (K | 1) + M) * sizeof(float);
-  if (lds > 160 * 1024) return ASR_EUNSUPPORTED;
-  const unsigned grid = (unsigned)((int64_t)B * ((Tmax + kFbankTile - 1) / kFbankTile));
-  return asr_launch<fbank_logmel_kernel>(dim3(grid), dim3(256), lds, stream, reim, ld, lengths, first, count, weights, nw, floor_v, feat,
-                                         sums, B, K, M, Tmax, hop);
+struct MelBank {                                 // the sparse filter bank of the log-mel first pass
+  const int32_t *first, *count;
+  const float* weights;
+  int nw;
+  float floor;
+};
+struct SpecAug {                                 // SpecAugment rows and where the augmented features, cut to T_out frames, go
+  const int32_t* params;
+  float* out;
+  int T_out;
+};
+
+// The finish of all four entries: first pass (log-mel through `bank`, log-magnitude of the K = F bins without one) -> feat (B, F, Tmax)
+// and sums; with `normalize` the squared deviations, then either the in-place normalisation or, with `aug`, the SpecAugment pass that
+// normalises on load.
+int features_finish(const float* reim, int64_t ld, const int32_t* lengths, float* feat, float* sums, float* sqdev, int B, int K, int F,
+                    int Tmax, int hop, const MelBank* bank, bool normalize, const SpecAug* aug, hipStream_t stream) {
+  ASR_CHECK_ARG(reim && lengths && feat && sums && sqdev && B >= 0 && K > 0 && F > 0 && Tmax >= 0 && hop > 0 && ld >= 2 * (int64_t)K);
+  if (bank) ASR_CHECK_ARG(bank->first && bank->count && bank->weights && bank->nw >= 0 && bank->floor > 0.f);
+  if (aug) ASR_CHECK_ARG(aug->out && aug->params && aug->T_out >= 0 && aug->T_out <= Tmax && feat != aug->out);
+  if (B == 0 || Tmax == 0) return ASR_OK;
+  AsrProfScope prof(ASR_OP_LAYOUT, stream);
+  const dim3 grid((unsigned)((int64_t)B * F * ((Tmax + 255) / 256))), block(256);
+  if (bank) {
+    const size_t lds = ((size_t)kFbankTile * (K | 1) + F) * sizeof(float);
+    if (lds > 160 * 1024) return ASR_EUNSUPPORTED;
+    const dim3 tiles((unsigned)((int64_t)B * ((Tmax + kFbankTile - 1) / kFbankTile)));
+    ASR_TRY(asr_launch<fbank_logmel_kernel>(tiles, block, lds, stream, reim, ld, lengths, bank->first, bank->count, bank->weights, bank->nw,
+                                            bank->floor, feat, sums, B, K, F, Tmax, hop));
+  } else {
+    ASR_TRY(asr_launch<spect_logmag_kernel>(grid, block, 0, stream, reim, ld, lengths, feat, sums, B, F, Tmax, hop));
+  }
+  if (!normalize) return ASR_OK;
+  ASR_TRY(asr_launch<spect_sqdev_kernel>(grid, block, 0, stream, feat, lengths, sums, sqdev, B, F, Tmax, hop));
+  if (aug) return spec_augment_launch(feat, Tmax, aug->out, aug->T_out, aug->params, lengths, sums, sqdev, hop, B, F, aug->T_out, stream);
+  return asr_launch<spect_normalize_kernel>(grid, block, 0, stream, feat, lengths, sums, sqdev, B, F, Tmax, hop);
 }
 
 }  // namespace
@@ -196,74 +214,32 @@ extern "C" int asr_stft_frames(const float* wav, int64_t wav_stride, const int32
   const int64_t total = (int64_t)B * Tmax * n_fft;
   if (total == 0) return ASR_OK;
   AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  stft_frames_kernel<<<(unsigned)ceil_div64(total, 256), 256, 0, stream>>>(wav, wav_stride, lengths, window, frames, B, Tmax, n_fft, hop);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  return asr_launch<stft_frames_kernel>(dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, stream, wav, wav_stride, lengths, window, frames,
+                                        B, Tmax, n_fft, hop);
 }
 
 extern "C" int asr_spect_finish(const float* reim, int64_t ld, const int32_t* lengths, float* spect, float* sums, float* sqdev, int B,
                                 int F, int Tmax, int hop, int normalize, hipStream_t stream) {
-  ASR_CHECK_ARG(reim && lengths && spect && sums && sqdev && B >= 0 && F > 0 && Tmax >= 0 && hop > 0 && ld >= 2 * F);
-  if (B == 0 || Tmax == 0) return ASR_OK;
-  AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  const unsigned grid = (unsigned)((int64_t)B * F * ((Tmax + 255) / 256));
-  spect_logmag_kernel<<<grid, 256, 0, stream>>>(reim, ld, lengths, spect, sums, B, F, Tmax, hop);
-  ASR_LAUNCH_CHECK();
-  if (normalize) {
-    spect_sqdev_kernel<<<grid, 256, 0, stream>>>(spect, lengths, sums, sqdev, B, F, Tmax, hop);
-    ASR_LAUNCH_CHECK();
-    spect_normalize_kernel<<<grid, 256, 0, stream>>>(spect, lengths, sums, sqdev, B, F, Tmax, hop);
-    ASR_LAUNCH_CHECK();
-  }
-  return ASR_OK;
+  return features_finish(reim, ld, lengths, spect, sums, sqdev, B, F, F, Tmax, hop, nullptr, normalize != 0, nullptr, stream);
 }
 
 extern "C" int asr_spect_finish_aug(const float* reim, int64_t ld, const int32_t* lengths, float* raw, float* sums, float* sqdev, float* out,
                                     const int32_t* params, int B, int F, int Tmax, int T_out, int hop, hipStream_t stream) {
-  ASR_CHECK_ARG(reim && lengths && raw && sums && sqdev && out && params && B >= 0 && F > 0 && Tmax >= 0 && hop > 0 && ld >= 2 * F);
-  ASR_CHECK_ARG(T_out >= 0 && T_out <= Tmax && raw != out);
-  if (B == 0 || Tmax == 0) return ASR_OK;
-  AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  const unsigned grid = (unsigned)((int64_t)B * F * ((Tmax + 255) / 256));
-  spect_logmag_kernel<<<grid, 256, 0, stream>>>(reim, ld, lengths, raw, sums, B, F, Tmax, hop);
-  ASR_LAUNCH_CHECK();
-  spect_sqdev_kernel<<<grid, 256, 0, stream>>>(raw, lengths, sums, sqdev, B, F, Tmax, hop);
-  ASR_LAUNCH_CHECK();
-  return spec_augment_launch(raw, Tmax, out, T_out, params, lengths, sums, sqdev, hop, B, F, T_out, stream);
+  const SpecAug aug = {params, out, T_out};
+  return features_finish(reim, ld, lengths, raw, sums, sqdev, B, F, F, Tmax, hop, nullptr, true, &aug, stream);
 }
-
-#define ASR_FBANK_CHECK_ARGS()                                                                                                          \
-  ASR_CHECK_ARG(reim && lengths && sums && sqdev && first && count && weights && B >= 0 && K > 0 && M > 0 && Tmax >= 0 && hop > 0 && \
-                nw >= 0 && ld >= 2 * (int64_t)K && floor > 0.f)
 
 extern "C" int asr_fbank_finish(const float* reim, int64_t ld, const int32_t* lengths, float* feat, float* sums, float* sqdev, int B, int K,
                                 int M, int Tmax, int hop, int normalize, const int32_t* first, const int32_t* count, const float* weights,
                                 int nw, float floor, hipStream_t stream) {
-  ASR_FBANK_CHECK_ARGS();
-  ASR_CHECK_ARG(feat);
-  if (B == 0 || Tmax == 0) return ASR_OK;
-  AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  const int rc = fbank_first_pass(reim, ld, lengths, feat, sums, B, K, M, Tmax, hop, first, count, weights, nw, floor, stream);
-  if (rc != ASR_OK || !normalize) return rc;
-  const unsigned grid = (unsigned)((int64_t)B * M * ((Tmax + 255) / 256));
-  spect_sqdev_kernel<<<grid, 256, 0, stream>>>(feat, lengths, sums, sqdev, B, M, Tmax, hop);
-  ASR_LAUNCH_CHECK();
-  spect_normalize_kernel<<<grid, 256, 0, stream>>>(feat, lengths, sums, sqdev, B, M, Tmax, hop);
-  ASR_LAUNCH_CHECK();
-  return ASR_OK;
+  const MelBank bank = {first, count, weights, nw, floor};
+  return features_finish(reim, ld, lengths, feat, sums, sqdev, B, K, M, Tmax, hop, &bank, normalize != 0, nullptr, stream);
 }
 
 extern "C" int asr_fbank_finish_aug(const float* reim, int64_t ld, const int32_t* lengths, float* raw, float* sums, float* sqdev, float* out,
                                     const int32_t* params, int B, int K, int M, int Tmax, int T_out, int hop, const int32_t* first,
                                     const int32_t* count, const float* weights, int nw, float floor, hipStream_t stream) {
-  ASR_FBANK_CHECK_ARGS();
-  ASR_CHECK_ARG(raw && out && params && T_out >= 0 && T_out <= Tmax && raw != out);
-  if (B == 0 || Tmax == 0) return ASR_OK;
-  AsrProfScope prof(ASR_OP_LAYOUT, stream);
-  const int rc = fbank_first_pass(reim, ld, lengths, raw, sums, B, K, M, Tmax, hop, first, count, weights, nw, floor, stream);
-  if (rc != ASR_OK) return rc;
-  const unsigned grid = (unsigned)((int64_t)B * M * ((Tmax + 255) / 256));
-  spect_sqdev_kernel<<<grid, 256, 0, stream>>>(raw, lengths, sums, sqdev, B, M, Tmax, hop);
-  ASR_LAUNCH_CHECK();
-  return spec_augment_launch(raw, Tmax, out, T_out, params, lengths, sums, sqdev, hop, B, M, T_out, stream);
+  const MelBank bank = {first, count, weights, nw, floor};
+  const SpecAug aug = {params, out, T_out};
+  return features_finish(reim, ld, lengths, raw, sums, sqdev, B, K, M, Tmax, hop, &bank, true, &aug, stream);
 }

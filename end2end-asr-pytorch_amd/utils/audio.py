@@ -448,7 +448,12 @@ def rir_bank(rir_dir, sample_rate, max_ms, device):
 
 
 def spec_frames(samples, hop, src_max_len=None):
-    """Frames the front end keeps of an utterance of `samples` samples: min(1 + max(samples, 2) // hop, --src-max-len)."""
+    """Frames the front end keeps of an utterance of `samples` samples: min(1 + max(samples, 2) // hop, --src-max-len).  The one
+    statement of the frame count on the Python side (the kernels' is spect_frames, csrc/spec_augment.h); `samples` is a number, or an
+    integer tensor of them, for which a tensor comes back."""
+    if hasattr(samples, "clamp"):
+        n = 1 + samples.clamp(min=2) // int(hop)
+        return n if src_max_len is None else n.clamp(max=int(src_max_len))
     n = 1 + max(int(samples), 2) // int(hop)
     return n if src_max_len is None else min(n, int(src_max_len))
 
